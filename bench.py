@@ -12,10 +12,17 @@ processes (it never touches the GPU itself), relays rank 0's JSON line and fails
 fewer than N GPUs.  Weak scaling: the global grid is n x n x (n*N), rank r assembles its z-slab, columns are
 range-sharded, the entries of the cross-slab pairs travel through an RCCL all-to-all-v.
 
-Prints ONE JSON line (rank 0).  Extra objects: "roofline" (dominant kernel, hipEvent-timed on the
-library's stream), "pipeline" (whole step against the compulsory bytes of SURVEY.md section 8d),
-"cpu_baseline" (the C oracle timed on this box's host, bounded sample), "extra.configs" (BASELINE.json
-configs 3 and 4, three steps each, measured after the headline loop).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` steps, writes the outputs of the
+last timed step when `--dump-outputs DIR` is given, and prints the line (metric, value, unit, higher_is_better,
+dtype, ms_per_step and the configuration).  `--full` adds, after the timed steps: "digest_ok" (the device CSC
+against the oracle's pin), "roofline" (dominant kernel, hipEvent-timed on the library's stream), "pipeline"
+(whole step against the compulsory bytes of SURVEY.md section 8d, stage breakdown from extra untimed steps),
+"first_call_ms", "extra.consumers", "cpu_baseline" (the C oracle timed on this box's host, bounded sample) and
+"extra.configs" (BASELINE.json configs 3 and 4, three steps each, measured after the headline loop).
+
+`--dump-outputs DIR`: the CSC of the last timed step (colptr, rowval, nzval) as DIR/<name>.npy in float64; arrays
+longer than DUMP_SAMPLE values are written as a fixed, seeded sample of their positions (see dump_outputs).  The
+inputs are fixed (seeded generator), so two builds run with the same arguments can be compared file for file.
 """
 import argparse
 import json
@@ -71,6 +78,26 @@ def csc_digest_ok(A, tag, pins):
     for a in (cp, rv, nz):
         h.update(memoryview(a).cast("B"))
     return h.hexdigest() == pins[tag]["csc"]
+
+
+DUMP_SAMPLE = 1 << 21   # values per dumped array at most: 3 arrays x 2 Mi x 8 B = 48 MiB in all
+
+
+def dump_outputs(out_dir, arrays, prefix="", sample=DUMP_SAMPLE, seed=0x5EED00D0):
+    """--dump-outputs: writes every array of `arrays` ({name: 1-D numpy array}) as out_dir/<prefix><name>.npy in float64
+    (colptr / rowval hold 1-based Int64 indices, exact in float64 below 2^53).  An array longer than `sample` is written
+    as its values at a fixed set of positions: `sample` draws from numpy's default_rng(seed) over its length, the first
+    and the last position added, sorted and deduplicated -- the same positions for arrays of the same length (rowval[k]
+    and nzval[k] stay paired) and from run to run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if len(a) > sample:
+            rng = np.random.default_rng(seed)
+            idx = np.unique(np.concatenate([rng.integers(0, len(a), sample - 2), [0, len(a) - 1]]))
+            a = a[idx]
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a.astype(np.float64))
 
 
 def cfg3_new_positions(n, seed=0x5EED0003):
@@ -958,8 +985,14 @@ def main():
     ap.add_argument("--n", type=int, default=int(os.environ.get("ESP_BENCH_N", "256")))
     ap.add_argument("--cpu-sample-n", type=int, default=int(os.environ.get("ESP_BENCH_CPU_N", "256")))
     ap.add_argument("--cpu-mt-n", type=int, default=int(os.environ.get("ESP_BENCH_CPU_MT_N", "192")))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra.configs measurements (configs 3 and 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beyond the headline: digest_ok, roofline, "
+                         "pipeline stage breakdown, first_call_ms, consumers, extra.configs, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the CSC of the last timed step (colptr, rowval, nzval; a fixed sample of the long arrays) "
+                         "as DIR/<name>.npy in float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the extra.configs and consumers measurements")
     ap.add_argument("--sharded", action="store_true",
                     help="use the column-shard exchange path even on one GPU (always used for --gpus > 1)")
     ap.add_argument("--scrambled", action="store_true",
@@ -971,6 +1004,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch(args, sys.argv[1:]))
     if os.environ.get("ESP_BENCH_LAUNCH_PROBE"):
@@ -1083,17 +1118,28 @@ def main():
         s = torch.tensor([float(sent)], dtype=torch.float64, device="cuda")
         dist.all_reduce(s, op=dist.ReduceOp.MAX)
         sent = int(s.item())
+    if args.dump_outputs:
+        # what a caller of the timed path receives after its last step: the CSC (sharded: this rank's column slice; the
+        # call is collective, every rank makes it, rank r > 0 writes rank<r>_*.npy)
+        if sharded:
+            _, _, cp, rv, nz = SA.local_slice()
+        else:
+            cp, rv, nz = A.sparse().arrays()
+        dump_outputs(args.dump_outputs, {"colptr": cp, "rowval": rv, "nzval": nz},
+                     prefix="" if rank == 0 else "rank%d_" % rank, sample=DUMP_SAMPLE // world)
+        del cp, rv, nz
     total_nnz = SA.nnz() if sharded else A.nnz()
     assert total_nnz == Z_total or os.environ.get("ESP_LOCAL_STOP"), (total_nnz, Z_total)   # (ablation runs produce nothing)
     tm = A.timing(clear=True)
     partition_kind = A.debug_last_partition()
     # untimed self-check of what the timed loop produced: the device CSC against the oracle's pin (fd_<n>_m1)
     digest_ok = None
-    if not sharded and rank == 0 and not os.environ.get("ESP_LOCAL_STOP") and not os.environ.get("ESP_BENCH_NO_DIGEST"):
+    if (args.full and not sharded and rank == 0 and not os.environ.get("ESP_LOCAL_STOP")
+            and not os.environ.get("ESP_BENCH_NO_DIGEST")):
         digest_ok = csc_digest_ok(A, "fd_%d_m1" % n, golden_digests())
     breakdown_steps = 0
     tm_all = tm
-    if timing_level == 3:   # stage breakdown: separate untimed steps with events around every big kernel
+    if args.full and timing_level == 3:   # stage breakdown: separate untimed steps with events around every big kernel
         breakdown_steps = min(3, args.steps)
         A.timing_enable(1)
         for _ in range(breakdown_steps):
@@ -1106,7 +1152,7 @@ def main():
     # ranking launches and the host round trip for their flags in every step) -- what the first assembly of a grid costs
     plan_reused = A.debug_last_plan_reused()
     first_call_ms = None
-    if not os.environ.get("ESP_BENCH_FORCE_PATH"):
+    if args.full and not os.environ.get("ESP_BENCH_FORCE_PATH"):
         A.debug_force_path(31)
         step()
         barrier()
@@ -1118,7 +1164,7 @@ def main():
         A.debug_force_path(0)
     # the consumers of the flushed CSC that stay on the device, on the matrix the timed loop built
     consumers = None
-    if rank == 0 and not sharded and not args.no_extra:
+    if args.full and rank == 0 and not sharded and not args.no_extra:
         try:
             consumers = consumer_lines(esp, torch, A, N, int(Z_total))
         except Exception as ex:
@@ -1126,7 +1172,8 @@ def main():
     Z = Z_total / world   # per-rank share of the final nnz (value below multiplies by world)
 
     out = None
-    if rank == 0:
+    ms_step = dt / args.steps * 1e3
+    if rank == 0 and args.full:
         # dominant kernel = the stage with the largest summed device time
         nsteps_all = breakdown_steps if breakdown_steps else args.steps
         stage_ms = {k: v[0] for k, v in tm_all.items() if isinstance(v, tuple)}
@@ -1145,8 +1192,8 @@ def main():
         avg_ms = max(dom_ms / max(dom_launches, 1), 1e-9)
         achieved = per_launch_bytes / (avg_ms * 1e-3) / 1e9
         algo_bytes = 2 * 16.0 * E + 16.0 * Z + 8.0 * (N / world + 1)   # 72.08 B per final nnz (per rank)
-        ms_step = dt / args.steps * 1e3
         traffic, traffic_round = pmc_traffic(dom) if (n == 256 and not sharded) else (None, None)
+    if rank == 0:
         out = {
             "metric": baseline_metric(),
             "value": Z * args.steps * world / dt,
@@ -1162,8 +1209,7 @@ def main():
             "data": "synthetic",
             "host_numa_node": numa_node,   # the process runs on the CPUs of the GPU's NUMA node (bind_near_gpu); None: unchanged
             # the timed steps repeat the previous assembly: the producer reused its plan (1) -- first_call_ms is the step without that
-            "plan_reused": plan_reused, "first_call_ms": first_call_ms,
-            "digest_ok": digest_ok,   # sha256 of the device CSC == the CPU oracle's (tests/golden/digests_large.txt); None: no pin for this size
+            "plan_reused": plan_reused,
             "config": {"workload": "fdrand %d^3 Float64/Int64 fresh build: device COO append (the producer writes every "
                                    "update to its radix bucket) -> LDS bucket sort + ordered fold -> CSC "
                                    "(BASELINE.json configs[1])" % n,
@@ -1175,6 +1221,11 @@ def main():
                                        % (world, world, "scrambled (blocks of 8 z-planes dealt round-robin)" if args.scrambled else "z-slab",
                                           gx, gy, nzg, " (BASELINE.json configs[4])" if args.global_n == 512 else "", sent))
                                       if sharded else "1 GPU"},
+        }
+    if rank == 0 and args.full:
+        out.update({
+            "first_call_ms": first_call_ms,
+            "digest_ok": digest_ok,   # sha256 of the device CSC == the CPU oracle's (tests/golden/digests_large.txt); None: no pin for this size
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          "traffic_from": ("profiles/pmc_traffic.json (%s)" % traffic_round) if traffic else None,
@@ -1188,14 +1239,14 @@ def main():
                          "stage_ms_from": ("%d untimed steps after the timed region, events around every big kernel"
                                            % breakdown_steps) if breakdown_steps else "timed region",
                          "flush_ms_per_step": tm["flush_ms"] / max(tm["flushes"], 1)},
-        }
-    if rank == 0 and world == 1 and not sharded and not args.no_extra:
+        })
+    if args.full and rank == 0 and world == 1 and not sharded and not args.no_extra:
         del A
         out["extra"] = {"configs": extra_configs(esp, torch, local, n, int(os.environ.get("ESP_CFG4_2D", "3163")),
                                                  int(os.environ.get("ESP_CFG4_3D", "216")))}
     if rank == 0 and consumers is not None:
         out.setdefault("extra", {})["consumers"] = consumers
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(args.cpu_sample_n, args.cpu_mt_n)
     if rank == 0:
         out["summary"] = summary_of(out)   # LAST key: the driver's record keeps the tail of the line

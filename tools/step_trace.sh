@@ -1,16 +1,17 @@
 #!/bin/bash
 # usage: tools/step_trace.sh [bench args, e.g. --sharded]
-# Ordered kernel trace of the LAST bench step (name, start offset us, duration us, gap to previous us) -> gpurun_out/step_trace.txt
+# Ordered kernel trace of the LAST bench step (name, start offset us, duration us, gap to previous us) -> $ESP_TOOL_OUT/step_trace.txt (default tool_out/)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-rm -rf gpurun_out/trc
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d gpurun_out/trc -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" > gpurun_out/trc.log 2>&1
-python3 - <<'P'
-import csv, glob
+O=${ESP_TOOL_OUT:-tool_out}; mkdir -p $O   # output folder (default tool_out/)
+rm -rf $O/trc
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/trc -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline "$@" > $O/trc.log 2>&1
+python3 - "$O" <<'P'
+import csv, glob, sys
 rows = []
-for f in glob.glob('gpurun_out/trc/**/*kernel_trace.csv', recursive=True):
+for f in glob.glob(sys.argv[1] + '/trc/**/*kernel_trace.csv', recursive=True):
     for r in csv.DictReader(open(f)):
         rows.append((int(r['Start_Timestamp']), int(r['End_Timestamp']), r['Kernel_Name'][:70]))
-for f in glob.glob('gpurun_out/trc/**/*memory_copy_trace.csv', recursive=True):
+for f in glob.glob(sys.argv[1] + '/trc/**/*memory_copy_trace.csv', recursive=True):
     for r in csv.DictReader(open(f)):
         rows.append((int(r['Start_Timestamp']), int(r['End_Timestamp']), 'COPY ' + r.get('Direction', '')))
 rows.sort()
@@ -18,7 +19,7 @@ rows.sort()
 mark = 'fd_count_k' if any('fd_count_k' in r[2] for r in rows) else 'fdrand_k'
 hits = [i for i, r in enumerate(rows) if mark in r[2]]
 last, prev = hits[-1], hits[-2]
-out = open('gpurun_out/step_trace.txt', 'w')
+out = open(sys.argv[1] + '/step_trace.txt', 'w')
 t0 = rows[prev][0]
 pe = t0
 for s, e, n in rows[prev:last]:
@@ -26,5 +27,5 @@ for s, e, n in rows[prev:last]:
     pe = e
 out.close()
 P
-rm -rf gpurun_out/trc
-cat gpurun_out/step_trace.txt
+rm -rf $O/trc
+cat $O/step_trace.txt
