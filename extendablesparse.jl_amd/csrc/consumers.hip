@@ -256,12 +256,7 @@ int32_t build_csr(esp_handle *h) {
     return ESP_OK;
 }
 
-extern "C" int32_t esp_mul(esp_handle *h, const double *x, double *r, int32_t on_device) {
-    if (!h || !x || !r) return ESP_ERR_INVALID;
-    if (h->count != 0) FAIL(h, ESP_ERR_STATE, "esp_mul: pending entries (flush first, like mul!(r, ext, x) does)");
-    (void)hipSetDevice(h->device);
-    if (!h->csc_valid) CK(init_empty_csc(h));
-    CK(fix_tail(h));
+int32_t csr_current(esp_handle *h) {
     if (h->csr_version != h->pattern_version) {
         CK(build_csr(h));
         h->csr_val_version = 0;
@@ -272,6 +267,16 @@ extern "C" int32_t esp_mul(esp_handle *h, const double *x, double *r, int32_t on
                            (const double *)h->nzval.p, h->nnz, (double *)h->csr_val.p);
         h->csr_val_version = h->values_version;
     }
+    return ESP_OK;
+}
+
+extern "C" int32_t esp_mul(esp_handle *h, const double *x, double *r, int32_t on_device) {
+    if (!h || !x || !r) return ESP_ERR_INVALID;
+    if (h->count != 0) FAIL(h, ESP_ERR_STATE, "esp_mul: pending entries (flush first, like mul!(r, ext, x) does)");
+    (void)hipSetDevice(h->device);
+    if (!h->csc_valid) CK(init_empty_csc(h));
+    CK(fix_tail(h));
+    CK(csr_current(h));
     const double *dx = x;
     double *dr = r;
     if (!on_device) {

@@ -269,6 +269,7 @@ extern "C" int32_t esp_create(int64_t m, int64_t n, int32_t device, int64_t capa
 
 extern "C" int32_t esp_destroy(esp_handle *h) {
     if (!h) return ESP_OK;
+    if (h->live_precons > 0) FAIL(h, ESP_ERR_STATE, "esp_destroy: %d preconditioner(s) still bound to this matrix (esp_precon_destroy first)", h->live_precons);
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
     if (h->sumtmp) {

@@ -7,6 +7,7 @@
 //   flush.hip      esp_flush: bucket kernel launch, join with a stored CSC, batch + tail, general path
 //   shard.hip      column shards (esp_shard_*) and the group API (group.hpp: exchange policy + RCCL transport)
 //   consumers.hip  what reads or edits the assembled CSC: getindex, dropzeros, pattern hash, mul!, Dirichlet, Jacobi / ILU0
+//   precon.hip     the point preconditioners' update! / ldiv! (esp_precon_*) and simple! (esp_simple) on the device CSC
 //   local_*.hip    the instantiations of the bucket kernel (local.hpp; local_h.hip: group3.hpp, the group tier with three workgroups per CU;
 //                  local_j.hip: group3_items.hpp, the same fed with the item records of an element-level batch)
 #pragma once
@@ -296,6 +297,7 @@ struct esp_handle {
     unsigned long long pattern_version = 1, csr_version = 0;
     unsigned long long values_version = 1, csr_val_version = 0;  // nzval changed / row-wise copy of the values
     DevBuf csr_rowptr, csr_perm, csr_col, csr_tmp, csr_val, mul_x, mul_r;
+    int live_precons = 0;  // esp_precon objects bound to this handle (precon.hip): esp_destroy refuses while any is alive
     // timing
     bool timing = false;
     int timing_level = 2;
@@ -520,6 +522,7 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out);
 int32_t flush_global(esp_handle *h, int mode, i64 *Zn_out);
 int32_t flush_pre_tail(esp_handle *h, int mode, i64 *Zn, bool *served);
 int32_t build_csr(esp_handle *h);
+int32_t csr_current(esp_handle *h);  // build_csr after a pattern change, the row-wise values after a value change
 int32_t dirichlet_call(esp_handle *h, uint8_t *marker, int32_t on_device, bool mark, double penalty);
 int32_t diag_setup(esp_handle *h, double *inv, int64_t *idiag, int32_t on_device, const char *what);
 int32_t shard_prepare(esp_handle *h, int P, espradix::Pass *out);

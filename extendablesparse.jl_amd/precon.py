@@ -1,0 +1,141 @@
+"""The point preconditioners (src/factorizations/jacobi.jl, ilu0.jl) and simple! (simple_iteration.jl) on the device CSC.
+
+JacobiPreconditioner(A) / ILU0Preconditioner(A) bind an esp_precon to the matrix's handle: construction is factorize!
+(create + update!), .update() is update!, .ldiv(v, out) is ldiv!(out, p, v) -- bit-identical to the reference loops.
+simple(A, b, Pl=...) is simple / simple!; u is bit-identical to the reference's loop, the residual norms agree to rounding
+(include/esparse_hip.h, esp_simple).  Vectors: NumPy arrays (copied through the device) or CUDA float64 torch tensors (used
+in place).  There is no CPU path: without a GPU the matrix itself raises NoDeviceError.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+
+from ._lib import ESP_PRECON_ILU0, ESP_PRECON_JACOBI
+from .matrix import ExtendableSparseMatrix, _vp
+
+
+def _is_cuda(x):
+    return hasattr(x, "is_cuda") and x.is_cuda
+
+
+def _check_cuda(t, n):
+    import torch
+    assert t.is_cuda and t.dtype == torch.float64 and t.numel() == n and t.is_contiguous()
+
+
+class _PointPreconditioner:
+    KIND = None
+
+    def __init__(self, A):
+        if not isinstance(A, ExtendableSparseMatrix):
+            raise TypeError("%s(A): A must be an ExtendableSparseMatrix" % type(self).__name__)
+        self.A = A
+        self._p = None
+        A.flush()
+        d = A._d
+        p = C.c_void_p()
+        d.ck(d.lib.esp_precon_create(d.h, self.KIND, C.byref(p)))  # factorize!: jacobi(A) / ilu0(A)
+        self._p = p
+
+    def _ck(self, rc):
+        self.A._d.ck(rc)
+
+    def _live(self):
+        if self._p is None:
+            raise ValueError("the preconditioner was closed")
+        return self._p
+
+    def update(self):
+        """update! (jacobi.jl:54-64, ilu0.jl:120-130): flush! first (host edits of a handed-out copy go up as well), then a
+        rebuild after a pattern change, else the values only."""
+        p = self._live()
+        self.A.flush()
+        self._ck(self.A._d.lib.esp_precon_update(p))
+        return self
+
+    def ldiv(self, v, out=None):
+        """ldiv!(out, p, v); out may be v.  NumPy arrays or CUDA torch tensors (float64, contiguous, n elements)."""
+        p = self._live()
+        A = self.A
+        A._push_edits()   # (a device consumer: host edits of a handed-out copy go up first, as for mul)
+        lib = A._d.lib
+        n = A.n
+        if _is_cuda(v):
+            import torch
+            _check_cuda(v, n)
+            u = out if out is not None else torch.empty(n, dtype=torch.float64, device=v.device)
+            _check_cuda(u, n)
+            torch.cuda.current_stream(v.device).synchronize()   # the library runs on its own stream
+            self._ck(lib.esp_precon_ldiv(p, C.c_void_p(v.data_ptr()), C.c_void_p(u.data_ptr()), 1))
+            return u
+        vv = np.ascontiguousarray(v, np.float64)
+        if vv.shape != (n,):
+            raise ValueError("DimensionMismatch")
+        u = out if out is not None else np.empty(n, np.float64)
+        if not (isinstance(u, np.ndarray) and u.dtype == np.float64 and u.shape == (n,) and u.flags.c_contiguous):
+            raise ValueError("out must be a contiguous float64 array of length n")
+        self._ck(lib.esp_precon_ldiv(p, _vp(vv), _vp(u), 0))
+        return u
+
+    def close(self):
+        if self._p is not None:
+            self.A._d.lib.esp_precon_destroy(self._p)
+            self._p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class JacobiPreconditioner(_PointPreconditioner):
+    """JacobiPreconditioner(A) (src/factorizations/jacobi.jl): ldiv! is u = invdiag .* v."""
+    KIND = ESP_PRECON_JACOBI
+
+
+class ILU0Preconditioner(_PointPreconditioner):
+    """ILU0Preconditioner(A) (src/factorizations/ilu0.jl): ldiv! as two row-parallel passes, bit-identical to the
+    reference's column loops."""
+    KIND = ESP_PRECON_ILU0
+
+
+def simple(A, b, u=None, Pl=None, maxiter=100, reltol=math.sqrt(np.finfo(np.float64).eps), abstol=0.0, log=False):
+    """simple / simple!(u, A, b; abstol, reltol, log, maxiter, Pl) (simple_iteration.jl:21-47): u <- u - Pl \\ (A u - b)
+    until norm(res)/r0 < reltol or norm(res) < abstol.  u = None starts from zeros (simple); a given u is updated in
+    place (simple!).  log=True returns (u, {"resnorm": history})."""
+    if Pl is None:
+        raise TypeError("simple: Pl is required (the reference's default `nothing` has no ldiv!)")
+    if not isinstance(Pl, _PointPreconditioner) or Pl.A is not A:
+        raise ValueError("simple: Pl must be a preconditioner of A")
+    p = Pl._live()
+    A.flush()
+    d = A._d
+    n = A.n
+    maxiter = int(maxiter)
+    if maxiter < 0:
+        raise ValueError("maxiter < 0")
+    hist = np.empty(maxiter + 1, np.float64)
+    its = C.c_int64()
+    if _is_cuda(b):
+        import torch
+        _check_cuda(b, n)
+        if u is None:
+            u = torch.zeros(n, dtype=torch.float64, device=b.device)
+        _check_cuda(u, n)
+        torch.cuda.current_stream(b.device).synchronize()
+        d.ck(d.lib.esp_simple(d.h, p, C.c_void_p(b.data_ptr()), C.c_void_p(u.data_ptr()), 1, maxiter, float(abstol),
+                              float(reltol), _vp(hist), C.byref(its)))
+    else:
+        bb = np.ascontiguousarray(b, np.float64)
+        if bb.shape != (n,):
+            raise ValueError("DimensionMismatch")
+        if u is None:
+            u = np.zeros(n, np.float64)
+        if not (isinstance(u, np.ndarray) and u.dtype == np.float64 and u.shape == (n,) and u.flags.c_contiguous):
+            raise ValueError("u must be a contiguous float64 array of length n")
+        d.ck(d.lib.esp_simple(d.h, p, _vp(bb), _vp(u), 0, maxiter, float(abstol), float(reltol), _vp(hist), C.byref(its)))
+    if log:
+        return u, {"resnorm": hist[:its.value + 1].copy()}
+    return u

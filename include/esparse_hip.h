@@ -290,6 +290,39 @@ int32_t esp_eliminate_dirichlet(esp_handle *h, const uint8_t *marker, int32_t on
 int32_t esp_jacobi_setup(esp_handle *h, double *invdiag, int32_t on_device);
 int32_t esp_ilu0_setup(esp_handle *h, double *xdiag, int64_t *idiag, int32_t on_device);
 
+/* ---- the point preconditioners and simple! on the device CSC of a square matrix -----------------------------------
+ * An esp_precon is _JacobiPreconditioner / _ILU0Preconditioner plus the update! wrapper around them
+ * (src/factorizations/jacobi.jl, ilu0.jl), bound to one handle; everything runs on the handle's stream and every call
+ * returns synchronised.  Pending entries -> ESP_ERR_STATE (flush first, as update! does); a rectangular matrix ->
+ * ESP_ERR_INVALID; nnz or n >= 2^32 - 16 -> ESP_ERR_UNSUPPORTED (32-bit positions and columns, as esp_mul's index).
+ * esp_precon_create = jacobi(A) / ilu0(A): ILU0 on a column without a stored diagonal -> ESP_ERR_INVALID, Jacobi gives Inf
+ *   there (jacobi.jl:5-12: getindex of a position that is not stored is zero).  The handle refuses esp_destroy
+ *   (ESP_ERR_STATE) while a preconditioner bound to it is alive.
+ * esp_precon_update = update! (jacobi.jl:54-64, ilu0.jl:120-130): after a pattern change since the last create / update
+ *   everything is rebuilt, else the values only (jacobi! / ilu0!).
+ * esp_precon_ldiv = ldiv!(u, p, v) (jacobi.jl:36-41, ilu0.jl:66-92), bit-identical; n doubles each, u may equal v;
+ *   on_device != 0: device pointers.  Like the reference, whose preconditioner holds A.cscmatrix by reference, ILU0 uses
+ *   the CURRENT off-diagonal values with the xdiag of the last update! after an in-place value change (updates of stored
+ *   positions, esp_eliminate_dirichlet, esp_set_nzval).  After a pattern change without update! the reference would
+ *   still use the old matrix object; here -> ESP_ERR_STATE (update! first). */
+typedef struct esp_precon esp_precon;
+#define ESP_PRECON_JACOBI 0
+#define ESP_PRECON_ILU0 1
+int32_t esp_precon_create(esp_handle *h, int32_t kind, esp_precon **out);
+int32_t esp_precon_update(esp_precon *p);
+int32_t esp_precon_ldiv(esp_precon *p, const double *v, double *u, int32_t on_device);
+int32_t esp_precon_destroy(esp_precon *p);
+/* simple!(u, A, b; abstol, reltol, maxiter, Pl = p) (src/factorizations/simple_iteration.jl:21-45) statement by
+ * statement: res = A*u - b; then per step ldiv!(upd, Pl, res), u .-= upd, mul!(res, A, u), res .-= b, r = norm(res),
+ * stop when (r / r0) < reltol || r < abstol (literally: r0 = 0 gives NaN or Inf there).  u (in/out) is bit-identical to
+ * the reference loop for any number of steps run (mul! as esp_mul).  norm is a fixed-order sum of squares (identical run to
+ * run) rather than BLAS nrm2: history and the stopping step agree with the reference to rounding of the norm only, and the
+ * sum of squares overflows for residual entries above about 1e154, where nrm2 would not.  history: maxiter+1 host doubles
+ * or NULL; *iterations = number of ldiv! steps taken (history holds iterations+1 norms).  b, u: n doubles; on_device != 0:
+ * device pointers.  p must be bound to h. */
+int32_t esp_simple(esp_handle *h, esp_precon *p, const double *b, double *u, int32_t on_device, int64_t maxiter,
+                   double abstol, double reltol, double *history, int64_t *iterations);
+
 /* ---- column-range shards (multi-GPU, one process per GPU) ------------------------
  * owner(col) = floor((col-1)*nshards/n).  esp_shard_counts: pending entries per owner.
  * esp_shard_export: stable partition of the pending entries by owner into the caller's
