@@ -100,6 +100,11 @@ SIGNATURES = {
     "esp_precon_ldiv": (i32, [vp, vp, vp, i32]),
     "esp_precon_destroy": (i32, [vp]),
     "esp_simple": (i32, [vp, vp, vp, vp, i32, i64, f64, f64, vp, P(i64)]),
+    "esp_matmul": (i32, [vp, vp, vp, P(i64)]),
+    "esp_add": (i32, [vp, vp, i32, vp, P(i64)]),
+    "esp_diag_scale": (i32, [vp, vp, i32, i32, vp]),
+    "esp_debug_matmul_tier": (i32, [vp, i32]),
+    "esp_device": (i32, [vp, P(i32)]),
     "esp_shard_counts": (i32, [vp, i32, vp]),
     "esp_shard_export": (i32, [vp, i32, vp, vp, vp]),
     "esp_shard_exchange_begin": (i32, [vp, i32, i32, i64, i64, P(vp), P(vp), vp]),

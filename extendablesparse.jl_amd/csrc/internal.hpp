@@ -8,6 +8,7 @@
 //   shard.hip      column shards (esp_shard_*) and the group API (group.hpp: exchange policy + RCCL transport)
 //   consumers.hip  what reads or edits the assembled CSC: getindex, dropzeros, pattern hash, mul!, Dirichlet, Jacobi / ILU0
 //   precon.hip     the point preconditioners' update! / ldiv! (esp_precon_*) and simple! (esp_simple) on the device CSC
+//   matops.hip     the algebra of assembled matrices on the device: A*B (esp_matmul), A+B / A-B (esp_add), Diagonal scaling
 //   local_*.hip    the instantiations of the bucket kernel (local.hpp; local_h.hip: group3.hpp, the group tier with three workgroups per CU;
 //                  local_j.hip: group3_items.hpp, the same fed with the item records of an element-level batch)
 #pragma once
@@ -297,6 +298,7 @@ struct esp_handle {
     unsigned long long pattern_version = 1, csr_version = 0;
     unsigned long long values_version = 1, csr_val_version = 0;  // nzval changed / row-wise copy of the values
     DevBuf csr_rowptr, csr_perm, csr_col, csr_tmp, csr_val, mul_x, mul_r;
+    int matmul_tier = 0;   // esp_debug_matmul_tier: 0 automatic, 1 fused where it fits, 2 generic only (matops.hip)
     int live_precons = 0;  // esp_precon objects bound to this handle (precon.hip): esp_destroy refuses while any is alive
     // timing
     bool timing = false;

@@ -555,6 +555,111 @@ function ilu0_setup(A::HIPResidentSparseMatrixCSC)
     esp_check(h, ccall((:esp_ilu0_setup, libesparse), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int64}, Int32), h, xdiag, idiag, 0))
     xdiag, idiag
 end
+# ExtendableSparseMatrixCSC(csc) (extendable.jl:61-63): the CSC attached to a fresh handle, its phash computed.  Both forms: the
+# reference's generic methods call T(sparse(A) op sparse(B)) with the concrete T = HIPResidentSparseMatrixCSC{Float64, Ti}.
+function HIPResidentSparseMatrixCSC{Float64, Ti}(csc::SparseMatrixCSC; host_edits = true, kwargs...) where {Ti <: HIPIndex}
+    csc = convert(SparseMatrixCSC{Float64, Ti}, csc)
+    m, n = size(csc)
+    A = HIPResidentSparseMatrixCSC{Float64, Ti}(m, n; host_edits = host_edits, kwargs...)
+    h = getfield(A, :buf).handle
+    esp_check(h, set_csc_call(h, csc))
+    setfield!(A, :host, csc); setfield!(A, :host_state, HOST_CURRENT); setfield!(A, :handed_out, true)
+    set_phash!(A)
+end
+HIPResidentSparseMatrixCSC(csc::SparseMatrixCSC{Float64, Ti}; kwargs...) where {Ti <: HIPIndex} =
+    HIPResidentSparseMatrixCSC{Float64, Ti}(csc; kwargs...)
+function set_phash!(A::HIPResidentSparseMatrixCSC)
+    h = getfield(A, :buf).handle
+    hsh = Ref{UInt64}(0)
+    esp_check(h, ccall((:esp_pattern_hash, libesparse), Int32, (Ptr{Cvoid}, Ptr{UInt64}), h, hsh))
+    setfield!(A, :phash, hsh[])
+    A
+end
+
+# The algebra of abstractextendablesparsematrixcsc.jl:224-280 on the device (esp_matmul / esp_add / esp_diag_scale), bit for bit
+# SparseArrays' spmatmul / map(+-, A, B) / Diagonal scaling.  The operands are flushed (sparse(A) flushes); the result is a new
+# matrix on the operands' device with nothing pending, its phash that of HIPResidentSparseMatrixCSC(csc).
+# A matrix moved to the CPU by to_cpu! takes the reference's generic methods.
+function handle_device(h::Ptr{Cvoid})
+    dev = Ref{Int32}(0)
+    esp_check(h, ccall((:esp_device, libesparse), Int32, (Ptr{Cvoid}, Ptr{Int32}), h, dev))
+    dev[]
+end
+function device_result(A::HIPResidentSparseMatrixCSC{Float64, Ti}, m, n) where {Ti <: HIPIndex}
+    HIPResidentSparseMatrixCSC{Float64, Ti}(m, n; host_edits = getfield(A, :host_edits),
+                                            device = handle_device(getfield(A, :buf).handle))
+end
+scratch_of(A::HIPResidentSparseMatrixCSC, B::SparseMatrixCSC) =
+    HIPResidentSparseMatrixCSC(B; host_edits = false, device = handle_device(getfield(A, :buf).handle))
+function device_matmul(A::HIPResidentSparseMatrixCSC, B::HIPResidentSparseMatrixCSC)
+    size(A, 2) == size(B, 1) || throw(DimensionMismatch("A has $(size(A, 2)) columns, B $(size(B, 1)) rows"))
+    flush!(A); flush!(B)
+    C = touch!(device_result(A, size(A, 1), size(B, 2)), HOST_STALE)
+    z = Ref{Int64}(0)
+    h = getfield(C, :buf).handle
+    esp_check(h, ccall((:esp_matmul, libesparse), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}),
+                       getfield(A, :buf).handle, getfield(B, :buf).handle, h, z))
+    set_phash!(C)
+end
+function device_add(A::HIPResidentSparseMatrixCSC, B::HIPResidentSparseMatrixCSC, op::Int32)
+    size(A) == size(B) || throw(DimensionMismatch("$(size(A)) and $(size(B))"))
+    flush!(A); flush!(B)
+    C = touch!(device_result(A, size(A)...), HOST_STALE)
+    z = Ref{Int64}(0)
+    h = getfield(C, :buf).handle
+    esp_check(h, ccall((:esp_add, libesparse), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Int64}),
+                       getfield(A, :buf).handle, getfield(B, :buf).handle, op, h, z))
+    set_phash!(C)
+end
+function device_diag(A::HIPResidentSparseMatrixCSC, d::Vector{Float64}, side::Int32)
+    length(d) == size(A, side == 0 ? 1 : 2) || throw(DimensionMismatch("Diagonal of size $(length(d))"))
+    flush!(A)
+    C = touch!(device_result(A, size(A)...), HOST_STALE)
+    h = getfield(C, :buf).handle
+    esp_check(h, ccall((:esp_diag_scale, libesparse), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int32, Int32, Ptr{Cvoid}),
+                       getfield(A, :buf).handle, d, side, 0, h))
+    set_phash!(C)
+end
+ondevice(A) = oncpu(A) === nothing
+function Base.:*(A::HIPResidentSparseMatrixCSC, B::HIPResidentSparseMatrixCSC)
+    ondevice(A) && ondevice(B) || return HIPResidentSparseMatrixCSC(sparse(A) * sparse(B))
+    device_matmul(A, B)
+end
+function Base.:+(A::HIPResidentSparseMatrixCSC, B::HIPResidentSparseMatrixCSC)
+    ondevice(A) && ondevice(B) || return HIPResidentSparseMatrixCSC(sparse(A) + sparse(B))
+    device_add(A, B, Int32(0))
+end
+function Base.:-(A::HIPResidentSparseMatrixCSC, B::HIPResidentSparseMatrixCSC)
+    ondevice(A) && ondevice(B) || return HIPResidentSparseMatrixCSC(sparse(A) - sparse(B))
+    device_add(A, B, Int32(1))
+end
+# ext ± csc and csc - ext return a SparseMatrixCSC, as the reference's methods do; the csc goes up to a scratch handle
+function Base.:+(A::HIPResidentSparseMatrixCSC, B::SparseMatrixCSC{Float64, Ti}) where {Ti <: HIPIndex}
+    ondevice(A) || return sparse(A) + B
+    sparse(device_add(A, scratch_of(A, B), Int32(0)))
+end
+function Base.:-(A::HIPResidentSparseMatrixCSC, B::SparseMatrixCSC{Float64, Ti}) where {Ti <: HIPIndex}
+    ondevice(A) || return sparse(A) - B
+    sparse(device_add(A, scratch_of(A, B), Int32(1)))
+end
+function Base.:+(A::SparseMatrixCSC{Float64, Ti}, B::HIPResidentSparseMatrixCSC) where {Ti <: HIPIndex}
+    ondevice(B) || return A + sparse(B)
+    sparse(device_add(scratch_of(B, A), B, Int32(0)))
+end
+function Base.:-(A::SparseMatrixCSC{Float64, Ti}, B::HIPResidentSparseMatrixCSC) where {Ti <: HIPIndex}
+    ondevice(B) || return A - sparse(B)
+    sparse(device_add(scratch_of(B, A), B, Int32(1)))
+end
+# (any real Diagonal: its entries as Float64, the product rounded as Float64 * Float64 like the reference's for Tv = Float64)
+function Base.:*(D::Diagonal{<:Real}, A::HIPResidentSparseMatrixCSC)
+    ondevice(A) || return HIPResidentSparseMatrixCSC(D * sparse(A))
+    device_diag(A, Vector{Float64}(D.diag), Int32(0))
+end
+function Base.:*(A::HIPResidentSparseMatrixCSC, D::Diagonal{<:Real})
+    ondevice(A) || return HIPResidentSparseMatrixCSC(sparse(A) * D)
+    device_diag(A, Vector{Float64}(D.diag), Int32(1))
+end
+
 function reset!(A::HIPResidentSparseMatrixCSC)                                 # extendable.jl:269-272 (phash kept)
     cpu = oncpu(A); cpu === nothing || (reset!(cpu); return A)
     buf = getfield(A, :buf)

@@ -106,6 +106,7 @@ class _Handle:
 
     def __init__(self, m, n, device=0, capacity_hint=0):
         self.lib = L.load()
+        self.device = device
         self.m, self.n = int(m), int(n)
         h = C.c_void_p()
         check(None, self.lib.esp_create(self.m, self.n, device, capacity_hint, C.byref(h)))
@@ -118,7 +119,7 @@ class _Handle:
         """A second handle with the same CSC and pending entries (device-to-device): Base.copy."""
         self.commit()
         c = object.__new__(_Handle)
-        c.lib, c.m, c.n = self.lib, self.m, self.n
+        c.lib, c.m, c.n, c.device = self.lib, self.m, self.n, self.device
         h = C.c_void_p()
         self.ck(self.lib.esp_clone(self.h, C.byref(h)))
         c.h, c._st, c._nst, c._held = h, None, 0, list(self._held)
@@ -665,6 +666,97 @@ class ExtendableSparseMatrix:
     def __matmul__(self, x):  # A*x (genericmtextendablesparsematrixcsc.jl:119-121)
         return self.mul(x)
 
+    # ---- the algebra of abstractextendablesparsematrixcsc.jl:224-280 on the device (esp_matmul / esp_add / esp_diag_scale):
+    # the operands are flushed first (the reference's sparse(A) flushes), the result is a new matrix with nothing pending whose
+    # phash is that of ExtendableSparseMatrixCSC(csc) (evaluated on first use) and whose host copy is stale.
+    def _new_result(self, m, n):
+        R = ExtendableSparseMatrix(m, n, device=self._d.device, host_edits=self.host_edits)
+        R._phash = None  # extendable.jl:61-63
+        return R
+
+    def _operand(self, other):
+        """`other` as a flushed device matrix: an ExtendableSparseMatrix itself, a host SparseMatrixCSC through a scratch handle."""
+        if isinstance(other, ExtendableSparseMatrix):
+            return other.flush()
+        return ExtendableSparseMatrix(other, device=self._d.device)
+
+    def matmul(self, B, tier=0):
+        """A * B (SparseArrays.spmatmul, bit for bit; include/esparse_hip.h esp_matmul).  tier: esp_debug_matmul_tier."""
+        if self.n != B.m:
+            raise ValueError("DimensionMismatch")
+        self.flush()
+        B.flush()
+        R = self._new_result(self.m, B.n)
+        d = R._d
+        if tier:
+            d.ck(d.lib.esp_debug_matmul_tier(d.h, int(tier)))
+        z = C.c_int64()
+        d.ck(d.lib.esp_matmul(self._d.h, B._d.h, d.h, C.byref(z)))
+        return R
+
+    def _addsub(self, other, op, reverse=False):
+        if (other.m, other.n) != (self.m, self.n):
+            raise ValueError("DimensionMismatch")
+        self.flush()
+        B = self._operand(other)
+        a, b = (B, self) if reverse else (self, B)
+        R = self._new_result(self.m, self.n)
+        z = C.c_int64()
+        R._d.ck(R._d.lib.esp_add(a._d.h, b._d.h, op, R._d.h, C.byref(z)))
+        if isinstance(other, ExtendableSparseMatrix):
+            return R
+        return R.cscmatrix  # ext ± csc, csc - ext: a SparseMatrixCSC, as the reference's methods return
+
+    def diag_scale(self, d, side="left", inplace=False):
+        """Diagonal(d) * A (side "left") or A * Diagonal(d) (side "right"): the pattern of A, computed zeros kept.
+        d: a NumPy vector or a CUDA float64 torch tensor.  inplace=True scales this matrix's values (lmul! / rmul!)."""
+        s = {"left": 0, "right": 1}[side]
+        nd = self.m if s == 0 else self.n
+        self.flush()
+        R = self if inplace else self._new_result(self.m, self.n)
+        if hasattr(d, "is_cuda") and d.is_cuda:
+            import torch
+            if not (d.dtype == torch.float64 and d.numel() == nd and d.is_contiguous()):
+                raise ValueError("DimensionMismatch")
+            torch.cuda.current_stream(d.device).synchronize()   # the library runs on its own stream
+            R._d.ck(R._d.lib.esp_diag_scale(self._d.h, C.c_void_p(d.data_ptr()), s, 1, R._d.h))
+        else:
+            dd = np.ascontiguousarray(d, np.float64)
+            if dd.shape != (nd,):
+                raise ValueError("DimensionMismatch")
+            R._d.ck(R._d.lib.esp_diag_scale(self._d.h, _vp(dd), s, 0, R._d.h))
+        if inplace:
+            self._touch()  # (values changed, the pattern stays: the host copy's nzval is stale)
+        return R
+
+    def __mul__(self, other):
+        """A * B with another ExtendableSparseMatrix, or A * Diagonal(d).  (A @ x stays mul!.)"""
+        if isinstance(other, ExtendableSparseMatrix):
+            return self.matmul(other)
+        if isinstance(other, Diagonal):
+            return self.diag_scale(other.diag, side="right")
+        return NotImplemented
+
+    def __add__(self, other):
+        if isinstance(other, (ExtendableSparseMatrix, SparseMatrixCSC)):
+            return self._addsub(other, ESP_OP_ADD)
+        return NotImplemented
+
+    def __sub__(self, other):
+        if isinstance(other, (ExtendableSparseMatrix, SparseMatrixCSC)):
+            return self._addsub(other, ESP_OP_SUB)
+        return NotImplemented
+
+    def __radd__(self, other):  # csc + ext
+        if isinstance(other, SparseMatrixCSC):
+            return self._addsub(other, ESP_OP_ADD, reverse=True)
+        return NotImplemented
+
+    def __rsub__(self, other):  # csc - ext
+        if isinstance(other, SparseMatrixCSC):
+            return self._addsub(other, ESP_OP_SUB, reverse=True)
+        return NotImplemented
+
     def reset(self):  # reset!: extendable.jl:269-272 (phash kept)
         self._handed_out = False
         self._host_state = self.HOST_STALE
@@ -791,6 +883,19 @@ class ExtendableSparseMatrix:
 
     def synchronize(self):
         self._d.ck(self._d.lib.esp_synchronize(self._d.h))
+
+
+class Diagonal:
+    """LinearAlgebra.Diagonal(d) as the left or right factor of an ExtendableSparseMatrix: Diagonal(d) * A scales row i by
+    d[i], A * Diagonal(d) column j by d[j] (esp_diag_scale).  d: a NumPy vector or a CUDA float64 torch tensor."""
+
+    def __init__(self, d):
+        self.diag = d if (hasattr(d, "is_cuda") and d.is_cuda) else np.ascontiguousarray(d, np.float64)
+
+    def __mul__(self, A):
+        if isinstance(A, ExtendableSparseMatrix):
+            return A.diag_scale(self.diag, side="left")
+        return NotImplemented
 
 
 class GenericExtendableSparseMatrixCSC:

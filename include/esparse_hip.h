@@ -323,6 +323,34 @@ int32_t esp_precon_destroy(esp_precon *p);
 int32_t esp_simple(esp_handle *h, esp_precon *p, const double *b, double *u, int32_t on_device, int64_t maxiter,
                    double abstol, double reltol, double *history, int64_t *iterations);
 
+/* ---- the algebra of assembled matrices on the device CSC (abstractextendablesparsematrixcsc.jl:224-280) -----------
+ * The reference evaluates these through SparseArrays; the device reproduces its documented rules bit for bit:
+ *   A*B   Gustavson (spmatmul): for every column i of B, every stored B[j,i] in stored order, every stored A[k,j] in stored
+ *         order, p = A[k,j]*B[j,i]; the first product reaching row k is assigned, later ones added in arrival order; every
+ *         reached row is stored (zeros kept), rows sorted; no FMA, no reordered sums.
+ *   A+B, A-B  map(f, A, B): both stored f(a,b), one stored f(a,0.0) / f(0.0,b); a result == 0 is not stored.
+ *   D*A, A*D  the pattern of A exactly; nzval[p] = d[row]*nzval[p] / d[col]*nzval[p].
+ * The operands must hold no pending entries (the reference's sparse(A) flushes first: flush them).  The result handle c
+ * is left as a flush that changed the pattern leaves it (a preconditioner bound to c needs update!); every call returns
+ * synchronised.  Operands and c on one device; a column window or column-shard use on any of them -> ESP_ERR_UNSUPPORTED;
+ * m or n above 2^32 -> ESP_ERR_UNSUPPORTED.  A failed allocation returns ESP_ERR_NOMEM and leaves c as it was. */
+/* C := A*B.  c: an empty handle of size (a.m, b.n) on the same device, no pending entries; its CSC is replaced.
+ * a == b is allowed; c must be neither.  Pending entries on a or b -> ESP_ERR_STATE (flush first);
+ * a.n != b.m -> ESP_ERR_INVALID; a column window / shard use on any operand -> ESP_ERR_UNSUPPORTED.
+ * Columns of at most 2048 products run in the fused tier (sorted and folded in LDS), longer ones through an ESP_COO flush of
+ * a scratch handle (the generic tier); *nnz_out = nnz(C). */
+int32_t esp_matmul(esp_handle *a, esp_handle *b, esp_handle *c, int64_t *nnz_out);
+/* C := A + B (op ESP_OP_ADD) or A - B (ESP_OP_SUB); zero results are not stored.  Same rules; sizes equal. */
+int32_t esp_add(esp_handle *a, esp_handle *b, int32_t op, esp_handle *c, int64_t *nnz_out);
+/* C := Diagonal(d) * A (side 0) or A * Diagonal(d) (side 1); the pattern of A.  c may equal a (in place: values only).
+ * d: a.m (side 0) or a.n (side 1) doubles; on_device != 0: a device pointer. */
+int32_t esp_diag_scale(esp_handle *a, const double *d, int32_t side, int32_t on_device, esp_handle *c);
+/* the device the handle lives on (a result handle of the calls above goes on its operands' device) */
+int32_t esp_device(const esp_handle *h, int32_t *device);
+/* test hook: 0 automatic, 1 every column through the fused tier where it fits, 2 every column through the generic tier.
+ * Set on the RESULT handle c of esp_matmul (automatic takes the fused tier wherever it fits: 1 behaves as 0). */
+int32_t esp_debug_matmul_tier(esp_handle *c, int32_t tier);
+
 /* ---- column-range shards (multi-GPU, one process per GPU) ------------------------
  * owner(col) = floor((col-1)*nshards/n).  esp_shard_counts: pending entries per owner.
  * esp_shard_export: stable partition of the pending entries by owner into the caller's
