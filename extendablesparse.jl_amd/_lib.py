@@ -105,6 +105,12 @@ SIGNATURES = {
     "esp_diag_scale": (i32, [vp, vp, i32, i32, vp]),
     "esp_debug_matmul_tier": (i32, [vp, i32]),
     "esp_device": (i32, [vp, P(i32)]),
+    "esp_transpose": (i32, [vp, vp, P(i64)]),
+    "esp_debug_transpose_path": (i32, [vp, i32]),
+    "esp_mul_transpose": (i32, [vp, vp, vp, i32]),
+    "esp_issymmetric": (i32, [vp, P(i32)]),
+    "esp_opnorm": (i32, [vp, f64, P(f64)]),
+    "esp_norm": (i32, [vp, f64, P(f64)]),
     "esp_shard_counts": (i32, [vp, i32, vp]),
     "esp_shard_export": (i32, [vp, i32, vp, vp, vp]),
     "esp_shard_exchange_begin": (i32, [vp, i32, i32, i64, i64, P(vp), P(vp), vp]),

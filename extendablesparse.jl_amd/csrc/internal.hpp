@@ -9,6 +9,7 @@
 //   consumers.hip  what reads or edits the assembled CSC: getindex, dropzeros, pattern hash, mul!, Dirichlet, Jacobi / ILU0
 //   precon.hip     the point preconditioners' update! / ldiv! (esp_precon_*) and simple! (esp_simple) on the device CSC
 //   matops.hip     the algebra of assembled matrices on the device: A*B (esp_matmul), A+B / A-B (esp_add), Diagonal scaling
+//   linalg.hip     transpose (esp_transpose), transpose(A)*x (esp_mul_transpose), issymmetric, opnorm, norm on the device CSC
 //   local_*.hip    the instantiations of the bucket kernel (local.hpp; local_h.hip: group3.hpp, the group tier with three workgroups per CU;
 //                  local_j.hip: group3_items.hpp, the same fed with the item records of an element-level batch)
 #pragma once
@@ -299,6 +300,7 @@ struct esp_handle {
     unsigned long long values_version = 1, csr_val_version = 0;  // nzval changed / row-wise copy of the values
     DevBuf csr_rowptr, csr_perm, csr_col, csr_tmp, csr_val, mul_x, mul_r;
     int matmul_tier = 0;   // esp_debug_matmul_tier: 0 automatic, 1 fused where it fits, 2 generic only (matops.hip)
+    int transpose_path = 0;  // esp_debug_transpose_path: 0 automatic, 1 the ESP_COO flush, 2 the counting sort (linalg.hip)
     int live_precons = 0;  // esp_precon objects bound to this handle (precon.hip): esp_destroy refuses while any is alive
     // timing
     bool timing = false;
@@ -529,6 +531,11 @@ int32_t dirichlet_call(esp_handle *h, uint8_t *marker, int32_t on_device, bool m
 int32_t diag_setup(esp_handle *h, double *inv, int64_t *idiag, int32_t on_device, const char *what);
 int32_t shard_prepare(esp_handle *h, int P, espradix::Pass *out);
 int32_t shard_offsets(esp_handle *h, int P, int64_t *offsets /* P+1 */);
+// matops.hip, shared with linalg.hip: the operand rules of the algebra calls (no pending entries, no column window or shard,
+// dimensions below 2^32; synchronised), a result CSC taken over by c (a pattern change), a device i64 read back
+int32_t check_operand(esp_handle *h, const char *what);
+void install(esp_handle *c, DevBuf &cp, DevBuf &rv, DevBuf &nz, i64 nnz);
+int32_t read_i64(esp_handle *h, const i64 *d_src, i64 *out);
 #pragma GCC visibility pop
 
 struct Span {

@@ -398,6 +398,9 @@ struct Temps {
     }
 };
 
+}  // namespace
+
+// (check_operand, install and read_i64 are shared with linalg.hip: internal.hpp)
 int32_t check_operand(esp_handle *h, const char *what) {
     if (h->count != 0) FAIL(h, ESP_ERR_STATE, "%s: pending entries (flush first, as sparse(A) does)", what);
     if (windowed(h) || h->shard_user) FAIL(h, ESP_ERR_UNSUPPORTED, "%s: a column window / column shard as an operand", what);
@@ -408,9 +411,11 @@ int32_t check_operand(esp_handle *h, const char *what) {
     HIPCK(h, hipStreamSynchronize(h->stream));
     return ESP_OK;
 }
+namespace {
 Csc64 csc_of(const esp_handle *h) {
     return Csc64{(const i64 *)h->colptr.p, (const i64 *)h->rowval.p, (const double *)h->nzval.p, h->n, h->nnz};
 }
+}  // namespace
 // c takes the new CSC (a pattern change, as a flush that rebuilds leaves it)
 void install(esp_handle *c, DevBuf &cp, DevBuf &rv, DevBuf &nz, i64 nnz) {
     std::swap(c->colptr, cp);
@@ -429,8 +434,6 @@ int32_t read_i64(esp_handle *h, const i64 *d_src, i64 *out) {
     *out = (i64)h->pin_scalar[0];
     return ESP_OK;
 }
-
-}  // namespace
 
 extern "C" int32_t esp_device(const esp_handle *h, int32_t *device) {
     if (!h || !device) return ESP_ERR_INVALID;

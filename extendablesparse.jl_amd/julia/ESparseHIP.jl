@@ -660,6 +660,72 @@ function Base.:*(A::HIPResidentSparseMatrixCSC, D::Diagonal{<:Real})
     device_diag(A, Vector{Float64}(D.diag), Int32(1))
 end
 
+# transpose, transpose(A)*x, issymmetric, norm and opnorm on the device (esp_transpose / esp_mul_transpose / esp_issymmetric /
+# esp_norm / esp_opnorm), as SparseArrays computes them (abstractextendablesparsematrixcsc.jl:188-217 forwards there).
+# transpose(A) itself stays Julia's lazy wrapper: copy of it (and permutedims) builds the transpose on the device.  A matrix moved
+# to the CPU by to_cpu!, and cond, keep the reference's methods.
+const TransposeOrAdjointHIP = Union{Transpose{Float64, <:HIPResidentSparseMatrixCSC}, Adjoint{Float64, <:HIPResidentSparseMatrixCSC}}
+function device_transpose(A::HIPResidentSparseMatrixCSC)
+    flush!(A)
+    C = touch!(device_result(A, size(A, 2), size(A, 1)), HOST_STALE)
+    z = Ref{Int64}(0)
+    h = getfield(C, :buf).handle
+    esp_check(h, ccall((:esp_transpose, libesparse), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int64}), getfield(A, :buf).handle, h, z))
+    set_phash!(C)
+end
+function Base.copy(At::Transpose{Float64, <:HIPResidentSparseMatrixCSC})
+    A = parent(At)
+    ondevice(A) || return HIPResidentSparseMatrixCSC(copy(transpose(sparse(A))))
+    device_transpose(A)
+end
+function Base.copy(At::Adjoint{Float64, <:HIPResidentSparseMatrixCSC})   # (real values: the transpose)
+    A = parent(At)
+    ondevice(A) || return HIPResidentSparseMatrixCSC(copy(adjoint(sparse(A))))
+    device_transpose(A)
+end
+Base.permutedims(A::HIPResidentSparseMatrixCSC) = copy(transpose(A))
+HIPResidentSparseMatrixCSC(At::TransposeOrAdjointHIP) = copy(At)
+function LinearAlgebra.mul!(r::Vector{Float64}, At::TransposeOrAdjointHIP, x::Vector{Float64})
+    A = parent(At)
+    cpu = oncpu(A); cpu === nothing || return mul!(r, transpose(cpu), x)
+    (length(x) == size(A, 1) && length(r) == size(A, 2)) || throw(DimensionMismatch("transpose(A) is $(size(A, 2)) x $(size(A, 1))"))
+    flush!(A)
+    h = getfield(A, :buf).handle
+    esp_check(h, ccall((:esp_mul_transpose, libesparse), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int32), h, x, r, 0))
+    r
+end
+Base.:*(At::TransposeOrAdjointHIP, x::Vector{Float64}) = mul!(Vector{Float64}(undef, size(parent(At), 2)), At, x)
+function LinearAlgebra.issymmetric(A::HIPResidentSparseMatrixCSC)
+    cpu = oncpu(A); cpu === nothing || return issymmetric(cpu)
+    flush!(A)
+    h = getfield(A, :buf).handle
+    res = Ref{Int32}(0)
+    esp_check(h, ccall((:esp_issymmetric, libesparse), Int32, (Ptr{Cvoid}, Ptr{Int32}), h, res))
+    res[] != 0
+end
+LinearAlgebra.ishermitian(A::HIPResidentSparseMatrixCSC) = issymmetric(A)
+function LinearAlgebra.norm(A::HIPResidentSparseMatrixCSC, p::Real = 2)
+    cpu = oncpu(A); cpu === nothing || return norm(cpu, p)
+    isnan(p) && throw(ArgumentError("norm: p is NaN"))
+    flush!(A)
+    h = getfield(A, :buf).handle
+    res = Ref{Float64}(0.0)
+    esp_check(h, ccall((:esp_norm, libesparse), Int32, (Ptr{Cvoid}, Float64, Ptr{Float64}), h, Float64(p), res))
+    res[]
+end
+function LinearAlgebra.opnorm(A::HIPResidentSparseMatrixCSC, p::Real = 2)
+    cpu = oncpu(A); cpu === nothing || return opnorm(cpu, p)
+    isnan(p) && throw(ArgumentError("invalid operator norm p=$p. Valid: 1, 2, Inf"))
+    flush!(A)
+    h = getfield(A, :buf).handle
+    res = Ref{Float64}(0.0)
+    rc = ccall((:esp_opnorm, libesparse), Int32, (Ptr{Cvoid}, Float64, Ptr{Float64}), h, Float64(p), res)
+    rc == Int32(-5) && throw(ArgumentError("2-norm not yet implemented for sparse matrices. Try opnorm(Array(A)) or opnorm(A, p) where p=1 or Inf."))
+    rc == Int32(-1) && throw(ArgumentError("invalid operator norm p=$p. Valid: 1, 2, Inf"))
+    esp_check(h, rc)
+    res[]
+end
+
 function reset!(A::HIPResidentSparseMatrixCSC)                                 # extendable.jl:269-272 (phash kept)
     cpu = oncpu(A); cpu === nothing || (reset!(cpu); return A)
     buf = getfield(A, :buf)

@@ -18,8 +18,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from ._lib import (ESP_COO, ESP_FLUSH_PLUS, ESP_FLUSH_ROUTED, ESP_OP_ADD, ESP_OP_SUB, ESP_RAWUPDATE, ESP_SET,
-                   ESP_UPDATE, BoundsError, check)
+from ._lib import (ESP_COO, ESP_ERR_INVALID, ESP_ERR_UNSUPPORTED, ESP_FLUSH_PLUS, ESP_FLUSH_ROUTED, ESP_OP_ADD, ESP_OP_SUB,
+                   ESP_RAWUPDATE, ESP_SET, ESP_UPDATE, BoundsError, check)
 
 _OPS = {"+": ESP_OP_ADD, "-": ESP_OP_SUB, ESP_OP_ADD: ESP_OP_ADD, ESP_OP_SUB: ESP_OP_SUB}
 try:  # operator.add / operator.sub are accepted like Julia's `+` / `-`
@@ -756,6 +756,76 @@ class ExtendableSparseMatrix:
         if isinstance(other, SparseMatrixCSC):
             return self._addsub(other, ESP_OP_SUB, reverse=True)
         return NotImplemented
+
+    # ---- transpose, transpose(A)*x, issymmetric, opnorm, norm on the device (esp_transpose / esp_mul_transpose / esp_issymmetric /
+    # esp_opnorm / esp_norm; abstractextendablesparsematrixcsc.jl:188-217): the matrix is flushed first, as sparse(A) flushes.
+    def transpose(self, path=0):
+        """copy(transpose(A)) (SparseArrays.halfperm!, bit for bit): a new n x m device matrix holding every stored entry,
+        explicit zeros included.  path: esp_debug_transpose_path (0 automatic, 1 generic, 2 counting sort)."""
+        self.flush()
+        R = self._new_result(self.n, self.m)
+        d = R._d
+        if path:
+            d.ck(d.lib.esp_debug_transpose_path(d.h, int(path)))
+        z = C.c_int64()
+        d.ck(d.lib.esp_transpose(self._d.h, d.h, C.byref(z)))
+        return R
+
+    @property
+    def T(self):
+        return self.transpose()
+
+    def adjoint(self):  # copy(adjoint(A)) of a real matrix
+        return self.transpose()
+
+    def mul_transpose(self, x, out=None):
+        """mul!(r, transpose(A), x) (SparseArrays' _At_or_Ac_mul_B!, bit for bit): r[j] is column j's products summed in stored
+        order.  x: m entries, r: n entries; NumPy arrays (copied through the device) or CUDA torch tensors (used in place)."""
+        self.flush()
+        d = self._d
+        if hasattr(x, "is_cuda") and x.is_cuda:
+            import torch
+            assert x.dtype == torch.float64 and x.numel() == self.m and x.is_contiguous()
+            r = out if out is not None else torch.empty(self.n, dtype=torch.float64, device=x.device)
+            assert r.is_cuda and r.dtype == torch.float64 and r.numel() == self.n and r.is_contiguous()
+            torch.cuda.current_stream(x.device).synchronize()   # the library runs on its own stream
+            d.ck(d.lib.esp_mul_transpose(d.h, C.c_void_p(x.data_ptr()), C.c_void_p(r.data_ptr()), 1))
+            return r
+        x = np.ascontiguousarray(x, np.float64)
+        if x.shape != (self.m,):
+            raise ValueError("DimensionMismatch")
+        r = out if out is not None else np.empty(self.n, np.float64)
+        d.ck(d.lib.esp_mul_transpose(d.h, _vp(x), _vp(r), 0))
+        return r
+
+    def issymmetric(self):
+        """issymmetric(A) = issymmetric(Matrix(A)): stored zeros count as absent, a stored NaN gives False."""
+        self.flush()
+        res = C.c_int32()
+        self._d.ck(self._d.lib.esp_issymmetric(self._d.h, C.byref(res)))
+        return bool(res.value)
+
+    def ishermitian(self):  # real matrix: issymmetric
+        return self.issymmetric()
+
+    def _norm_call(self, fn, p):
+        self.flush()
+        d = self._d
+        res = C.c_double()
+        rc = fn(d.h, float(p), C.byref(res))
+        if rc in (ESP_ERR_INVALID, ESP_ERR_UNSUPPORTED):  # the reference's ArgumentError
+            msg = d.lib.esp_last_error(d.h)
+            raise ValueError(msg.decode() if msg else "invalid p=%r" % (p,))
+        d.ck(rc)
+        return res.value
+
+    def opnorm(self, p=2):
+        """opnorm(A, p) of SparseArrays (p = 1, 2, Inf; 2 only for a single row or column, as SparseArrays)."""
+        return self._norm_call(self._d.lib.esp_opnorm, p)
+
+    def norm(self, p=2):
+        """norm(A, p) = norm(nonzeros(A), p) over the stored values."""
+        return self._norm_call(self._d.lib.esp_norm, p)
 
     def reset(self):  # reset!: extendable.jl:269-272 (phash kept)
         self._handed_out = False

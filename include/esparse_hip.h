@@ -351,6 +351,42 @@ int32_t esp_device(const esp_handle *h, int32_t *device);
  * Set on the RESULT handle c of esp_matmul (automatic takes the fused tier wherever it fits: 1 behaves as 0). */
 int32_t esp_debug_matmul_tier(esp_handle *c, int32_t tier);
 
+/* ---- transpose, transpose(A)*x, issymmetric, opnorm, norm on the device CSC (abstractextendablesparsematrixcsc.jl:188-217) ----
+ * The reference evaluates these through SparseArrays; the device reproduces its documented rules:
+ *   copy(transpose(A))  halfperm!: an n x m CSC of every stored entry, explicit zeros included, rows ascending in every column;
+ *                       bitwise (-0.0 and NaN payloads kept).
+ *   transpose(A)*x      r[j] = 0.0; tmp = 0.0; tmp += nzval[k]*x[rowval[k]] over column j in stored order; r[j] += tmp; bitwise.
+ *   issymmetric(A)      issymmetric(Matrix(A)): false for a rectangular matrix; a stored zero of either sign counts as absent;
+ *                       every other stored v at (i,j), the diagonal included, needs v == A[j,i] (0.0 where not stored), so a
+ *                       stored NaN gives false.  Exact.
+ *   opnorm(A, p)        opnorm(::AbstractSparseMatrixCSC, p) branch by branch (m == 0 or n == 0: 0.0; m == 1 and n == 1: the
+ *                       norms of the stored values; otherwise the column-sum (p = 1) and row-sum (p = Inf) loops, max
+ *                       propagating NaN).  Bitwise, except the 1-row / 1-column norm(nzval, 1 or 2) cases (BLAS asum / nrm2 in
+ *                       the reference): relative error <= 1e-13, identical run to run.
+ *   norm(A, p)          norm(nonzeros(A), p) over the stored values (none: 0.0).  p = Inf, -Inf, 0: bitwise; p = 1, 2 and every
+ *                       other p: relative error <= 1e-13, identical run to run; norm(A, 2) is scaled by the largest |v| and neither
+ *                       overflows nor underflows where nrm2 does not.  NaN among the values gives NaN (its payload is not pinned).
+ * The operand must hold no pending entries (ESP_ERR_STATE: flush first, as sparse(A) does); a column window or column-shard use
+ * -> ESP_ERR_UNSUPPORTED; m or n above 2^32 -> ESP_ERR_UNSUPPORTED.  Every call returns synchronised.
+ * Deviation: p NaN -> ESP_ERR_INVALID (SparseArrays would return 0.0 for an empty matrix and throw otherwise). */
+/* C := copy(transpose(A)).  c: an empty handle of size (a.n, a.m) on a's device, c != a (else ESP_ERR_INVALID), no pending entries;
+ * its CSC is replaced (a pattern change: a preconditioner bound to c needs update!).  A failed call (ESP_ERR_NOMEM included)
+ * leaves c as it was.  Nothing else the call allocates outlives it.  *nnz_out = nnz(A). */
+int32_t esp_transpose(esp_handle *a, esp_handle *c, int64_t *nnz_out);
+/* test hook on the RESULT handle c of esp_transpose: 0 automatic (= 2), 1 the generic path (the entries as ESP_COO records with the
+ * keys swapped, flushed into an empty CSC of a scratch handle; an esp_debug_fail_next_bucket_stage armed on c is met by that flush),
+ * 2 the counting sort (row counts, a scatter, every column sorted by row; a row of A longer than 4096 entries takes path 1) */
+int32_t esp_debug_transpose_path(esp_handle *c, int32_t path);
+/* r := transpose(A)*x (= adjoint(A)*x for real A); x: m doubles, r: n doubles; on_device != 0: device pointers (as esp_mul) */
+int32_t esp_mul_transpose(esp_handle *h, const double *x, double *r, int32_t on_device);
+/* *result = 1 if issymmetric(A) (= ishermitian(A) for real A), else 0 */
+int32_t esp_issymmetric(esp_handle *h, int32_t *result);
+/* *result = opnorm(A, p); p = 2 with m, n > 1 -> ESP_ERR_UNSUPPORTED ("2-norm not yet implemented"); p outside 1, 2, Inf where the
+ * branch needs one of them -> ESP_ERR_INVALID.  p = Inf uses esp_mul's row-wise index (built on first use after a pattern change). */
+int32_t esp_opnorm(esp_handle *h, double p, double *result);
+/* *result = norm(A, p) */
+int32_t esp_norm(esp_handle *h, double p, double *result);
+
 /* ---- column-range shards (multi-GPU, one process per GPU) ------------------------
  * owner(col) = floor((col-1)*nshards/n).  esp_shard_counts: pending entries per owner.
  * esp_shard_export: stable partition of the pending entries by owner into the caller's
