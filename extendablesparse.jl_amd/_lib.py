@@ -120,6 +120,7 @@ SIGNATURES = {
     "esp_shard_plan": (i32, [vp, i32, i32, i64]),
     "esp_debug_last_shard_source": (i32, [vp, P(i32)]),
     "esp_debug_last_local_small": (i32, [vp, P(i32)]),
+    "esp_debug_last_bucket_pairs": (i32, [vp, P(i32)]),
     "esp_debug_last_lazy_items": (i32, [vp, P(i32)]),
     "esp_debug_last_sum_join": (i32, [vp, P(i32)]),
     "esp_debug_last_sum_ms": (i32, [vp, P(C.c_double), P(C.c_double)]),

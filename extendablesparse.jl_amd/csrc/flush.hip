@@ -2,6 +2,7 @@
 #include "internal.hpp"
 
 bool esplocal::launch(const Variant &v, unsigned grid, hipStream_t stream, const Args &a) {
+    if (v.pair) return launch_pair(v, grid, stream, a);
     if (v.g3) return launch_group3(v, grid, stream, a);
     if (v.grp) return v.shortg ? launch_group_short(v, grid, stream, a) : launch_group(v, grid, stream, a);
     if (v.pieces) return v.small_variant ? launch_pieces_small(v, grid, stream, a) : v.fresh ? launch_pieces_fresh(v, grid, stream, a) : launch_pieces_stored(v, grid, stream, a);
@@ -206,6 +207,15 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
                         h->force_path != ESP_PATH_NO_SMALL_VARIANT && !stop_env;
     }
     h->last_local_small = small_variant ? 1 : 0;
+    // The small variant's PAIR form (pair_k, local_w.hip): one workgroup takes two neighbouring buckets of the table -- a fresh
+    // matrix whose segments write colptr themselves, 4-byte keys of one kind, one bucket per segment of the table (a FINE
+    // partition's segments are several buckets already), at most 12 pending entries per column.  A pair with a longer column run
+    // or rows spread over 2^19 or more makes the flush run again with local_k, which then serves the handle.  force_path 42: never.
+    const bool pair_ok = small_variant && direct && Z0 == 0 && st.npieces == 0 && st.key_bytes == 4 && st.fb == 0 && !st.lazy &&
+                         !windowed(h) && h->L.rb < 32 && h->seen_maxrun == 0 &&
+                         (double)h->count <= (double)esplocal::PAIR_RUN * (double)std::max<i64>(col_end - col_begin, 1) &&
+                         h->force_path != ESP_PATH_NO_BUCKET_PAIRS && h->force_path != ESP_PATH_GENERIC_FOLD;
+    bool used_pair = false;
     std::function<int32_t(bool)> launch_all;
     bool used_g3 = false;
     bool want_wide = h->g3_wide && h->force_path != ESP_PATH_NO_WIDE_GROUP3;
@@ -267,6 +277,26 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
         const i64 max_grid = h->force_path == ESP_PATH_MANY_LAUNCHES ? 64 : esplocal::MAX_GRID;  // 4: test hook, many launches
         launch_all = [&, max_grid](bool allow_g3) -> int32_t {
         used_g3 = false;
+        used_pair = false;
+        if (pair_ok && !h->pair_off) {
+            // (S / 2 segments, rounded up; their granules end where the grand total is read back: status[S - 1])
+            const int Sp = (S + 1) / 2;
+            esplocal::Args ap = a;
+            ap.S = Sp;
+            ap.pair_buckets = S;
+            ap.status = status + (S - Sp);
+            const int keys = st.kind == ESP_UPDATE ? 2 : 1;
+            esplocal::Variant var{true, false, false, true, keys};
+            var.pair = true;
+            h->last_fold_update = keys == 2 ? 1 : 0;
+            for (i64 first = 0; first < Sp; first += max_grid) {
+                ap.first = first;
+                if (!esplocal::launch(var, (unsigned)std::min<i64>(max_grid, Sp - first), h->stream, ap))
+                    FAIL(h, ESP_ERR_STATE, "esp_flush: internal error (no pair kernel for this flush)");
+            }
+            used_pair = true;
+            return ESP_OK;
+        }
         for (i64 first = 0; first < S; first += max_grid) {
             const unsigned grid = (unsigned)std::min<i64>(max_grid, S - first);
             a.first = first;
@@ -300,7 +330,7 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
             // (packed keys of ONE known adding kind whose bits below the prefix fit 32 -- a shuffled stream of triplets after the
             // flush's own passes: the same kernel, the keys narrowed as they are loaded; not its wide form)
             const bool k64_ok = keys == 0 && st.key_bytes == 8 && st.npieces == 0 && st.rem_bits <= 32 && !want_wide &&
-                                (a.kind_all == ESP_UPDATE || a.kind_all == ESP_RAWUPDATE) && h->force_path == ESP_PATH_AUTO;
+                                (a.kind_all == ESP_UPDATE || a.kind_all == ESP_RAWUPDATE) && paths_auto(h);
             if (!var.g3 && k64_ok && allow_g3 && grp && Z0 == 0 && a.cl_bits >= 0 && a.cl_bits <= esplocal::G3_CL_BITS && a.cl_bits + a.rb <= 32 &&
                 a.rb <= 30 && longest <= 128.0 && !h->g3_off && !a.no_group && !a.stop_after) {
                 var.g3 = var.g3k64 = true;
@@ -392,6 +422,19 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
         sp.add(1);
     }
     CK(read_back());
+    if (used_pair && ((u32)(h->pin_scalar[1] >> 32) & esplocal::PAIR_REFUSED)) {
+        // a pair the kernel does not take: once more with local_k (it writes every output a fresh-matrix flush has), and it serves
+        // this handle from now on
+        h->pair_off = true;
+        CK(reset_launch_state());
+        {
+            Span sp(h, ESP_ST_LOCAL);
+            CK(launch_all(true));
+            sp.add(1);
+        }
+        CK(read_back());
+    }
+    h->last_pair = used_pair ? 1 : 0;
     h->last_lazy_items = 0;
     h->last_sum_join = 0;
     if (st.lazy) {
@@ -741,7 +784,7 @@ int32_t flush_rebuild(esp_handle *h, const Sorted &st, int mode, i64 *Znew, bool
     *served = false;
     const i64 Z0 = h->nnz, T = st.total;
     if (mode != ESP_FLUSH_ROUTED || Z0 == 0 || T <= 0 || st.npieces != 0 || !st.seg_start || st.key_bytes != 8 || st.has_base) return ESP_OK;
-    if (windowed(h) || h->shard_user || h->win_base != 0 || h->force_path != ESP_PATH_AUTO) return ESP_OK;
+    if (windowed(h) || h->shard_user || h->win_base != 0 || !paths_auto(h)) return ESP_OK;
     const int clb = st.rem_bits - h->L.rb;
     if (clb < 0 || clb > esplocal::CL_MAX_BITS || st.S < 2 || ((i64)st.S << clb) < h->n) return ESP_OK;
     if (Z0 + T >= 0xFFFFFFF0ll) return ESP_OK;
@@ -833,6 +876,7 @@ extern "C" int32_t esp_flush(esp_handle *h, int32_t mode, int64_t *new_nnz, int3
     }
     i64 Zn = 0;
     h->last_rebuild = 0;
+    h->last_pair = 0;
     bool use_local = h->force_path != ESP_PATH_GENERAL;
     if (h->ones_pending && windowed(h)) CK(fix_tail(h));  // (cannot happen: a window is declared through fix_tail)
     if (h->pre.valid) {  // the producer's partition serves this flush if nothing changed since (appends BEHIND it may have)

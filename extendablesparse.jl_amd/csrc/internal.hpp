@@ -11,7 +11,8 @@
 //   matops.hip     the algebra of assembled matrices on the device: A*B (esp_matmul), A+B / A-B (esp_add), Diagonal scaling
 //   linalg.hip     transpose (esp_transpose), transpose(A)*x (esp_mul_transpose), issymmetric, opnorm, norm on the device CSC
 //   local_*.hip    the instantiations of the bucket kernel (local.hpp; local_h.hip: group3.hpp, the group tier with three workgroups per CU;
-//                  local_j.hip: group3_items.hpp, the same fed with the item records of an element-level batch)
+//                  local_j.hip: group3_items.hpp, the same fed with the item records of an element-level batch;
+//                  local_w.hip: pair_k, the small variant's form with two producer buckets per workgroup)
 #pragma once
 #include <stdio.h>
 #include <stdlib.h>
@@ -65,6 +66,8 @@ struct esp_handle {
     int chunk_pb = 0;
     int runs_skip = 0, runs_penalty = 0;  // back-off after a stream turned out not to be pre-sorted
     bool g3_off = false;                  // a segment of this handle's matrix did not fit the three-workgroup group kernel: not tried again
+    bool pair_off = false;                // ... a pair of buckets did not fit the small variant's pair form (pair_k): not tried again
+    int last_pair = 0;                    // the last flush's bucket kernel was pair_k (esp_debug_last_bucket_pairs)
     bool hits_off = false;                // the re-assembly form of the group kernel met a batch that was no re-assembly of the stored pattern: not tried again (until reset!)
     bool g3_wide = false;                 // ... for its rows alone (spread over more than 2^18): the kernel's wide form serves this handle
     bool debug_fail_bucket = false;       // esp_debug_fail_next_bucket_stage (test hook, one shot)
@@ -594,6 +597,8 @@ static inline unsigned grid_for(i64 n, int threads) { return (unsigned)std::max<
 
 
 // ---- small helpers
+// no force_path, or one that pins the bucket kernel's form alone (42: one bucket per workgroup): every other choice automatic
+static inline bool paths_auto(const esp_handle *h) { return h->force_path == ESP_PATH_AUTO || h->force_path == ESP_PATH_NO_BUCKET_PAIRS; }
 static inline bool windowed(const esp_handle *h) { return h->win_excl && (h->wc0 > 0 || h->wc1 < h->n); }
 
 // first entry and number of entries of the per-column arrays (colptr, colend: n+1 entries) a flush touches

@@ -80,6 +80,7 @@ struct Args {
                       // PIECES with a 4-byte-key piece (a shard's own range, KEYS 4 / 5): the same for THAT piece, whose fine table is
     const i64 *own_fine;  // ... this one: 2^fb entries per segment (+ 1), absolute positions like the piece's row of pstart
     double *hits_out; // group3_k's re-assembly form (HITS): the new values of the stored positions (a second nzval array)
+    i64 pair_buckets; // pair_k (local_w.hip): buckets of the segment table; segment s = its buckets [2 s, min(2 s + 2, pair_buckets))
 };
 constexpr int MAX_PIECES = 64;
 
@@ -108,7 +109,12 @@ struct Variant {
     bool g3hits = false;  // ... its re-assembly form: additions over a stored pattern the same mesh built (all-or-nothing, see group_columns)
     bool g3wide = false;  // ... its form for segments whose rows spread over more than 2^18 (two sorts per run, two workgroups per CU)
     bool g3k64 = false;   // ... fed packed 8-byte keys of one known kind whose bits below the prefix fit 32 (the radix passes' output)
+    bool pair = false;    // the PAIR form of the small variant: two producer buckets per workgroup (pair_k, local_w.hip)
 };
+// pair_k: a fresh matrix, 4-byte keys of one kind, 12 entries per lane (two buckets of at most 3072), column runs of at most 12
+constexpr int PAIR_ITEMS = 12;
+constexpr int PAIR_RUN = 12;
+constexpr u32 PAIR_REFUSED = 128u;  // Args::err: a pair the kernel does not take (the flush runs again with local_k)
 // enqueues the kernel; false when the combination has no instantiation
 bool launch(const Variant &v, unsigned grid, hipStream_t stream, const Args &a);
 bool launch_regular(const Variant &v, unsigned grid, hipStream_t stream, const Args &a);        // local_a.hip
@@ -119,6 +125,7 @@ bool launch_pieces_small(const Variant &v, unsigned grid, hipStream_t stream, co
 bool launch_group(const Variant &v, unsigned grid, hipStream_t stream, const Args &a);          // local_f.hip
 bool launch_group_short(const Variant &v, unsigned grid, hipStream_t stream, const Args &a);    // local_g.hip
 bool launch_group3(const Variant &v, unsigned grid, hipStream_t stream, const Args &a);         // local_h.hip
+bool launch_pair(const Variant &v, unsigned grid, hipStream_t stream, const Args &a);           // local_w.hip
 
 
 }  // namespace esplocal

@@ -645,7 +645,7 @@ int32_t append_tail_partitioned(esp_handle *h, const i64 *d_rows, const i64 *d_c
     double Ee = 0.0;
     // (short stored columns: the tail's flush rebuilds the matrix with the stored entries as the first piece of every segment
     // -- flush_rebuild --, so a segment must hold its columns' stored entries too, and suit the small variant of the bucket kernel)
-    const bool rebuild = h->force_path == ESP_PATH_AUTO && (double)h->nnz <= 10.0 * (double)h->n && (double)(h->nnz + count) <= 14.0 * (double)h->n;
+    const bool rebuild = paths_auto(h) && (double)h->nnz <= 10.0 * (double)h->n && (double)(h->nnz + count) <= 14.0 * (double)h->n;
     const i64 cap0 = h->plan_cap;
     if (rebuild) h->plan_cap = 6 * esplocal::THREADS;
     int pb = plan_prefix_bits(h, rebuild ? count + h->nnz : count, K, &Ee);
@@ -718,7 +718,7 @@ static void plan_passes(const esp_handle *h, i64 E, int K, int *planned_out, int
 // sort_msd resumes behind the pass (esp_handle::PrePass).  *took = false: not applicable, the caller packs in stream order.
 int32_t append_first_pass(esp_handle *h, const i64 *d_rows, const i64 *d_cols, const double *d_vals, int kind, int op, i64 count, bool *took) {
     *took = false;
-    if (h->count != 0 || count < ((i64)1 << 18) || count >= 0xFFFFFFF0ll || h->shard_user || windowed(h) || h->force_path != ESP_PATH_AUTO) return ESP_OK;
+    if (h->count != 0 || count < ((i64)1 << 18) || count >= 0xFFFFFFF0ll || h->shard_user || windowed(h) || !paths_auto(h)) return ESP_OK;
     const int K = window_bits(h);
     int planned = 0, npass = 0;
     double Ee = 0.0;
@@ -820,7 +820,7 @@ int32_t sort_msd(esp_handle *h, Sorted *out) {
     plan_passes(h, E, K, &planned, &npass, &Ee);
     // the first pass ran while the entries were appended (append_first_pass): its tables stand, the loop resumes behind it
     const bool resume = pre0.valid && pre0.count == E && h->pend_off == 0 && pre0.K == K && pre0.base == h->win_base && pre0.span == h->win_span &&
-                        !h->item_mode && !fixed_bits && h->force_path == ESP_PATH_AUTO && !h->shard_user;
+                        !h->item_mode && !fixed_bits && paths_auto(h) && !h->shard_user;
     if (resume) planned = pre0.planned, npass = pre0.npass, Ee = pre0.Ee;
 
     int cur = 0, S = 1, done = 0;
@@ -950,7 +950,7 @@ int32_t sort_msd(esp_handle *h, Sorted *out) {
         // bits) out of a pass, into the next and into the bucket kernel (12 bytes per entry instead of 16; the bucket kernel takes
         // its 4-byte-key forms).  Any force_path: packed keys throughout
         const int rem_out = K - done - bits;
-        const bool k32_now = k32_written || (!h->item_mode && !fixed_bits && h->force_path == ESP_PATH_AUTO && h->pend_off == 0 &&
+        const bool k32_now = k32_written || (!h->item_mode && !fixed_bits && paths_auto(h) && h->pend_off == 0 &&
                                              h->kind_uniform >= 0 && h->kind_noted == h->count && !windowed(h) && !h->shard_user &&
                                              rem_out <= 32 && rem_out <= esplocal::MAX_REM_BITS && out->key_bytes != 4);
         p.k32_in = k32_written ? 1 : 0;

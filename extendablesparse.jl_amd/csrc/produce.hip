@@ -66,7 +66,7 @@ extern "C" int32_t esp_generate_fdrand_range(esp_handle *h, int64_t nx, int64_t 
     bool took = false;
     const esp_handle::GenPlan &gp = h->genplan;
     const bool reuse = gp.valid && gp.nx == nx && gp.ny == ny && gp.nz == nz && gp.g0 == node_begin && gp.g1 == node_end && gp.kind == kind &&
-                       gp.E == E && h->count == 0 && h->force_path == ESP_PATH_AUTO && !h->part_assembled &&
+                       gp.E == E && h->count == 0 && paths_auto(h) && !h->part_assembled &&
                        gp.base == h->win_base && gp.span == h->win_span && gp.keys_at == h->keys.p && h->runs_skip == 0 &&
                        // (a shard: the plan was made for the exchange the caller announced -- esp_shard_plan -- and that one only)
                        (h->shard_user ? (h->shard_plan.valid && gp.pre.mw_P == h->shard_plan.P && gp.pre.mw_me == h->shard_plan.me &&
@@ -452,7 +452,7 @@ int32_t pending_materialize(esp_handle *h) {
 // here; a handle that already holds a matrix assembles over it (re-assembly kernels read expanded entries), so its batches
 // are expanded at once.  force_path 39 (ESP_PATH_NO_LAZY_ITEMS): never; any other forced path but 36: never either.
 bool lazy_items_wanted(const esp_handle *h, int kind) {
-    if (h->force_path != ESP_PATH_AUTO && h->force_path != ESP_PATH_LATE_TOTAL) return false;
+    if (!paths_auto(h) && h->force_path != ESP_PATH_LATE_TOTAL) return false;
     if (kind != ESP_UPDATE && kind != ESP_RAWUPDATE) return false;
     if (h->count != 0 || windowed(h) || h->shard_user) return false;
     // (over a stored pattern: only when the handle's last flush over it hit -- the re-assembly form of the fused kernel)

@@ -408,6 +408,11 @@ extern "C" int32_t esp_debug_last_local_small(const esp_handle *h, int32_t *smal
     *small = h->last_group3 == 4 ? 5 : h->last_group3 == 3 ? 4 : h->last_group3 == 2 ? 3 : h->last_group3 ? 2 : h->last_local_small;
     return ESP_OK;
 }
+extern "C" int32_t esp_debug_last_bucket_pairs(const esp_handle *h, int32_t *on) {
+    if (!h || !on) return ESP_ERR_INVALID;
+    *on = h->last_pair;
+    return ESP_OK;
+}
 extern "C" int32_t esp_debug_last_shard_source(const esp_handle *h, int32_t *kind) {
     if (!h || !kind) return ESP_ERR_INVALID;
     *kind = h->last_shard_source;

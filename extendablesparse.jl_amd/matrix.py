@@ -891,6 +891,12 @@ class ExtendableSparseMatrix:
         self._d.ck(self._d.lib.esp_debug_last_local_small(self._d.h, C.byref(p)))
         return p.value
 
+    def debug_last_bucket_pairs(self):
+        """1: the last flush's bucket kernel took two producer buckets per workgroup (the small variant's pair form)"""
+        p = C.c_int32()
+        self._d.ck(self._d.lib.esp_debug_last_bucket_pairs(self._d.h, C.byref(p)))
+        return p.value
+
     def debug_last_lazy_items(self):
         """1: the last flush's bucket kernel formed its updates from sorted item records (the expansion never ran)"""
         p = C.c_int32()

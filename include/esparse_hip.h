@@ -561,6 +561,8 @@ typedef enum {
                                         (up to 4 more prefix bits, so that 4-byte keys serve, with the bucket kernel taking 2 .. 16
                                         neighbouring buckets as one segment): packed 8-byte keys as before round 6 -- for a
                                         shard's producer too (its own range: 2^fb buckets per digit of the exchange plan)      */
+    ESP_PATH_NO_BUCKET_PAIRS = 42,   /* never the PAIR form of the small bucket kernel (two producer buckets per workgroup, see
+                                        esp_debug_last_bucket_pairs): one bucket per workgroup, local_k's small variant       */
     ESP_PATH_NO_PLAN_REUSE = 31      /* esp_append_device / esp_commit of one kind on an empty buffer always count their columns
                                         (never the run lists of the previous, identical-looking batch)                      */
 } esp_debug_path;
@@ -600,6 +602,11 @@ int32_t esp_debug_last_fold_update(const esp_handle *h, int32_t *on);
  * 2^18 -- a mesh numbered without locality: every run sorted twice; esp_debug_force_path(33): never); 4 / 5 when it was that
  * kernel's re-assembly form over a stored pattern (plain / wide; esp_debug_force_path(34): never) */
 int32_t esp_debug_last_local_small(const esp_handle *h, int32_t *small);
+/* 1 when the bucket kernel of the last flush was the small variant's PAIR form (esp_debug_last_local_small then reports 1): one
+ * workgroup took two neighbouring producer buckets -- up to 512 columns and 6144 entries -- as one segment (a fresh matrix, 4-byte
+ * keys of one kind, at most 12 pending entries per column; a pair with a longer column run or rows spread over 2^19 or more sends
+ * the flush, and the handle's later ones, to the one-bucket kernel); esp_debug_force_path(42): never */
+int32_t esp_debug_last_bucket_pairs(const esp_handle *h, int32_t *on);
 /* 1 when the bucket kernel of the last flush formed its updates from the sorted ITEM records of an item partition
  * (esp_generate_fem in a shuffled order, esp_append_elements on an empty buffer of a fresh matrix): the expansion -- every
  * update stored once at its bucket position, read again by the bucket kernel -- never ran (csrc/group3_items.hpp);
