@@ -16,7 +16,7 @@ ESP_ERR_UNSUPPORTED, ESP_ERR_STATE, ESP_ERR_NODEVICE = -5, -6, -7
 ESP_SET, ESP_UPDATE, ESP_RAWUPDATE, ESP_COO = 0, 1, 2, 3
 ESP_OP_ADD, ESP_OP_SUB = 0, 1
 ESP_FLUSH_ROUTED, ESP_FLUSH_PLUS = 0, 1
-ESP_PRECON_JACOBI, ESP_PRECON_ILU0 = 0, 1
+ESP_PRECON_JACOBI, ESP_PRECON_ILU0, ESP_PRECON_ILUAM = 0, 1, 2
 STAGES = ("append", "hist", "scan", "scatter", "local", "fold", "colptr", "merge", "copy")
 ESP_ST_COUNT = len(STAGES)
 
@@ -99,6 +99,8 @@ SIGNATURES = {
     "esp_precon_update": (i32, [vp]),
     "esp_precon_ldiv": (i32, [vp, vp, vp, i32]),
     "esp_precon_destroy": (i32, [vp]),
+    "esp_precon_get_factor": (i32, [vp, vp, i32]),
+    "esp_precon_levels": (i32, [vp, P(i64)]),
     "esp_simple": (i32, [vp, vp, vp, vp, i32, i64, f64, f64, vp, P(i64)]),
     "esp_matmul": (i32, [vp, vp, vp, P(i64)]),
     "esp_add": (i32, [vp, vp, i32, vp, P(i64)]),

@@ -1,4 +1,5 @@
 // precon.hip -- libesparse_hip: the point preconditioners' update! / ldiv! and the simple! iteration on the device CSC
+// (ILUAM's analysis, factorization and solves: iluam.hip; its create / update! / ldiv! / simple! enter here)
 // (see internal.hpp for the map of the translation units)
 //
 // ldiv! of ILU0 (factorizations/ilu0.jl:66-92) reads like two triangular sweeps, but neither carries a dependency chain:
@@ -21,20 +22,6 @@
 // re-gathered with the STORED xdiag (ldiv!) or with the new one (update!).
 #include "internal.hpp"
 
-struct esp_precon {
-    esp_handle *h = nullptr;
-    int kind = 0;
-    i64 n = 0, nnz = 0;
-    unsigned long long pattern_version = 0;  // the pattern the split layout (and invdiag/xdiag) belongs to
-    unsigned long long values_version = 0;   // the nzval the pre-scaled values were gathered from
-    DevBuf diag;                             // invdiag (Jacobi) / xdiag (ILU0), n
-    DevBuf lptr, uptr;                       // n+1 each (u32)
-    DevBuf lcol, ucol, lpos, upos;           // per part entry (u32)
-    DevBuf dpos;                             // CSC position of every row's diagonal (u32, ILU0)
-    DevBuf lval, uval;                       // per part entry (f64, pre-scaled)
-    DevBuf u1, res, partial, scanws, hv, hu; // scratch: pass-1 result, residual, sums of squares, scan, host staging
-};
-
 namespace {
 
 constexpr int PT = 256;       // threads = rows per workgroup of the row kernels
@@ -55,22 +42,23 @@ __global__ void split_count_k(const u64 *__restrict__ rp, const u32 *__restrict_
     }
     lcnt[i] = nl;
     ucnt[i] = (u32)(e - b) - nl - nd;
-    dpos[i] = nd ? perm[b + nl] : 0u;  // (ILU0 refused a missing diagonal before the build)
+    dpos[i] = nd ? perm[b + nl] : 0u;  // (ILU0 / ILUAM refused a missing diagonal before the build)
 }
 __global__ void split_fill_k(const u64 *__restrict__ rp, const u32 *__restrict__ tcol, const u32 *__restrict__ perm, i64 n,
                              const u32 *__restrict__ lptr, const u32 *__restrict__ uptr, u32 *__restrict__ lcol,
-                             u32 *__restrict__ lpos, u32 *__restrict__ ucol, u32 *__restrict__ upos) {
+                             u32 *__restrict__ lpos, u32 *__restrict__ ucol, u32 *__restrict__ upos, bool reversed) {
     const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const u64 b = rp[i], e = rp[i + 1];
     const u32 nl = lptr[i + 1] - lptr[i], nu = uptr[i + 1] - uptr[i];
+    // reversed (ILUAM): the forward substitution runs j = 1:n, the backward one j = n:-1:1 (ilu_Al-Kurdi_Mittal.jl:133-155)
     for (u32 t = 0; t < nl; t++) {  // lower part: decreasing column (ilu0.jl:78-83 runs j = n:-1:1)
-        const u64 k = b + nl - 1 - t;
+        const u64 k = reversed ? b + t : b + nl - 1 - t;
         lcol[lptr[i] + t] = tcol[k];
         lpos[lptr[i] + t] = perm[k];
     }
     for (u32 t = 0; t < nu; t++) {  // upper part: increasing column (ilu0.jl:85-90 runs j = 1:n)
-        const u64 k = e - nu + t;
+        const u64 k = reversed ? e - 1 - t : e - nu + t;
         ucol[uptr[i] + t] = tcol[k];
         upos[uptr[i] + t] = perm[k];
     }
@@ -224,7 +212,9 @@ int32_t check_handle(esp_handle *h, const char *what) {
     return ESP_OK;
 }
 
-// invdiag / xdiag from the current nzval (jacobi! / ilu0!); ILU0 without a stored diagonal -> ESP_ERR_INVALID
+}  // namespace
+
+// invdiag / xdiag from the current nzval (jacobi! / ilu0!); ILU0 / ILUAM without a stored diagonal -> ESP_ERR_INVALID
 int32_t diag_refresh(esp_precon *p) {
     esp_handle *h = p->h;
     const i64 n = p->n;
@@ -237,16 +227,17 @@ int32_t diag_refresh(esp_precon *p) {
     espfold::Csc c{(const i64 *)h->colptr.p, (const i64 *)h->rowval.p, (double *)h->nzval.p, h->nnz};
     hipLaunchKernelGGL(precon_diag_k, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, c, n, (double *)p->diag.p, d_missing);
     HIPCK(h, hipGetLastError());
-    if (p->kind != ESP_PRECON_ILU0) return ESP_OK;  // (Jacobi: Inf there, nothing to read back)
+    if (p->kind == ESP_PRECON_JACOBI) return ESP_OK;  // (Inf there, nothing to read back)
     HIPCK(h, hipMemcpyAsync(h->pin_scalar, d_missing, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCK(h, hipStreamSynchronize(h->stream));
     if (h->pin_scalar[0] != ~0ull)
-        FAIL(h, ESP_ERR_INVALID, "ilu0: column %llu has no stored diagonal entry (the reference reads an undefined idiag there)",
-             (unsigned long long)h->pin_scalar[0]);
+        FAIL(h, ESP_ERR_INVALID, "%s: column %llu has no stored diagonal entry (the reference reads an undefined %s there)",
+             p->kind == ESP_PRECON_ILU0 ? "ilu0" : "iluam", (unsigned long long)h->pin_scalar[0],
+             p->kind == ESP_PRECON_ILU0 ? "idiag" : "diag[j]");
     return ESP_OK;
 }
 
-int32_t split_build(esp_precon *p) {
+int32_t split_build(esp_precon *p, bool reversed) {
     esp_handle *h = p->h;
     const i64 n = p->n;
     CK(csr_current(h));
@@ -276,10 +267,12 @@ int32_t split_build(esp_precon *p) {
     if (n > 0)
         hipLaunchKernelGGL(split_fill_k, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, rp, (const u32 *)h->csr_col.p,
                            (const u32 *)h->csr_perm.p, n, (const u32 *)lptr, (const u32 *)uptr, (u32 *)p->lcol.p, (u32 *)p->lpos.p,
-                           (u32 *)p->ucol.p, (u32 *)p->upos.p);
+                           (u32 *)p->ucol.p, (u32 *)p->upos.p, reversed);
     HIPCK(h, hipGetLastError());
     return ESP_OK;
 }
+
+namespace {
 
 // fresh: xdiag from the current diagonal as well (ilu0!), else the stored xdiag (ldiv! after an in-place value change)
 int32_t split_scale(esp_precon *p, bool fresh) {
@@ -310,14 +303,15 @@ int32_t precon_ready(esp_precon *p, const char *what) {
 }
 
 // ldiv! on device vectors (v may equal u; tmp: n doubles of scratch)
-void ldiv_launch(esp_precon *p, const double *v, double *u) {
+int32_t ldiv_launch(esp_precon *p, const double *v, double *u) {
     esp_handle *h = p->h;
     const i64 n = p->n;
-    if (n == 0) return;
+    if (n == 0) return ESP_OK;
+    if (p->kind == ESP_PRECON_ILUAM) return iluam_solve(p, v, u, false);
     const unsigned g = grid_for(n, PT);
     if (p->kind == ESP_PRECON_JACOBI) {
         hipLaunchKernelGGL(jacobi_ldiv_k, dim3(g), dim3(PT), 0, h->stream, (const double *)p->diag.p, v, u, n);
-        return;
+        return ESP_OK;
     }
     double *u1 = (double *)p->u1.p;  // pass 1 writes the scratch: its neighbours still read v (which may be u)
     hipLaunchKernelGGL((row_chain_k<ILU_LOWER, u32>), dim3(g), dim3(PT), 0, h->stream, (const u32 *)p->lptr.p, (const u32 *)p->lcol.p,
@@ -325,12 +319,13 @@ void ldiv_launch(esp_precon *p, const double *v, double *u) {
     hipLaunchKernelGGL((row_chain_k<ILU_UPPER, u32>), dim3(g), dim3(PT), 0, h->stream, (const u32 *)p->uptr.p, (const u32 *)p->ucol.p,
                        (const double *)p->uval.p, (const double *)nullptr, (const double *)u1, (const double *)nullptr, u, n,
                        (double *)nullptr);
+    return ESP_OK;
 }
 
 }  // namespace
 
 extern "C" int32_t esp_precon_create(esp_handle *h, int32_t kind, esp_precon **out) {
-    if (!h || !out || (kind != ESP_PRECON_JACOBI && kind != ESP_PRECON_ILU0)) return ESP_ERR_INVALID;
+    if (!h || !out || (kind != ESP_PRECON_JACOBI && kind != ESP_PRECON_ILU0 && kind != ESP_PRECON_ILUAM)) return ESP_ERR_INVALID;
     *out = nullptr;
     CK(check_handle(h, "esp_precon_create"));
     esp_precon *p = new esp_precon();
@@ -356,9 +351,11 @@ extern "C" int32_t esp_precon_update(esp_precon *p) {
     p->pattern_version = 0;  // (a failure below leaves a preconditioner that refuses ldiv! until the next good update!)
     if (p->kind == ESP_PRECON_JACOBI) {
         CK(diag_refresh(p));          // jacobi(A) / jacobi!
+    } else if (p->kind == ESP_PRECON_ILUAM) {
+        CK(iluam_update(p, rebuild)); // iluAM(A) / the numeric factorization on the kept analysis
     } else if (rebuild) {             // ilu0(A)
         CK(diag_refresh(p));          // (refuses a missing diagonal before the layout is built)
-        CK(split_build(p));
+        CK(split_build(p, false));
         CK(ensure(h, p->u1, sizeof(double) * (size_t)std::max<i64>(p->n, 1)));
         CK(split_scale(p, false));
     } else {                          // ilu0!: xdiag and the scaled values in one pass
@@ -382,7 +379,7 @@ extern "C" int32_t esp_precon_ldiv(esp_precon *p, const double *v, double *u, in
         HIPCK(h, hipMemcpyAsync(p->hv.p, v, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->stream));
         dv = du = (double *)p->hv.p;
     }
-    ldiv_launch(p, dv, du);
+    CK(ldiv_launch(p, dv, du));
     HIPCK(h, hipGetLastError());
     if (!on_device) HIPCK(h, hipMemcpyAsync(u, du, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     HIPCK(h, hipStreamSynchronize(h->stream));
@@ -397,6 +394,7 @@ extern "C" int32_t esp_precon_destroy(esp_precon *p) {
     for (DevBuf *b : {&p->diag, &p->lptr, &p->uptr, &p->lcol, &p->ucol, &p->lpos, &p->upos, &p->dpos, &p->lval, &p->uval, &p->u1, &p->res,
                       &p->partial, &p->scanws, &p->hv, &p->hu})
         release(*b);
+    iluam_release(p);
     h->live_precons--;
     delete p;
     return ESP_OK;
@@ -447,6 +445,8 @@ extern "C" int32_t esp_simple(esp_handle *h, esp_precon *p, const double *b, dou
             if (p->kind == ESP_PRECON_JACOBI) {
                 hipLaunchKernelGGL(jacobi_sub_k, dim3((unsigned)nb), dim3(PT), 0, h->stream, (const double *)p->diag.p,
                                    (const double *)res, du, n);
+            } else if (p->kind == ESP_PRECON_ILUAM) {
+                CK(iluam_solve(p, res, du, true));
             } else {
                 double *u1 = (double *)p->u1.p;
                 hipLaunchKernelGGL((row_chain_k<ILU_LOWER, u32>), dim3((unsigned)nb), dim3(PT), 0, h->stream, (const u32 *)p->lptr.p,

@@ -1,6 +1,7 @@
-"""The point preconditioners (src/factorizations/jacobi.jl, ilu0.jl) and simple! (simple_iteration.jl) on the device CSC.
+"""The preconditioners (src/factorizations/jacobi.jl, ilu0.jl; ILUAMPreconditioner of
+src/experimental/ExtendableSparseMatrixParallel/iluam.jl) and simple! (simple_iteration.jl) on the device CSC.
 
-JacobiPreconditioner(A) / ILU0Preconditioner(A) bind an esp_precon to the matrix's handle: construction is factorize!
+JacobiPreconditioner(A) / ILU0Preconditioner(A) / ILUAMPreconditioner(A) bind an esp_precon to the matrix's handle: construction is factorize!
 (create + update!), .update() is update!, .ldiv(v, out) is ldiv!(out, p, v) -- bit-identical to the reference loops.
 simple(A, b, Pl=...) is simple / simple!; u is bit-identical to the reference's loop, the residual norms agree to rounding
 (include/esparse_hip.h, esp_simple).  Vectors: NumPy arrays (copied through the device) or CUDA float64 torch tensors (used
@@ -11,7 +12,7 @@ import math
 
 import numpy as np
 
-from ._lib import ESP_PRECON_ILU0, ESP_PRECON_JACOBI
+from ._lib import ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_JACOBI
 from .matrix import ExtendableSparseMatrix, _vp
 
 
@@ -99,6 +100,27 @@ class ILU0Preconditioner(_PointPreconditioner):
     """ILU0Preconditioner(A) (src/factorizations/ilu0.jl): ldiv! as two row-parallel passes, bit-identical to the
     reference's column loops."""
     KIND = ESP_PRECON_ILU0
+
+
+class ILUAMPreconditioner(_PointPreconditioner):
+    """ILUAMPreconditioner(A) (src/experimental/ExtendableSparseMatrixParallel/iluam.jl): a real ILU(0) on A's pattern, the
+    factorization and both triangular solves level by level on the device, bit-identical to the reference's sequential
+    loops.  It owns a copy of the values: a value change of A reaches ldiv only through update()."""
+    KIND = ESP_PRECON_ILUAM
+
+    def factor(self):
+        """the factorization's values in CSC position order (the reference's ILU.nzval): unit-lower L scaled below the
+        diagonal, U on and above it"""
+        p = self._live()
+        out = np.empty(self.A.nnz(), np.float64)
+        self._ck(self.A._d.lib.esp_precon_get_factor(p, _vp(out), 0))
+        return out
+
+    def levels(self):
+        """level counts of the three schedules: (factorization columns, forward rows, backward rows)"""
+        out = (C.c_int64 * 3)()
+        self._ck(self.A._d.lib.esp_precon_levels(self._live(), out))
+        return tuple(int(x) for x in out)
 
 
 def simple(A, b, u=None, Pl=None, maxiter=100, reltol=math.sqrt(np.finfo(np.float64).eps), abstol=0.0, log=False):

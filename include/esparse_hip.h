@@ -291,7 +291,7 @@ int32_t esp_jacobi_setup(esp_handle *h, double *invdiag, int32_t on_device);
 int32_t esp_ilu0_setup(esp_handle *h, double *xdiag, int64_t *idiag, int32_t on_device);
 
 /* ---- the point preconditioners and simple! on the device CSC of a square matrix -----------------------------------
- * An esp_precon is _JacobiPreconditioner / _ILU0Preconditioner plus the update! wrapper around them
+ * An esp_precon is _JacobiPreconditioner / _ILU0Preconditioner (or ILUAMPrecon, below) plus the update! wrapper around them
  * (src/factorizations/jacobi.jl, ilu0.jl), bound to one handle; everything runs on the handle's stream and every call
  * returns synchronised.  Pending entries -> ESP_ERR_STATE (flush first, as update! does); a rectangular matrix ->
  * ESP_ERR_INVALID; nnz or n >= 2^32 - 16 -> ESP_ERR_UNSUPPORTED (32-bit positions and columns, as esp_mul's index).
@@ -312,6 +312,32 @@ int32_t esp_precon_create(esp_handle *h, int32_t kind, esp_precon **out);
 int32_t esp_precon_update(esp_precon *p);
 int32_t esp_precon_ldiv(esp_precon *p, const double *v, double *u, int32_t on_device);
 int32_t esp_precon_destroy(esp_precon *p);
+/* ILUAMPreconditioner (src/experimental/ExtendableSparseMatrixParallel/iluam.jl; the loops of ilu_Al-Kurdi_Mittal.jl in the
+ * same directory): a real ILU(0) on A's own pattern, bit-identical to the reference's sequential loops.
+ * esp_precon_create(h, ESP_PRECON_ILUAM) = iluAM(A) (lines 68-120): nzval = copy(A.nzval); for j = 1:n, for every stored
+ *   position v of column j above the diagonal in increasing row i, and every position w of column i below its diagonal whose
+ *   row is stored in column j at position k: nzval[k] -= nzval[v]*nzval[w]; then every position of column j below the
+ *   diagonal is divided by nzval[diag[j]].  Unit-lower L (scaled, strictly below the diagonal) and U (on and above it).
+ *   On the device the columns run level by level (column j after every column i < j with a stored A[i,j]), one kernel
+ *   launch per level; a column writes only its own positions and reads only finished columns, so the order inside a level
+ *   does not matter.  The analysis (diagonal positions, row parts, three level schedules) runs on the device after a pattern
+ *   change only.  A column without a stored diagonal -> ESP_ERR_INVALID (the reference reads an undefined diag[j]); a zero
+ *   pivot is no error (Inf / NaN propagate).
+ * esp_precon_update: after a pattern change iluAM(A) (iluam.jl:22-31).  DEVIATION: with the pattern kept the reference
+ *   calls iluam!, which does not exist (iluAM! at lines 17-66 reads n before defining it and never stores its result); the
+ *   device does what was evidently meant: the numeric factorization on the kept analysis.
+ * esp_precon_ldiv = ldiv!(x, ILU, b) (lines 160-175 with 122-157): forward y[i] = ((0 - l_ij1*y[j1]) - ...) + b[i], the
+ *   stored j < i in INCREASING order; backward x[i] = ((y[i] - u_ij1*x[j1]) - ...)/u_ii, the stored j > i in DECREASING
+ *   order, a true division; each level of rows is one launch.  x may alias b (ldiv!(ILU, b)).
+ *   The factorization owns a copy of the values: an in-place value change of A without update! does NOT change ldiv!
+ *   (unlike ILU0).  A pattern change without update! -> ESP_ERR_STATE.
+ * esp_precon_get_factor: the factorization's nnz values in CSC position order (the reference's ILU.nzval), host doubles or,
+ *   on_device != 0, device doubles; ESP_ERR_INVALID for the other kinds.
+ * esp_precon_levels: out[0..2] = the level counts of the three schedules (factorization columns, forward rows, backward
+ *   rows); zeros for the other kinds. */
+#define ESP_PRECON_ILUAM 2
+int32_t esp_precon_get_factor(esp_precon *p, double *nzval, int32_t on_device);
+int32_t esp_precon_levels(esp_precon *p, int64_t out[3]);
 /* simple!(u, A, b; abstol, reltol, maxiter, Pl = p) (src/factorizations/simple_iteration.jl:21-45) statement by
  * statement: res = A*u - b; then per step ldiv!(upd, Pl, res), u .-= upd, mul!(res, A, u), res .-= b, r = norm(res),
  * stop when (r / r0) < reltol || r < abstol (literally: r0 = 0 gives NaN or Inf there).  u (in/out) is bit-identical to

@@ -4,15 +4,125 @@ on device vectors, update! values-only, the first build after a pattern change (
 work; every call also returns synchronised.  Prints one JSON line: ms and the algorithmic bytes of DESIGN.md.
 
     python tools/precon_bench.py [--n 256] [--iters 50] [--warmup 5]
+
+--kind iluam times ILUAMPreconditioner instead: the first build (analysis + factorization), a values-only update!, ldiv! on
+device vectors, one simple! step, and the number of kernel launches of one ldiv! (computed from the level sizes of the
+stencil cube by the library's grouping rule; the kernel trace of DESIGN.md section 5e counts the same).  --tol-n M adds
+simple! to reltol = 1e-8 on fdrand(M,M,M), b = ones, with ILU0 and with ILUAM: iterations and wall time of each.
+--cpu-model adds the host time of the sequential reference loops (tests/iluam_model.c) at the same size.
+
+    python tools/precon_bench.py --kind iluam [--n 256] [--iters 10] [--tol-n 40] [--cpu-model]
 """
 import argparse
 import ctypes as C
 import json
 import os
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+def cube_level_sizes(n):
+    """members of the levels of fdrand(n,n,n)'s three schedules: the nodes (i,j,k) with i + j + k = l"""
+    import numpy as np
+    one = np.ones(n, np.int64)
+    return np.convolve(np.convolve(one, one), one)
+
+
+def grouped_launches(sizes, wg=256):
+    """the library's rule (iluam.hip, build_schedule): a level wider than a workgroup is a launch of its own, consecutive
+    levels that together fit one workgroup share one"""
+    launches, room = 0, 0
+    for c in sizes:
+        if c > wg:
+            launches, room = launches + 1, 0
+        elif c <= room:
+            room -= c
+        else:
+            launches, room = launches + 1, wg - c
+    return launches
+
+
+def bench_iluam(a, torch, esp):
+    import numpy as np
+    A = esp.fdrand(a.n, a.n, a.n)
+    d = A._d
+    stream = torch.cuda.current_stream()
+    d.ck(d.lib.esp_set_stream(d.h, C.c_void_p(stream.cuda_stream)))
+    N, Z = A.n, A.nnz()
+    v = torch.randn(N, dtype=torch.float64, device="cuda")
+    u = torch.empty_like(v)
+    b = torch.ones_like(v)
+
+    def timed(fn, reps, warmup=a.warmup):
+        for _ in range(warmup):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    out = {"workload": "iluam_fdrand", "n": a.n, "N": N, "nnz": Z}
+    Pw = esp.ILU0Preconditioner(A)     # builds the row-wise index esp_mul shares, so that the build below is ILUAM's own
+    Pw.close()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    P = esp.ILUAMPreconditioner(A)     # first build: row parts, three level analyses, numeric factorization
+    e1.record()
+    e1.synchronize()
+    out["iluam_create_ms"] = e0.elapsed_time(e1)
+    out["levels"] = list(P.levels())
+    out["iluam_update_values_ms"] = timed(lambda: P.update(), max(3, a.iters // 3), warmup=1)
+    assert list(P.levels()) == out["levels"]
+    out["iluam_ldiv_ms"] = timed(lambda: P.ldiv(v, out=u), a.iters)
+
+    def run_simple(k):
+        x = torch.zeros_like(v)
+        esp.simple(A, b, u=x, Pl=P, maxiter=k, reltol=0.0)
+
+    t_long = timed(lambda: run_simple(a.iters + 1), 2, warmup=1)
+    t_short = timed(lambda: run_simple(1), 2, warmup=1)
+    out["simple_iluam_step_ms"] = (t_long - t_short) / a.iters
+    sizes = cube_level_sizes(a.n)
+    assert len(sizes) == out["levels"][1]
+    out["ldiv_launches"] = 2 * grouped_launches(sizes)      # forward + backward (the backward sizes are the mirror image)
+    out["factor_launches"] = grouped_launches(sizes)
+    if a.cpu_model:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import tempfile
+        from iluam_modellib import Model
+        arrays = tuple(np.array(x, copy=True) for x in A.sparse().arrays())
+        with tempfile.TemporaryDirectory() as td:
+            M = Model(td)
+            t0 = time.perf_counter()
+            f, dg = M.factor(arrays)
+            out["cpu_model_factor_ms"] = (time.perf_counter() - t0) * 1e3
+            hv = v.cpu().numpy()
+            t0 = time.perf_counter()
+            M.ldiv(arrays, f, dg, hv)
+            out["cpu_model_ldiv_ms"] = (time.perf_counter() - t0) * 1e3
+    P.close()
+    if a.tol_n:
+        m = a.tol_n
+        B = esp.fdrand(m, m, m)
+        ones = torch.ones(B.n, dtype=torch.float64, device="cuda")
+        for name, cls in (("ilu0", esp.ILU0Preconditioner), ("iluam", esp.ILUAMPreconditioner)):
+            Q = cls(B)
+            esp.simple(B, ones, Pl=Q, maxiter=3, reltol=0.0)   # warm-up
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            _, log = esp.simple(B, ones, Pl=Q, maxiter=a.tol_maxiter, reltol=1e-8, log=True)
+            dt = time.perf_counter() - t0                       # (esp_simple returns synchronised)
+            r = log["resnorm"]
+            out["tol_%s" % name] = {"n": m, "iterations": len(r) - 1, "converged": bool(r[-1] / r[0] < 1e-8), "ms": dt * 1e3}
+            Q.close()
+    print(json.dumps({k: (round(x, 4) if isinstance(x, float) else x) for k, x in out.items()}))
 
 
 def main():
@@ -20,11 +130,17 @@ def main():
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--kind", choices=["point", "iluam"], default="point")
+    ap.add_argument("--tol-n", type=int, default=0)
+    ap.add_argument("--tol-maxiter", type=int, default=100000)
+    ap.add_argument("--cpu-model", action="store_true")
     a = ap.parse_args()
     import torch
     torch.cuda.init()
     from esparse_loader import load
     esp = load()
+    if a.kind == "iluam":
+        return bench_iluam(a, torch, esp)
     A = esp.fdrand(a.n, a.n, a.n)
     d = A._d
     stream = torch.cuda.current_stream()
