@@ -123,6 +123,8 @@ SIGNATURES = {
     "esp_debug_last_shard_source": (i32, [vp, P(i32)]),
     "esp_debug_last_local_small": (i32, [vp, P(i32)]),
     "esp_debug_last_bucket_pairs": (i32, [vp, P(i32)]),
+    "esp_debug_last_predicted": (i32, [vp, P(i32)]),
+    "esp_debug_spoil_predicted": (i32, [vp]),
     "esp_debug_last_lazy_items": (i32, [vp, P(i32)]),
     "esp_debug_last_sum_join": (i32, [vp, P(i32)]),
     "esp_debug_last_sum_ms": (i32, [vp, P(C.c_double), P(C.c_double)]),

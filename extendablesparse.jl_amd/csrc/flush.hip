@@ -158,7 +158,6 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
     CK(ensure(h, h->segout, sizeof(u64) * (size_t)(S + 2 + G + 512)));
     u64 *status = (u64 *)h->segout.p;
     const size_t status_bytes = sizeof(u64) * (size_t)(S + 2 + G + 512);
-    HIPCK(h, hipMemsetAsync(status, 0, status_bytes, h->stream));
     CK(ensure(h, h->colend, sizeof(u64) * (size_t)(N1 + espscan::workspace_elems(N1))));
     esplocal::Args a;
     memset(&a, 0, sizeof a);
@@ -216,6 +215,19 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
                          (double)h->count <= (double)esplocal::PAIR_RUN * (double)std::max<i64>(col_end - col_begin, 1) &&
                          h->force_path != ESP_PATH_NO_BUCKET_PAIRS && h->force_path != ESP_PATH_GENERIC_FOLD;
     bool used_pair = false;
+    // ... and its PREDICTED form (pair_pred_k): the batch repeats the producer plan of the handle's last flush (GenPlan / RawPlan:
+    // the same buckets) and nothing lies behind it, and that flush left the offsets its look-back found (esp_handle::PredTable) --
+    // every pair writes at the table's offset when it emits the table's count, no ticket and no look-back; a pair that emits
+    // another count (structural zeros moved) stores nothing and the flush runs again with pair_k.  force_path 43: never.
+    const bool pred_batch = pair_ok && paths_auto(h) && h->force_path != ESP_PATH_NO_PREDICTED_OFFSETS && h->pre.valid && h->pre.tail == 0 &&
+                            h->count == h->pre.E && st.seg_start == (const i64 *)h->seg[1].p && (h->genplan.valid || h->rawplan.valid);
+    bool use_pred = pred_batch && !h->pair_off && h->last_plan_reused == 1 && h->pred.gen == h->plan_gen && h->pred.S == S && h->pred.tab.p &&
+                    h->pred.misses < 2 && h->force_path != ESP_PATH_MANY_LAUNCHES;
+    // (the predicted form reads the error / longest-run words and leaves the grand total in the last granule: nothing else to clear)
+    if (use_pred)
+        HIPCK(h, hipMemsetAsync(status + (S - 1), 0, 3 * sizeof(u64), h->stream));
+    else
+        HIPCK(h, hipMemsetAsync(status, 0, status_bytes, h->stream));
     std::function<int32_t(bool)> launch_all;
     bool used_g3 = false;
     bool want_wide = h->g3_wide && h->force_path != ESP_PATH_NO_WIDE_GROUP3;
@@ -289,9 +301,13 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
             esplocal::Variant var{true, false, false, true, keys};
             var.pair = true;
             h->last_fold_update = keys == 2 ? 1 : 0;
+            // (what the output arrays hold: a stale table must not send a pair's stores outside them)
+            const u64 out_cap = (u64)std::min(h->keys2.bytes / sizeof(i64), h->vals2.bytes / sizeof(double));
             for (i64 first = 0; first < Sp; first += max_grid) {
                 ap.first = first;
-                if (!esplocal::launch(var, (unsigned)std::min<i64>(max_grid, Sp - first), h->stream, ap))
+                const unsigned grid = (unsigned)std::min<i64>(max_grid, Sp - first);
+                if (!(use_pred ? esplocal::launch_pair_predicted(var, grid, h->stream, ap, (const u64 *)h->pred.tab.p, out_cap)
+                               : esplocal::launch(var, grid, h->stream, ap)))
                     FAIL(h, ESP_ERR_STATE, "esp_flush: internal error (no pair kernel for this flush)");
             }
             used_pair = true;
@@ -422,6 +438,24 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
         sp.add(1);
     }
     CK(read_back());
+    const bool pred_tried = use_pred && used_pair;
+    if (pred_tried && ((u32)(h->pin_scalar[1] >> 32) & (esplocal::PRED_MISS | esplocal::PAIR_REFUSED))) {
+        // a pair emitted another count than the table says (it stored nothing; the others wrote their slices): once more with the
+        // look-back form, which rewrites everything a fresh-matrix flush writes -- the pending entries are where they were
+        use_pred = false;
+        h->pred.misses++;
+        h->pred.last = 2;
+        CK(reset_launch_state());
+        {
+            Span sp(h, ESP_ST_LOCAL);
+            CK(launch_all(true));
+            sp.add(1);
+        }
+        CK(read_back());
+    } else if (pred_tried) {
+        h->pred.misses = 0;
+        h->pred.last = 1;
+    }
     if (used_pair && ((u32)(h->pin_scalar[1] >> 32) & esplocal::PAIR_REFUSED)) {
         // a pair the kernel does not take: once more with local_k (it writes every output a fresh-matrix flush has), and it serves
         // this handle from now on
@@ -500,6 +534,20 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
     if (lookback_err & 4u) FAIL(h, ESP_ERR_HIP, "esp_flush: internal error (early segment total differs from the folded total)");
     const i64 Zn = (i64)(h->pin_scalar[0] & esplocal::ST_VAL);
     *Zn_out = Zn;
+    if (pred_batch && used_pair && !use_pred && Zn > 0 && !a.stop_after) {
+        // a look-back flush of a kept plan that succeeded: its pairs' offsets, from the fresh colptr, for the next flush of the plan
+        // (not once two predictions in a row have missed: the stream's zeros move every time)
+        if (h->pred.gen != h->plan_gen) h->pred.misses = 0;
+        const int Sp = (S + 1) / 2;
+        h->pred.gen = h->plan_gen;
+        h->pred.S = S;
+        if (h->pred.misses < 2) {
+            if (ensure(h, h->pred.tab, sizeof(u64) * (size_t)(Sp + 1)) == ESP_OK)
+                esplocal::launch_pair_record(h->stream, (const i64 *)h->colptr.p, col_end, a.cl_bits + 1, Sp, (u64 *)h->pred.tab.p);
+            else
+                h->pred.gen = 0;  // (no memory for the table: the flush itself is done -- no prediction, that is all)
+        }
+    }
     // (history for the next flush over a stored pattern: fewer than a quarter of the entries opened a new position)
     if (Z0 > 0 && st.expect_hits < 0 && st.total > 0) h->seen_hits = Zn * 4 <= st.total;
     if (a.stop_after || Zn == 0) return ESP_OK;
@@ -877,6 +925,7 @@ extern "C" int32_t esp_flush(esp_handle *h, int32_t mode, int64_t *new_nnz, int3
     i64 Zn = 0;
     h->last_rebuild = 0;
     h->last_pair = 0;
+    h->pred.last = 0;
     bool use_local = h->force_path != ESP_PATH_GENERAL;
     if (h->ones_pending && windowed(h)) CK(fix_tail(h));  // (cannot happen: a window is declared through fix_tail)
     if (h->pre.valid) {  // the producer's partition serves this flush if nothing changed since (appends BEHIND it may have)

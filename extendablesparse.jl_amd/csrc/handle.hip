@@ -111,7 +111,7 @@ void release(DevBuf &b) {
 
 void release_all(esp_handle *h) {
     for (DevBuf *b : {&h->keys, &h->vals, &h->keys2, &h->vals2, &h->hist, &h->segs, &h->colend, &h->newkey,
-                      &h->newval, &h->heads, &h->misc, &h->colptr, &h->colptr2, &h->rowval, &h->nzval, &h->rowval2,
+                      &h->newval, &h->heads, &h->misc, &h->pred.tab, &h->colptr, &h->colptr2, &h->rowval, &h->nzval, &h->rowval2,
                       &h->nzval2, &h->seg[0], &h->seg[1], &h->tilef[0], &h->tilef[1], &h->segcnt, &h->segout, &h->tseg, &h->ttile, &h->runbuf, &h->chunkbuf, &h->parttab, &h->piecetab, &h->asmwork, &h->sumrange, &h->csr_rowptr, &h->csr_perm, &h->csr_col, &h->csr_tmp, &h->csr_val, &h->mul_x, &h->mul_r, &h->lazy_hold, &h->elemplan.sorted, &h->elemplan.cellrec, &h->elemplan.segtab, &h->stage.d_rows, &h->stage.d_cols, &h->stage.d_vals, &h->stage.d_kinds, &h->bulk.d_rows, &h->bulk.d_cols, &h->bulk.d_vals, &h->bulk.d_kinds})
         release(*b);
     for (esp_handle::StageArea *sa : {&h->stage, &h->bulk}) {
@@ -315,8 +315,9 @@ extern "C" int32_t esp_release_buffers(esp_handle *h) {
     h->count = 0;
     h->chunk_cap = 0;
     h->chunk_pb = 0;
-    h->rawplan.valid = false;
-    h->genplan.valid = false;
+    drop_raw_plan(h);
+    drop_gen_plan(h);
+    h->pred.gen = 0;  // (its table went with the buffers)
     h->elemplan.valid = false;
     h->shard_offsets.plan_id = 0;  // (the counts it vouches for lived in parttab)
     pending_changed(h);

@@ -183,6 +183,20 @@ struct esp_handle {
         esprun::PartOut out;
         PrePart pre;
     } genplan;
+    // Both plans above say that the next batch is cut into the same buckets as the last one.  What the bucket kernel's pair form
+    // (local_w.hip) resolves by look-back -- where every pair of buckets starts in the output -- then repeats as well unless
+    // structural zeros move: the offsets the last look-back flush of the plan found are kept (one tiny launch over the fresh
+    // colptr) and the next flush of the same plan runs the kernel's PREDICTED form on them, which checks every pair's count
+    // and stores nothing where it differs; the flush then runs again with the look-back kernel and records anew.
+    // plan_gen numbers the plans: it moves wherever genplan / rawplan is made or dropped (plan_made / drop_*_plan below).
+    u64 plan_gen = 1;
+    struct PredTable {
+        DevBuf tab;          // Sp + 1 offsets (u64): pair s writes [tab[s], tab[s + 1])
+        u64 gen = 0;         // the plan it belongs to (0: none)
+        int S = 0;           // buckets of that flush (Sp = (S + 1) / 2 pairs)
+        int misses = 0;      // flushes in a row whose prediction missed; 2: not tried again until the plan changes
+        int last = 0;        // esp_debug_last_predicted: 0 not tried, 1 served, 2 tried and missed
+    } pred;
     // esp_elements_keep_plan: the item order, the cell records and the segment table of the last esp_append_elements on an
     // empty buffer (cells of 3 / 4 nodes) are kept in buffers of their own, so that esp_append_elements_again -- the same
     // connectivity, new element matrices: a time step of an instationary / nonlinear code -- goes straight to the expansion
@@ -316,6 +330,17 @@ struct esp_handle {
 };
 
 extern thread_local std::string g_err;
+
+// a kept producer plan is made / dropped: the offsets kept for its flushes (esp_handle::PredTable) belong to no later plan
+static inline void plan_made(esp_handle *h) { h->plan_gen++; }
+static inline void drop_raw_plan(esp_handle *h) {
+    if (h->rawplan.valid) h->plan_gen++;
+    h->rawplan.valid = false;
+}
+static inline void drop_gen_plan(esp_handle *h) {
+    if (h->genplan.valid) h->plan_gen++;
+    h->genplan.valid = false;
+}
 
 // the pending entries changed: whatever was derived from them is stale
 static inline void pending_changed(esp_handle *h) {
@@ -641,7 +666,9 @@ static inline unsigned grid_for(i64 n, int threads) { return (unsigned)std::max<
 
 // ---- small helpers
 // no force_path, or one that pins the bucket kernel's form alone (42: one bucket per workgroup): every other choice automatic
-static inline bool paths_auto(const esp_handle *h) { return h->force_path == ESP_PATH_AUTO || h->force_path == ESP_PATH_NO_BUCKET_PAIRS; }
+static inline bool paths_auto(const esp_handle *h) {
+    return h->force_path == ESP_PATH_AUTO || h->force_path == ESP_PATH_NO_BUCKET_PAIRS || h->force_path == ESP_PATH_NO_PREDICTED_OFFSETS;
+}
 static inline bool windowed(const esp_handle *h) { return h->win_excl && (h->wc0 > 0 || h->wc1 < h->n); }
 
 // first entry and number of entries of the per-column arrays (colptr, colend: n+1 entries) a flush touches

@@ -115,6 +115,8 @@ struct Variant {
 constexpr int PAIR_ITEMS = 12;
 constexpr int PAIR_RUN = 12;
 constexpr u32 PAIR_REFUSED = 128u;  // Args::err: a pair the kernel does not take (the flush runs again with local_k)
+constexpr u32 PRED_MISS = 256u;     // Args::err: a pair of the PREDICTED form emitted another count than its table says, or its place
+                                    // lies outside the output arrays: it stored nothing (the flush runs again with pair_k)
 // enqueues the kernel; false when the combination has no instantiation
 bool launch(const Variant &v, unsigned grid, hipStream_t stream, const Args &a);
 bool launch_regular(const Variant &v, unsigned grid, hipStream_t stream, const Args &a);        // local_a.hip
@@ -126,6 +128,11 @@ bool launch_group(const Variant &v, unsigned grid, hipStream_t stream, const Arg
 bool launch_group_short(const Variant &v, unsigned grid, hipStream_t stream, const Args &a);    // local_g.hip
 bool launch_group3(const Variant &v, unsigned grid, hipStream_t stream, const Args &a);         // local_h.hip
 bool launch_pair(const Variant &v, unsigned grid, hipStream_t stream, const Args &a);           // local_w.hip
+// ... its PREDICTED form: pair s writes at pred[s] (a table of a.S + 1 offsets: the exclusive prefix sums the handle's last
+// flush of the same plan found) when it emits pred[s + 1] - pred[s] entries and they end within out_cap; no ticket, no look-back
+bool launch_pair_predicted(const Variant &v, unsigned grid, hipStream_t stream, const Args &a, const u64 *pred, u64 out_cap);
+// pred[s] = colptr[first column of pair s] - 1 for s < Sp, pred[Sp] = colptr[col_end] - 1: the table a look-back flush leaves
+void launch_pair_record(hipStream_t stream, const i64 *colptr, i64 col_end, int ncl_bits, int Sp, u64 *pred);
 
 
 }  // namespace esplocal

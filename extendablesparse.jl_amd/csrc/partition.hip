@@ -103,8 +103,8 @@ int32_t sort_pending_lsd(esp_handle *h, const u64 **sk, const double **sv) {
 
 
 int32_t chunk_arrays(esp_handle *h, i64 Ccap, int pb, ChunkArrays *out, bool keep_plan) {
-    if (!keep_plan) h->rawplan.valid = false;  // (whoever asks for the run tables is about to rewrite them)
-    h->genplan.valid = false;
+    if (!keep_plan) drop_raw_plan(h);  // (whoever asks for the run tables is about to rewrite them)
+    drop_gen_plan(h);
     const i64 NB = (i64)1 << pb;
     const i64 RM = Ccap * esprun::RMAX;
     size_t off = 0;
@@ -553,7 +553,7 @@ int32_t append_partitioned(esp_handle *h, const i64 *d_rows, const i64 *d_cols, 
             HIPCK(h, hipStreamSynchronize(h->stream));
             HIPCK(h, hipGetLastError());
             if (h->pin_scalar[0] != ~0ull) {
-                h->rawplan.valid = false;
+                drop_raw_plan(h);
                 FAIL(h, ESP_ERR_BOUNDS, "BoundsError: entry %llu of the batch has an index outside %lld x %lld (or a bad kind)",
                      (unsigned long long)h->pin_scalar[0], (long long)h->m, (long long)h->n);
             }
@@ -563,7 +563,7 @@ int32_t append_partitioned(esp_handle *h, const i64 *d_rows, const i64 *d_cols, 
                 Ee = rp.Ee;
                 fb = rp.fb, maxlen_c = rp.maxlen_c;
             } else {
-                h->rawplan.valid = false;  // (another stream: the full path below, which makes a plan of its own)
+                drop_raw_plan(h);  // (another stream: the full path below, which makes a plan of its own)
             }
         }
     }
@@ -601,6 +601,7 @@ int32_t append_partitioned(esp_handle *h, const i64 *d_rows, const i64 *d_cols, 
     np.kind = kind, np.K = K, np.pb = pb, np.key_bytes = kb;
     np.fb = fb, np.maxlen_c = maxlen_c;
     np.base = h->win_base, np.span = h->win_span, np.Ee = Ee;
+    plan_made(h);
     }
     h->last_plan_reused = reused ? 1 : 0;
     h->runs_penalty = 0;
@@ -727,8 +728,8 @@ int32_t append_first_pass(esp_handle *h, const i64 *d_rows, const i64 *d_cols, c
     const int bits0 = (planned + npass - 1) / npass;
     if (K - bits0 < h->L.rb) return ESP_OK;  // (the digit must follow from the column alone)
     CK(reserve_append(h, count));
-    h->rawplan.valid = false;
-    h->genplan.valid = false;
+    drop_raw_plan(h);
+    drop_gen_plan(h);
     CK(ensure(h, h->misc, 256));
     unsigned long long *d_err = (unsigned long long *)h->misc.p;
     unsigned long long *d_maxlen = (unsigned long long *)h->misc.p + 24;
@@ -797,8 +798,8 @@ int32_t append_first_pass(esp_handle *h, const i64 *d_rows, const i64 *d_cols, c
 }
 
 int32_t sort_msd(esp_handle *h, Sorted *out) {
-    h->rawplan.valid = false;  // (the segment tables are rewritten)
-    h->genplan.valid = false;
+    drop_raw_plan(h);  // (the segment tables are rewritten)
+    drop_gen_plan(h);
     const esp_handle::PrePass pre0 = h->prepass;
     h->prepass.valid = false;
     const i64 E = h->count;

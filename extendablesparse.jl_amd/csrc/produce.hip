@@ -122,6 +122,7 @@ extern "C" int32_t esp_generate_fdrand_range(esp_handle *h, int64_t nx, int64_t 
             np.out = ps.out;
             np.pre = h->pre;
             np.valid = true;
+            plan_made(h);
         }
     }
     if (!took) {  // stream order (the PART launch left without a store when the stream turned out not to be pre-sorted)

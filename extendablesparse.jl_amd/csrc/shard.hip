@@ -10,7 +10,7 @@ int32_t shard_prepare(esp_handle *h, int P, espradix::Pass *out) {
     h->shard_user = true;
     CK(pending_materialize(h));
     h->part_valid = h->part_assembled = false;  // (its tables share scratch arrays with this path)
-    h->genplan.valid = h->rawplan.valid = false;  // (seg[1] and the histogram arrays are rewritten: a kept producer plan would read them)
+    drop_gen_plan(h), drop_raw_plan(h);  // (seg[1] and the histogram arrays are rewritten: a kept producer plan would read them)
     if ((double)h->n * (double)P >= 9.0e18) FAIL(h, ESP_ERR_UNSUPPORTED, "shards: n*nshards overflows");
     const i64 E = h->count;
     int bits = 1;
@@ -411,6 +411,23 @@ extern "C" int32_t esp_debug_last_local_small(const esp_handle *h, int32_t *smal
 extern "C" int32_t esp_debug_last_bucket_pairs(const esp_handle *h, int32_t *on) {
     if (!h || !on) return ESP_ERR_INVALID;
     *on = h->last_pair;
+    return ESP_OK;
+}
+extern "C" int32_t esp_debug_last_predicted(const esp_handle *h, int32_t *state) {
+    if (!h || !state) return ESP_ERR_INVALID;
+    *state = h->pred.last;
+    return ESP_OK;
+}
+extern "C" int32_t esp_debug_spoil_predicted(esp_handle *h) {
+    if (!h) return ESP_ERR_INVALID;
+    if (h->pred.gen == 0 || !h->pred.tab.p || h->pred.S < 1) FAIL(h, ESP_ERR_STATE, "esp_debug_spoil_predicted: the handle holds no offset table");
+    (void)hipSetDevice(h->device);
+    u64 *at = (u64 *)h->pred.tab.p + ((h->pred.S + 1) / 2) / 2;
+    HIPCK(h, hipMemcpyAsync(h->pin_scalar, at, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    h->pin_scalar[0] += 1;
+    HIPCK(h, hipMemcpyAsync(at, h->pin_scalar, 8, hipMemcpyHostToDevice, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
     return ESP_OK;
 }
 extern "C" int32_t esp_debug_last_shard_source(const esp_handle *h, int32_t *kind) {

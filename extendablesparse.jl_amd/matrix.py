@@ -897,6 +897,16 @@ class ExtendableSparseMatrix:
         self._d.ck(self._d.lib.esp_debug_last_bucket_pairs(self._d.h, C.byref(p)))
         return p.value
 
+    def debug_last_predicted(self):
+        """What the last flush did with the pair kernel's predicted offsets: 0 not tried, 1 served, 2 tried and missed"""
+        p = C.c_int32()
+        self._d.ck(self._d.lib.esp_debug_last_predicted(self._d.h, C.byref(p)))
+        return p.value
+
+    def debug_spoil_predicted(self):
+        """Test hook (esp_debug_spoil_predicted): the next flush that tries the kept offset table misses."""
+        self._d.ck(self._d.lib.esp_debug_spoil_predicted(self._d.h))
+
     def debug_last_lazy_items(self):
         """1: the last flush's bucket kernel formed its updates from sorted item records (the expansion never ran)"""
         p = C.c_int32()

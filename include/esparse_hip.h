@@ -589,6 +589,10 @@ typedef enum {
                                         shard's producer too (its own range: 2^fb buckets per digit of the exchange plan)      */
     ESP_PATH_NO_BUCKET_PAIRS = 42,   /* never the PAIR form of the small bucket kernel (two producer buckets per workgroup, see
                                         esp_debug_last_bucket_pairs): one bucket per workgroup, local_k's small variant       */
+    ESP_PATH_NO_PREDICTED_OFFSETS = 43, /* never the PREDICTED form of the pair kernel (a flush that repeats the producer plan of
+                                        the handle's last flush takes every pair's output offset from the table that flush left, see
+                                        esp_debug_last_predicted): always the ticket + look-back form; no table is recorded.  Counts
+                                        as automatic for every other choice, like 42                                          */
     ESP_PATH_NO_PLAN_REUSE = 31      /* esp_append_device / esp_commit of one kind on an empty buffer always count their columns
                                         (never the run lists of the previous, identical-looking batch)                      */
 } esp_debug_path;
@@ -633,6 +637,15 @@ int32_t esp_debug_last_local_small(const esp_handle *h, int32_t *small);
  * keys of one kind, at most 12 pending entries per column; a pair with a longer column run or rows spread over 2^19 or more sends
  * the flush, and the handle's later ones, to the one-bucket kernel); esp_debug_force_path(42): never */
 int32_t esp_debug_last_bucket_pairs(const esp_handle *h, int32_t *on);
+/* what the last flush did with the pair kernel's PREDICTED form: 0 not tried (no table for the batch's plan: the plan was not
+ * reused, entries lie behind the batch, the table belongs to another plan, two predictions in a row missed), 1 served (every pair
+ * emitted the count the table of the handle's last flush of this plan says: no ticket, no look-back), 2 tried and missed (some
+ * pair's count differs -- structural zeros moved; the pairs that differ stored nothing, the flush ran again with the look-back
+ * form and left a new table).  esp_debug_last_bucket_pairs reports 1 in all three cases; esp_debug_force_path(43): never tried */
+int32_t esp_debug_last_predicted(const esp_handle *h, int32_t *state);
+/* test hook: adds 1 to the middle entry of the kept offset table, so that the next flush that tries it misses (ESP_ERR_STATE
+ * when the handle holds no table) */
+int32_t esp_debug_spoil_predicted(esp_handle *h);
 /* 1 when the bucket kernel of the last flush formed its updates from the sorted ITEM records of an item partition
  * (esp_generate_fem in a shuffled order, esp_append_elements on an empty buffer of a fresh matrix): the expansion -- every
  * update stored once at its bucket position, read again by the bucket kernel -- never ran (csrc/group3_items.hpp);

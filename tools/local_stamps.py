@@ -18,6 +18,8 @@ n = 256
 fdim = int(os.environ.get("ESP_STAMP_FEM_DIM", "3"))
 N = fem ** fdim if fem else n ** 3
 A = esp.ExtendableSparseMatrix(N, N, capacity_hint=0 if fem else 12 * n * n * (n - 1) + 6 * n * n)
+if os.environ.get("ESP_STAMP_FORCE_PATH"):
+    A.debug_force_path(int(os.environ["ESP_STAMP_FORCE_PATH"]))
 reasm = int(os.environ.get("ESP_STAMP_REASM", "0"))   # 1: stamps of the SECOND flush (re-assembly over the existing CSC)
 cfg3 = int(os.environ.get("ESP_STAMP_CFG3", "0"))     # 1: config 3 -- stamps of the LAST bucket kernel of its flush (the tail's)
 if cfg3:
@@ -49,6 +51,7 @@ for it in range(3):
         os.environ["ESP_LOCAL_STAMPS"] = "gpurun_out/stamps.bin"
     A.flush()
 st16 = np.fromfile("gpurun_out/stamps.bin", dtype=np.uint64).reshape(-1, 16).astype(np.int64)
+st16 = st16[st16[:, 0] > 0]   # (the pair kernels stamp S / 2 of the S rows)
 st = st16[:, :8]
 d = np.diff(st, axis=1) * 0.01  # 100 MHz ticks -> us
 names = ["segment known -> loads arrived", "column count + scan", "scatter to LDS", "sort (+early look-back) + fold",
@@ -60,9 +63,15 @@ span = (st[:, 7].max() - st[:, 0].min()) * 0.01
 print("kernel span %.1f us, %.0f segments resident on average" % (span, (st[:, 7] - st[:, 0]).sum() * 0.01 / span))
 # inside "sort + fold" (register tier with early publication): 3 = run start, 8 = sorted + counted,
 # 9 = barrier passed, 10 = fold done (wave 0), 11 = look-back done (last wave), 4 = phase end
+# (pair_pred_k, the predicted form the third flush of this script runs, has no look-back and leaves stamp 11 empty;
+# ESP_STAMP_FORCE_PATH=43 pins the look-back form pair_k)
 if st16[:, 8].any():
-    for nm, a, b in (("sort + count (wave 0)", 3, 8), ("barrier wait", 8, 9), ("fold (wave 0)", 9, 10),
-                     ("look-back (last wave)", 9, 11), ("phase end after fold", 10, 4), ("phase end after look-back", 11, 4)):
+    lb = st16[:, 11].any()
+    if not lb:
+        print("  no look-back stamps: the predicted form ran")
+    for nm, a, b in (("sort + count (wave 0)", 3, 8), ("barrier wait", 8, 9), ("fold (wave 0)", 9, 10)) + \
+                    ((("look-back (last wave)", 9, 11), ("look-back wait behind the fold (last wave)", 10, 11)) if lb else ()) + \
+                    (("phase end after fold", 10, 4),) + ((("phase end after look-back", 11, 4),) if lb else ()):
         x = (st16[:, b] - st16[:, a]) * 0.01
         print("  %-36s median %6.2f  p90 %6.2f" % (nm, np.median(x), np.percentile(x, 90)))
 if st16[:, 14].any():   # group tier: 2 = counts scanned, 12 = keys scattered + row range known, 13 = sorted (wave 0), 14 = folded (wave 0)
