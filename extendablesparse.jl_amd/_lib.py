@@ -123,6 +123,7 @@ SIGNATURES = {
     "esp_debug_last_shard_source": (i32, [vp, P(i32)]),
     "esp_debug_last_local_small": (i32, [vp, P(i32)]),
     "esp_debug_last_bucket_pairs": (i32, [vp, P(i32)]),
+    "esp_debug_last_bucket_cut": (i32, [vp, P(i32), P(i32)]),
     "esp_debug_last_predicted": (i32, [vp, P(i32)]),
     "esp_debug_spoil_predicted": (i32, [vp]),
     "esp_debug_last_lazy_items": (i32, [vp, P(i32)]),

@@ -469,6 +469,8 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
         CK(read_back());
     }
     h->last_pair = used_pair ? 1 : 0;
+    h->last_cl_bits = a.cl_bits;
+    h->last_buckets = S;
     h->last_lazy_items = 0;
     h->last_sum_join = 0;
     if (st.lazy) {

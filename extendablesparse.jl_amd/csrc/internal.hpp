@@ -68,6 +68,7 @@ struct esp_handle {
     int runs_skip = 0, runs_penalty = 0;  // back-off after a stream turned out not to be pre-sorted
     bool g3_off = false;                  // a segment of this handle's matrix did not fit the three-workgroup group kernel: not tried again
     bool pair_off = false;                // ... a pair of buckets did not fit the small variant's pair form (pair_k): not tried again
+    int last_cl_bits = -1, last_buckets = 0;  // the cut the last flush's bucket kernel worked on (esp_debug_last_bucket_cut)
     int last_pair = 0;                    // the last flush's bucket kernel was pair_k (esp_debug_last_bucket_pairs)
     bool hits_off = false;                // the re-assembly form of the group kernel met a batch that was no re-assembly of the stored pattern: not tried again (until reset!)
     bool g3_wide = false;                 // ... for its rows alone (spread over more than 2^18): the kernel's wide form serves this handle

@@ -413,6 +413,12 @@ extern "C" int32_t esp_debug_last_bucket_pairs(const esp_handle *h, int32_t *on)
     *on = h->last_pair;
     return ESP_OK;
 }
+extern "C" int32_t esp_debug_last_bucket_cut(const esp_handle *h, int32_t *cl_bits, int32_t *buckets) {
+    if (!h || !cl_bits || !buckets) return ESP_ERR_INVALID;
+    *cl_bits = h->last_cl_bits;
+    *buckets = h->last_buckets;
+    return ESP_OK;
+}
 extern "C" int32_t esp_debug_last_predicted(const esp_handle *h, int32_t *state) {
     if (!h || !state) return ESP_ERR_INVALID;
     *state = h->pred.last;

@@ -897,6 +897,12 @@ class ExtendableSparseMatrix:
         self._d.ck(self._d.lib.esp_debug_last_bucket_pairs(self._d.h, C.byref(p)))
         return p.value
 
+    def debug_last_bucket_cut(self):
+        """(cl_bits, buckets) of the last flush's bucket kernel: a bucket of the table holds 2^cl_bits columns"""
+        c, b = C.c_int32(), C.c_int32()
+        self._d.ck(self._d.lib.esp_debug_last_bucket_cut(self._d.h, C.byref(c), C.byref(b)))
+        return c.value, b.value
+
     def debug_last_predicted(self):
         """What the last flush did with the pair kernel's predicted offsets: 0 not tried, 1 served, 2 tried and missed"""
         p = C.c_int32()

@@ -637,6 +637,9 @@ int32_t esp_debug_last_local_small(const esp_handle *h, int32_t *small);
  * keys of one kind, at most 12 pending entries per column; a pair with a longer column run or rows spread over 2^19 or more sends
  * the flush, and the handle's later ones, to the one-bucket kernel); esp_debug_force_path(42): never */
 int32_t esp_debug_last_bucket_pairs(const esp_handle *h, int32_t *on);
+/* the cut the bucket kernel of the last flush worked on: column bits of one bucket of the table (a bucket holds 2^cl_bits columns;
+ * -1: the buckets are no whole columns) and the number of buckets -- the pair form takes two neighbouring ones per workgroup */
+int32_t esp_debug_last_bucket_cut(const esp_handle *h, int32_t *cl_bits, int32_t *buckets);
 /* what the last flush did with the pair kernel's PREDICTED form: 0 not tried (no table for the batch's plan: the plan was not
  * reused, entries lie behind the batch, the table belongs to another plan, two predictions in a row missed), 1 served (every pair
  * emitted the count the table of the handle's last flush of this plan says: no ticket, no look-back), 2 tried and missed (some

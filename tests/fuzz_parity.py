@@ -4,7 +4,11 @@ patterns, stream orders (sorted / clustered / shuffled), multi-flush sequences, 
 every result compared bit for bit with the CPU oracle.  usage: tests/fuzz_parity.py [seconds] [seed]   (test infrastructure: it runs the CPU oracle)
 ESP_FUZZ_FOCUS=k32: shapes and batches that reach the 4-byte keys / UPDATE-only fold of the bucket kernel;
 ESP_FUZZ_FOCUS=elements: only the element-level append (esp_append_elements) and Base.sum (esp_flush_sum) cases;
-ESP_FUZZ_FOCUS=sum: only Base.sum over buffers of per-entry calls (esp_flush_sum's general path)."""
+ESP_FUZZ_FOCUS=sum: only Base.sum over buffers of per-entry calls (esp_flush_sum's general path);
+ESP_FUZZ_FOCUS=pairs: only shapes inside the window of the pair bucket kernels (csrc/local_w.hip: many columns, one kind, ascending
+columns, column runs of 0 .. 12 and now and then 13, rows near the diagonal or up to 2^19 and more away, a random
+esp_debug_plan_cap), 2 .. 4 batches over the same columns on one handle with reset! between them (new values, other rows, other
+zeros); the run fails unless it saw the pair kernel serve, refuse, the predicted form serve and miss at least once each."""
 import os
 import sys
 import time
@@ -20,6 +24,7 @@ torch.cuda.init()
 from esparse_loader import load  # noqa: E402
 from oracle import oracle as orc  # noqa: E402
 from refmodel import assert_csc_equal  # noqa: E402
+import pair_streams  # noqa: E402
 
 esp = load()
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
@@ -28,6 +33,19 @@ rng = np.random.default_rng(seed)
 t_end = time.time() + budget
 cases = 0
 paths = {}
+FOCUS = os.environ.get("ESP_FUZZ_FOCUS")
+pair_cover = {"pair_served": 0, "pair_refused": 0, "predicted_served": 0, "predicted_missed": 0}
+
+
+def pair_state(d):
+    """(esp_debug_last_bucket_pairs, esp_debug_last_predicted) of a device handle: whether a pair kernel ran, and its predicted form"""
+    import ctypes as C
+    a, b = C.c_int32(), C.c_int32()
+    d.ck(d.lib.esp_debug_last_bucket_pairs(d.h, C.byref(a)))
+    d.ck(d.lib.esp_debug_last_predicted(d.h, C.byref(b)))
+    return a.value, b.value
+
+
 def generator_case():
     """Device-side producers: the producer-side partition (append = partition), its fall-backs and what follows it --
     a second producer call, a host append, a flush over the stored pattern -- on grids whose lines and planes do not line
@@ -44,7 +62,7 @@ def generator_case():
     N = nx * ny * nz
     if N > 3000000:
         return None
-    force = int(rng.choice([0, 0, 0, 0, 14, 15, 16, 18, 13, 4, 19, 31, 40]))
+    force = int(rng.choice([0, 0, 0, 0, 14, 15, 16, 18, 13, 4, 19, 31, 40, 42, 43]))
     kind = int(rng.choice([1, 1, 2]))
     mode = int(rng.choice([0, 1, 2]))
     A = esp.ExtendableSparseMatrix(N, N)
@@ -102,7 +120,7 @@ def generator_case():
             print("FLUSH FAILED generator case", dict(nx=nx, ny=ny, nz=nz, force=force, kind=kind, mode=mode, rnd=rnd, how=str(how), seed=seed))
             raise
         O.flush()
-        key = ("gen", A.debug_last_partition(), A.debug_last_key_bytes(), A.debug_last_local_small())
+        key = ("gen", A.debug_last_partition(), A.debug_last_key_bytes(), A.debug_last_local_small()) + pair_state(A._d)
         paths[key] = paths.get(key, 0) + 1
         try:
             assert_csc_equal(A.sparse().arrays(), O.arrays())
@@ -143,7 +161,7 @@ def fem_case():
             print("FLUSH FAILED fem case", dict(dim=dim, npd=npd, order=order, force=force, rnd=rnd, seed=seed))
             raise
         O.flush()
-        key = ("fem", A.debug_last_partition(), A.debug_last_key_bytes(), A.debug_last_local_small())
+        key = ("fem", A.debug_last_partition(), A.debug_last_key_bytes(), A.debug_last_local_small()) + pair_state(A._d)
         paths[key] = paths.get(key, 0) + 1
         try:
             assert_csc_equal(A.sparse().arrays(), O.arrays())
@@ -218,7 +236,8 @@ def elements_case():
                 print("MISMATCH elements/sum case", dict(nloc=nloc, m=m, n=n, nc=nc, span=span, kind=kind, p=p, rnd=rnd, sub=sub, diag=dg is not None,
                                                          lazy=lz.value, case=cases))
                 raise
-        paths[("elem_sum", p)] = paths.get(("elem_sum", p), 0) + 1
+        key = ("elem_sum", p) + pair_state(home._d)
+        paths[key] = paths.get(key, 0) + 1
         return True
     if len(I) > 3000000 and nloc * nloc > 40:
         return None                                                       # (the oracle's list walks: keep the case short)
@@ -252,7 +271,7 @@ def elements_case():
             print("FLUSH FAILED elements case", dict(nloc=nloc, m=m, n=n, nc=nc, span=span, kind=kind, force=force, rnd=rnd, how=str(how)))
             raise
         O.flush()
-        key = ("elem", nloc, A.debug_last_partition(), A.debug_last_key_bytes(), A.debug_last_local_small())
+        key = ("elem", nloc, A.debug_last_partition(), A.debug_last_key_bytes(), A.debug_last_local_small()) + pair_state(A._d)
         paths[key] = paths.get(key, 0) + 1
         try:
             assert_csc_equal(A.sparse().arrays(), O.arrays())
@@ -320,13 +339,103 @@ def sum_case():
         except AssertionError:
             print("MISMATCH sum case", dict(p=p, m=m, n=n, shape=shape, rnd=rnd, one_by_one=one_by_one, batched=flag.value, case=cases))
             raise
-        key = ("sum", shape, flag.value if nonempty else -1)
+        key = ("sum", shape, flag.value if nonempty else -1) + pair_state(home._d)
         paths[key] = paths.get(key, 0) + 1
+    return True
+
+
+def pairs_case():
+    """Shapes inside the pair kernels' window (csrc/flush.hip, pair_ok; tests/pair_streams.py): more than 2^16 columns, one kind,
+    ascending columns, 7.2 .. 12 entries per column on average in runs of 0 .. 12 (one pair of buckets filled to the brim), now and
+    then a run of 13 in a light bucket; rows near the diagonal, or (m = 2^21) a few of them 2^18 .. 2^19 and more away; a random
+    esp_debug_plan_cap (buckets of 128 .. 8 columns); force 42 / 43 now and then.  2 .. 4 batches over the same columns on one
+    handle with reset! between them: new values / rows moved by one / other zeros; every flush against the oracle.  The first cases
+    of a run take the four profiles in turn, so that a short run meets every outcome."""
+    profiles = ("values", "zeros", "long_run", "span")
+    profile = profiles[cases % 4] if cases < 8 else str(rng.choice(profiles))
+    n = int(rng.choice([70000, 120000, 200000, 300000])) + int(rng.integers(0, 600))
+    wide = profile == "span" or rng.random() < 0.25
+    m = (1 << 21) if wide else n + 16
+    kind = int(rng.choice([0, 1, 1, 2, 3]))
+    p12, p0 = float(rng.uniform(0.5, 0.8)), float(rng.uniform(0.0, 0.08))
+    L = rng.choice(13, n, p=[p0] + [(1.0 - p0 - p12) / 11.0] * 11 + [p12]).astype(np.int64)
+    for _ in range(int(rng.integers(0, 4))):                 # empty stretches, aligned to buckets or not
+        a = int(rng.integers(0, n - 1100))
+        if rng.random() < 0.5:
+            a -= a % 256
+        L[a:a + int(rng.choice([256, 300, 512, 1024]))] = 0
+    a = 512 * int(rng.integers(0, n // 512))
+    L[a:a + 512] = 12
+    expect_refused = False
+    if profile == "long_run" or rng.random() < 0.08:
+        c = int(rng.integers(0, n - 20))
+        L[c + 1:c + 17] = 4
+        L[c] = 13
+        expect_refused = True
+    J = np.repeat(np.arange(1, n + 1, dtype=np.int64), L)
+    cnt = len(J)
+    I = np.clip(J + 8 + rng.integers(-3, 4, cnt), 1, m)
+    if wide:
+        for _ in range(int(rng.integers(1, 4))):
+            e = int(rng.integers(0, cnt))
+            d = int(rng.choice([2 ** 18 - 600, 2 ** 18, 2 ** 18 + 600, 2 ** 19 - 1100, 2 ** 19, 2 ** 19 + 600]))
+            I[e] = J[e] + d
+            expect_refused = expect_refused or d >= 2 ** 19
+    cap_cols = int(rng.choice([0, 0, 0, 128, 64, 32, 8]))
+    force = int(rng.choice([0, 0, 0, 0, 42, 43]))
+    how = str(rng.choice(["host", "device"]))
+    sub = rng.random() < 0.25
+    A = esp.ExtendableSparseMatrix(m, n)
+    A.debug_force_path(force)
+    if cap_cols:
+        A.debug_plan_cap(pair_streams.plan_cap_for(cnt / n, cap_cols))
+    Z = rng.random(cnt) < 0.1
+    Ik = I
+    for k in range(int(rng.integers(2, 5))):
+        change = "values" if k == 0 else {"values": str(rng.choice(["values", "rows"])), "zeros": "zeros"}.get(profile, str(rng.choice(["values", "rows", "zeros"])))
+        if change == "rows":
+            Ik = Ik + 1
+        elif change == "zeros":
+            Z = rng.random(cnt) < 0.1
+        V = rng.standard_normal(cnt)
+        V[Z] = 0.0
+        V[rng.random(cnt) < 0.01] = -0.0
+        A.reset()
+        if how == "host":
+            A.append(kind, Ik, J, V, op="-" if sub else "+")
+        else:
+            dev = [torch.from_numpy(np.ascontiguousarray(x)).cuda() for x in (Ik, J, V)]
+            A.append_device(kind, *dev, op="-" if sub else "+")
+        info = dict(profile=profile, m=m, n=n, kind=kind, cnt=cnt, cap_cols=cap_cols, force=force, how=how, sub=sub, batch=k, change=change, case=cases)
+        try:
+            A.flush()
+        except Exception:
+            print("FLUSH FAILED seed", seed, "pairs case", info)
+            raise
+        pairs, pred = pair_state(A._d)
+        cut = A.debug_last_bucket_cut()[0]
+        if os.environ.get("ESP_FUZZ_VERBOSE"):
+            print("pairs", info, "pair kernel", pairs, "predicted", pred, "cl_bits", cut, flush=True)
+        key = ("pairs", profile, A.debug_last_key_bytes(), A.debug_last_local_small(), cut, pairs, pred)
+        paths[key] = paths.get(key, 0) + 1
+        pair_cover["pair_served"] += pairs == 1
+        pair_cover["pair_refused"] += pairs == 0 and force != 42 and expect_refused and A.debug_last_local_small() == 1
+        pair_cover["predicted_served"] += pred == 1
+        pair_cover["predicted_missed"] += pred == 2
+        try:
+            assert_csc_equal(A.sparse().arrays(), pair_streams.oracle_csc(orc, m, n, kind, Ik, J, V, sub=sub))
+        except AssertionError:
+            print("MISMATCH seed", seed, "pairs case", info, "pair kernel", pairs, "predicted", pred, "cl_bits", cut)
+            raise
     return True
 
 
 max_cases = int(os.environ.get("ESP_FUZZ_MAXCASES", "0"))
 while time.time() < t_end and (max_cases == 0 or cases < max_cases):
+    if FOCUS == "pairs":
+        if pairs_case():
+            cases += 1
+        continue
     if (rng.random() < 0.08 or os.environ.get("ESP_FUZZ_FOCUS") == "sum") and os.environ.get("ESP_FUZZ_FOCUS") not in ("k32", "elements"):
         if sum_case():
             cases += 1
@@ -354,7 +463,7 @@ while time.time() < t_end and (max_cases == 0 or cases < max_cases):
     A = esp.ExtendableSparseMatrix(m, n)
     A.debug_plan_cap(plan_cap)
     O = orc.ExtendableSparseMatrix(m, n)
-    force = int(rng.choice([0, 0, 0, 2, 3, 4, 5, 12, 13, 14, 15, 17, 18, 23]))
+    force = int(rng.choice([0, 0, 0, 2, 3, 4, 5, 12, 13, 14, 15, 17, 18, 23, 42, 43]))
     if focus:
         force = int(rng.choice([0, 0, 13, 15, 4, 18]))
     A.debug_force_path(force)
@@ -403,7 +512,7 @@ while time.time() < t_end and (max_cases == 0 or cases < max_cases):
             raise
         O.flush()
         key = (A.debug_last_path(), A.debug_last_partition(), A.debug_last_key_bytes(), int(A.debug_last_fold_update()),
-               A.debug_last_local_small())
+               A.debug_last_local_small()) + pair_state(A._d)
         paths[key] = paths.get(key, 0) + 1
         try:
             assert_csc_equal(A.sparse().arrays(), O.arrays())
@@ -411,4 +520,10 @@ while time.time() < t_end and (max_cases == 0 or cases < max_cases):
             print("MISMATCH seed", seed, "case", cases, dict(m=m, n=n, force=force, flush=f, cnt=cnt, per_col=per_col, order=str(order)))
             raise
     cases += 1
-print("fuzz ok: cases", cases, "paths (pipeline, partition, key bytes, update-only fold, small bucket kernel | gen, partition, key bytes, small):", paths)
+if FOCUS == "pairs":
+    missing = [k for k, v in pair_cover.items() if not v]
+    print("pairs focus: flushes per outcome", {k: int(v) for k, v in pair_cover.items()})
+    if missing:
+        print("fuzz FAILED: the pairs focus ended without a flush that was", missing, "paths", paths)
+        sys.exit(1)
+print("fuzz ok: cases", cases, "paths (pipeline, partition, key bytes, update-only fold, small bucket kernel, pair kernel, predicted | gen, partition, key bytes, small, pair kernel, predicted):", paths)
