@@ -9,6 +9,7 @@
 //   consumers.hip  what reads or edits the assembled CSC: getindex, dropzeros, pattern hash, mul!, Dirichlet, Jacobi / ILU0
 //   precon.hip     the point preconditioners' update! / ldiv! (esp_precon_*) and simple! (esp_simple) on the device CSC
 //   iluam.hip      ILUAMPreconditioner: level analysis, level-scheduled ILU(0) factorization and triangular solves
+//   krylov.hip     preconditioned conjugate gradients (esp_cg): fused vector kernels, ordered dot products, scalars on the device
 //   matops.hip     the algebra of assembled matrices on the device: A*B (esp_matmul), A+B / A-B (esp_add), Diagonal scaling
 //   linalg.hip     transpose (esp_transpose), transpose(A)*x (esp_mul_transpose), issymmetric, opnorm, norm on the device CSC
 //   local_*.hip    the instantiations of the bucket kernel (local.hpp; local_h.hip: group3.hpp, the group tier with three workgroups per CU;
@@ -321,6 +322,11 @@ struct esp_handle {
     int matmul_tier = 0;   // esp_debug_matmul_tier: 0 automatic, 1 fused where it fits, 2 generic only (matops.hip)
     int transpose_path = 0;  // esp_debug_transpose_path: 0 automatic, 1 the ESP_COO flush, 2 the counting sort (linalg.hip)
     int live_precons = 0;  // esp_precon objects bound to this handle (precon.hip): esp_destroy refuses while any is alive
+    // esp_cg's work vectors (krylov.hip), sized on first use: residual, search direction, Pl \ r and A*u, the partial sums of the
+    // three dot products, and the device copies of host b / x
+    struct Krylov {
+        DevBuf r, u, c, part, hb, hx;
+    } kry;
     // timing
     bool timing = false;
     int timing_level = 2;
@@ -539,6 +545,10 @@ int32_t split_build(esp_precon *p, bool reversed);
 int32_t iluam_update(esp_precon *p, bool rebuild);
 int32_t iluam_solve(esp_precon *p, const double *v, double *dst, bool sub);
 void iluam_release(esp_precon *p);
+// precon.hip, for krylov.hip: the checks in front of a solve (p == nullptr: those of the handle alone); pass 1 of ILU0's ldiv!
+// into the scratch p->u1 (pass 2 is krylov.hip's own: it carries the dot product)
+int32_t solver_ready(esp_handle *h, esp_precon *p, const char *what);
+void ilu0_lower_launch(esp_precon *p, const double *v);
 int32_t ensure(esp_handle *h, DevBuf &b, size_t need, bool keep = false);
 void release(DevBuf &b);
 void release_all(esp_handle *h);

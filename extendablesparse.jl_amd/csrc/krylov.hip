@@ -1,0 +1,324 @@
+// krylov.hip -- libesparse_hip: preconditioned conjugate gradients (esp_cg) on the device CSC
+// (see internal.hpp for the map of the translation units)
+//
+// The algorithm is IterativeSolvers.jl's cg! with a left preconditioner (its PCGIterable).  That package is not part of the
+// reference tree: the statement sequence below is RESTATED from its documented behaviour, not read from its source.
+//
+//   cg!(x, A, b; Pl, abstol = 0, reltol = sqrt(eps), maxiter = n, initially_zero)
+//     u = 0;  rho = 1
+//     r = b                     (initially_zero)   |   c = A*x;  r = b - c   (x given)
+//     residual = norm(r);  tol = max(reltol*residual, abstol)
+//     for iteration = 1, 2, ...   while iteration-1 < maxiter and not residual <= tol:
+//         c = Pl \ r
+//         rho_prev = rho;  rho = dot(c, r);  beta = rho/rho_prev
+//         u = c + beta*u                           (the product rounded, then the sum)
+//         c = A*u                                  (mul! exactly as esp_mul: 0 + the row's products in increasing column)
+//         alpha = rho / dot(u, c)
+//         x = x + alpha*u;   r = r - alpha*c;   residual = norm(r)
+//     converged = residual <= tol
+//
+// `not residual <= tol` is `residual > tol` for every number; a NaN residual (a breakdown: dot(u, c) = 0, an indefinite matrix)
+// is no error and does not stop the loop, which then ends at maxiter, as the package's does.  Every division is a true double
+// division, no product and sum is contracted.
+// DEVIATION: without Pl the package switches to its unpreconditioned iterator (the same in exact arithmetic, not in rounding);
+// here Pl = Identity runs the statements above with c = r (no copy is made: the kernels read r in c's place).
+//
+// The summation shape.  The package's dot and norm are BLAS calls whose order of summation is not defined; here every dot
+// product (norm(r) = sqrt(dot(r, r))) is ONE fixed-shape sum that depends on n alone:
+//   level 0  the products p[i] = a[i]*b[i] in chunks of 256 consecutive i (the last one padded with +0.0); a chunk is folded by
+//            the tree  for w = 128, 64, ..., 1: s[t] = s[t] + s[t + w] (t < w);  partial0[q] = s[0]
+//   level 1  the same tree over groups of 256 consecutive partial0 (padded with +0.0): partial1[g]
+//   level 2  lane t of 256 adds partial1[t], partial1[t + 256], ... in that order to 0.0, then the same tree over the lanes
+// (one value per lane up to n = 2^24).  So x, r and the whole residual history are identical run to run and bit-identical to
+// tests/cg_model.c, which restates the statements and this shape as plain loops; against the package itself they agree to
+// the rounding of the dot products only.  The sums of squares overflow for entries above about 1e154, where nrm2 would not.
+//
+// Kernels of one iteration (ILU0; Jacobi and Identity have one launch in place of the first two, ILUAM its level launches
+// and a dot kernel):
+//   row_chain_k<ILU_LOWER>   pass 1 of ldiv! (precon.hip, unchanged)
+//   row_dot_k<UPPER_DOT>     pass 2, c[i] stored, level 0 of dot(c, r)
+//   fold_k                   level 1
+//   direction_k              level 2 of rho (and of rho_prev) redone by every workgroup, beta = rho/rho_prev, u = c + beta*u
+//   row_dot_k<MUL_DOT>       c = A*u over the row-wise index, level 0 of dot(u, c)
+//   fold_k
+//   update_k                 level 2 of rho and of dot(u, c) redone, alpha, x += alpha*u, r -= alpha*c, level 0 of dot(r, r)
+//   fold_k
+//   finish_k                 level 2 of dot(r, r) -> one double, read back through pin_scalar; the host takes the square root
+//                            (correctly rounded on both sides of the comparison with the model) and runs the stopping test
+// A value crosses workgroups only at a kernel boundary: no flags, no grid barrier, no fence.  rho_prev is not kept in a slot:
+// the partial1 array of rho alternates between two places, and the first iteration is told that rho_prev = 1.
+#include "internal.hpp"
+
+namespace {
+
+constexpr int KT = 256;       // threads of every kernel = rows / elements of a chunk of the summation shape
+constexpr int KCAP = 2048;    // part entries a workgroup stages in LDS, as precon.hip's row kernels
+constexpr unsigned KGRID = 2048;  // workgroups of the grid-stride vector kernels (256 CUs x 8)
+
+// the tree of the summation shape over the 256 values v of a workgroup; the sum in thread 0.  The steps w = 128 and 64 go
+// through LDS, w = 32 .. 1 pair the lanes of wave 0 with each other: the same pairs in the same order.
+__device__ __forceinline__ double tree256(double v, double *sred) {
+    const int t = threadIdx.x;
+    sred[t] = v;
+    __syncthreads();
+    if (t < 128) sred[t] = sred[t] + sred[t + 128];
+    __syncthreads();
+    double a = 0.0;
+    if (t < 64) {
+        a = sred[t] + sred[t + 64];
+        for (int w = 32; w > 0; w >>= 1) a = a + __shfl_down(a, w, 64);
+    }
+    return a;
+}
+// level 2 from the partial1 array, the result in every thread (sred is free again on return)
+__device__ __forceinline__ double level2(const double *__restrict__ p1, i64 nb1, double *sred) {
+    double a = 0.0;
+    for (i64 q = threadIdx.x; q < nb1; q += KT) a = a + p1[q];
+    const double s = tree256(a, sred);
+    __syncthreads();
+    if (threadIdx.x == 0) sred[0] = s;
+    __syncthreads();
+    const double r = sred[0];
+    __syncthreads();
+    return r;
+}
+
+// level 1: partial1[g] from partial0[256 g .. 256 g + 255]
+__global__ __launch_bounds__(KT) void fold_k(const double *__restrict__ p0, i64 nb0, double *__restrict__ p1) {
+    __shared__ double sred[KT];
+    const i64 q = (i64)blockIdx.x * KT + threadIdx.x;
+    const double s = tree256(q < nb0 ? p0[q] : 0.0, sred);
+    if (threadIdx.x == 0) p1[blockIdx.x] = s;
+}
+__global__ __launch_bounds__(KT) void finish_k(const double *__restrict__ p1, i64 nb1, double *__restrict__ out) {
+    __shared__ double sred[KT];
+    const double s = level2(p1, nb1, sred);
+    if (threadIdx.x == 0) out[0] = s;
+}
+
+// the ordered row gathers that carry a dot product: a workgroup owns 256 consecutive rows = one chunk of the shape
+enum RowDotMode {
+    UPPER_DOT = 0,  // pass 2 of ILU0's ldiv!: dst[i] = src[i] - sum_{j>i, increasing} val*src[j];  partial of dst[i]*other[i]
+    MUL_DOT = 1     // mul!: dst[i] = 0 + sum val*src[j], increasing j;                              partial of dst[i]*other[i]
+};
+template <int MODE, typename P>
+__global__ __launch_bounds__(KT) void row_dot_k(const P *__restrict__ ptr, const u32 *__restrict__ col, const double *__restrict__ val,
+                                                const double *__restrict__ src, const double *__restrict__ other,
+                                                double *__restrict__ dst, i64 n, double *__restrict__ p0) {
+    __shared__ u32 scol[KCAP];
+    __shared__ double sval[KCAP];
+    __shared__ double sred[KT];
+    const i64 r0 = (i64)blockIdx.x * KT;
+    const i64 i = r0 + threadIdx.x;
+    const i64 rend = std::min<i64>(r0 + KT, n);
+    const u64 s = (u64)ptr[r0], e = (u64)ptr[rend];
+    const bool staged = e - s <= (u64)KCAP;
+    if (staged) {
+        const int cnt = (int)(e - s);
+        for (int t = threadIdx.x; t < cnt; t += KT) {
+            scol[t] = col[s + t];
+            sval[t] = val[s + t];
+        }
+    }
+    __syncthreads();
+    double prod = 0.0;
+    if (i < n) {
+        const u64 kb = (u64)ptr[i], ke = (u64)ptr[i + 1];
+        double acc = MODE == MUL_DOT ? 0.0 : src[i];
+        for (u64 k = kb; k < ke; k++) {
+            const u32 c = staged ? scol[k - s] : col[k];
+            const double a = staged ? sval[k - s] : val[k];
+            if (MODE == MUL_DOT) acc = acc + a * src[c];
+            else acc = acc - a * src[c];
+        }
+        dst[i] = acc;
+        prod = acc * other[i];
+    }
+    const double t = tree256(prod, sred);
+    if (threadIdx.x == 0) p0[blockIdx.x] = t;
+}
+
+// the vector kernels: a workgroup takes the chunks blockIdx.x, blockIdx.x + gridDim.x, ...
+// c = invdiag .* r (Jacobi's ldiv!) with level 0 of dot(c, r); inv == nullptr: level 0 of dot(a, b) alone (Identity: a = b = r;
+// ILUAM: a = c, b = r)
+__global__ __launch_bounds__(KT) void dot_k(const double *__restrict__ inv, const double *__restrict__ a, const double *__restrict__ b,
+                                            double *__restrict__ c, i64 n, i64 nb0, double *__restrict__ p0) {
+    __shared__ double sred[KT];
+    for (i64 q = blockIdx.x; q < nb0; q += gridDim.x) {
+        const i64 i = q * KT + threadIdx.x;
+        double prod = 0.0;
+        if (i < n) {
+            if (inv) {
+                const double ci = inv[i] * b[i];
+                c[i] = ci;
+                prod = ci * b[i];
+            } else {
+                prod = a[i] * b[i];
+            }
+        }
+        const double t = tree256(prod, sred);
+        if (threadIdx.x == 0) p0[q] = t;
+        __syncthreads();
+    }
+}
+// r = b (c == nullptr) or r = b - c, with level 0 of dot(r, r)
+__global__ __launch_bounds__(KT) void start_k(const double *__restrict__ b, const double *__restrict__ c, double *__restrict__ r, i64 n,
+                                              i64 nb0, double *__restrict__ p0) {
+    __shared__ double sred[KT];
+    for (i64 q = blockIdx.x; q < nb0; q += gridDim.x) {
+        const i64 i = q * KT + threadIdx.x;
+        double prod = 0.0;
+        if (i < n) {
+            const double ri = c ? b[i] - c[i] : b[i];
+            r[i] = ri;
+            prod = ri * ri;
+        }
+        const double t = tree256(prod, sred);
+        if (threadIdx.x == 0) p0[q] = t;
+        __syncthreads();
+    }
+}
+// beta = rho/rho_prev (rho_prev = 1 in the first iteration: prev == nullptr); u = c + beta*u, two elements per lane
+__global__ __launch_bounds__(KT) void direction_k(const double *__restrict__ rho_p1, const double *__restrict__ prev_p1, i64 nb1,
+                                                  const double *__restrict__ c, double *__restrict__ u, i64 n) {
+    __shared__ double sred[KT];
+    const double rho = level2(rho_p1, nb1, sred);
+    const double rho_prev = prev_p1 ? level2(prev_p1, nb1, sred) : 1.0;
+    const double beta = rho / rho_prev;
+    const i64 n2 = n >> 1;
+    const double2 *c2 = (const double2 *)c;
+    double2 *u2 = (double2 *)u;
+    for (i64 k = (i64)blockIdx.x * KT + threadIdx.x; k < n2; k += (i64)gridDim.x * KT) {
+        const double2 cv = c2[k];
+        double2 uv = u2[k];
+        uv.x = cv.x + beta * uv.x;
+        uv.y = cv.y + beta * uv.y;
+        u2[k] = uv;
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) u[n - 1] = c[n - 1] + beta * u[n - 1];
+}
+// alpha = rho / dot(u, c); x = x + alpha*u; r = r - alpha*c, with level 0 of dot(r, r)
+__global__ __launch_bounds__(KT) void update_k(const double *__restrict__ rho_p1, const double *__restrict__ uc_p1, i64 nb1,
+                                               const double *__restrict__ u, const double *__restrict__ c, double *__restrict__ x,
+                                               double *__restrict__ r, i64 n, i64 nb0, double *__restrict__ p0) {
+    __shared__ double sred[KT];
+    const double rho = level2(rho_p1, nb1, sred);
+    const double uc = level2(uc_p1, nb1, sred);
+    const double alpha = rho / uc;
+    for (i64 q = blockIdx.x; q < nb0; q += gridDim.x) {
+        const i64 i = q * KT + threadIdx.x;
+        double prod = 0.0;
+        if (i < n) {
+            x[i] = x[i] + alpha * u[i];
+            const double ri = r[i] - alpha * c[i];
+            r[i] = ri;
+            prod = ri * ri;
+        }
+        const double t = tree256(prod, sred);
+        if (threadIdx.x == 0) p0[q] = t;
+        __syncthreads();
+    }
+}
+
+}  // namespace
+
+extern "C" int32_t esp_cg(esp_handle *h, esp_precon *p, const double *b, double *x, int32_t on_device, int32_t initially_zero,
+                          int64_t maxiter, double abstol, double reltol, double *history, int64_t *iterations, int32_t *converged) {
+    if (!h || !b || !x || maxiter < 0) return ESP_ERR_INVALID;
+    if (p && p->h != h) FAIL(h, ESP_ERR_INVALID, "esp_cg: the preconditioner belongs to another matrix");
+    CK(solver_ready(h, p, "esp_cg"));
+    CK(csr_current(h));
+    const i64 n = h->n;
+    const i64 nb0 = ceil_div<i64>(n, KT), nb1 = ceil_div<i64>(nb0, KT);
+    const size_t vbytes = sizeof(double) * (size_t)std::max<i64>(n, 1);
+    esp_handle::Krylov &w = h->kry;
+    CK(ensure(h, w.r, vbytes));
+    CK(ensure(h, w.u, vbytes));
+    CK(ensure(h, w.c, vbytes));
+    CK(ensure(h, w.part, sizeof(double) * (size_t)(nb0 + 4 * nb1 + 8)));
+    const double *db = b;
+    double *dx = x;
+    if (!on_device) {
+        CK(ensure(h, w.hb, vbytes));
+        CK(ensure(h, w.hx, vbytes));
+        HIPCK(h, hipMemcpyAsync(w.hb.p, b, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+        HIPCK(h, hipMemcpyAsync(w.hx.p, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+        db = (const double *)w.hb.p;
+        dx = (double *)w.hx.p;
+    }
+    double *r = (double *)w.r.p, *u = (double *)w.u.p, *c = (double *)w.c.p;
+    double *p0 = (double *)w.part.p, *p1_rho[2] = {p0 + nb0, p0 + nb0 + nb1}, *p1_uc = p0 + nb0 + 2 * nb1, *p1_rr = p0 + nb0 + 3 * nb1;
+    double *d_out = p0 + nb0 + 4 * nb1;
+    const u64 *rp = (const u64 *)h->csr_rowptr.p + 1;
+    const unsigned g0 = (unsigned)std::max<i64>(nb0, 1), g1 = (unsigned)std::max<i64>(nb1, 1);
+    const unsigned gv = (unsigned)std::min<i64>(std::max<i64>(nb0, 1), KGRID);
+    auto fold = [&](double *p1) { hipLaunchKernelGGL(fold_k, dim3(g1), dim3(KT), 0, h->stream, (const double *)p0, nb0, p1); };
+    auto mul_dot = [&](const double *src, const double *other) {  // c = A*src, level 0 of dot(c, other)
+        hipLaunchKernelGGL((row_dot_k<MUL_DOT, u64>), dim3(g0), dim3(KT), 0, h->stream, rp, (const u32 *)h->csr_col.p,
+                           (const double *)h->csr_val.p, src, other, c, n, p0);
+    };
+    // residual = norm(r) from level 0 in p0: one read-back (the stop test runs on the host)
+    auto residual = [&](double *out) -> int32_t {
+        if (n == 0) {
+            *out = 0.0;
+            return ESP_OK;
+        }
+        fold(p1_rr);
+        hipLaunchKernelGGL(finish_k, dim3(1), dim3(KT), 0, h->stream, (const double *)p1_rr, nb1, d_out);
+        HIPCK(h, hipGetLastError());
+        HIPCK(h, hipMemcpyAsync(h->pin_scalar, d_out, 8, hipMemcpyDeviceToHost, h->stream));
+        HIPCK(h, hipStreamSynchronize(h->stream));
+        *out = sqrt(*(const double *)h->pin_scalar);
+        return ESP_OK;
+    };
+    if (n > 0) {
+        HIPCK(h, hipMemsetAsync(u, 0, sizeof(double) * (size_t)n, h->stream));  // u = 0
+        if (!initially_zero) mul_dot(dx, dx);                                   // c = A*x (its partials are not used)
+        hipLaunchKernelGGL(start_k, dim3(gv), dim3(KT), 0, h->stream, db, initially_zero ? (const double *)nullptr : (const double *)c, r,
+                           n, nb0, p0);
+    }
+    double res = 0.0;
+    CK(residual(&res));
+    if (history) history[0] = res;
+    const double tol = std::max(reltol * res, abstol);
+    int64_t it = 0;
+    const double *z = p ? c : r;  // Pl \ r (Identity: r itself)
+    while (it < maxiter && !(res <= tol)) {
+        it++;
+        if (n > 0) {
+            double *rho = p1_rho[it & 1];
+            // c = Pl \ r with level 0 of dot(c, r)
+            if (!p) {
+                hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)nullptr, (const double *)r, (const double *)r,
+                                   (double *)nullptr, n, nb0, p0);
+            } else if (p->kind == ESP_PRECON_JACOBI) {
+                hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)p->diag.p, (const double *)nullptr,
+                                   (const double *)r, c, n, nb0, p0);
+            } else if (p->kind == ESP_PRECON_ILUAM) {
+                CK(iluam_solve(p, r, c, false));
+                hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)nullptr, (const double *)c, (const double *)r,
+                                   (double *)nullptr, n, nb0, p0);
+            } else {
+                ilu0_lower_launch(p, r);
+                hipLaunchKernelGGL((row_dot_k<UPPER_DOT, u32>), dim3(g0), dim3(KT), 0, h->stream, (const u32 *)p->uptr.p,
+                                   (const u32 *)p->ucol.p, (const double *)p->uval.p, (const double *)p->u1.p, (const double *)r, c, n, p0);
+            }
+            fold(rho);
+            // rho_prev = rho; rho = dot(c, r); beta = rho/rho_prev; u = c + beta*u
+            hipLaunchKernelGGL(direction_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)rho,
+                               it == 1 ? (const double *)nullptr : (const double *)p1_rho[(it - 1) & 1], nb1, z, u, n);
+            mul_dot(u, u);  // c = A*u with level 0 of dot(u, c)
+            fold(p1_uc);
+            // alpha = rho / dot(u, c); x += alpha*u; r -= alpha*c
+            hipLaunchKernelGGL(update_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)rho, (const double *)p1_uc, nb1,
+                               (const double *)u, (const double *)c, dx, r, n, nb0, p0);
+        }
+        CK(residual(&res));
+        if (history) history[it] = res;
+    }
+    if (iterations) *iterations = it;
+    if (converged) *converged = res <= tol ? 1 : 0;
+    if (!on_device) HIPCK(h, hipMemcpyAsync(x, dx, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    return ESP_OK;
+}

@@ -324,6 +324,14 @@ int32_t ldiv_launch(esp_precon *p, const double *v, double *u) {
 
 }  // namespace
 
+int32_t solver_ready(esp_handle *h, esp_precon *p, const char *what) { return p ? precon_ready(p, what) : check_handle(h, what); }
+
+void ilu0_lower_launch(esp_precon *p, const double *v) {
+    hipLaunchKernelGGL((row_chain_k<ILU_LOWER, u32>), dim3(grid_for(p->n, PT)), dim3(PT), 0, p->h->stream, (const u32 *)p->lptr.p,
+                       (const u32 *)p->lcol.p, (const double *)p->lval.p, (const double *)p->diag.p, v, (const double *)nullptr,
+                       (double *)p->u1.p, p->n, (double *)nullptr);
+}
+
 extern "C" int32_t esp_precon_create(esp_handle *h, int32_t kind, esp_precon **out) {
     if (!h || !out || (kind != ESP_PRECON_JACOBI && kind != ESP_PRECON_ILU0 && kind != ESP_PRECON_ILUAM)) return ESP_ERR_INVALID;
     *out = nullptr;

@@ -6,6 +6,8 @@ JacobiPreconditioner(A) / ILU0Preconditioner(A) / ILUAMPreconditioner(A) bind an
 simple(A, b, Pl=...) is simple / simple!; u is bit-identical to the reference's loop, the residual norms agree to rounding
 (include/esparse_hip.h, esp_simple).  Vectors: NumPy arrays (copied through the device) or CUDA float64 torch tensors (used
 in place).  There is no CPU path: without a GPU the matrix itself raises NoDeviceError.
+cg(A, b, Pl=...) is IterativeSolvers' cg / cg! with any of the preconditioners (or none) as the left preconditioner: x and the
+residual history are identical run to run and bit-identical to the statement-by-statement model (include/esparse_hip.h, esp_cg).
 """
 import ctypes as C
 import math
@@ -161,3 +163,48 @@ def simple(A, b, u=None, Pl=None, maxiter=100, reltol=math.sqrt(np.finfo(np.floa
     if log:
         return u, {"resnorm": hist[:its.value + 1].copy()}
     return u
+
+
+def cg(A, b, Pl=None, x=None, abstol=0.0, reltol=math.sqrt(np.finfo(np.float64).eps), maxiter=None, log=False):
+    """cg / cg!(x, A, b; Pl, abstol, reltol, maxiter, log) of IterativeSolvers.jl (include/esparse_hip.h, esp_cg): preconditioned
+    conjugate gradients until norm(r) <= max(reltol*norm(r0), abstol) or maxiter (None: n) iterations.  x = None starts from zeros
+    (cg); a given x is updated in place (cg!).  Pl: a preconditioner of A, or None (Identity).
+    log=True returns (x, {"resnorm": the norm after every iteration, "r0": the initial one, "iters": k, "isconverged": bool})."""
+    if not isinstance(A, ExtendableSparseMatrix):
+        raise TypeError("cg(A, b): A must be an ExtendableSparseMatrix")
+    if Pl is not None and (not isinstance(Pl, _PointPreconditioner) or Pl.A is not A):
+        raise ValueError("cg: Pl must be a preconditioner of A, or None")
+    p = Pl._live() if Pl is not None else None
+    A.flush()
+    d = A._d
+    n = A.n
+    maxiter = n if maxiter is None else int(maxiter)
+    if maxiter < 0:
+        raise ValueError("maxiter < 0")
+    hist = np.empty(maxiter + 1, np.float64)
+    its = C.c_int64()
+    conv = C.c_int32()
+    zero = 1 if x is None else 0
+    if _is_cuda(b):
+        import torch
+        _check_cuda(b, n)
+        if x is None:
+            x = torch.zeros(n, dtype=torch.float64, device=b.device)
+        _check_cuda(x, n)
+        torch.cuda.current_stream(b.device).synchronize()   # the library runs on its own stream
+        d.ck(d.lib.esp_cg(d.h, p, C.c_void_p(b.data_ptr()), C.c_void_p(x.data_ptr()), 1, zero, maxiter, float(abstol),
+                          float(reltol), _vp(hist), C.byref(its), C.byref(conv)))
+    else:
+        bb = np.ascontiguousarray(b, np.float64)
+        if bb.shape != (n,):
+            raise ValueError("DimensionMismatch")
+        if x is None:
+            x = np.zeros(n, np.float64)
+        if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.shape == (n,) and x.flags.c_contiguous):
+            raise ValueError("x must be a contiguous float64 array of length n")
+        d.ck(d.lib.esp_cg(d.h, p, _vp(bb), _vp(x), 0, zero, maxiter, float(abstol), float(reltol), _vp(hist), C.byref(its),
+                          C.byref(conv)))
+    if log:
+        k = its.value
+        return x, {"resnorm": hist[1:k + 1].copy(), "r0": float(hist[0]), "iters": k, "isconverged": bool(conv.value)}
+    return x

@@ -348,6 +348,27 @@ int32_t esp_precon_levels(esp_precon *p, int64_t out[3]);
  * device pointers.  p must be bound to h. */
 int32_t esp_simple(esp_handle *h, esp_precon *p, const double *b, double *u, int32_t on_device, int64_t maxiter,
                    double abstol, double reltol, double *history, int64_t *iterations);
+/* cg / cg!(x, A, b; Pl = p, abstol, reltol, maxiter, initially_zero) of IterativeSolvers.jl (its preconditioned iterator,
+ * restated from the package's documented behaviour: the package is not part of the reference tree) on the device CSC:
+ *   u = 0; rho = 1; r = b (initially_zero != 0: x is taken to hold zeros) or r = b - A*x; residual = norm(r);
+ *   tol = max(reltol*residual, abstol); then, while fewer than maxiter iterations ran and not residual <= tol:
+ *   c = Pl \ r; rho_prev = rho; rho = dot(c, r); beta = rho/rho_prev; u = c + beta*u; c = A*u; alpha = rho/dot(u, c);
+ *   x = x + alpha*u; r = r - alpha*c; residual = norm(r).  *converged = residual <= tol.
+ * p == NULL is Identity (c = r).  DEVIATION: the package runs its unpreconditioned iterator there, equal in exact arithmetic,
+ * not in rounding.  A breakdown (dot(u, c) = 0, an indefinite matrix) is no error: Inf / NaN propagate, a NaN residual does
+ * not stop the loop, which ends at maxiter.  ldiv! and mul! are those of esp_precon_ldiv and esp_mul, bit for bit.  dot and
+ * norm (BLAS in the package, order undefined) are one fixed-shape ordered sum that depends on n alone -- chunks of 256
+ * products folded by a pairwise tree, the same tree over groups of 256 chunk sums, then a strided sum and the tree once more
+ * (csrc/krylov.hip states it in full) -- so x and the history are identical run to run and bit-identical to a model that
+ * restates the statements and that shape; against the package they agree to the rounding of the dot products only.
+ * history: maxiter+1 host doubles or NULL: history[0] the initial residual norm, history[k] the norm after iteration k;
+ * *iterations = iterations run.  b, x: n doubles, device pointers when on_device != 0; x is updated in place.
+ * Errors as esp_simple: p bound to another handle -> ESP_ERR_INVALID; pending entries, or a pattern change since p's last
+ * update! -> ESP_ERR_STATE; a rectangular matrix -> ESP_ERR_INVALID; nnz or n >= 2^32 - 16 -> ESP_ERR_UNSUPPORTED.
+ * Runs on the handle's stream, returns synchronised.  The work vectors (3 n doubles, the partial sums, 2 n more for host
+ * vectors) belong to the handle: sized on first use, released with it. */
+int32_t esp_cg(esp_handle *h, esp_precon *p, const double *b, double *x, int32_t on_device, int32_t initially_zero,
+               int64_t maxiter, double abstol, double reltol, double *history, int64_t *iterations, int32_t *converged);
 
 /* ---- the algebra of assembled matrices on the device CSC (abstractextendablesparsematrixcsc.jl:224-280) -----------
  * The reference evaluates these through SparseArrays; the device reproduces its documented rules bit for bit:

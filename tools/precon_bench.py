@@ -12,6 +12,14 @@ simple! to reltol = 1e-8 on fdrand(M,M,M), b = ones, with ILU0 and with ILUAM: i
 --cpu-model adds the host time of the sequential reference loops (tests/iluam_model.c) at the same size.
 
     python tools/precon_bench.py --kind iluam [--n 256] [--iters 10] [--tol-n 40] [--cpu-model]
+
+--kind cg times preconditioned conjugate gradients (esp_cg): for Identity, Jacobi, ILU0 and ILUAM the time of one CG iteration
+(a run of --iters + 1 iterations minus a run of 1, reltol = 0) and, from the same process, one simple! step of the same
+preconditioner measured twice (its run-to-run spread); then iterations and wall time to reltol = 1e-8 with b = ones at --n
+and at --tol-n.  --cg-only NAME restricts it to one preconditioner and skips simple! and the solves (what a kernel trace wants:
+rocprofv3 --kernel-trace --stats -- python tools/precon_bench.py --kind cg --cg-only ilu0 --iters 20 --warmup 0).
+
+    python tools/precon_bench.py --kind cg [--n 256] [--iters 20] [--tol-n 40] [--tol-maxiter 20000]
 """
 import argparse
 import ctypes as C
@@ -125,12 +133,90 @@ def bench_iluam(a, torch, esp):
     print(json.dumps({k: (round(x, 4) if isinstance(x, float) else x) for k, x in out.items()}))
 
 
+def bench_cg(a, torch, esp):
+    A = esp.fdrand(a.n, a.n, a.n)
+    d = A._d
+    stream = torch.cuda.current_stream()
+    d.ck(d.lib.esp_set_stream(d.h, C.c_void_p(stream.cuda_stream)))
+    N, Z = A.n, A.nnz()
+    b = torch.ones(N, dtype=torch.float64, device="cuda")
+    kinds = {"identity": lambda M: None, "jacobi": esp.JacobiPreconditioner, "ilu0": esp.ILU0Preconditioner,
+             "iluam": esp.ILUAMPreconditioner}
+    names = [a.cg_only] if a.cg_only else list(kinds)
+
+    def timed(fn, reps):
+        for _ in range(a.warmup):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    def per_step(run):
+        """ms of one iteration: a run of iters + 1 minus a run of 1 (both include the start-up and the zeroed vector)"""
+        return (timed(lambda: run(a.iters + 1), 2) - timed(lambda: run(1), 2)) / a.iters
+
+    out = {"workload": "cg_fdrand", "n": a.n, "N": N, "nnz": Z, "iters": a.iters}
+    # what one CG iteration moves beyond the ldiv! and the mul! of a simple! step: u = c + beta*u (3 N doubles), x += alpha*u and
+    # r -= alpha*c (6 N), r read once more by the preconditioner's dot product (N)
+    out["extra_vector_GB"] = round(8 * 10 * N / 1e9, 3)
+    for name in names:
+        P = kinds[name](A)
+        rec = {}
+        rec["cg_iteration_ms"] = per_step(lambda k: esp.cg(A, b, Pl=P, maxiter=k, reltol=0.0))
+        if P is not None and not a.cg_only:
+            step = lambda k: esp.simple(A, b, u=torch.zeros_like(b), Pl=P, maxiter=k, reltol=0.0)
+            rec["simple_step_ms"] = [per_step(step), per_step(step)]
+        if not a.cg_only:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            x, log = esp.cg(A, b, Pl=P, maxiter=a.tol_maxiter, reltol=1e-8, log=True)
+            dt = time.perf_counter() - t0                   # (esp_cg returns synchronised)
+            true = torch.linalg.vector_norm(b - A.mul(x)).item()
+            last = log["resnorm"][-1] if log["iters"] else log["r0"]
+            rec["tol"] = {"n": a.n, "iterations": log["iters"], "converged": log["isconverged"], "ms": dt * 1e3,
+                          "true_over_recurrence": true / last}
+        if P is not None:
+            P.close()
+        out[name] = rec
+    if a.tol_n and not a.cg_only:
+        m = a.tol_n
+        B = esp.fdrand(m, m, m)
+        ones = torch.ones(B.n, dtype=torch.float64, device="cuda")
+        for name in names:
+            Q = kinds[name](B)
+            esp.cg(B, ones, Pl=Q, maxiter=3, reltol=0.0)   # warm-up
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            _, log = esp.cg(B, ones, Pl=Q, maxiter=a.tol_maxiter, reltol=1e-8, log=True)
+            dt = time.perf_counter() - t0
+            out[name]["tol_small"] = {"n": m, "iterations": log["iters"], "converged": log["isconverged"], "ms": dt * 1e3}
+            if Q is not None:
+                Q.close()
+
+    def rnd(x):
+        if isinstance(x, float):
+            return round(x, 4)
+        if isinstance(x, dict):
+            return {k: rnd(y) for k, y in x.items()}
+        if isinstance(x, list):
+            return [rnd(y) for y in x]
+        return x
+
+    print(json.dumps(rnd(out)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--kind", choices=["point", "iluam"], default="point")
+    ap.add_argument("--kind", choices=["point", "iluam", "cg"], default="point")
+    ap.add_argument("--cg-only", choices=["identity", "jacobi", "ilu0", "iluam"], default=None)
     ap.add_argument("--tol-n", type=int, default=0)
     ap.add_argument("--tol-maxiter", type=int, default=100000)
     ap.add_argument("--cpu-model", action="store_true")
@@ -141,6 +227,8 @@ def main():
     esp = load()
     if a.kind == "iluam":
         return bench_iluam(a, torch, esp)
+    if a.kind == "cg":
+        return bench_cg(a, torch, esp)
     A = esp.fdrand(a.n, a.n, a.n)
     d = A._d
     stream = torch.cuda.current_stream()
