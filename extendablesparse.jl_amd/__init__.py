@@ -12,7 +12,7 @@ from .matrix import (Diagonal, ExtendableSparseMatrix, GenericExtendableSparseMa
 from . import fdrand as fdrand_module
 from .fdrand import fdrand, fdrand_, fdrand_coo, fdrand_device_
 from .sharded import GroupShardedMatrix, owner_ranges
-from .precon import ILU0Preconditioner, ILUAMPreconditioner, JacobiPreconditioner, cg, simple
+from .precon import ILU0Preconditioner, ILUAMPreconditioner, JacobiPreconditioner, bicgstabl, cg, simple
 
 # aliases mirroring src/ExtendableSparse.jl:34-39
 ExtendableSparseMatrixCSC = ExtendableSparseMatrix

@@ -103,6 +103,7 @@ SIGNATURES = {
     "esp_precon_levels": (i32, [vp, P(i64)]),
     "esp_simple": (i32, [vp, vp, vp, vp, i32, i64, f64, f64, vp, P(i64)]),
     "esp_cg": (i32, [vp, vp, vp, vp, i32, i32, i64, f64, f64, vp, P(i64), P(i32)]),
+    "esp_bicgstabl": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i64, f64, f64, vp, P(i64), P(i64), P(i32)]),
     "esp_matmul": (i32, [vp, vp, vp, P(i64)]),
     "esp_add": (i32, [vp, vp, i32, vp, P(i64)]),
     "esp_diag_scale": (i32, [vp, vp, i32, i32, vp]),

@@ -8,6 +8,8 @@ simple(A, b, Pl=...) is simple / simple!; u is bit-identical to the reference's 
 in place).  There is no CPU path: without a GPU the matrix itself raises NoDeviceError.
 cg(A, b, Pl=...) is IterativeSolvers' cg / cg! with any of the preconditioners (or none) as the left preconditioner: x and the
 residual history are identical run to run and bit-identical to the statement-by-statement model (include/esparse_hip.h, esp_cg).
+bicgstabl(A, b, l, Pl=...) is IterativeSolvers' bicgstabl / bicgstabl! for non-symmetric matrices, held to its model in the same
+way (include/esparse_hip.h, esp_bicgstabl).
 """
 import ctypes as C
 import math
@@ -207,4 +209,70 @@ def cg(A, b, Pl=None, x=None, abstol=0.0, reltol=math.sqrt(np.finfo(np.float64).
     if log:
         k = its.value
         return x, {"resnorm": hist[1:k + 1].copy(), "r0": float(hist[0]), "iters": k, "isconverged": bool(conv.value)}
+    return x
+
+
+def bicgstabl(A, b, l=2, Pl=None, x=None, abstol=0.0, reltol=math.sqrt(np.finfo(np.float64).eps), max_mv_products=None,
+              r_shadow=None, log=False):
+    """bicgstabl / bicgstabl!(x, A, b, l; Pl, abstol, reltol, max_mv_products, log) of IterativeSolvers.jl for non-symmetric
+    systems (include/esparse_hip.h, esp_bicgstabl): BiCGStab(l), 1 <= l <= 4, with Pl as the LEFT preconditioner, until the
+    preconditioned norm(r) <= max(reltol*norm(r0), abstol) or max_mv_products (None: n) matrix-vector products, tested before
+    every outer iteration of 2l products.  x = None starts from zeros; a given x is updated in place.  Pl: a preconditioner of A,
+    or None (Identity).  r_shadow: the shadow residual (None: the initial preconditioned residual; the package draws rand(n)).
+    log=True returns (x, {"resnorm": the norm after every outer iteration, "r0": the initial one, "iters": outer iterations,
+    "mvps": matrix-vector products, "isconverged": bool})."""
+    if not isinstance(A, ExtendableSparseMatrix):
+        raise TypeError("bicgstabl(A, b): A must be an ExtendableSparseMatrix")
+    if Pl is not None and (not isinstance(Pl, _PointPreconditioner) or Pl.A is not A):
+        raise ValueError("bicgstabl: Pl must be a preconditioner of A, or None")
+    p = Pl._live() if Pl is not None else None
+    A.flush()
+    d = A._d
+    n = A.n
+    l = int(l)
+    max_mv_products = n if max_mv_products is None else int(max_mv_products)
+    if max_mv_products < 0:
+        raise ValueError("max_mv_products < 0")
+    hist = np.empty(-(-max_mv_products // (2 * l)) + 1 if l >= 1 else 1, np.float64)   # (l < 1: the call refuses)
+    its, mvs = C.c_int64(), C.c_int64()
+    conv = C.c_int32()
+    zero = 1 if x is None else 0
+    if _is_cuda(b):
+        import torch
+        _check_cuda(b, n)
+        if x is None:
+            x = torch.zeros(n, dtype=torch.float64, device=b.device)
+        _check_cuda(x, n)
+        rs = None
+        if r_shadow is not None:
+            if not _is_cuda(r_shadow):
+                raise ValueError("r_shadow must live where b does")
+            if r_shadow.numel() != n:
+                raise ValueError("DimensionMismatch")
+            _check_cuda(r_shadow, n)
+            rs = C.c_void_p(r_shadow.data_ptr())
+        torch.cuda.current_stream(b.device).synchronize()   # the library runs on its own stream
+        d.ck(d.lib.esp_bicgstabl(d.h, p, l, C.c_void_p(b.data_ptr()), C.c_void_p(x.data_ptr()), rs, 1, zero, max_mv_products,
+                                 float(abstol), float(reltol), _vp(hist), C.byref(its), C.byref(mvs), C.byref(conv)))
+    else:
+        bb = np.ascontiguousarray(b, np.float64)
+        if bb.shape != (n,):
+            raise ValueError("DimensionMismatch")
+        if x is None:
+            x = np.zeros(n, np.float64)
+        if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.shape == (n,) and x.flags.c_contiguous):
+            raise ValueError("x must be a contiguous float64 array of length n")
+        rs = None
+        if r_shadow is not None:
+            if _is_cuda(r_shadow):
+                raise ValueError("r_shadow must live where b does")
+            rs = np.ascontiguousarray(r_shadow, np.float64)
+            if rs.shape != (n,):
+                raise ValueError("DimensionMismatch")
+        d.ck(d.lib.esp_bicgstabl(d.h, p, l, _vp(bb), _vp(x), _vp(rs) if rs is not None else None, 0, zero, max_mv_products,
+                                 float(abstol), float(reltol), _vp(hist), C.byref(its), C.byref(mvs), C.byref(conv)))
+    if log:
+        k = its.value
+        return x, {"resnorm": hist[1:k + 1].copy(), "r0": float(hist[0]), "iters": k, "mvps": mvs.value,
+                   "isconverged": bool(conv.value)}
     return x

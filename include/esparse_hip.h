@@ -369,6 +369,40 @@ int32_t esp_simple(esp_handle *h, esp_precon *p, const double *b, double *u, int
  * vectors) belong to the handle: sized on first use, released with it. */
 int32_t esp_cg(esp_handle *h, esp_precon *p, const double *b, double *x, int32_t on_device, int32_t initially_zero,
                int64_t maxiter, double abstol, double reltol, double *history, int64_t *iterations, int32_t *converged);
+/* bicgstabl / bicgstabl!(x, A, b, l; Pl = p, abstol, reltol, max_mv_products, initially_zero) of IterativeSolvers.jl for
+ * NON-SYMMETRIC systems (restated from the package's documented behaviour: the package is not part of the reference tree;
+ * docs/src/iter.md:97-102 solves with it) on the device CSC, 1 <= l <= 4 (anything else -> ESP_ERR_INVALID):
+ *   mv = 0; rs[0] = b (initially_zero != 0: x is taken to hold zeros) or rs[0] = b - A*x, mv = 1; rs[0] = Pl \ rs[0] (LEFT
+ *   preconditioning: every residual and norm is the preconditioned one); us[0..l] = 0; omega = sigma = 1; rt = r_shadow, or a
+ *   copy of rs[0]; residual = norm(rs[0]); tol = max(reltol*residual, abstol); then, while mv < max_mv_products and not
+ *   residual <= tol (mv is tested before an outer iteration, not inside it):
+ *     sigma = -omega*sigma; for j = 0..l-1: rho = dot(rt, rs[j]); beta = rho/sigma; us[k] = rs[k] - beta*us[k] (k = 0..j);
+ *       us[j+1] = Pl \ (A*us[j]); sigma = dot(rt, us[j+1]); alpha = rho/sigma; rs[k] = rs[k] - alpha*us[k+1] (k = 0..j);
+ *       rs[j+1] = Pl \ (A*rs[j]); x = x + alpha*us[0];
+ *     mv += 2l; M[i][k] = dot(rs[i], rs[k]); gamma[1..l] = M[1..l,1..l] \ M[1..l,0] by an LU factorization WITHOUT pivoting
+ *       (inv = 1/G[k][k]; G[i][k] *= inv; G[i][j] -= G[i][k]*G[k][j]), forward substitution with the unit lower factor, back
+ *       substitution with a true division, the inner index increasing;
+ *     us[0] -= gamma[k]*us[k]; x += gamma[k]*rs[k-1]; rs[0] -= gamma[k]*rs[k], each for k = 1..l in increasing k, one rounded
+ *       product and one sum or difference per term; omega = gamma[l]; residual = norm(rs[0]) (a fresh dot product).
+ *   *converged = residual <= tol.
+ * ldiv! and mul! are those of esp_precon_ldiv and esp_mul, bit for bit; dot, norm and M are esp_cg's ordered sum; every division
+ * is a true double division: x and the history are identical run to run and bit-identical to tests/bicgstabl_model.c, which
+ * restates the statements as plain loops and is normative for the order of every operation.
+ * DEVIATIONS from the package: r_shadow (n doubles on the same side as b, or NULL) is an argument and defaults to the initial
+ * preconditioned residual -- the package draws rand(n) --, so a solve is reproducible; dot, norm and the Gram matrix (BLAS in
+ * the package, the system solved by a pivoting LU) are as stated; p == NULL is Identity with no copies.
+ * A breakdown (sigma = 0, a singular M) is no error: Inf / NaN propagate, a NaN residual does not stop the loop, which ends at
+ * max_mv_products.  n = 1 always breaks down: the first BiCG step solves the system exactly, rs[0] = rs[1] = 0, the
+ * minimal-residual system is 0/0 and x and the norms are NaN from the first outer iteration on (as in the package).
+ * history: ceil(max_mv_products/(2l)) + 1 host doubles or NULL: history[0] the initial norm, history[k] the norm after outer
+ * iteration k; *iterations = outer iterations run, *mv_products = mv.  b, x: n doubles, device pointers when on_device != 0; x
+ * is updated in place.  Errors, stream use and "returns synchronised" exactly as esp_cg (max_mv_products < 0 ->
+ * ESP_ERR_INVALID).  The work vectors (2(l+1) + 1 vectors of n doubles, n more in front of ILU0 / ILUAM and for the initial
+ * residual, the partial sums, 8 scalars; 2 n more for host vectors) belong to the handle: sized on first use, released with it;
+ * ESP_ERR_NOMEM leaves the handle usable. */
+int32_t esp_bicgstabl(esp_handle *h, esp_precon *p, int32_t l, const double *b, double *x, const double *r_shadow,
+                      int32_t on_device, int32_t initially_zero, int64_t max_mv_products, double abstol, double reltol,
+                      double *history, int64_t *iterations, int64_t *mv_products, int32_t *converged);
 
 /* ---- the algebra of assembled matrices on the device CSC (abstractextendablesparsematrixcsc.jl:224-280) -----------
  * The reference evaluates these through SparseArrays; the device reproduces its documented rules bit for bit:

@@ -20,6 +20,15 @@ and at --tol-n.  --cg-only NAME restricts it to one preconditioner and skips sim
 rocprofv3 --kernel-trace --stats -- python tools/precon_bench.py --kind cg --cg-only ilu0 --iters 20 --warmup 0).
 
     python tools/precon_bench.py --kind cg [--n 256] [--iters 20] [--tol-n 40] [--tol-maxiter 20000]
+
+--kind bicgstabl times BiCGStab(l) (esp_bicgstabl): for Identity, Jacobi, ILU0 and ILUAM and l = 1, 2, 4 (--ls) the time of one
+OUTER iteration (2l matrix-vector products; a run of --iters + 1 outer iterations minus a run of 1, reltol = 0), measured twice,
+and beside it the same statements composed from what the package offered before esp_bicgstabl -- A.mul, P.ldiv, torch vector
+operations, torch.dot and torch.linalg.solve on device tensors, the scalars kept on the device, one read-back per outer iteration:
+what a user would have written --, measured twice in the same process (the two alternate), and the ratio composed / fused.  --cg-only NAME
+restricts it to one preconditioner, --no-composed leaves the composition out (what a kernel trace wants).
+
+    python tools/precon_bench.py --kind bicgstabl [--n 256] [--iters 5] [--ls 1,2,4] [--cg-only ilu0] [--no-composed]
 """
 import argparse
 import ctypes as C
@@ -210,16 +219,119 @@ def bench_cg(a, torch, esp):
     print(json.dumps(rnd(out)))
 
 
+def composed_bicgstabl(torch, A, P, b, l, outer):
+    """the statements of esp_bicgstabl (include/esparse_hip.h) from the package's parts: `outer` outer iterations from x = 0"""
+    ldiv = (lambda v, out: P.ldiv(v, out=out)) if P is not None else (lambda v, out: out.copy_(v))
+    rs = [torch.zeros_like(b) for _ in range(l + 1)]
+    us = [torch.zeros_like(b) for _ in range(l + 1)]
+    x = torch.zeros_like(b)
+    t = torch.empty_like(b)
+    ldiv(b, rs[0])
+    rt = rs[0].clone()
+    omega = sigma = torch.ones((), dtype=torch.float64, device=b.device)
+    hist = [torch.linalg.vector_norm(rs[0]).item()]
+    for _ in range(outer):
+        sigma = -omega * sigma
+        for j in range(l):
+            rho = torch.dot(rt, rs[j])
+            beta = rho / sigma
+            for k in range(j + 1):
+                torch.sub(rs[k], us[k] * beta, out=us[k])
+            ldiv(A.mul(us[j], out=t), us[j + 1])
+            sigma = torch.dot(rt, us[j + 1])
+            alpha = rho / sigma
+            for k in range(j + 1):
+                rs[k].sub_(us[k + 1] * alpha)
+            ldiv(A.mul(rs[j], out=t), rs[j + 1])
+            x.add_(us[0] * alpha)
+        R = torch.stack(rs)
+        M = R @ R.T
+        gamma = torch.linalg.solve(M[1:, 1:], M[1:, 0])
+        for k in range(1, l + 1):
+            us[0].sub_(us[k] * gamma[k - 1])
+        for k in range(1, l + 1):
+            x.add_(rs[k - 1] * gamma[k - 1])
+        for k in range(1, l + 1):
+            rs[0].sub_(rs[k] * gamma[k - 1])
+        omega = gamma[l - 1]
+        hist.append(torch.linalg.vector_norm(rs[0]).item())   # the stop test's read-back
+    return x, hist
+
+
+def bench_bicgstabl(a, torch, esp):
+    A = esp.fdrand(a.n, a.n, a.n)
+    d = A._d
+    stream = torch.cuda.current_stream()
+    d.ck(d.lib.esp_set_stream(d.h, C.c_void_p(stream.cuda_stream)))
+    N, Z = A.n, A.nnz()
+    b = torch.ones(N, dtype=torch.float64, device="cuda")
+    kinds = {"identity": lambda M: None, "jacobi": esp.JacobiPreconditioner, "ilu0": esp.ILU0Preconditioner,
+             "iluam": esp.ILUAMPreconditioner}
+    names = [a.cg_only] if a.cg_only else list(kinds)
+    ls = [int(v) for v in a.ls.split(",")]
+
+    def timed(fn, reps):
+        for _ in range(a.warmup):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    def per_outer(run):
+        """ms of one outer iteration: a run of iters + 1 minus a run of 1 (both include the start-up and the zeroed vectors)"""
+        return (timed(lambda: run(a.iters + 1), 2) - timed(lambda: run(1), 2)) / a.iters
+
+    out = {"workload": "bicgstabl_fdrand", "n": a.n, "N": N, "nnz": Z, "iters": a.iters}
+    for name in names:
+        P = kinds[name](A)
+        rec = {}
+        for l in ls:
+            fused = lambda k: esp.bicgstabl(A, b, l=l, Pl=P, max_mv_products=2 * l * k, reltol=0.0)
+            if a.no_composed:
+                r = {"fused_outer_ms": [per_outer(fused), per_outer(fused)]}
+            else:   # the two alternate: fused, composed, fused, composed
+                comp = lambda k: composed_bicgstabl(torch, A, P, b, l, k)
+                t = [per_outer(fused), per_outer(comp), per_outer(fused), per_outer(comp)]
+                r = {"fused_outer_ms": t[0::2], "composed_outer_ms": t[1::2]}
+                r["composed_over_fused"] = min(r["composed_outer_ms"]) / min(r["fused_outer_ms"])
+                # the two run the same statements: their histories agree to the rounding of the sums
+                _, log = esp.bicgstabl(A, b, l=l, Pl=P, max_mv_products=4 * l, reltol=0.0, log=True)
+                _, hist = composed_bicgstabl(torch, A, P, b, l, 2)
+                r["history_rel_diff"] = max(abs(g - w) / w for g, w in zip([log["r0"]] + list(log["resnorm"]), hist))
+            rec["l%d" % l] = r
+        if P is not None:
+            P.close()
+        out[name] = rec
+
+    def rnd(x):
+        if isinstance(x, float):
+            return float("%.4g" % x)
+        if isinstance(x, dict):
+            return {k: rnd(y) for k, y in x.items()}
+        if isinstance(x, list):
+            return [rnd(y) for y in x]
+        return x
+
+    print(json.dumps(rnd(out)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--kind", choices=["point", "iluam", "cg"], default="point")
+    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl"], default="point")
     ap.add_argument("--cg-only", choices=["identity", "jacobi", "ilu0", "iluam"], default=None)
     ap.add_argument("--tol-n", type=int, default=0)
     ap.add_argument("--tol-maxiter", type=int, default=100000)
     ap.add_argument("--cpu-model", action="store_true")
+    ap.add_argument("--ls", default="1,2,4")
+    ap.add_argument("--no-composed", action="store_true")
     a = ap.parse_args()
     import torch
     torch.cuda.init()
@@ -229,6 +341,8 @@ def main():
         return bench_iluam(a, torch, esp)
     if a.kind == "cg":
         return bench_cg(a, torch, esp)
+    if a.kind == "bicgstabl":
+        return bench_bicgstabl(a, torch, esp)
     A = esp.fdrand(a.n, a.n, a.n)
     d = A._d
     stream = torch.cuda.current_stream()
