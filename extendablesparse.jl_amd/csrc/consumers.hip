@@ -271,7 +271,8 @@ int32_t csr_current(esp_handle *h) {
 }
 
 extern "C" int32_t esp_mul(esp_handle *h, const double *x, double *r, int32_t on_device) {
-    if (!h || !x || !r) return ESP_ERR_INVALID;
+    if (!h) return ESP_ERR_INVALID;
+    if ((!x && h->n > 0) || (!r && h->m > 0)) return ESP_ERR_INVALID;  // (a vector without elements may have no address)
     if (h->count != 0) FAIL(h, ESP_ERR_STATE, "esp_mul: pending entries (flush first, like mul!(r, ext, x) does)");
     (void)hipSetDevice(h->device);
     if (!h->csc_valid) CK(init_empty_csc(h));
@@ -282,7 +283,7 @@ extern "C" int32_t esp_mul(esp_handle *h, const double *x, double *r, int32_t on
     if (!on_device) {
         CK(ensure(h, h->mul_x, sizeof(double) * (size_t)std::max<i64>(h->n, 1)));
         CK(ensure(h, h->mul_r, sizeof(double) * (size_t)std::max<i64>(h->m, 1)));
-        HIPCK(h, hipMemcpyAsync(h->mul_x.p, x, sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, h->stream));
+        if (h->n > 0) HIPCK(h, hipMemcpyAsync(h->mul_x.p, x, sizeof(double) * (size_t)h->n, hipMemcpyHostToDevice, h->stream));
         dx = (const double *)h->mul_x.p;
         dr = (double *)h->mul_r.p;
     }
@@ -290,7 +291,7 @@ extern "C" int32_t esp_mul(esp_handle *h, const double *x, double *r, int32_t on
         hipLaunchKernelGGL(spmv_rows_k, dim3(grid_for(h->m, 256)), dim3(256), 0, h->stream, (const u64 *)h->csr_rowptr.p,
                            (const double *)h->csr_val.p, (const u32 *)h->csr_col.p, dx, h->m, dr);
     HIPCK(h, hipGetLastError());
-    if (!on_device) HIPCK(h, hipMemcpyAsync(r, dr, sizeof(double) * (size_t)h->m, hipMemcpyDeviceToHost, h->stream));
+    if (!on_device && h->m > 0) HIPCK(h, hipMemcpyAsync(r, dr, sizeof(double) * (size_t)h->m, hipMemcpyDeviceToHost, h->stream));
     HIPCK(h, hipStreamSynchronize(h->stream));
     return ESP_OK;
 }

@@ -272,7 +272,8 @@ int32_t esp_pattern_hash(esp_handle *h, uint64_t *hash);
  * A[i,j]*x[j] over the entries of row i in increasing column order, products and sums rounded
  * separately -- bit-identical to the reference's column loop (no atomics; a row-wise index of the CSC is
  * built on first use after a pattern change).  x has n, r has m elements; on_device != 0: both are
- * device pointers (a consumer that never leaves the GPU).  Pending entries -> ESP_ERR_STATE: flush first. */
+ * device pointers (a consumer that never leaves the GPU); x may be NULL when n == 0 and r when m == 0 (a vector
+ * without elements need not have an address).  Pending entries -> ESP_ERR_STATE: flush first. */
 int32_t esp_mul(esp_handle *h, const double *x, double *r, int32_t on_device);
 
 /* mark_dirichlet(A; penalty) / eliminate_dirichlet!(A, marker) (sparsematrixcsc.jl:97-140) on the device CSC
