@@ -129,6 +129,7 @@ SIGNATURES = {
     "esp_debug_last_predicted": (i32, [vp, P(i32)]),
     "esp_debug_spoil_predicted": (i32, [vp]),
     "esp_debug_last_lazy_items": (i32, [vp, P(i32)]),
+    "esp_debug_last_lazy_stencil": (i32, [vp, P(i32)]),
     "esp_debug_last_sum_join": (i32, [vp, P(i32)]),
     "esp_debug_last_sum_ms": (i32, [vp, P(C.c_double), P(C.c_double)]),
     "esp_debug_last_sum_batched": (i32, [vp, P(C.c_int32)]),

@@ -222,7 +222,10 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
     const bool pred_batch = pair_ok && paths_auto(h) && h->force_path != ESP_PATH_NO_PREDICTED_OFFSETS && h->pre.valid && h->pre.tail == 0 &&
                             h->count == h->pre.E && st.seg_start == (const i64 *)h->seg[1].p && (h->genplan.valid || h->rawplan.valid);
     bool use_pred = pred_batch && !h->pair_off && h->last_plan_reused == 1 && h->pred.gen == h->plan_gen && h->pred.S == S && h->pred.tab.p &&
-                    h->pred.misses < 2 && h->force_path != ESP_PATH_MANY_LAUNCHES;
+                    h->pred.misses < 2 && h->force_path != ESP_PATH_MANY_LAUNCHES && !st.no_pred;
+    // A stencil batch that was never written (esp_handle::LazyStencil): the predicted form's fused kernel (pair_gen_pred_k) or
+    // nothing -- the caller issues the PART launch that was held back and comes again with the entries.
+    if (st.stencil && !use_pred) return ESP_RETRY_EXPANDED;
     // (the predicted form reads the error / longest-run words and leaves the grand total in the last granule: nothing else to clear)
     if (use_pred)
         HIPCK(h, hipMemsetAsync(status + (S - 1), 0, 3 * sizeof(u64), h->stream));
@@ -306,6 +309,11 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
             for (i64 first = 0; first < Sp; first += max_grid) {
                 ap.first = first;
                 const unsigned grid = (unsigned)std::min<i64>(max_grid, Sp - first);
+                if (use_pred && st.stencil) {
+                    if (!esplocal::launch_pair_gen_predicted(var, grid, h->stream, ap, st.stencil->a, (const u64 *)h->pred.tab.p, out_cap))
+                        return ESP_RETRY_EXPANDED;  // (a cut the fused kernel does not take: nothing has happened)
+                    continue;
+                }
                 if (!(use_pred ? esplocal::launch_pair_predicted(var, grid, h->stream, ap, (const u64 *)h->pred.tab.p, out_cap)
                                : esplocal::launch(var, grid, h->stream, ap)))
                     FAIL(h, ESP_ERR_STATE, "esp_flush: internal error (no pair kernel for this flush)");
@@ -446,6 +454,7 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
         h->pred.misses++;
         h->pred.last = 2;
         CK(reset_launch_state());
+        if (st.stencil) return ESP_RETRY_EXPANDED;  // (the look-back form reads the entries: the held-back PART launch first)
         {
             Span sp(h, ESP_ST_LOCAL);
             CK(launch_all(true));
@@ -536,6 +545,7 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
     if (lookback_err & 4u) FAIL(h, ESP_ERR_HIP, "esp_flush: internal error (early segment total differs from the folded total)");
     const i64 Zn = (i64)(h->pin_scalar[0] & esplocal::ST_VAL);
     *Zn_out = Zn;
+    if (st.stencil) h->last_lazy_stencil = 1;  // (served: the batch was never written; the table stays as it is)
     if (pred_batch && used_pair && !use_pred && Zn > 0 && !a.stop_after) {
         // a look-back flush of a kept plan that succeeded: its pairs' offsets, from the fresh colptr, for the next flush of the plan
         // (not once two predictions in a row have missed: the stream's zeros move every time)
@@ -942,6 +952,11 @@ extern "C" int32_t esp_flush(esp_handle *h, int32_t mode, int64_t *new_nnz, int3
         (h->pre.tail != 0 || !use_local || windowed(h) || h->shard_user || h->part_assembled ||
          (h->nnz != 0 && !(h->seen_hits && !h->hits_off && mode == ESP_FLUSH_ROUTED))))
         CK(lazy_expand(h));
+    // ... and a stencil batch whose PART launch was held back only on a fresh, unwindowed matrix with nothing behind it
+    if (h->pre.valid && h->lazyst.on &&
+        (h->pre.tail != 0 || !use_local || windowed(h) || h->shard_user || h->part_assembled || h->nnz != 0))
+        CK(lazy_expand(h));
+    if (h->last_lazy_stencil == 1) h->last_lazy_stencil = 0;  // (the state of an earlier flush)
     bool served = false, split = false, tail_direct = false;
     i64 Zsplit = 0;  // new entries of the batch's own flush
     if (h->pre.valid && h->pre.tail > 0 && h->nnz > 0 && mode == ESP_FLUSH_ROUTED && h->force_path != ESP_PATH_BATCH_TAIL_ONE_FLUSH) {
@@ -1058,6 +1073,17 @@ extern "C" int32_t esp_flush(esp_handle *h, int32_t mode, int64_t *new_nnz, int3
                 rc_local = flush_local(h, st, mode, &Zn);
             }
             // (a failed flush leaves the batch pending as it was: still items, or expanded by the retry)
+        } else if (h->lazyst.on) {
+            st.stencil = &h->lazyst;  // (sk / sv: the arrays the held-back PART launch would fill -- the fused kernel reads neither)
+            rc_local = flush_local(h, st, mode, &Zn);
+            if (rc_local == ESP_RETRY_EXPANDED) {  // (no prediction at flush time, or it missed: the entries, then the parent's way)
+                CK(lazy_expand(h));
+                st.stencil = nullptr;
+                st.no_pred = h->pred.last == 2;  // (a miss was counted: straight to the look-back form, which records the table anew)
+                CK(ensure(h, h->keys2, sizeof(u64) * (size_t)E));
+                CK(ensure(h, h->vals2, sizeof(double) * (size_t)E));
+                rc_local = flush_local(h, st, mode, &Zn);
+            }
         } else {
             rc_local = flush_local(h, st, mode, &Zn);
         }

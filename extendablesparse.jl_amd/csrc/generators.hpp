@@ -90,8 +90,9 @@ constexpr int FD_MAX_PER_NODE = 15;  // 3 pairs x 4 + 3 boundary terms
 
 // n / d for n, d < 2^32 with magic = 2^64 / d + 1 (host: fd_magic)
 __device__ __forceinline__ u32 fast_div(u32 n, u64 magic) { return (u32)__umul64hi(magic, (u64)n); }
-// node g (0-based l-1) -> (i,j,k), 1-based
-__device__ __forceinline__ void fd_node(const FdArgs &a, i64 g, i64 *i, i64 *j, i64 *k) {
+// node g (0-based l-1) -> (i,j,k), 1-based  (A: FdArgs, or whoever carries nx, ny, fast and the two magics: esplocal::FdSource)
+template <class A>
+__device__ __forceinline__ void fd_node(const A &a, i64 g, i64 *i, i64 *j, i64 *k) {
     if (a.fast) {
         const u32 g32 = (u32)g, nx = (u32)a.nx, nxny = (u32)(a.nx * a.ny);
         const u32 k0 = fast_div(g32, a.magic_nxny);

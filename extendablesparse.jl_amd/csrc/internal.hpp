@@ -136,6 +136,20 @@ struct esp_handle {
     } lazy;
     DevBuf lazy_hold;            // esp_append_elements_host: the uploaded element matrices of a batch that stayed a list of items (the fused
                                  // bucket kernel or lazy_expand gathers from them); released by the next flush / reset / upload
+    // The stencil generator's counterpart (round 13): a full-range batch that repeats the handle's last plan (GenPlan) on a fresh
+    // matrix whose last flush of that plan left its offset table (PredTable) is not written at all -- the PART launch is held
+    // back, `pre` describes the batch as E entries lying bucket by bucket, and the flush's fused pair kernel (pair_gen_pred_k,
+    // local_x.hip) forms every column's updates itself.  Everybody else calls lazy_expand() first, which issues the PART launch
+    // with the arguments kept here and finds the handle as it always was.  on implies pre.valid; gen: the plan it was armed
+    // under (whatever rewrites the plan's tables expands or drops the descriptor first -- lazy_expand refuses a stale one).
+    struct LazyStencil {
+        bool on = false;
+        bool armed = false;      // set in the generator call; turned into `on` beside pre.valid = true (after pending_changed)
+        u64 gen = 0;
+        unsigned grid = 0;       // workgroups of the PART launch
+        espgen::FdArgs a;        // its argument block (part = GenPlan::out; the output arrays are filled in by lazy_expand)
+    } lazyst;
+    int last_lazy_stencil = 0;   // esp_debug_last_lazy_stencil: 0 not armed, 1 the fused kernel served the flush, 2 armed, then expanded
     int last_rebuild = 0;        // the last flush's tail rebuilt the matrix (flush_rebuild: the stored CSC as the first piece of a fresh flush)
     int last_lazy_items = 0;     // the last flush's bucket kernel formed its updates from item records (esp_debug_last_lazy_items)
     int last_sum_join = 0;     // esp_debug_last_sum_join
@@ -367,7 +381,7 @@ static inline void pending_changed(esp_handle *h) {
     if (h->pre.valid && h->pre_keep && h->count >= h->pre.E)
         h->pre.tail = h->count - h->pre.E;
     else
-        h->pre.valid = false, h->lazy.on = false;
+        h->pre.valid = false, h->lazy.on = false, h->lazyst.on = false;
     h->prepass.valid = false;
     h->pre_keep = false;
     h->tailpart.valid = false;  // (append_tail_partitioned sets it after this call)
@@ -455,6 +469,8 @@ struct Sorted {
     const i64 *pstart = nullptr;
     const void *const *ptab = nullptr;
     const esp_handle::LazyItems *lazy = nullptr;  // sk holds sorted ITEM records, seg_start counts their updates: the fused bucket kernel or nothing
+    const esp_handle::LazyStencil *stencil = nullptr;  // sk / sv hold nothing yet: the fused predicted pair kernel (local_x.hip) or ESP_RETRY_EXPANDED
+    bool no_pred = false;  // the flush comes back after a missed prediction of the fused kernel: the look-back form at once
     bool has_base = false;  // the segments' key base, if it is not the handle's window / shard range
     int expect_hits = -1;   // 1 / 0: the caller knows what the entries will mostly do over the stored pattern; -1: the handle's history
     u64 base = 0;
@@ -581,7 +597,8 @@ bool launch_group3_items_multi(int nloc, bool diag, const u32 *vlist, const Mult
                                hipStream_t stream, const Args &a);  // local_j.hip
 }
 constexpr int32_t ESP_RETRY_EXPANDED = 1000;  // flush_local to esp_flush: expand the items (lazy_expand) and call again -- never leaves the library
-int32_t lazy_expand(esp_handle *h);   // produce.hip: the expansion of a batch held as sorted items (esp_handle::LazyItems)
+int32_t lazy_expand(esp_handle *h);   // produce.hip: the expansion of a batch held as sorted items (esp_handle::LazyItems) or as the
+                                      // stencil generator's held-back PART launch (esp_handle::LazyStencil)
 // may an item partition on this handle leave its batch unexpanded?  (kind: what its updates are; produce.hip)
 bool lazy_items_wanted(const esp_handle *h, int kind);
 int32_t settle_offset(esp_handle *h);
@@ -679,9 +696,11 @@ static inline unsigned grid_for(i64 n, int threads) { return (unsigned)std::max<
 
 
 // ---- small helpers
-// no force_path, or one that pins the bucket kernel's form alone (42: one bucket per workgroup): every other choice automatic
+// no force_path, or one that pins the bucket kernel's form alone (42: one bucket per workgroup, 43: no predicted offsets, 44: the
+// stencil batch is always written): every other choice automatic
 static inline bool paths_auto(const esp_handle *h) {
-    return h->force_path == ESP_PATH_AUTO || h->force_path == ESP_PATH_NO_BUCKET_PAIRS || h->force_path == ESP_PATH_NO_PREDICTED_OFFSETS;
+    return h->force_path == ESP_PATH_AUTO || h->force_path == ESP_PATH_NO_BUCKET_PAIRS || h->force_path == ESP_PATH_NO_PREDICTED_OFFSETS ||
+           h->force_path == ESP_PATH_NO_LAZY_STENCIL;
 }
 static inline bool windowed(const esp_handle *h) { return h->win_excl && (h->wc0 > 0 || h->wc1 < h->n); }
 

@@ -5,6 +5,10 @@
 #include "common.hpp"
 #include "fold.hpp"
 
+namespace espgen {
+struct FdArgs;  // generators.hpp
+}
+
 namespace esplocal {
 
 constexpr int THREADS = 512;
@@ -131,6 +135,10 @@ bool launch_pair(const Variant &v, unsigned grid, hipStream_t stream, const Args
 // ... its PREDICTED form: pair s writes at pred[s] (a table of a.S + 1 offsets: the exclusive prefix sums the handle's last
 // flush of the same plan found) when it emits pred[s + 1] - pred[s] entries and they end within out_cap; no ticket, no look-back
 bool launch_pair_predicted(const Variant &v, unsigned grid, hipStream_t stream, const Args &a, const u64 *pred, u64 out_cap);
+// ... and the predicted form that FORMS the pair's updates itself (pair_gen_pred_k, local_x.hip): the batch is the stencil
+// generator's over the full node range and was never written (esp_handle::LazyStencil) -- keys_in / vals_in / seg_start are not read
+bool launch_pair_gen_predicted(const Variant &v, unsigned grid, hipStream_t stream, const Args &a, const espgen::FdArgs &fd, const u64 *pred,
+                               u64 out_cap);  // local_x.hip
 // pred[s] = colptr[first column of pair s] - 1 for s < Sp, pred[Sp] = colptr[col_end] - 1: the table a look-back flush leaves
 void launch_pair_record(hipStream_t stream, const i64 *colptr, i64 col_end, int ncl_bits, int Sp, u64 *pred);
 

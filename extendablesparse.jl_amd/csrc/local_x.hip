@@ -1,0 +1,188 @@
+// local_x.hip -- pair_gen_pred_k: the PREDICTED pair form of the bucket kernel (pair_pred_k, local_w.hip) for a batch of the
+// stencil generator that was never written (esp_handle::LazyStencil): the workgroup FORMS the updates of its 512 columns.
+//
+// The generator is a pure function of (grid, seed, rand_mode, kind) and a node number, and the updates that land in column l
+// come from at most four nodes -- l - nx ny, l - nx, l - 1 and l itself.  Sorted by (row, call order), as pair_pred_k sorts a
+// column's run, they are
+//   rows l - nx ny, l - nx, l - 1 : one update each, -v of the pair the neighbour started towards l
+//   row  l                        : +v of those three pairs, then the node's own terms in call order: +vx, the x boundary
+//                                   term, +vy, the y boundary term, +vz, the z boundary term
+//   rows l + 1, l + nx, l + nx ny : one update each, -v of the node's own pairs
+// -- at most 12 updates over at most 7 rows, the rows strictly increasing wherever the pairs exist (no x pair when nx = 1 ...).
+// The run is therefore born sorted: no load, no counting sort, no sorting network (dropped), and the LDS holds the dense
+// records only (512 x 7 x 12 B = 42 KiB: three workgroups per CU).  Everything from "entries the run emits" on is
+// pair_pred_k: the scan of the emitted counts, the checks against the table that raise PRED_MISS and store nothing, the fold
+// through espfold::fold_step_update / fold_step_sel, dense records in LDS, coalesced rowval / nzval stores, the lane's colptr,
+// the grand total in the last granule.  No ticket, no look-back, nothing that waits for another workgroup.
+//
+// Where the values come from is the template parameter SRC (FdSource: the built-in generator's draws, the expressions and the
+// operation order of espgen::fdrand_part_k -- compiled without FMA contraction like every unit); a source that reads edge
+// coefficients from a caller's arrays fills the same StencilColumn.
+#include "generators.hpp"
+#include "local.hpp"
+
+namespace esplocal {
+
+namespace {
+constexpr int G_ROWS = 7;                  // rows a column of the 7-point stencil can hold
+constexpr int G_CAP = THREADS * G_ROWS;    // records of a pair
+}  // namespace
+
+// What column l = g + 1 receives.  lo[q] / hi[q]: the pair towards l - stride[q] / l + stride[2 - q] exists (q = 0, 1, 2: the
+// strides nx ny, nx, 1); v: the pair's value -- the off-diagonal update is -v, the diagonal one +v; b / vb: the node's boundary
+// terms in x, y, z.
+struct StencilColumn {
+    i64 stride[3];
+    bool lo[3], hi[3], b[3];
+    double vlo[3], vhi[3], vb[3];
+};
+
+// the built-in generator (espgen::FdArgs without the producer's tables)
+struct FdSource {
+    i64 nx, ny, nz;
+    double hx, hy, hz;
+    u64 seed;
+    int rand_mode;
+    int fast;
+    u64 magic_nx, magic_nxny;
+
+    __device__ __forceinline__ void column(i64 g, StencilColumn &c) const {
+        i64 i, j, k;
+        espgen::fd_node(*this, g, &i, &j, &k);
+        const i64 nxy = nx * ny;
+        const int md = rand_mode;
+        // draw q of node gg: counter 6 gg + q (espgen::fd_rand_z)
+        auto z0 = [&](i64 gg) -> u64 { return seed + (6ull * (u64)gg + 1ull) * ESP_GOLDEN; };
+        const u64 zg = z0(g);
+        c.stride[0] = nxy, c.stride[1] = nx, c.stride[2] = 1;
+        c.lo[0] = k > 1, c.lo[1] = j > 1, c.lo[2] = i > 1;
+        c.hi[0] = i < nx, c.hi[1] = j < ny, c.hi[2] = k < nz;
+        c.b[0] = i == 1 || i == nx;
+        c.b[1] = ny > 2 && (j == 1 || j == ny);
+        c.b[2] = nz > 2 && (k == 1 || k == nz);
+        // (a neighbour that does not exist: some draw nobody looks at -- every lane does the same arithmetic)
+        c.vlo[0] = espgen::fd_rand_z(md, z0(g - nxy), 4) * hx * hy / hz;
+        c.vlo[1] = espgen::fd_rand_z(md, z0(g - nx), 2) * hx * hz / hy;
+        c.vlo[2] = espgen::fd_rand_z(md, z0(g - 1), 0) * hy * hz / hx;
+        c.vhi[0] = espgen::fd_rand_z(md, zg, 0) * hy * hz / hx;
+        c.vb[0] = espgen::fd_rand_z(md, zg, 1) * hy * hz;
+        c.vhi[1] = espgen::fd_rand_z(md, zg, 2) * hx * hz / hy;
+        c.vb[1] = espgen::fd_rand_z(md, zg, 3) * hx * hz;
+        c.vhi[2] = espgen::fd_rand_z(md, zg, 4) * hx * hy / hz;
+        c.vb[2] = espgen::fd_rand_z(md, zg, 5) * hx * hy;
+    }
+};
+
+template <int KEYS, class SRC>
+__global__ __launch_bounds__(THREADS, 6) void pair_gen_pred_k(Args a, SRC src, const u64 *pred, u64 out_cap) {
+    static_assert(KEYS == 1 || KEYS == 2, "one kind: 2 = every update is an UPDATE");
+    constexpr bool UPD = KEYS == 2;
+    __shared__ u32 srow[G_CAP];     // the records' rows (1-based) ...
+    __shared__ double sval[G_CAP];  // ... and values
+    __shared__ u32 lw[WAVES];
+
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int s = (int)(a.first + (i64)blockIdx.x);
+    if (s >= a.S) return;
+    const u64 dst = esp_uniform_u64(pred[s]);
+    const u64 dst_next = esp_uniform_u64(pred[s + 1]);
+    const int ncl = 2 << a.cl_bits;
+    const u64 hi = ((u64)s << (a.rem_bits + 1)) + a.base;  // the pair's prefix: that of its first bucket
+    const i64 c_lo = (i64)(hi >> a.rb);
+    const i64 c_hi = min(c_lo + (i64)ncl, a.col_end);
+    const bool has = c_lo + t < c_hi;  // lane t owns column c_lo + t
+    // ---- the column's run, folded as it is formed: row q of the seven (rows strictly increasing where they exist)
+    bool present[G_ROWS];
+    double acc[G_ROWS];
+    u32 row[G_ROWS];
+#pragma unroll
+    for (int q = 0; q < G_ROWS; q++) present[q] = false, acc[q] = 0.0, row[q] = 0u;
+    if (has) {
+        StencilColumn c;
+        src.column(c_lo + t, c);
+        const i64 l = c_lo + t + 1;
+        auto step = [&](int q, bool on, double v) {
+            if (!on) return;
+            if constexpr (UPD)
+                espfold::fold_step_update(present[q], acc[q], v);
+            else
+                espfold::fold_step_sel(present[q], acc[q], a.kind32, v);
+        };
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            row[q] = (u32)(l - c.stride[q]);
+            row[4 + q] = (u32)(l + c.stride[2 - q]);
+            step(q, c.lo[q], -c.vlo[q]);
+        }
+        row[3] = (u32)l;
+#pragma unroll
+        for (int q = 0; q < 3; q++) step(3, c.lo[q], c.vlo[q]);
+#pragma unroll
+        for (int q = 0; q < 3; q++) {
+            step(3, c.hi[q], c.vhi[q]);
+            step(3, c.b[q], c.vb[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < 3; q++) step(4 + q, c.hi[q], -c.vhi[q]);
+    }
+    // entries the run emits: one per row that one of its updates creates
+    u32 ec = 0;
+#pragma unroll
+    for (int q = 0; q < G_ROWS; q++) ec += present[q] ? 1u : 0u;
+    const u32 einc = esp_wave_scan_add(ec);
+    if (lane == 63) lw[w] = einc;
+    __syncthreads();
+    u32 at0 = einc - ec, total = 0;
+#pragma unroll
+    for (int i = 0; i < WAVES; i++) {
+        at0 += i < w ? lw[i] : 0u;
+        total += lw[i];
+    }
+    // the pair's place is the table's when it emits what the table says and ends inside the output arrays (pair_pred_k's
+    // condition, the same answer in every lane); else nothing is stored
+    const bool hit = dst_next >= dst && dst_next - dst == (u64)total && dst <= out_cap && (u64)total <= out_cap - dst && (s > 0 || dst == 0);
+    if (!hit) {
+        if (t == 0) atomicOr(a.err, PRED_MISS);
+        return;
+    }
+    {
+        u32 at = at0;
+#pragma unroll
+        for (int q = 0; q < G_ROWS; q++) {
+            if (present[q]) {
+                srow[at] = row[q];
+                sval[at] = acc[q];
+                at++;
+            }
+        }
+    }
+    __syncthreads();
+    // ---- coalesced stores; the lane of a column writes its colptr
+    for (int p = t; p < (int)total; p += THREADS) {
+        a.out_row[dst + p] = (i64)srow[p];
+        a.out_val[dst + p] = sval[p];
+    }
+    if (has) a.colptr_out[c_lo + t] = (i64)(dst + at0) + 1;
+    if (s == a.S - 1 && t == 0) {
+        a.colptr_out[a.col_end] = (i64)(dst + total) + 1;
+        a.status[s] = ST_PRE | ((dst + (u64)total) & ST_VAL);  // (the grand total where the host reads it: lb_complete's last granule)
+    }
+}
+
+bool launch_pair_gen_predicted(const Variant &v, unsigned grid, hipStream_t stream, const Args &a, const espgen::FdArgs &fd, const u64 *pred,
+                               u64 out_cap) {
+    // (whole columns, at most 512 of them per pair, rows that fit the records' 32 bits)
+    if (!v.fresh || v.pieces || a.cl_bits < 0 || (2 << a.cl_bits) > THREADS || a.rb >= 32 || !a.colptr_out) return false;
+    const FdSource src{fd.nx, fd.ny, fd.nz, fd.hx, fd.hy, fd.hz, fd.seed, fd.rand_mode, fd.fast, fd.magic_nx, fd.magic_nxny};
+    if (v.keys == 1) {
+        hipLaunchKernelGGL((pair_gen_pred_k<1, FdSource>), dim3(grid), dim3(THREADS), 0, stream, a, src, pred, out_cap);
+        return true;
+    }
+    if (v.keys == 2) {
+        hipLaunchKernelGGL((pair_gen_pred_k<2, FdSource>), dim3(grid), dim3(THREADS), 0, stream, a, src, pred, out_cap);
+        return true;
+    }
+    return false;
+}
+
+}  // namespace esplocal

@@ -34,7 +34,8 @@ extern "C" int32_t esp_generate_fdrand_range(esp_handle *h, int64_t nx, int64_t 
     (void)hipSetDevice(h->device);
     const i64 off_b = fd_offset_host(nx, ny, nz, node_begin);
     const i64 E = fd_offset_host(nx, ny, nz, node_end) - off_b;
-    CK(reserve_append(h, E));
+    h->lazyst.armed = false;
+    CK(reserve_append(h, E));  // (expands a batch this handle still holds back: this call then goes behind it)
     espgen::FdArgs a;
     a.nx = nx;
     a.ny = ny;
@@ -81,14 +82,27 @@ extern "C" int32_t esp_generate_fdrand_range(esp_handle *h, int64_t nx, int64_t 
         // the flag words: flush_pre_tail, flush_rebuild, a shard's assemble and a failed flush all write there; the plan's own
         // longest bucket fitted, or the plan would not have been kept)
         HIPCK(h, hipMemsetAsync((unsigned long long *)h->misc.p + 24, 0, 64, h->stream));
-        Span sp(h, ESP_ST_APPEND);
-        if (gp.out.k32)
-            hipLaunchKernelGGL((espgen::fdrand_part_k<true, true>), grid, block, 0, h->stream, a);
-        else if (gp.out.s32)
-            hipLaunchKernelGGL((espgen::fdrand_part_k<true, false>), grid, block, 0, h->stream, a);
-        else
-            hipLaunchKernelGGL((espgen::fdrand_part_k<false, false>), grid, block, 0, h->stream, a);
-        sp.add(1);
+        // The whole grid on a fresh, unwindowed matrix whose last flush of this plan left its offset table: the launch is held
+        // back (esp_handle::LazyStencil) -- the flush's fused pair kernel forms the updates itself, lazy_expand launches for
+        // everybody else.  force_path 43 / 44: never.
+        const bool lazy = node_begin == 0 && node_end == N && !h->shard_user && !windowed(h) && gp.out.k32 && gp.pre.fb == 0 && gp.pre.mw_P == 0 &&
+                          h->nnz == 0 && h->force_path != ESP_PATH_NO_PREDICTED_OFFSETS && h->force_path != ESP_PATH_NO_LAZY_STENCIL &&
+                          h->pred.gen == h->plan_gen && h->pred.tab.p && h->pred.misses < 2 && !h->pair_off;
+        if (lazy) {
+            h->lazyst.a = a;
+            h->lazyst.grid = grid.x;
+            h->lazyst.gen = h->plan_gen;
+            h->lazyst.armed = true;
+        } else {
+            Span sp(h, ESP_ST_APPEND);
+            if (gp.out.k32)
+                hipLaunchKernelGGL((espgen::fdrand_part_k<true, true>), grid, block, 0, h->stream, a);
+            else if (gp.out.s32)
+                hipLaunchKernelGGL((espgen::fdrand_part_k<true, false>), grid, block, 0, h->stream, a);
+            else
+                hipLaunchKernelGGL((espgen::fdrand_part_k<false, false>), grid, block, 0, h->stream, a);
+            sp.add(1);
+        }
         h->pre = gp.pre;
         h->pre.valid = false;  // (set below, once the entries are counted in)
         took = true;
@@ -135,6 +149,9 @@ extern "C" int32_t esp_generate_fdrand_range(esp_handle *h, int64_t nx, int64_t 
     h->count += E;
     pending_changed(h);
     if (took) h->pre.valid = true;  // (else: whatever pending_changed left -- an earlier batch with this call as its tail)
+    h->lazyst.on = took && h->lazyst.armed;
+    h->lazyst.armed = false;
+    h->last_lazy_stencil = 0;  // (1: the flush that serves the batch; 2: lazy_expand)
     return ESP_OK;
 }
 
@@ -464,7 +481,35 @@ bool lazy_items_wanted(const esp_handle *h, int kind) {
 }
 // The expansion that was put off: sorted items (in the keys array) -> updates, bucket by bucket, into the scratch pair; then
 // the pairs trade places.  Afterwards the handle is what item_produce_fem / elements_by_items used to leave.
+// ... and the stencil generator's batch whose PART launch was held back (esp_handle::LazyStencil): the launch, with the arguments
+// and under the span of the generator call -- the handle is then what that call leaves when it launches at once.
+static int32_t lazy_expand_stencil(esp_handle *h) {
+    esp_handle::LazyStencil &ls = h->lazyst;
+    ls.on = false;
+    if (!h->pre.valid) return ESP_OK;
+    h->last_lazy_stencil = 2;
+    // (the tables the launch reads are the plan's: nobody rewrites them while a descriptor is armed under it)
+    if (ls.gen != h->plan_gen || !h->genplan.valid) FAIL(h, ESP_ERR_STATE, "internal error: a held-back stencil batch outlived its plan");
+    if ((i64)std::min(h->keys.bytes / sizeof(u64), h->vals.bytes / sizeof(double)) < h->pre.E)
+        FAIL(h, ESP_ERR_STATE, "internal error: a held-back stencil batch without its buffer");
+    espgen::FdArgs a = ls.a;
+    a.part.keys_out = (u64 *)h->keys.p;
+    a.part.vals_out = (double *)h->vals.p;
+    a.keys = (u64 *)h->keys.p;
+    a.vals = (double *)h->vals.p;
+    (void)hipSetDevice(h->device);
+    HIPCK(h, hipMemsetAsync((unsigned long long *)h->misc.p + 24, 0, 64, h->stream));  // (the block the PART launch looks at: see the generator call)
+    {
+        Span sp(h, ESP_ST_APPEND);
+        hipLaunchKernelGGL((espgen::fdrand_part_k<true, true>), dim3(ls.grid), dim3(espgen::THREADS), 0, h->stream, a);
+        sp.add(1);
+    }
+    HIPCK(h, hipGetLastError());
+    return ESP_OK;
+}
+
 int32_t lazy_expand(esp_handle *h) {
+    if (h->lazyst.on) return lazy_expand_stencil(h);
     if (!h->lazy.on) return ESP_OK;
     h->lazy.on = false;
     if (!h->pre.valid) return ESP_OK;

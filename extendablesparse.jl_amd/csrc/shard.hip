@@ -398,6 +398,11 @@ extern "C" int32_t esp_debug_last_lazy_items(const esp_handle *h, int32_t *on) {
     *on = h->last_lazy_items;
     return ESP_OK;
 }
+extern "C" int32_t esp_debug_last_lazy_stencil(const esp_handle *h, int32_t *state) {
+    if (!h || !state) return ESP_ERR_INVALID;
+    *state = h->last_lazy_stencil;
+    return ESP_OK;
+}
 extern "C" int32_t esp_debug_last_sum_join(const esp_handle *h, int32_t *segments) {
     if (!h || !segments) return ESP_ERR_INVALID;
     *segments = h->last_sum_join;

@@ -919,6 +919,13 @@ class ExtendableSparseMatrix:
         self._d.ck(self._d.lib.esp_debug_last_lazy_items(self._d.h, C.byref(p)))
         return p.value
 
+    def debug_last_lazy_stencil(self):
+        """The last fdrand! batch's held-back PART launch: 0 not armed, 1 the fused pair kernel served the flush (the batch was
+        never written), 2 armed, then written after all"""
+        p = C.c_int32()
+        self._d.ck(self._d.lib.esp_debug_last_lazy_stencil(self._d.h, C.byref(p)))
+        return p.value
+
     def debug_last_rebuild(self):
         """1: the last flush rebuilt the matrix for the entries behind a re-assembly's batch (stored entries as a first piece)"""
         p = C.c_int32()

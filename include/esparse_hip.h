@@ -649,7 +649,11 @@ typedef enum {
                                         the handle's last flush takes every pair's output offset from the table that flush left, see
                                         esp_debug_last_predicted): always the ticket + look-back form; no table is recorded.  Counts
                                         as automatic for every other choice, like 42                                          */
-    ESP_PATH_NO_PLAN_REUSE = 31      /* esp_append_device / esp_commit of one kind on an empty buffer always count their columns
+    ESP_PATH_NO_LAZY_STENCIL = 44,   /* the stencil generator always writes its batch (the PART launch runs in the generator call):
+                                        never the fused form in which a repeated full-range batch on a fresh matrix stays unwritten
+                                        and the predicted pair kernel forms every column's updates itself (see
+                                        esp_debug_last_lazy_stencil).  Counts as automatic for every other choice, like 42 and 43 */
+    ESP_PATH_NO_PLAN_REUSE = 31     /* esp_append_device / esp_commit of one kind on an empty buffer always count their columns
                                         (never the run lists of the previous, identical-looking batch)                      */
 } esp_debug_path;
 /* last_path reports which pipeline the last flush took (1 = LDS bucket path, 2 = general).
@@ -711,6 +715,13 @@ int32_t esp_debug_spoil_predicted(esp_handle *h);
  * esp_debug_force_path(39): never.  2 (on the destination of esp_flush_sum): the folds of all buffers ran as ONE launch over their
  * item records and the combine flush read the folded records as pieces (every buffer held an element batch with the same plan) */
 int32_t esp_debug_last_lazy_items(const esp_handle *h, int32_t *on);
+/* what became of the last esp_generate_fdrand batch's held-back PART launch: 0 not armed (the batch was written in the generator
+ * call: not a repeat of the handle's last plan over the full node range on a fresh matrix, no offset table for the plan, a shard,
+ * a column window, esp_debug_force_path(43 / 44)), 1 the flush's fused pair kernel formed the updates itself and the batch was
+ * never written (esp_debug_last_predicted and _last_bucket_pairs then report 1), 2 armed and then written after all (something
+ * other than that flush needed the entries -- an append behind the batch, a read of the pending buffer, a clone, a shard call, a
+ * second generator call -- or the prediction missed) */
+int32_t esp_debug_last_lazy_stencil(const esp_handle *h, int32_t *state);
 /* how many neighbouring segments of the folds' plan the combine flush of the last esp_flush_sum of that kind (last_lazy_items 2)
  * joined into one (1, 2, 4 or 8: as many as keep the longest joined segment within the bucket kernel's capacity); 0 otherwise */
 int32_t esp_debug_last_sum_join(const esp_handle *h, int32_t *segments);
