@@ -226,8 +226,15 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
     // A stencil batch that was never written (esp_handle::LazyStencil): the predicted form's fused kernel (pair_gen_pred_k) or
     // nothing -- the caller issues the PART launch that was held back and comes again with the entries.
     if (st.stencil && !use_pred) return ESP_RETRY_EXPANDED;
+    // The fused kernel stores its grand total and its error bits straight into pinned host memory (esp_handle::pin_words): the host
+    // clears the words here and reads them after the synchronise -- no memset in front of the kernel, no copy behind it.  (The
+    // window flag is not fetched: the batch is armed on unwindowed handles only.  The stream is idle: the handle's last flush
+    // ended with a synchronise.)
+    const bool fused = st.stencil && use_pred;
     // (the predicted form reads the error / longest-run words and leaves the grand total in the last granule: nothing else to clear)
-    if (use_pred)
+    if (fused)
+        h->pin_words[0] = h->pin_words[1] = h->pin_words[2] = 0ull;
+    else if (use_pred)
         HIPCK(h, hipMemsetAsync(status + (S - 1), 0, 3 * sizeof(u64), h->stream));
     else
         HIPCK(h, hipMemsetAsync(status, 0, status_bytes, h->stream));
@@ -279,6 +286,7 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
         a.ticket = (u32 *)(status + tick_at);
         a.err = (u32 *)(status + S) + 1;
         a.maxrun_seen = (u32 *)(status + S) + 2;  // (zeroed with the granules)
+        a.host_words = fused ? (u64 *)h->pin_words_dev : nullptr;
         {
             a.stop_after = stop_env ? atoi(stop_env) : 0;
             a.stamps = nullptr;
@@ -372,6 +380,15 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
         };
     }
     auto read_back = [&]() -> int32_t {
+        if (fused) {  // (the words are in host memory already -- in the slots' layout: no longest run, no window flag on this path)
+            HIPCK(h, hipStreamSynchronize(h->stream));
+            const volatile unsigned long long *w = h->pin_words;
+            h->pin_scalar[0] = w[0];
+            h->pin_scalar[1] = w[1] << 32;
+            h->pin_scalar[2] = 0ull;
+            h->pin_scalar[3] = 0ull;
+            return ESP_OK;
+        }
         HIPCK(h, hipMemcpyAsync(h->pin_scalar, status + (S - 1), 24, hipMemcpyDeviceToHost, h->stream));  // last granule | ticket, err | maxrun
         HIPCK(h, hipMemcpyAsync(h->pin_scalar + 3, (u32 *)h->misc.p + 60, 4, hipMemcpyDeviceToHost, h->stream));
         HIPCK(h, hipStreamSynchronize(h->stream));

@@ -247,10 +247,19 @@ extern "C" int32_t esp_create(int64_t m, int64_t n, int32_t device, int64_t capa
         FAIL((esp_handle *)nullptr, ESP_ERR_HIP, "esp_create: cannot create a stream on device %d", device);
     }
     h->own_stream = true;
-    if (hipHostMalloc((void **)&h->pin_scalar, 64, hipHostMallocDefault) != hipSuccess) {
+    // (8 slots for the small copies, then the 8 of pin_words: the default flags give mapped, coherent host memory)
+    if (hipHostMalloc((void **)&h->pin_scalar, 128, hipHostMallocDefault) != hipSuccess) {
         (void)hipStreamDestroy(h->stream);
         delete h;
         FAIL((esp_handle *)nullptr, ESP_ERR_NOMEM, "esp_create: pinned scalar allocation failed");
+    }
+    memset(h->pin_scalar, 0, 128);
+    h->pin_words = h->pin_scalar + 8;
+    if (hipHostGetDevicePointer((void **)&h->pin_words_dev, h->pin_words, 0) != hipSuccess || !h->pin_words_dev) {
+        (void)hipHostFree(h->pin_scalar);
+        (void)hipStreamDestroy(h->stream);
+        delete h;
+        FAIL((esp_handle *)nullptr, ESP_ERR_HIP, "esp_create: no device address for the pinned result words");
     }
     int32_t st = init_empty_csc(h);
     if (st == ESP_OK && capacity_hint > 0) {

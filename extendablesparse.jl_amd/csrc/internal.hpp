@@ -289,7 +289,12 @@ struct esp_handle {
         size_t bytes = 0;  // each
         hipEvent_t ev[2] = {nullptr, nullptr};
     } bounce;
-    unsigned long long *pin_scalar = nullptr;  // pinned, 8 slots
+    unsigned long long *pin_scalar = nullptr;  // pinned, 8 slots: the target of every small copy to the host
+    // ... and, on a 64-byte line of their own behind them, the result words a flush's fused stencil kernel stores straight into
+    // host memory (esplocal::Args::host_words: grand total | error bits | spare) -- never a copy target; pin_words_dev is the
+    // address the device uses for them
+    unsigned long long *pin_words = nullptr;
+    unsigned long long *pin_words_dev = nullptr;
     u64 *pin_mw = nullptr;  // pinned source of prepart_begin's asynchronous upload of the window bases (<= MW_MAX)
     hipEvent_t pin_mw_done = nullptr;
     // kind bookkeeping of the pending batch: when every pending entry was appended with ONE known kind the run-based

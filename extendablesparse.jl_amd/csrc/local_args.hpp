@@ -85,6 +85,10 @@ struct Args {
     const i64 *own_fine;  // ... this one: 2^fb entries per segment (+ 1), absolute positions like the piece's row of pstart
     double *hits_out; // group3_k's re-assembly form (HITS): the new values of the stored positions (a second nzval array)
     i64 pair_buckets; // pair_k (local_w.hip): buckets of the segment table; segment s = its buckets [2 s, min(2 s + 2, pair_buckets))
+    // pair_gen_pred_k (local_x.hip): three result words in pinned host memory (their device address), zeroed by the host before the
+    // launch and read by it after the stream's synchronise -- [0] the grand total, [1] error bits (PRED_MISS), [2] spare.  The
+    // kernel writes no status granule and no err word: nothing is cleared before it and nothing copied after it
+    u64 *host_words;
 };
 constexpr int MAX_PIECES = 64;
 

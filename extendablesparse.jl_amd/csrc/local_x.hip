@@ -13,7 +13,8 @@
 // records only (512 x 7 x 12 B = 42 KiB: three workgroups per CU).  Everything from "entries the run emits" on is
 // pair_pred_k: the scan of the emitted counts, the checks against the table that raise PRED_MISS and store nothing, the fold
 // through espfold::fold_step_update / fold_step_sel, dense records in LDS, coalesced rowval / nzval stores, the lane's colptr,
-// the grand total in the last granule.  No ticket, no look-back, nothing that waits for another workgroup.
+// the grand total and a miss in pinned host memory (Args::host_words).  No ticket, no look-back, nothing that waits for another
+// workgroup, no memset in front of the launch and no copy behind it.
 //
 // Where the values come from is the template parameter SRC (FdSource: the built-in generator's draws, the expressions and the
 // operation order of espgen::fdrand_part_k -- compiled without FMA contraction like every unit); a source that reads edge
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(THREADS, 6) void pair_gen_pred_k(Args a, SRC src, c
     // condition, the same answer in every lane); else nothing is stored
     const bool hit = dst_next >= dst && dst_next - dst == (u64)total && dst <= out_cap && (u64)total <= out_cap - dst && (s > 0 || dst == 0);
     if (!hit) {
-        if (t == 0) atomicOr(a.err, PRED_MISS);
+        if (t == 0) a.host_words[1] = (u64)PRED_MISS;  // (the same constant from every missing pair: a plain store)
         return;
     }
     {
@@ -165,14 +166,14 @@ __global__ __launch_bounds__(THREADS, 6) void pair_gen_pred_k(Args a, SRC src, c
     if (has) a.colptr_out[c_lo + t] = (i64)(dst + at0) + 1;
     if (s == a.S - 1 && t == 0) {
         a.colptr_out[a.col_end] = (i64)(dst + total) + 1;
-        a.status[s] = ST_PRE | ((dst + (u64)total) & ST_VAL);  // (the grand total where the host reads it: lb_complete's last granule)
+        a.host_words[0] = ST_PRE | ((dst + (u64)total) & ST_VAL);  // (the grand total, in the form of lb_complete's last granule)
     }
 }
 
 bool launch_pair_gen_predicted(const Variant &v, unsigned grid, hipStream_t stream, const Args &a, const espgen::FdArgs &fd, const u64 *pred,
                                u64 out_cap) {
     // (whole columns, at most 512 of them per pair, rows that fit the records' 32 bits)
-    if (!v.fresh || v.pieces || a.cl_bits < 0 || (2 << a.cl_bits) > THREADS || a.rb >= 32 || !a.colptr_out) return false;
+    if (!v.fresh || v.pieces || a.cl_bits < 0 || (2 << a.cl_bits) > THREADS || a.rb >= 32 || !a.colptr_out || !a.host_words) return false;
     const FdSource src{fd.nx, fd.ny, fd.nz, fd.hx, fd.hy, fd.hz, fd.seed, fd.rand_mode, fd.fast, fd.magic_nx, fd.magic_nxny};
     if (v.keys == 1) {
         hipLaunchKernelGGL((pair_gen_pred_k<1, FdSource>), dim3(grid), dim3(THREADS), 0, stream, a, src, pred, out_cap);
