@@ -337,6 +337,8 @@ extern "C" int32_t esp_bicgstabl(esp_handle *h, esp_precon *p, int32_t l, const 
     const unsigned g0 = (unsigned)std::max<i64>(nb0, 1), g1 = (unsigned)std::max<i64>(nb1, 1);
     const unsigned gv = (unsigned)std::min<i64>(std::max<i64>(nb0, 1), KGRID);
     const double *const nil = nullptr;
+    esp_precon *const blk = block_permuted(p) ? p : nullptr;  // BlockPreconditioner, permuted path: gather, inner ldiv!, scatter, dot_k
+    p = fused_precon(p);                                      // ... identity path: the inner kind's own branch on its buffers
     auto fold = [&](double *dst) { hipLaunchKernelGGL(fold_k, dim3(g1), dim3(KT), 0, h->stream, (const double *)p0, nb0, dst); };
     // dst = A*src (mul!), level 0 of dot(dst, rt) when dot
     auto mul = [&](const double *src, double *dst, bool dot) {
@@ -345,8 +347,9 @@ extern "C" int32_t esp_bicgstabl(esp_handle *h, esp_precon *p, int32_t l, const 
     };
     // dst = Pl \ src for ILU0 / ILUAM (src != dst), level 0 of dot(dst, rt) when dot
     auto ldiv = [&](const double *src, double *dst, bool dot) -> int32_t {
-        if (p->kind == ESP_PRECON_ILUAM) {
-            CK(iluam_solve(p, src, dst, false));
+        if (blk || p->kind == ESP_PRECON_ILUAM) {
+            if (blk) CK(block_ldiv_launch(blk, src, dst, false));
+            else CK(iluam_solve(p, src, dst, false));
             if (dot)
                 hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, h->stream, nil, (const double *)dst, (const double *)rt,
                                    (double *)nullptr, n, nb0, p0);
@@ -362,7 +365,7 @@ extern "C" int32_t esp_bicgstabl(esp_handle *h, esp_precon *p, int32_t l, const 
     auto pmul = [&](const double *src, double *dst, bool dot) -> int32_t {
         if (!p) {
             mul(src, dst, dot);
-        } else if (p->kind == ESP_PRECON_JACOBI) {
+        } else if (!blk && p->kind == ESP_PRECON_JACOBI) {
             hipLaunchKernelGGL((row_dot_k<MUL_JAC_DOT, u64>), dim3(g0), dim3(KT), 0, h->stream, rp, (const u32 *)h->csr_col.p,
                                (const double *)h->csr_val.p, src, (const double *)rt, dst, n, dot ? p0 : (double *)nullptr,
                                (const double *)p->diag.p);
@@ -393,7 +396,7 @@ extern "C" int32_t esp_bicgstabl(esp_handle *h, esp_precon *p, int32_t l, const 
         if (!initially_zero) mul(dx, rs + ns, false);  // A*x in rs[1], which is free until the first BiCG step
         hipLaunchKernelGGL(start_k, dim3(gv), dim3(KT), 0, h->stream, db, initially_zero ? nil : (const double *)(rs + ns), r0, n, nb0,
                            p0);
-        if (p && p->kind == ESP_PRECON_JACOBI)  // rs[0] = invdiag .* r0
+        if (p && !blk && p->kind == ESP_PRECON_JACOBI)  // rs[0] = invdiag .* r0
             hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)p->diag.p, nil, (const double *)r0, rs, n, nb0, p0);
         else if (p) CK(ldiv(r0, rs, false));
         const double *src = nullptr;

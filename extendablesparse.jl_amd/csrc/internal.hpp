@@ -9,6 +9,7 @@
 //   consumers.hip  what reads or edits the assembled CSC: getindex, dropzeros, pattern hash, mul!, Dirichlet, Jacobi / ILU0
 //   precon.hip     the point preconditioners' update! / ldiv! (esp_precon_*) and simple! (esp_simple) on the device CSC
 //   iluam.hip      ILUAMPreconditioner: level analysis, level-scheduled ILU(0) factorization and triangular solves
+//   block.hip      BlockPreconditioner: the masked block matrix B of a partitioning (identity / permuted path) and the object around it
 //   krylov.hip     preconditioned conjugate gradients (esp_cg): fused vector kernels, ordered dot products, scalars on the device
 //   bicgstabl.hip  BiCGStab(l) for non-symmetric systems (esp_bicgstabl): the same design with l+1 residuals and search vectors;
 //                  krylov.hpp holds what the two solvers share
@@ -557,7 +558,21 @@ struct esp_precon {
     // t belongs to row sched[1 / 2].order[t], so a level's slice is contiguous (8.3 against 11.2 ms per ldiv! at 256^3)
     DevBuf fval;
     IluamSched sched[3];  // 0: columns of the factorization, 1: rows of the forward solve, 2: rows of the backward solve
+    // BlockPreconditioner (kind ESP_PRECON_BLOCK, block.hip): h is A; the block matrix B -- the stored A[i,j] with part(i) == part(j)
+    // -- lives in the internal handle bh (A's device and stream), inner is an ordinary preconditioner of inner_kind bound to bh.
+    // blk_path 0 (every partition increasing): B keeps A's numbering, ldiv! is inner's on the caller's vectors.  blk_path 1: B is
+    // renumbered by blk_new (position in the concatenated partitions); ldiv! gathers into blk_t, solves into blk_s, scatters.
+    esp_handle *bh = nullptr;
+    esp_precon *inner = nullptr;
+    int inner_kind = 0, blk_path = 0, blk_force = 0;
+    bool blk_increasing = false, blk_rebuild = false;
+    DevBuf blk_new, blk_part;  // u32 n each: new(i), part(i)
+    DevBuf blk_src;            // u32 nnz(B): the position in A's nzval entry q of B came from
+    DevBuf blk_t, blk_s;       // f64 n each (permuted path)
 };
+// the identity-path block preconditioner stands for its inner one in the solvers' fused branches
+static inline esp_precon *fused_precon(esp_precon *p) { return p && p->kind == ESP_PRECON_BLOCK && p->blk_path == 0 ? p->inner : p; }
+static inline bool block_permuted(const esp_precon *p) { return p && p->kind == ESP_PRECON_BLOCK && p->blk_path != 0; }
 
 #pragma GCC visibility push(hidden)
 // precon.hip: smallest column without a stored diagonal -> ESP_ERR_INVALID (ILU0 / ILUAM), invdiag / xdiag into p->diag;
@@ -573,6 +588,19 @@ void iluam_release(esp_precon *p);
 // into the scratch p->u1 (pass 2 is krylov.hip's own: it carries the dot product)
 int32_t solver_ready(esp_handle *h, esp_precon *p, const char *what);
 void ilu0_lower_launch(esp_precon *p, const double *v);
+// precon.hip, for block.hip: the checks of every preconditioner call on the handle; ldiv! on device vectors (u may be v)
+int32_t precon_check_handle(esp_handle *h, const char *what);
+int32_t precon_ldiv_launch(esp_precon *p, const double *v, double *u);
+// block.hip: update! (rebuild of B and the inner preconditioner / the value gather and the inner values-only update), ldiv! on
+// device vectors (sub: u[i] = u[i] - x[i], simple!'s step), release of B, the inner preconditioner and every buffer
+int32_t block_update(esp_precon *p);
+int32_t block_follow_stream(esp_precon *p);
+int32_t block_ldiv_launch(esp_precon *p, const double *v, double *u, bool sub);
+void block_release(esp_precon *p);
+// linalg.hip, for block.hip: every column of (cp: 0-based starts, rowC, valC) sorted by row, valC carried along; the caller
+// found maxlen <= COLSORT_BLOCK and listed the nlong columns longer than COLSORT_LANE
+constexpr int COLSORT_LANE = 32, COLSORT_BLOCK = 4096;
+void sort_columns_launch(hipStream_t s, const i64 *cp, i64 nC, i64 *rowC, u64 *valC, i64 maxlen, const u32 *list, i64 nlong);
 int32_t ensure(esp_handle *h, DevBuf &b, size_t need, bool keep = false);
 void release(DevBuf &b);
 void release_all(esp_handle *h);

@@ -156,6 +156,8 @@ extern "C" int32_t esp_cg(esp_handle *h, esp_precon *p, const double *b, double 
     const double tol = std::max(reltol * res, abstol);
     int64_t it = 0;
     const double *z = p ? c : r;  // Pl \ r (Identity: r itself)
+    esp_precon *const blk = block_permuted(p) ? p : nullptr;  // BlockPreconditioner, permuted path: gather, inner ldiv!, scatter, dot_k
+    p = fused_precon(p);                                      // ... identity path: the inner kind's own branch on its buffers
     while (it < maxiter && !(res <= tol)) {
         it++;
         if (n > 0) {
@@ -163,6 +165,10 @@ extern "C" int32_t esp_cg(esp_handle *h, esp_precon *p, const double *b, double 
             // c = Pl \ r with level 0 of dot(c, r)
             if (!p) {
                 hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)nullptr, (const double *)r, (const double *)r,
+                                   (double *)nullptr, n, nb0, p0);
+            } else if (blk) {
+                CK(block_ldiv_launch(blk, r, c, false));
+                hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)nullptr, (const double *)c, (const double *)r,
                                    (double *)nullptr, n, nb0, p0);
             } else if (p->kind == ESP_PRECON_JACOBI) {
                 hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)p->diag.p, (const double *)nullptr,

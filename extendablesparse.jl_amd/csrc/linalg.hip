@@ -218,6 +218,17 @@ __global__ void tp_add_one_k(i64 *__restrict__ p, i64 n) {
     if (i < n) p[i] += 1;
 }
 
+}  // namespace
+static_assert(TP_LANE == COLSORT_LANE && TP_BLOCK == COLSORT_BLOCK, "internal.hpp states the column sorts' limits");
+void sort_columns_launch(hipStream_t s, const i64 *cp, i64 nC, i64 *rowC, u64 *valC, i64 maxlen, const u32 *list, i64 nlong) {
+    const dim3 gc(grid_for(nC, MT));
+    if (maxlen >= 2 && maxlen <= 8) hipLaunchKernelGGL(tp_sort_lane_k<3>, gc, dim3(MT), 0, s, cp, nC, rowC, valC);
+    else if (maxlen > 8 && maxlen <= 16) hipLaunchKernelGGL(tp_sort_lane_k<4>, gc, dim3(MT), 0, s, cp, nC, rowC, valC);
+    else if (maxlen > 16) hipLaunchKernelGGL(tp_sort_lane_k<5>, gc, dim3(MT), 0, s, cp, nC, rowC, valC);
+    if (nlong > 0) hipLaunchKernelGGL(tp_sort_block_k, dim3((unsigned)nlong), dim3(MT), 0, s, cp, list, rowC, valC);
+}
+namespace {
+
 // ---- transpose(A)*x: one lane per column, a wave for a column longer than MV_LONG ---------------------------------------------
 __global__ __launch_bounds__(MT) void mv_t_k(Csc64 A, const double *__restrict__ x, double *__restrict__ r) {
     const i64 j = (i64)blockIdx.x * MT + threadIdx.x;
@@ -429,12 +440,7 @@ int32_t transpose_counting(esp_handle *c, const Csc64 &A, i64 nC, Temps &tmp, bo
     CK(ensure(h, nz, sizeof(u64) * (size_t)A.nnz));
     HIPCK(h, hipMemsetAsync(cnt.p, 0, sizeof(u32) * (size_t)nC, s));
     hipLaunchKernelGGL(tp_scatter_k, dim3(grid_for(A.nnz, TP_TILE)), dim3(MT), 0, s, A, (const i64 *)cp.p, (u32 *)cnt.p, (i64 *)rv.p, (u64 *)nz.p);
-    const dim3 gc(grid_for(nC, MT));
-    if (maxlen >= 2 && maxlen <= 8) hipLaunchKernelGGL(tp_sort_lane_k<3>, gc, dim3(MT), 0, s, (const i64 *)cp.p, nC, (i64 *)rv.p, (u64 *)nz.p);
-    else if (maxlen > 8 && maxlen <= 16) hipLaunchKernelGGL(tp_sort_lane_k<4>, gc, dim3(MT), 0, s, (const i64 *)cp.p, nC, (i64 *)rv.p, (u64 *)nz.p);
-    else if (maxlen > 16) hipLaunchKernelGGL(tp_sort_lane_k<5>, gc, dim3(MT), 0, s, (const i64 *)cp.p, nC, (i64 *)rv.p, (u64 *)nz.p);
-    if (nlong > 0)
-        hipLaunchKernelGGL(tp_sort_block_k, dim3((unsigned)nlong), dim3(MT), 0, s, (const i64 *)cp.p, (const u32 *)list.p, (i64 *)rv.p, (u64 *)nz.p);
+    sort_columns_launch(s, (const i64 *)cp.p, nC, (i64 *)rv.p, (u64 *)nz.p, maxlen, (const u32 *)list.p, nlong);
     hipLaunchKernelGGL(tp_add_one_k, dim3(grid_for(nC + 1, MT)), dim3(MT), 0, s, (i64 *)cp.p, nC + 1);
     HIPCK(h, hipGetLastError());
     HIPCK(h, hipStreamSynchronize(s));

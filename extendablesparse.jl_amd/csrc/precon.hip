@@ -299,6 +299,7 @@ int32_t precon_ready(esp_precon *p, const char *what) {
     if (h->pattern_version != p->pattern_version || h->nnz != p->nnz)
         FAIL(h, ESP_ERR_STATE, "%s: the matrix pattern changed since the preconditioner's last update! (update! first)", what);
     if (p->kind == ESP_PRECON_ILU0 && p->values_version != h->values_version) CK(split_scale(p, false));  // current nzval, stored xdiag
+    if (p->kind == ESP_PRECON_BLOCK) CK(block_follow_stream(p));  // (B holds copies: the values as of the last update!, ILU0 included)
     return ESP_OK;
 }
 
@@ -307,6 +308,7 @@ int32_t ldiv_launch(esp_precon *p, const double *v, double *u) {
     esp_handle *h = p->h;
     const i64 n = p->n;
     if (n == 0) return ESP_OK;
+    if (p->kind == ESP_PRECON_BLOCK) return block_ldiv_launch(p, v, u, false);
     if (p->kind == ESP_PRECON_ILUAM) return iluam_solve(p, v, u, false);
     const unsigned g = grid_for(n, PT);
     if (p->kind == ESP_PRECON_JACOBI) {
@@ -325,6 +327,8 @@ int32_t ldiv_launch(esp_precon *p, const double *v, double *u) {
 }  // namespace
 
 int32_t solver_ready(esp_handle *h, esp_precon *p, const char *what) { return p ? precon_ready(p, what) : check_handle(h, what); }
+int32_t precon_check_handle(esp_handle *h, const char *what) { return check_handle(h, what); }
+int32_t precon_ldiv_launch(esp_precon *p, const double *v, double *u) { return ldiv_launch(p, v, u); }
 
 void ilu0_lower_launch(esp_precon *p, const double *v) {
     hipLaunchKernelGGL((row_chain_k<ILU_LOWER, u32>), dim3(grid_for(p->n, PT)), dim3(PT), 0, p->h->stream, (const u32 *)p->lptr.p,
@@ -352,6 +356,7 @@ extern "C" int32_t esp_precon_create(esp_handle *h, int32_t kind, esp_precon **o
 
 extern "C" int32_t esp_precon_update(esp_precon *p) {
     if (!p) return ESP_ERR_INVALID;
+    if (p->kind == ESP_PRECON_BLOCK) return block_update(p);  // B and the inner preconditioner (block.hip)
     esp_handle *h = p->h;
     CK(check_handle(h, "esp_precon_update"));
     p->n = h->n;
@@ -399,6 +404,7 @@ extern "C" int32_t esp_precon_destroy(esp_precon *p) {
     esp_handle *h = p->h;
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
+    block_release(p);
     for (DevBuf *b : {&p->diag, &p->lptr, &p->uptr, &p->lcol, &p->ucol, &p->lpos, &p->upos, &p->dpos, &p->lval, &p->uval, &p->u1, &p->res,
                       &p->partial, &p->scanws, &p->hv, &p->hu})
         release(*b);
@@ -447,10 +453,14 @@ extern "C" int32_t esp_simple(esp_handle *h, esp_precon *p, const double *b, dou
     CK(residual(&r0));
     if (history) history[0] = r0;
     int64_t it = 0;
+    esp_precon *const blk = block_permuted(p) ? p : nullptr;  // BlockPreconditioner, permuted path: gather, inner ldiv!, scatter
+    p = fused_precon(p);                                      // ... identity path: the inner kind's own branch on its buffers
     for (int64_t i = 1; i <= maxiter; i++) {
         // ldiv!(upd, Pl, res); u .-= upd -- upd[i] rounded, then u[i] - upd[i]
         if (n > 0) {
-            if (p->kind == ESP_PRECON_JACOBI) {
+            if (blk) {
+                CK(block_ldiv_launch(blk, res, du, true));
+            } else if (p->kind == ESP_PRECON_JACOBI) {
                 hipLaunchKernelGGL(jacobi_sub_k, dim3((unsigned)nb), dim3(PT), 0, h->stream, (const double *)p->diag.p,
                                    (const double *)res, du, n);
             } else if (p->kind == ESP_PRECON_ILUAM) {

@@ -10,13 +10,15 @@ cg(A, b, Pl=...) is IterativeSolvers' cg / cg! with any of the preconditioners (
 residual history are identical run to run and bit-identical to the statement-by-statement model (include/esparse_hip.h, esp_cg).
 bicgstabl(A, b, l, Pl=...) is IterativeSolvers' bicgstabl / bicgstabl! for non-symmetric matrices, held to its model in the same
 way (include/esparse_hip.h, esp_bicgstabl).
+BlockPreconditioner(A, partitioning, factorization) (src/factorizations/blockpreconditioner.jl) solves every A[part, part] with one
+of the three point kinds: one block matrix and one inner preconditioner on the device, bit-identical to the per-block loops.
 """
 import ctypes as C
 import math
 
 import numpy as np
 
-from ._lib import ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_JACOBI
+from ._lib import ESP_PRECON_BLOCK, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_JACOBI
 from .matrix import ExtendableSparseMatrix, _vp
 
 
@@ -122,6 +124,78 @@ class ILUAMPreconditioner(_PointPreconditioner):
 
     def levels(self):
         """level counts of the three schedules: (factorization columns, forward rows, backward rows)"""
+        out = (C.c_int64 * 3)()
+        self._ck(self.A._d.lib.esp_precon_levels(self._live(), out))
+        return tuple(int(x) for x in out)
+
+
+class BlockPreconditioner(_PointPreconditioner):
+    """BlockPreconditioner(A; partitioning, factorization) (src/factorizations/blockpreconditioner.jl, docs/src/iter.md):
+    ldiv! is u[part] = factorization(A[part, part]) \\ v[part] for every partition, bit-identical to the reference's per-block
+    loops (include/esparse_hip.h, esp_precon_block_create).
+
+    partitioning: a sequence of index sequences or ranges in the index base of A[i, j] (1-based, like Julia's 1:2:n), which
+    together hold every index 1..n exactly once.  factorization: JacobiPreconditioner, ILU0Preconditioner or
+    ILUAMPreconditioner; it is required.  .path is 0 when every partition is increasing (nothing is permuted), else 1.
+    The blocks are factorized from copies: a value change of A reaches ldiv only through update(), for ILU0 too."""
+    KIND = ESP_PRECON_BLOCK
+
+    def __init__(self, A, partitioning=None, factorization=None):
+        if not isinstance(A, ExtendableSparseMatrix):
+            raise TypeError("BlockPreconditioner(A, ...): A must be an ExtendableSparseMatrix")
+        if factorization is None:
+            raise TypeError("BlockPreconditioner: factorization is required -- the reference's default, LUFactorization, is not "
+                            "on the device; pass JacobiPreconditioner, ILU0Preconditioner or ILUAMPreconditioner")
+        if not (isinstance(factorization, type) and issubclass(factorization, _PointPreconditioner)
+                and factorization.KIND in (ESP_PRECON_JACOBI, ESP_PRECON_ILU0, ESP_PRECON_ILUAM)):
+            raise TypeError("BlockPreconditioner: factorization must be JacobiPreconditioner, ILU0Preconditioner or "
+                            "ILUAMPreconditioner (the reference's default, LUFactorization, is not on the device)")
+        self.A = A
+        self._p = None
+        self.factorization = factorization
+        if partitioning is None:            # blockpreconditioner.jl:46-48: one partition 1:n
+            partitioning = [range(1, A.n + 1)]
+        parts = [np.asarray(part, np.int64).reshape(-1) for part in partitioning]
+        ptr = np.zeros(len(parts) + 1, np.int64)
+        np.cumsum([len(part) for part in parts], out=ptr[1:])
+        idx = np.ascontiguousarray(np.concatenate(parts) - 1 if parts else np.empty(0, np.int64), np.int64)
+        A.flush()
+        d = A._d
+        p = C.c_void_p()
+        d.ck(d.lib.esp_precon_block_create(d.h, factorization.KIND, len(parts), _vp(ptr), _vp(idx), 0, C.byref(p)))
+        self._p = p
+
+    def _block(self):
+        b, path = C.c_void_p(), C.c_int32()
+        self._ck(self.A._d.lib.esp_precon_block_matrix(self._live(), C.byref(b), C.byref(path)))
+        return b, path.value
+
+    @property
+    def path(self):
+        """0: the identity path (every partition increasing), 1: the permuted path"""
+        return self._block()[1]
+
+    def block_matrix(self):
+        """the block matrix B as host CSC arrays (colptr, rowval, nzval), Julia layout -- for tests and inspection"""
+        b, _ = self._block()
+        lib = self.A._d.lib
+        nnz = C.c_int64()
+        self._ck(lib.esp_nnz(b, C.byref(nnz)))
+        cp, rv, nz = np.empty(self.A.n + 1, np.int64), np.empty(nnz.value, np.int64), np.empty(nnz.value, np.float64)
+        self._ck(lib.esp_get_csc(b, _vp(cp), _vp(rv), _vp(nz)))
+        return cp, rv, nz
+
+    def factor(self):
+        """the inner ILUAM factorization's values in B's position order"""
+        b, _ = self._block()
+        nnz = C.c_int64()
+        self._ck(self.A._d.lib.esp_nnz(b, C.byref(nnz)))
+        out = np.empty(nnz.value, np.float64)
+        self._ck(self.A._d.lib.esp_precon_get_factor(self._live(), _vp(out), 0))
+        return out
+
+    def levels(self):
+        """the inner preconditioner's level counts (ILUAM: the maximum over the blocks, not their sum)"""
         out = (C.c_int64 * 3)()
         self._ck(self.A._d.lib.esp_precon_levels(self._live(), out))
         return tuple(int(x) for x in out)

@@ -339,6 +339,44 @@ int32_t esp_precon_destroy(esp_precon *p);
 #define ESP_PRECON_ILUAM 2
 int32_t esp_precon_get_factor(esp_precon *p, double *nzval, int32_t on_device);
 int32_t esp_precon_levels(esp_precon *p, int64_t out[3]);
+/* BlockPreconditioner (src/factorizations/blockpreconditioner.jl, docs/src/iter.md): the unknowns are split into partitions, every
+ * A[part, part] is factorized with Jacobi, ILU0 or ILUAM (inner_kind), and ldiv! solves the partitions independently:
+ * u[part] = inner(A[part, part]) \ v[part].  The reference builds np submatrices and runs np factorizations and solves; the device
+ * builds ONE matrix B -- exactly the stored entries A[i,j] with part(i) == part(j), explicit zeros, -0.0 and NaN payloads kept
+ * bitwise -- and runs ONE inner preconditioner on it: a point factorization of a block-diagonal matrix decouples into the
+ * factorizations of its blocks, row by row, the same operations in the same order, so the result is bit-identical to the
+ * reference's per-block loops, and ILUAM's level count is the maximum over the blocks instead of their sum.
+ *   path 0 (identity: every partition strictly increasing -- ranges and strided ranges, the reference's documented cases): B keeps A's
+ *     numbering; ldiv! is exactly the inner kind's launches on v and u: no further launch, copy or scratch.
+ *   path 1 (permuted: anything else): B is renumbered by new(i), the position of i in the concatenation of the partitions, every
+ *     column sorted by row; ldiv! adds one gather and one scatter through two n-vectors the preconditioner owns.
+ * partitions: part_ptr[0..nparts] (part_ptr[0] = 0, non-decreasing, part_ptr[nparts] = n), part_idx[n] 0-based indices that hold
+ * every index 0..n-1 exactly once; host arrays, or device arrays when on_device != 0.  The arrays are copied: the caller may free
+ * them after the call.  Empty partitions, nparts == 0 with n == 0, and n == 0 are valid.
+ * The result is an esp_precon bound to h; esp_precon_update / _ldiv / _destroy, esp_simple, esp_cg and esp_bicgstabl take it
+ * unchanged, with the stream use and "returns synchronised" rules of the other kinds.  esp_precon_update after a pattern change of
+ * A rebuilds B and the inner preconditioner; with the pattern kept it gathers B's values and runs the inner kind's values-only
+ * update (bitwise what a fresh create gives).  esp_precon_get_factor and esp_precon_levels answer for the inner preconditioner (the
+ * factor: nnz(B) values in B's position order).
+ * VALUE SEMANTICS: the reference factorizes COPIES A[part, part], so ldiv! sees the values as of the last update! -- for ILU0 too.
+ * This differs from the unblocked ILU0 above, which reads A's current off-diagonal values.  A pattern change of A without
+ * update! -> ESP_ERR_STATE, as for the other kinds.
+ * ESP_ERR_INVALID: a rectangular matrix; inner_kind outside the three; nparts < 0; a malformed part_ptr; an index out of range,
+ *   repeated or missing (esp_last_error names the first offending one); for ILU0 and ILUAM a column without a stored diagonal (a
+ *   block's diagonal is A's).  DEVIATION: the reference only warns when the lengths do not add up to n and then leaves u untouched
+ *   there -- undefined memory inside cg.
+ * ESP_ERR_STATE: pending entries.  ESP_ERR_UNSUPPORTED: the unblocked kinds' limits; a column window / column shard on h.
+ * ESP_ERR_NOMEM leaves A usable, and a failed create or rebuild of B leaves any earlier state of p as it was; once B has been replaced
+ * (or its values overwritten by a values-only update!) a failure of the inner update! leaves p refusing ldiv! (ESP_ERR_STATE) until
+ * the next good update!, as for the other kinds.  h refuses esp_destroy while the preconditioner lives; esp_precon_destroy releases B, the inner
+ * preconditioner and every buffer. */
+#define ESP_PRECON_BLOCK 3
+int32_t esp_precon_block_create(esp_handle *h, int32_t inner_kind, int64_t nparts, const int64_t *part_ptr, const int64_t *part_idx,
+                                int32_t on_device, esp_precon **out);
+/* test / inspection: the internal handle holding B (borrowed: read it with esp_get_csc / esp_nnz only); path = 0 identity, 1 permuted */
+int32_t esp_precon_block_matrix(esp_precon *p, esp_handle **b, int32_t *path);
+/* test hook, takes effect at the next esp_precon_update (which then rebuilds B): 0 automatic, 1 force the permuted path */
+int32_t esp_debug_block_path(esp_precon *p, int32_t path);
 /* simple!(u, A, b; abstol, reltol, maxiter, Pl = p) (src/factorizations/simple_iteration.jl:21-45) statement by
  * statement: res = A*u - b; then per step ldiv!(upd, Pl, res), u .-= upd, mul!(res, A, u), res .-= b, r = norm(res),
  * stop when (r / r0) < reltol || r < abstol (literally: r0 = 0 gives NaN or Inf there).  u (in/out) is bit-identical to

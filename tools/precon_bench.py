@@ -29,6 +29,23 @@ what a user would have written --, measured twice in the same process (the two a
 restricts it to one preconditioner, --no-composed leaves the composition out (what a kernel trace wants).
 
     python tools/precon_bench.py --kind bicgstabl [--n 256] [--iters 5] [--ls 1,2,4] [--cg-only ilu0] [--no-composed]
+
+--kind block times BlockPreconditioner (esp_precon_block_create) against the unblocked preconditioner of the same kind, for Jacobi,
+ILU0 and ILUAM (--cg-only NAME: one of them): create, the values-only update! and ldiv! on device vectors for (a) the unblocked
+preconditioner, (b) odd / even unknowns, (c) 8 and (d) 64 contiguous slabs (identity path), (e) a seeded random permutation in 8
+parts (permuted path).  All five stay alive and are timed in --rounds alternating rounds of --iters warm calls each; reported: the
+median over the rounds, every round's value, and for ldiv! the unblocked kind's spread over the rounds (max - min), the yardstick of
+"identity-path ldiv! takes no more than the unblocked one".  ILUAM's level counts are listed for each.
+
+    python tools/precon_bench.py --kind block [--n 256] [--iters 20] [--rounds 5] [--cg-only ilu0]
+
+--kind block-trace is what a kernel trace wants: one preconditioner (--cg-only NAME, --block-config a..e), a create and --iters
+ldiv! calls on device vectors (--iters 0: the create alone; the difference of two traces is the kernel list of ldiv!).
+--kind block-trace-diff --dirs WITH WITHOUT [--iters K] reads the two traces' *_kernel_stats.csv / *_memory_copy_stats.csv and prints the
+kernels and copies per ldiv! call.
+
+    rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d OUT -- \
+        python tools/precon_bench.py --kind block-trace --cg-only ilu0 --block-config b --n 64 --iters 25 --warmup 0
 """
 import argparse
 import ctypes as C
@@ -320,12 +337,155 @@ def bench_bicgstabl(a, torch, esp):
     print(json.dumps(rnd(out)))
 
 
+def block_partitioning(np, N, config):
+    """1-based partitions of 1..N for the configurations b .. e of --kind block"""
+    if config == "b":
+        return [np.arange(1, N + 1, 2), np.arange(2, N + 1, 2)]
+    if config in ("c", "d"):
+        k = 8 if config == "c" else 64
+        cuts = [(N * i) // k for i in range(k + 1)]
+        return [np.arange(cuts[i] + 1, cuts[i + 1] + 1) for i in range(k)]
+    perm = np.random.default_rng(15).permutation(N) + 1
+    cuts = [(N * i) // 8 for i in range(9)]
+    return [perm[cuts[i]:cuts[i + 1]] for i in range(8)]
+
+
+def make_block(esp, np, A, cls, config):
+    return cls(A) if config == "a" else esp.BlockPreconditioner(A, block_partitioning(np, A.n, config), cls)
+
+
+def bench_block(a, torch, esp):
+    import statistics
+
+    import numpy as np
+    A = esp.fdrand(a.n, a.n, a.n)
+    d = A._d
+    stream = torch.cuda.current_stream()
+    d.ck(d.lib.esp_set_stream(d.h, C.c_void_p(stream.cuda_stream)))
+    N, Z = A.n, A.nnz()
+    v = torch.randn(N, dtype=torch.float64, device="cuda")
+    u = torch.empty_like(v)
+    kinds = {"jacobi": esp.JacobiPreconditioner, "ilu0": esp.ILU0Preconditioner, "iluam": esp.ILUAMPreconditioner}
+    names = [a.cg_only] if a.cg_only else list(kinds)
+    configs = ["a", "b", "c", "d", "e"]
+    labels = {"a": "unblocked", "b": "odd_even", "c": "slabs8", "d": "slabs64", "e": "random8_permuted"}
+
+    def timed(fn, reps, warmup):
+        for _ in range(warmup):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    out = {"workload": "block_precon_fdrand", "n": a.n, "N": N, "nnz": Z, "iters": a.iters, "rounds": a.rounds}
+    Pw = esp.ILU0Preconditioner(A)     # builds A's row-wise index once, so that no create below pays for it
+    Pw.close()
+    for name in names:
+        rec, P = {}, {}
+        print("block bench: %s" % name, file=sys.stderr, flush=True)
+        for c in configs:
+            parts = None if c == "a" else block_partitioning(np, N, c)   # (the host-side index arrays are not part of create)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            P[c] = kinds[name](A) if c == "a" else esp.BlockPreconditioner(A, parts, kinds[name])
+            r = {"create_ms": (time.perf_counter() - t0) * 1e3}             # (create returns synchronised; the partition upload included)
+            if c != "a":
+                r["path"] = P[c].path
+                b, _ = P[c]._block()
+                z = C.c_int64()
+                d.ck(d.lib.esp_nnz(b, C.byref(z)))
+                r["nnz_B"] = z.value
+            if name == "iluam":
+                r["levels"] = list(P[c].levels())
+            rec[labels[c]] = r
+        upd = {c: [] for c in configs}
+        ldv = {c: [] for c in configs}
+        for rnd_i in range(a.rounds):                                       # the five alternate inside every round
+            for c in configs:
+                ldv[c].append(timed(lambda: P[c].ldiv(v, out=u), a.iters, a.warmup if rnd_i == 0 else 1))
+            for c in configs:
+                upd[c].append(timed(lambda: P[c].update(), max(2, a.iters // 5), 1))
+        for c in configs:
+            r = rec[labels[c]]
+            r["ldiv_ms"], r["ldiv_rounds_ms"] = statistics.median(ldv[c]), ldv[c]
+            r["update_values_ms"], r["update_rounds_ms"] = statistics.median(upd[c]), upd[c]
+        spread = max(ldv["a"]) - min(ldv["a"])
+        rec["unblocked_ldiv_spread_ms"] = spread
+        rec["identity_within_unblocked_plus_spread"] = {labels[c]: bool(rec[labels[c]]["ldiv_ms"] <= rec["unblocked"]["ldiv_ms"] + spread)
+                                                        for c in ("b", "c", "d")}
+        for c in configs:
+            P[c].close()
+        out[name] = rec
+
+    def rnd(x):
+        if isinstance(x, float):
+            return float("%.5g" % x)
+        if isinstance(x, dict):
+            return {k: rnd(y) for k, y in x.items()}
+        if isinstance(x, list):
+            return [rnd(y) for y in x]
+        return x
+
+    print(json.dumps(rnd(out)))
+
+
+def bench_block_trace(a, torch, esp):
+    import numpy as np
+    A = esp.fdrand(a.n, a.n, a.n)
+    d = A._d
+    d.ck(d.lib.esp_set_stream(d.h, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    v = torch.randn(A.n, dtype=torch.float64, device="cuda")
+    u = torch.empty_like(v)
+    cls = {"jacobi": esp.JacobiPreconditioner, "ilu0": esp.ILU0Preconditioner, "iluam": esp.ILUAMPreconditioner}[a.cg_only or "ilu0"]
+    P = make_block(esp, np, A, cls, a.block_config)
+    torch.cuda.synchronize()
+    for _ in range(a.iters):
+        P.ldiv(v, out=u)
+    torch.cuda.synchronize()
+    print(json.dumps({"workload": "block_trace", "n": a.n, "kind": a.cg_only or "ilu0", "config": a.block_config, "ldiv_calls": a.iters,
+                      "path": getattr(P, "path", None)}))
+    P.close()
+
+
+def block_trace_diff(a):
+    """kernels and copies per ldiv! call: the trace of create + K ldiv! minus the trace of the create alone"""
+    import csv
+    import glob
+
+    def counts(d, what):
+        """calls per name: from the --stats table (Name, Calls) where there is one, else the rows of the trace"""
+        c = {}
+        stats = glob.glob(os.path.join(d, "**", "*_%s_stats.csv" % what), recursive=True)
+        col = "Kernel_Name" if what == "kernel" else "Direction"
+        for f in stats or glob.glob(os.path.join(d, "**", "*_%s_trace.csv" % what), recursive=True):
+            with open(f, newline="") as fh:
+                for row in csv.DictReader(fh):
+                    key = row["Name"] if stats else row.get(col, "?")
+                    c[key] = c.get(key, 0) + (int(row["Calls"]) if stats else 1)
+        return c
+
+    with_d, without_d = a.dirs
+    out = {"ldiv_calls": a.iters}
+    for what, src in (("kernels_per_ldiv", "kernel"), ("copies_per_ldiv", "memory_copy")):
+        w, wo = counts(with_d, src), counts(without_d, src)
+        out[what] = {k: (w.get(k, 0) - wo.get(k, 0)) / a.iters for k in sorted(set(w) | set(wo)) if w.get(k, 0) != wo.get(k, 0)}
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl"], default="point")
+    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "block", "block-trace", "block-trace-diff"], default="point")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--block-config", choices=["a", "b", "c", "d", "e"], default="b")
+    ap.add_argument("--dirs", nargs=2, default=None)
     ap.add_argument("--cg-only", choices=["identity", "jacobi", "ilu0", "iluam"], default=None)
     ap.add_argument("--tol-n", type=int, default=0)
     ap.add_argument("--tol-maxiter", type=int, default=100000)
@@ -333,6 +493,8 @@ def main():
     ap.add_argument("--ls", default="1,2,4")
     ap.add_argument("--no-composed", action="store_true")
     a = ap.parse_args()
+    if a.kind == "block-trace-diff":
+        return block_trace_diff(a)
     import torch
     torch.cuda.init()
     from esparse_loader import load
@@ -343,6 +505,10 @@ def main():
         return bench_cg(a, torch, esp)
     if a.kind == "bicgstabl":
         return bench_bicgstabl(a, torch, esp)
+    if a.kind == "block":
+        return bench_block(a, torch, esp)
+    if a.kind == "block-trace":
+        return bench_block_trace(a, torch, esp)
     A = esp.fdrand(a.n, a.n, a.n)
     d = A._d
     stream = torch.cuda.current_stream()
