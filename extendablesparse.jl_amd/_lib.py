@@ -16,7 +16,8 @@ ESP_ERR_UNSUPPORTED, ESP_ERR_STATE, ESP_ERR_NODEVICE = -5, -6, -7
 ESP_SET, ESP_UPDATE, ESP_RAWUPDATE, ESP_COO = 0, 1, 2, 3
 ESP_OP_ADD, ESP_OP_SUB = 0, 1
 ESP_FLUSH_ROUTED, ESP_FLUSH_PLUS = 0, 1
-ESP_PRECON_JACOBI, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_BLOCK = 0, 1, 2, 3
+ESP_PRECON_JACOBI, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_BLOCK, ESP_PRECON_AMG = 0, 1, 2, 3, 4
+ESP_AMG_DENSE_MAX = 512
 STAGES = ("append", "hist", "scan", "scatter", "local", "fold", "colptr", "merge", "copy")
 ESP_ST_COUNT = len(STAGES)
 
@@ -104,6 +105,11 @@ SIGNATURES = {
     "esp_precon_block_create": (i32, [vp, i32, i64, vp, vp, i32, P(vp)]),
     "esp_precon_block_matrix": (i32, [vp, P(vp), P(i32)]),
     "esp_debug_block_path": (i32, [vp, i32]),
+    "esp_precon_amg_create": (i32, [vp, i32, i32, i32, i32, f64, P(vp)]),
+    "esp_precon_amg_levels": (i32, [vp, P(i32)]),
+    "esp_precon_amg_level": (i32, [vp, i32, P(vp), P(vp), P(i64), P(f64), P(i32)]),
+    "esp_precon_amg_aggregates": (i32, [vp, i32, vp, i32]),
+    "esp_precon_amg_coarse_inverse": (i32, [vp, vp, i32]),
     "esp_simple": (i32, [vp, vp, vp, vp, i32, i64, f64, f64, vp, P(i64)]),
     "esp_cg": (i32, [vp, vp, vp, vp, i32, i32, i64, f64, f64, vp, P(i64), P(i32)]),
     "esp_bicgstabl": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i64, f64, f64, vp, P(i64), P(i64), P(i32)]),

@@ -49,7 +49,7 @@
 //                     Jacobi    row_dot_k<MUL_JAC_DOT>: the gathered row sum times invdiag[i] before the store -- one launch,
 //                               bitwise ldiv! of mul!
 //                     ILU0      row_dot_k<MUL_DOT> into the scratch (no dot), row_chain_k<ILU_LOWER>, row_dot_k<UPPER_DOT>
-//                     ILUAM     the matvec into the scratch, the level launches of iluam_solve, dot_k
+//                     ILUAM     the matvec into the scratch, the level launches of iluam_solve, dot_k (AMG: the V-cycle's launches)
 //   fold_k          level 1 of sigma
 //   bicg_upd_k      level 2 of rho and sigma redone, alpha, rs[0..j] -= alpha*us[1..j+1], x += alpha*us[0] in one launch
 //   pmul            rs[j+1] = Pl \ (A*rs[j]) with level 0 of dot(rt, rs[j+1]) = the next rho (not for rs[l]: nothing reads it)
@@ -347,8 +347,9 @@ extern "C" int32_t esp_bicgstabl(esp_handle *h, esp_precon *p, int32_t l, const 
     };
     // dst = Pl \ src for ILU0 / ILUAM (src != dst), level 0 of dot(dst, rt) when dot
     auto ldiv = [&](const double *src, double *dst, bool dot) -> int32_t {
-        if (blk || p->kind == ESP_PRECON_ILUAM) {
+        if (blk || p->kind == ESP_PRECON_ILUAM || p->kind == ESP_PRECON_AMG) {
             if (blk) CK(block_ldiv_launch(blk, src, dst, false));
+            else if (p->kind == ESP_PRECON_AMG) CK(amg_solve(p, src, dst, false));
             else CK(iluam_solve(p, src, dst, false));
             if (dot)
                 hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, h->stream, nil, (const double *)dst, (const double *)rt,

@@ -10,6 +10,8 @@
 //   precon.hip     the point preconditioners' update! / ldiv! (esp_precon_*) and simple! (esp_simple) on the device CSC
 //   iluam.hip      ILUAMPreconditioner: level analysis, level-scheduled ILU(0) factorization and triangular solves
 //   block.hip      BlockPreconditioner: the masked block matrix B of a partitioning (identity / permuted path) and the object around it
+//   amg.hip        AMGPreconditioner: smoothed aggregation (MIS(2) aggregates by Luby rounds, the level hierarchy from the algebra
+//                  calls on internal handles, the fused V-cycle kernels)
 //   krylov.hip     preconditioned conjugate gradients (esp_cg): fused vector kernels, ordered dot products, scalars on the device
 //   bicgstabl.hip  BiCGStab(l) for non-symmetric systems (esp_bicgstabl): the same design with l+1 residuals and search vectors;
 //                  krylov.hpp holds what the two solvers share
@@ -569,6 +571,9 @@ struct esp_precon {
     DevBuf blk_new, blk_part;  // u32 n each: new(i), part(i)
     DevBuf blk_src;            // u32 nnz(B): the position in A's nzval entry q of B came from
     DevBuf blk_t, blk_s;       // f64 n each (permuted path)
+    // AMGPreconditioner (kind ESP_PRECON_AMG, amg.hip): the parameters and the level hierarchy (internal handles of every A_l and
+    // P_l, the weights, the cycle's vectors, the dense inverse of the coarsest level)
+    struct AmgData *amg = nullptr;
 };
 // the identity-path block preconditioner stands for its inner one in the solvers' fused branches
 static inline esp_precon *fused_precon(esp_precon *p) { return p && p->kind == ESP_PRECON_BLOCK && p->blk_path == 0 ? p->inner : p; }
@@ -597,6 +602,11 @@ int32_t block_update(esp_precon *p);
 int32_t block_follow_stream(esp_precon *p);
 int32_t block_ldiv_launch(esp_precon *p, const double *v, double *u, bool sub);
 void block_release(esp_precon *p);
+// amg.hip: update! (the whole hierarchy is rebuilt every time), the V-cycle on device vectors (u may be v; sub: u[i] = u[i] - x[i],
+// simple!'s step; launches on the handle's stream only), release of the hierarchy
+int32_t amg_update(esp_precon *p);
+int32_t amg_solve(esp_precon *p, const double *v, double *u, bool sub);
+void amg_release(esp_precon *p);
 // linalg.hip, for block.hip: every column of (cp: 0-based starts, rowC, valC) sorted by row, valC carried along; the caller
 // found maxlen <= COLSORT_BLOCK and listed the nlong columns longer than COLSORT_LANE
 constexpr int COLSORT_LANE = 32, COLSORT_BLOCK = 4096;

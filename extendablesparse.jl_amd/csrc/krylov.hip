@@ -173,8 +173,9 @@ extern "C" int32_t esp_cg(esp_handle *h, esp_precon *p, const double *b, double 
             } else if (p->kind == ESP_PRECON_JACOBI) {
                 hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)p->diag.p, (const double *)nullptr,
                                    (const double *)r, c, n, nb0, p0);
-            } else if (p->kind == ESP_PRECON_ILUAM) {
-                CK(iluam_solve(p, r, c, false));
+            } else if (p->kind == ESP_PRECON_ILUAM || p->kind == ESP_PRECON_AMG) {
+                if (p->kind == ESP_PRECON_AMG) CK(amg_solve(p, r, c, false));  // the V-cycle's launches, then dot_k
+                else CK(iluam_solve(p, r, c, false));
                 hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)nullptr, (const double *)c, (const double *)r,
                                    (double *)nullptr, n, nb0, p0);
             } else {

@@ -310,6 +310,7 @@ int32_t ldiv_launch(esp_precon *p, const double *v, double *u) {
     if (n == 0) return ESP_OK;
     if (p->kind == ESP_PRECON_BLOCK) return block_ldiv_launch(p, v, u, false);
     if (p->kind == ESP_PRECON_ILUAM) return iluam_solve(p, v, u, false);
+    if (p->kind == ESP_PRECON_AMG) return amg_solve(p, v, u, false);
     const unsigned g = grid_for(n, PT);
     if (p->kind == ESP_PRECON_JACOBI) {
         hipLaunchKernelGGL(jacobi_ldiv_k, dim3(g), dim3(PT), 0, h->stream, (const double *)p->diag.p, v, u, n);
@@ -357,6 +358,7 @@ extern "C" int32_t esp_precon_create(esp_handle *h, int32_t kind, esp_precon **o
 extern "C" int32_t esp_precon_update(esp_precon *p) {
     if (!p) return ESP_ERR_INVALID;
     if (p->kind == ESP_PRECON_BLOCK) return block_update(p);  // B and the inner preconditioner (block.hip)
+    if (p->kind == ESP_PRECON_AMG) return amg_update(p);      // the whole hierarchy (amg.hip)
     esp_handle *h = p->h;
     CK(check_handle(h, "esp_precon_update"));
     p->n = h->n;
@@ -409,6 +411,7 @@ extern "C" int32_t esp_precon_destroy(esp_precon *p) {
                       &p->partial, &p->scanws, &p->hv, &p->hu})
         release(*b);
     iluam_release(p);
+    amg_release(p);
     h->live_precons--;
     delete p;
     return ESP_OK;
@@ -465,6 +468,8 @@ extern "C" int32_t esp_simple(esp_handle *h, esp_precon *p, const double *b, dou
                                    (const double *)res, du, n);
             } else if (p->kind == ESP_PRECON_ILUAM) {
                 CK(iluam_solve(p, res, du, true));
+            } else if (p->kind == ESP_PRECON_AMG) {
+                CK(amg_solve(p, res, du, true));
             } else {
                 double *u1 = (double *)p->u1.p;
                 hipLaunchKernelGGL((row_chain_k<ILU_LOWER, u32>), dim3((unsigned)nb), dim3(PT), 0, h->stream, (const u32 *)p->lptr.p,

@@ -12,13 +12,16 @@ bicgstabl(A, b, l, Pl=...) is IterativeSolvers' bicgstabl / bicgstabl! for non-s
 way (include/esparse_hip.h, esp_bicgstabl).
 BlockPreconditioner(A, partitioning, factorization) (src/factorizations/blockpreconditioner.jl) solves every A[part, part] with one
 of the three point kinds: one block matrix and one inner preconditioner on the device, bit-identical to the per-block loops.
+AMGPreconditioner(A) (= SA_AMGPreconditioner, ext/ExtendableSparseAlgebraicMultigridExt.jl) is a smoothed-aggregation V-cycle whose
+hierarchy is built on the device; the algorithm is the one include/esparse_hip.h states (esp_precon_amg_create), bit-identical to
+tests/amg_model.c.
 """
 import ctypes as C
 import math
 
 import numpy as np
 
-from ._lib import ESP_PRECON_BLOCK, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_JACOBI
+from ._lib import ESP_PRECON_AMG, ESP_PRECON_BLOCK, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_JACOBI
 from .matrix import ExtendableSparseMatrix, _vp
 
 
@@ -199,6 +202,81 @@ class BlockPreconditioner(_PointPreconditioner):
         out = (C.c_int64 * 3)()
         self._ck(self.A._d.lib.esp_precon_levels(self._live(), out))
         return tuple(int(x) for x in out)
+
+
+class AMGPreconditioner(_PointPreconditioner):
+    """AMGPreconditioner(A; max_levels, max_coarse, presweeps, postsweeps, theta) (the reference's SA_AMGPreconditioner,
+    ext/ExtendableSparseAlgebraicMultigridExt.jl): ldiv! is one smoothed-aggregation V-cycle (include/esparse_hip.h,
+    esp_precon_amg_create): MIS(2) aggregates, P = (I - w.*A)*T, Galerkin coarse matrices, weighted-Jacobi sweeps, a dense
+    inverse on the coarsest level.  The stored pattern must be structurally symmetric and hold every diagonal entry.  The
+    hierarchy is built from copies: a value change of A reaches ldiv only through update(), which rebuilds everything."""
+    KIND = ESP_PRECON_AMG
+
+    def __init__(self, A, max_levels=10, max_coarse=64, presweeps=1, postsweeps=1, theta=0.0):
+        if not isinstance(A, ExtendableSparseMatrix):
+            raise TypeError("AMGPreconditioner(A): A must be an ExtendableSparseMatrix")
+        for name, v, lo in (("max_levels", max_levels, 1), ("max_coarse", max_coarse, 1), ("presweeps", presweeps, 1),
+                            ("postsweeps", postsweeps, 0)):
+            if int(v) != v or v < lo:
+                raise ValueError("AMGPreconditioner: %s = %r (an integer >= %d)" % (name, v, lo))
+        if not (theta >= 0.0 and math.isfinite(theta)):
+            raise ValueError("AMGPreconditioner: theta = %r (finite, >= 0)" % (theta,))
+        self.A = A
+        self._p = None
+        A.flush()
+        d = A._d
+        p = C.c_void_p()
+        d.ck(d.lib.esp_precon_amg_create(d.h, int(max_levels), int(max_coarse), int(presweeps), int(postsweeps), float(theta),
+                                         C.byref(p)))
+        self._p = p
+
+    @property
+    def levels(self):
+        """the number of levels of the hierarchy"""
+        k = C.c_int32()
+        self._ck(self.A._d.lib.esp_precon_amg_levels(self._live(), C.byref(k)))
+        return k.value
+
+    def _csc(self, h, n):
+        lib = self.A._d.lib
+        nnz = C.c_int64()
+        self._ck(lib.esp_nnz(h, C.byref(nnz)))
+        cp, rv, nz = np.empty(n + 1, np.int64), np.empty(nnz.value, np.int64), np.empty(nnz.value, np.float64)
+        self._ck(lib.esp_get_csc(h, _vp(cp), _vp(rv), _vp(nz)))
+        return cp, rv, nz
+
+    def level(self, l):
+        """level l as a dict: n, rho, rounds (the Luby rounds of its aggregation, 0 where none ran), A and P as host CSC arrays
+        (colptr, rowval, nzval), Julia layout; P is None on the coarsest level -- for tests and inspection"""
+        a, pr = C.c_void_p(), C.c_void_p()
+        n, rho, rounds = C.c_int64(), C.c_double(), C.c_int32()
+        self._ck(self.A._d.lib.esp_precon_amg_level(self._live(), int(l), C.byref(a), C.byref(pr), C.byref(n), C.byref(rho),
+                                                    C.byref(rounds)))
+        out = {"n": n.value, "rho": rho.value, "rounds": rounds.value, "A": self._csc(a, n.value), "P": None}
+        if pr.value:
+            m, nc = C.c_int64(), C.c_int64()
+            self._ck(self.A._d.lib.esp_size(pr, C.byref(m), C.byref(nc)))
+            out["P"] = self._csc(pr, nc.value)
+        return out
+
+    def aggregates(self, l):
+        """the aggregate (0-based) of every unknown of level l"""
+        a, n = C.c_void_p(), C.c_int64()
+        self._ck(self.A._d.lib.esp_precon_amg_level(self._live(), int(l), C.byref(a), None, C.byref(n), None, None))
+        out = np.empty(n.value, np.int64)
+        self._ck(self.A._d.lib.esp_precon_amg_aggregates(self._live(), int(l), _vp(out), 0))
+        return out
+
+    def coarse_inverse(self):
+        """the dense inverse of the coarsest level (n_L x n_L); raises if that level is only smoothed"""
+        a, n = C.c_void_p(), C.c_int64()
+        self._ck(self.A._d.lib.esp_precon_amg_level(self._live(), self.levels - 1, C.byref(a), None, C.byref(n), None, None))
+        out = np.empty((n.value, n.value), np.float64)
+        self._ck(self.A._d.lib.esp_precon_amg_coarse_inverse(self._live(), _vp(out), 0))
+        return out
+
+
+SA_AMGPreconditioner = AMGPreconditioner
 
 
 def simple(A, b, u=None, Pl=None, maxiter=100, reltol=math.sqrt(np.finfo(np.float64).eps), abstol=0.0, log=False):

@@ -377,6 +377,48 @@ int32_t esp_precon_block_create(esp_handle *h, int32_t inner_kind, int64_t npart
 int32_t esp_precon_block_matrix(esp_precon *p, esp_handle **b, int32_t *path);
 /* test hook, takes effect at the next esp_precon_update (which then rebuilds B): 0 automatic, 1 force the permuted path */
 int32_t esp_debug_block_path(esp_precon *p, int32_t path);
+/* AMGPreconditioner (ext/ExtendableSparseAlgebraicMultigridExt.jl: SA_AMGPreconditioner): a smoothed-aggregation V-cycle.
+ * AlgebraicMultigrid.jl is not part of the reference tree, its aggregation is a sequential greedy sweep and its spectral-radius
+ * estimate starts from rand: the algorithm here is stated in full, tests/amg_model.c restates it as plain loops
+ * and is normative for the order of every operation, and the device result is bit-identical to that model.  In short, level by
+ * level from A_0 = a copy of A: dinv = 1/a_ii (esp_jacobi_setup), rho = opnorm(Diagonal(dinv)*A_l, Inf), w = ((4/3)/rho)*dinv;
+ * strong edges {i,j} (both entries stored): m = max(|a_ij|, |a_ji|) != 0 and m*m >= (theta*theta)*(|a_ii|*|a_jj|); aggregates = a
+ * distance-2 maximal independent set of the strong graph found by Luby rounds over a fixed hash of the index (parallel and
+ * reproducible), roots numbered in index order, the other nodes joined in two passes; T[i, agg(i)] = 1; P_l = T + (Diagonal(-w)*A_l)*T
+ * and A_{l+1} = transpose(P_l)*(A_l*P_l) by the rules of esp_diag_scale, esp_matmul, esp_add and esp_transpose.  Level l is the
+ * coarsest when n_l <= max_coarse, l + 1 == max_levels or the aggregation leaves n_{l+1} == n_l; a coarsest level of at most
+ * ESP_AMG_DENSE_MAX unknowns is solved with its dense inverse (Gauss-Jordan, partial pivoting, a zero pivot is no error), a larger
+ * one is only smoothed.
+ * esp_precon_ldiv = one V-cycle from x = 0: presweeps weighted-Jacobi sweeps x = x + w.*(b - A_l*x) (the first one is x = w.*b),
+ *   r = b - A_l*x, b_c = transpose(P_l)*r (esp_mul_transpose's rule), the cycle on level l+1, x = x + P_l*x_c, postsweeps sweeps;
+ *   every product A_l*x and P_l*x_c in esp_mul's order.  u may alias v.  With presweeps == postsweeps and a symmetric A the
+ *   operator is symmetric (what esp_cg needs).  On device vectors one call is launches on the handle's stream only: no copy, no
+ *   allocation, no synchronisation before the end.
+ * esp_precon_amg_create: max_levels >= 1, 1 <= max_coarse <= ESP_AMG_DENSE_MAX, presweeps >= 1, postsweeps >= 0, theta >= 0 and
+ *   finite; -1 for any of the four integers / a negative theta selects the default: 10, 64, 1, 1, 0.0.  n == 0 and n == 1 are valid.
+ *   The result is an esp_precon bound to h; esp_precon_update / _ldiv / _destroy, esp_simple, esp_cg and esp_bicgstabl take it
+ *   unchanged, with the stream use and "returns synchronised" rules of the other kinds.
+ * esp_precon_update rebuilds the whole hierarchy every time, as the reference's update! does (no values-only form).  The
+ *   hierarchy is built from copies: ldiv! sees A as of the last update!; a pattern change of A without update! -> ESP_ERR_STATE.
+ * esp_precon_get_factor -> ESP_ERR_INVALID, esp_precon_levels gives zeros; AMG is no inner kind of esp_precon_block_create.
+ * ESP_ERR_INVALID: a rectangular matrix; an argument out of range; a column without a stored diagonal (the smallest is named).
+ * ESP_ERR_STATE: pending entries.  ESP_ERR_UNSUPPORTED: a column window / column shard on h; n or nnz >= 2^32 - 16; a stored
+ *   pattern that is not structurally symmetric (some stored (i,j) without a stored (j,i); the smallest such column is named; only
+ *   the pattern is tested, on level 0: convection-diffusion matrices pass).  A stored zero diagonal is no error: Inf / NaN propagate.
+ * ESP_ERR_NOMEM from a failed create or rebuild leaves A usable; after a failed rebuild p refuses ldiv! (ESP_ERR_STATE) until the
+ *   next good update!.  h refuses esp_destroy while the preconditioner lives.
+ * Inspection (tests, tools): the number of levels; per level the BORROWED handles of A_l and P_l (read them with esp_get_csc /
+ *   esp_nnz only; P_l is NULL on the coarsest level), n_l, rho_l and the Luby rounds its aggregation took (0 where none ran); the
+ *   aggregate of every unknown of a level (n_l int64, 0-based, host or device; ESP_ERR_INVALID for a level that was not
+ *   aggregated); the dense inverse of the coarsest level (n_L*n_L doubles, row-major; ESP_ERR_INVALID if it has none). */
+#define ESP_PRECON_AMG 4
+#define ESP_AMG_DENSE_MAX 512
+int32_t esp_precon_amg_create(esp_handle *h, int32_t max_levels, int32_t max_coarse, int32_t presweeps, int32_t postsweeps,
+                              double theta, esp_precon **out);
+int32_t esp_precon_amg_levels(esp_precon *p, int32_t *nlevels);
+int32_t esp_precon_amg_level(esp_precon *p, int32_t level, esp_handle **a, esp_handle **prolong, int64_t *n, double *rho, int32_t *rounds);
+int32_t esp_precon_amg_aggregates(esp_precon *p, int32_t level, int64_t *agg, int32_t on_device);
+int32_t esp_precon_amg_coarse_inverse(esp_precon *p, double *inv, int32_t on_device);
 /* simple!(u, A, b; abstol, reltol, maxiter, Pl = p) (src/factorizations/simple_iteration.jl:21-45) statement by
  * statement: res = A*u - b; then per step ldiv!(upd, Pl, res), u .-= upd, mul!(res, A, u), res .-= b, r = norm(res),
  * stop when (r / r0) < reltol || r < abstol (literally: r0 = 0 gives NaN or Inf there).  u (in/out) is bit-identical to

@@ -46,6 +46,13 @@ kernels and copies per ldiv! call.
 
     rocprofv3 --kernel-trace --memory-copy-trace --stats --output-format csv -d OUT -- \
         python tools/precon_bench.py --kind block-trace --cg-only ilu0 --block-config b --n 64 --iters 25 --warmup 0
+
+--kind amg times AMGPreconditioner (esp_precon_amg_create) on fdrand(n,n,n): the setup (create; then update!, which rebuilds the
+whole hierarchy, --rounds times: median, min, max), ldiv! on device vectors (--rounds rounds of --iters calls each: median, min,
+max), the level sizes, the operator complexity (the stored entries of all A_l over those of A_0) and the Luby rounds of every
+level, and cg to reltol = 1e-8 with b = ones with AMG and with ILU0: iterations and wall time of each (the second of two solves).
+
+    python tools/precon_bench.py --kind amg [--n 64] [--iters 20] [--rounds 5] [--tol-maxiter 20000]
 """
 import argparse
 import ctypes as C
@@ -477,12 +484,84 @@ def block_trace_diff(a):
     print(json.dumps(out))
 
 
+def bench_amg(a, torch, esp):
+    import statistics
+    A = esp.fdrand(a.n, a.n, a.n)
+    d = A._d
+    stream = torch.cuda.current_stream()
+    d.ck(d.lib.esp_set_stream(d.h, C.c_void_p(stream.cuda_stream)))
+    N, Z = A.n, A.nnz()
+    v = torch.randn(N, dtype=torch.float64, device="cuda")
+    u = torch.empty_like(v)
+    b = torch.ones_like(v)
+
+    def span(fn, reps):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    def stats(xs):
+        return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "runs": len(xs)}
+
+    out = {"workload": "amg_fdrand", "n": a.n, "N": N, "nnz": Z}
+    t0 = time.perf_counter()
+    P = esp.AMGPreconditioner(A)                      # the first build (the level handles' indices included)
+    out["create_first_ms"] = (time.perf_counter() - t0) * 1e3
+    note = lambda: print(json.dumps(out), file=sys.stderr, flush=True)   # (what is known so far, should a later phase be cut short)
+    note()
+    out["setup_ms"] = stats([span(P.update, 1) for _ in range(max(a.rounds, 1))])
+    lib, p = d.lib, P._p
+    sizes, nnzs, rounds = [], [], []
+    for l in range(P.levels):
+        ha, n, rho, rd, z = C.c_void_p(), C.c_int64(), C.c_double(), C.c_int32(), C.c_int64()
+        d.ck(lib.esp_precon_amg_level(p, l, C.byref(ha), None, C.byref(n), C.byref(rho), C.byref(rd)))
+        d.ck(lib.esp_nnz(ha, C.byref(z)))
+        sizes.append(n.value), nnzs.append(z.value), rounds.append(rd.value)
+    out["level_sizes"], out["level_nnz"], out["luby_rounds"] = sizes, nnzs, rounds
+    out["operator_complexity"] = sum(nnzs) / max(nnzs[0], 1)
+    note()
+    for _ in range(a.warmup):
+        P.ldiv(v, out=u)
+    out["ldiv_ms"] = stats([span(lambda: P.ldiv(v, out=u), a.iters) for _ in range(max(a.rounds, 1))])
+    note()
+    Q = esp.ILU0Preconditioner(A)
+    for name, pl in (("amg", P), ("ilu0", Q)):
+        rec = None
+        for _ in range(2):                            # (the first solve sizes the work vectors)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            x, log = esp.cg(A, b, Pl=pl, maxiter=a.tol_maxiter, reltol=1e-8, log=True)
+            dt = time.perf_counter() - t0             # (esp_cg returns synchronised)
+            rec = {"iterations": log["iters"], "converged": log["isconverged"], "ms": dt * 1e3}
+        rec["true_residual_over_b"] = (torch.linalg.vector_norm(b - A.mul(x)) / torch.linalg.vector_norm(b)).item()
+        out["cg_" + name] = rec
+        note()
+    P.close()
+    Q.close()
+
+    def rnd(x):
+        if isinstance(x, float):
+            return float("%.5g" % x)
+        if isinstance(x, dict):
+            return {k: rnd(y) for k, y in x.items()}
+        if isinstance(x, list):
+            return [rnd(y) for y in x]
+        return x
+
+    print(json.dumps(rnd(out)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "block", "block-trace", "block-trace-diff"], default="point")
+    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "block", "block-trace", "block-trace-diff", "amg"], default="point")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--block-config", choices=["a", "b", "c", "d", "e"], default="b")
     ap.add_argument("--dirs", nargs=2, default=None)
@@ -509,6 +588,8 @@ def main():
         return bench_block(a, torch, esp)
     if a.kind == "block-trace":
         return bench_block_trace(a, torch, esp)
+    if a.kind == "amg":
+        return bench_amg(a, torch, esp)
     A = esp.fdrand(a.n, a.n, a.n)
     d = A._d
     stream = torch.cuda.current_stream()
