@@ -18,6 +18,8 @@ ESP_OP_ADD, ESP_OP_SUB = 0, 1
 ESP_FLUSH_ROUTED, ESP_FLUSH_PLUS = 0, 1
 ESP_PRECON_JACOBI, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_BLOCK, ESP_PRECON_AMG = 0, 1, 2, 3, 4
 ESP_AMG_DENSE_MAX = 512
+ESP_ORTH_MGS, ESP_ORTH_CGS, ESP_ORTH_DGKS = 0, 1, 2
+ESP_GMRES_RESTART_MAX = 64
 STAGES = ("append", "hist", "scan", "scatter", "local", "fold", "colptr", "merge", "copy")
 ESP_ST_COUNT = len(STAGES)
 
@@ -113,6 +115,7 @@ SIGNATURES = {
     "esp_simple": (i32, [vp, vp, vp, vp, i32, i64, f64, f64, vp, P(i64)]),
     "esp_cg": (i32, [vp, vp, vp, vp, i32, i32, i64, f64, f64, vp, P(i64), P(i32)]),
     "esp_bicgstabl": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i64, f64, f64, vp, P(i64), P(i64), P(i32)]),
+    "esp_gmres": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i64, f64, f64, vp, P(i64), P(i64), P(i64), P(i32)]),
     "esp_matmul": (i32, [vp, vp, vp, P(i64)]),
     "esp_add": (i32, [vp, vp, i32, vp, P(i64)]),
     "esp_diag_scale": (i32, [vp, vp, i32, i32, vp]),

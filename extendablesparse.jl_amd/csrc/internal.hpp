@@ -14,7 +14,9 @@
 //                  calls on internal handles, the fused V-cycle kernels)
 //   krylov.hip     preconditioned conjugate gradients (esp_cg): fused vector kernels, ordered dot products, scalars on the device
 //   bicgstabl.hip  BiCGStab(l) for non-symmetric systems (esp_bicgstabl): the same design with l+1 residuals and search vectors;
-//                  krylov.hpp holds what the two solvers share
+//                  krylov.hpp holds what the solvers share
+//   gmres.hip      restarted GMRES (esp_gmres): fused modified Gram-Schmidt steps, batched classical / DGKS passes behind a device
+//                  predicate, H, the residual recurrence, the rotations and y in a scalar block on the device
 //   matops.hip     the algebra of assembled matrices on the device: A*B (esp_matmul), A+B / A-B (esp_add), Diagonal scaling
 //   linalg.hip     transpose (esp_transpose), transpose(A)*x (esp_mul_transpose), issymmetric, opnorm, norm on the device CSC
 //   local_*.hip    the instantiations of the bucket kernel (local.hpp; local_h.hip: group3.hpp, the group tier with three workgroups per CU;
@@ -348,7 +350,8 @@ struct esp_handle {
     int live_precons = 0;  // esp_precon objects bound to this handle (precon.hip): esp_destroy refuses while any is alive
     // esp_cg's work vectors (krylov.hip), sized on first use: residual, search direction, Pl \ r and A*u, the partial sums of the
     // three dot products, and the device copies of host b / x.  esp_bicgstabl (bicgstabl.hip) shares part, hb and hx and adds
-    // bv: its 2(l+1) + 1 vectors (rs[0..l], us[0..l], the shadow residual), t: A*v in front of ILU0 / ILUAM, sc: the scalar block
+    // bv: its 2(l+1) + 1 vectors (rs[0..l], us[0..l], the shadow residual), t: A*v in front of ILU0 / ILUAM, sc: the scalar block.
+    // esp_gmres (gmres.hip) uses the same buffers: bv holds its restart+1 basis vectors, sc its H, nullvec, rhs, h, c and scalars
     struct Krylov {
         DevBuf r, u, c, part, hb, hx, bv, t, sc;
     } kry;

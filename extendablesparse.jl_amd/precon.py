@@ -10,6 +10,9 @@ cg(A, b, Pl=...) is IterativeSolvers' cg / cg! with any of the preconditioners (
 residual history are identical run to run and bit-identical to the statement-by-statement model (include/esparse_hip.h, esp_cg).
 bicgstabl(A, b, l, Pl=...) is IterativeSolvers' bicgstabl / bicgstabl! for non-symmetric matrices, held to its model in the same
 way (include/esparse_hip.h, esp_bicgstabl).
+gmres(A, b, Pl=..., restart=..., orth_meth=...) is IterativeSolvers' gmres / gmres!, restarted GMRES with modified or classical
+Gram-Schmidt or DGKS re-orthogonalisation, the fallback where BiCGStab(l) breaks down, held to its model in the same way
+(include/esparse_hip.h, esp_gmres).
 BlockPreconditioner(A, partitioning, factorization) (src/factorizations/blockpreconditioner.jl) solves every A[part, part] with one
 of the three point kinds: one block matrix and one inner preconditioner on the device, bit-identical to the per-block loops.
 AMGPreconditioner(A) (= SA_AMGPreconditioner, ext/ExtendableSparseAlgebraicMultigridExt.jl) is a smoothed-aggregation V-cycle whose
@@ -21,7 +24,7 @@ import math
 
 import numpy as np
 
-from ._lib import ESP_PRECON_AMG, ESP_PRECON_BLOCK, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_JACOBI
+from ._lib import ESP_ORTH_CGS, ESP_ORTH_DGKS, ESP_ORTH_MGS, ESP_PRECON_AMG, ESP_PRECON_BLOCK, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_JACOBI
 from .matrix import ExtendableSparseMatrix, _vp
 
 
@@ -426,5 +429,62 @@ def bicgstabl(A, b, l=2, Pl=None, x=None, abstol=0.0, reltol=math.sqrt(np.finfo(
     if log:
         k = its.value
         return x, {"resnorm": hist[1:k + 1].copy(), "r0": float(hist[0]), "iters": k, "mvps": mvs.value,
+                   "isconverged": bool(conv.value)}
+    return x
+
+
+_ORTH = {"mgs": ESP_ORTH_MGS, "cgs": ESP_ORTH_CGS, "dgks": ESP_ORTH_DGKS}
+
+
+def gmres(A, b, Pl=None, x=None, restart=None, maxiter=None, abstol=0.0, reltol=math.sqrt(np.finfo(np.float64).eps), orth_meth="mgs",
+          log=False):
+    """gmres / gmres!(x, A, b; Pl, abstol, reltol, restart, maxiter, orth_meth, log) of IterativeSolvers.jl for non-symmetric
+    systems (include/esparse_hip.h, esp_gmres): restarted GMRES with Pl as the LEFT preconditioner, until the preconditioned
+    residual norm <= max(reltol*norm(r0), abstol) or maxiter (None: n) iterations.  restart (None: max(1, min(20, n)); at most 64)
+    is the length of a cycle; orth_meth is "mgs" (modified Gram-Schmidt, the package's default), "cgs" (classical) or "dgks"
+    (classical with up to three correction passes).  x = None starts from zeros; a given x is updated in place.  Pl: a
+    preconditioner of A, or None (Identity).
+    log=True returns (x, {"resnorm": the norm after every iteration, "r0": the initial one, "iters": iterations, "mvps":
+    matrix-vector products, "reorth": DGKS correction passes, "isconverged": bool})."""
+    if not isinstance(A, ExtendableSparseMatrix):
+        raise TypeError("gmres(A, b): A must be an ExtendableSparseMatrix")
+    if Pl is not None and (not isinstance(Pl, _PointPreconditioner) or Pl.A is not A):
+        raise ValueError("gmres: Pl must be a preconditioner of A, or None")
+    if orth_meth not in _ORTH:
+        raise ValueError("gmres: orth_meth = %r (one of 'mgs', 'cgs', 'dgks')" % (orth_meth,))
+    p = Pl._live() if Pl is not None else None
+    A.flush()
+    d = A._d
+    n = A.n
+    restart = max(1, min(20, n)) if restart is None else int(restart)
+    maxiter = n if maxiter is None else int(maxiter)
+    if maxiter < 0:
+        raise ValueError("maxiter < 0")
+    hist = np.empty(maxiter + 1, np.float64)
+    its, mvs, reorth = C.c_int64(), C.c_int64(), C.c_int64()
+    conv = C.c_int32()
+    zero = 1 if x is None else 0
+    if _is_cuda(b):
+        import torch
+        _check_cuda(b, n)
+        if x is None:
+            x = torch.zeros(n, dtype=torch.float64, device=b.device)
+        _check_cuda(x, n)
+        torch.cuda.current_stream(b.device).synchronize()   # the library runs on its own stream
+        d.ck(d.lib.esp_gmres(d.h, p, C.c_void_p(b.data_ptr()), C.c_void_p(x.data_ptr()), 1, zero, restart, _ORTH[orth_meth], maxiter,
+                             float(abstol), float(reltol), _vp(hist), C.byref(its), C.byref(mvs), C.byref(reorth), C.byref(conv)))
+    else:
+        bb = np.ascontiguousarray(b, np.float64)
+        if bb.shape != (n,):
+            raise ValueError("DimensionMismatch")
+        if x is None:
+            x = np.zeros(n, np.float64)
+        if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.shape == (n,) and x.flags.c_contiguous):
+            raise ValueError("x must be a contiguous float64 array of length n")
+        d.ck(d.lib.esp_gmres(d.h, p, _vp(bb), _vp(x), 0, zero, restart, _ORTH[orth_meth], maxiter, float(abstol), float(reltol),
+                             _vp(hist), C.byref(its), C.byref(mvs), C.byref(reorth), C.byref(conv)))
+    if log:
+        k = its.value
+        return x, {"resnorm": hist[1:k + 1].copy(), "r0": float(hist[0]), "iters": k, "mvps": mvs.value, "reorth": reorth.value,
                    "isconverged": bool(conv.value)}
     return x

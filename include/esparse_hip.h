@@ -484,6 +484,65 @@ int32_t esp_cg(esp_handle *h, esp_precon *p, const double *b, double *x, int32_t
 int32_t esp_bicgstabl(esp_handle *h, esp_precon *p, int32_t l, const double *b, double *x, const double *r_shadow,
                       int32_t on_device, int32_t initially_zero, int64_t max_mv_products, double abstol, double reltol,
                       double *history, int64_t *iterations, int64_t *mv_products, int32_t *converged);
+/* gmres / gmres!(x, A, b; Pl = p, abstol, reltol, restart, maxiter, initially_zero, orth_meth) of IterativeSolvers.jl: restarted
+ * GMRES(m) for NON-SYMMETRIC systems, the robust fallback where BiCGStab(l) breaks down (restated from the package's documented
+ * behaviour: the package is not part of the reference tree; test/test_parilu0.jl:16-17 solves with it) on the device CSC.  LEFT
+ * preconditioning: every residual and norm is the preconditioned one.  V is n x (restart+1), H (restart+1) x restart, nullvec
+ * has restart+1 entries, all 1.0 at the start:
+ *   init:  V1 = b (initially_zero != 0: x is taken to hold zeros) or b - A*x (mv += 1); V1 = Pl \ V1; beta = norm(V1);
+ *          V1 = V1 * (1.0/beta)
+ *   start: beta = init; acc = 1; current = beta; tol = max(reltol*current, abstol); k = 1; it = 0; history[0] = current
+ *   while it < maxiter and not current <= tol:
+ *     w = V[k+1] = Pl \ (A*V[k]); mv += 1
+ *     orthogonalise w against V[1..k] -> H[1..k,k], nrm (below); w = w * (1.0/nrm); H[k+1,k] = nrm
+ *     s = 0; for i = 1..k increasing: s = s + nullvec[i]*H[i,k]
+ *     nullvec[k+1] = -(s / H[k+1,k]); acc = acc + nullvec[k+1]*nullvec[k+1]; current = beta / sqrt(acc)
+ *     k += 1; it += 1; history[it] = current
+ *     if k == restart+1 or current <= tol or it == maxiter:
+ *       m = k-1; rhs = (beta, 0, .., 0) of length k
+ *       for i = 1..m (Givens, column by column):
+ *         f = H[i,i]; g = H[i+1,i]; g == 0 ? (c,s) = (1,0) : (r = sqrt(f*f + g*g); c = f/r; s = g/r)
+ *         H[i,i] = c*f + s*g
+ *         for j = i+1..m: t = -s*H[i,j] + c*H[i+1,j]; H[i,j] = c*H[i,j] + s*H[i+1,j]; H[i+1,j] = t
+ *         t = -s*rhs[i] + c*rhs[i+1]; rhs[i] = c*rhs[i] + s*rhs[i+1]; rhs[i+1] = t
+ *       for i = m..1: z = rhs[i]; for j = i+1..m increasing: z = z - H[i,j]*rhs[j]; rhs[i] = z / H[i,i]
+ *       x[e] = (..((x[e] + rhs[1]*V[e,1]) + rhs[2]*V[e,2]) ..) + rhs[m]*V[e,m]
+ *       k = 1
+ *       if not current <= tol and it < maxiter: beta = init (never initially_zero; mv += 1); acc = 1  (current is NOT reset)
+ *   *converged = current <= tol.
+ * orth_meth, the package's three:
+ *   ESP_ORTH_MGS (the default of the package): for i = 1..k: H[i,k] = dot(V[i], w); w = w - H[i,k]*V[i];  nrm = norm(w)
+ *   ESP_ORTH_CGS:  h[j] = dot(V[j], w) for j = 1..k, all from the same w; w[e] = (..(w[e] - h[1]*V[e,1]) - ..) - h[k]*V[e,k];
+ *                  nrm = norm(w); H[1..k,k] = h
+ *   ESP_ORTH_DGKS: CGS first, then proj = sqrt(h[1]^2 + .. + h[k]^2) (sequential from 0.0, increasing j); eta = 1.0/sqrt(2.0);
+ *                  while nrm < eta*proj and passes < 3: c[j] = dot(V[j], w) for j = 1..k; proj = that norm of c; w -= the same
+ *                  ordered combination with c; h[j] = h[j] + c[j]; nrm = norm(w); passes += 1.  A NaN makes the test false.
+ * ldiv! and mul! are those of esp_precon_ldiv and esp_mul, bit for bit; dot is esp_cg's ordered sum, norm(v) = sqrt(dot(v, v));
+ * every product is rounded before its sum, every division and square root is the correctly rounded one: x, the whole history,
+ * the counters and the flag are identical run to run and bit-identical to tests/gmres_model.c, which restates the statements as
+ * plain loops and is normative for the order of every operation.
+ * DEVIATIONS from the package: dot, norm and the two gemv's (BLAS in the package) use the stated order; Givens is the plain formula
+ * above, without LAPACK's scaling: it overflows where f*f does; the DGKS loop is capped at 3 correction passes (the package has no
+ * cap); x is also formed when maxiter ends a cycle part-way (by its documented behaviour the package forms x only at a restart or
+ * on convergence and would return an x that does not belong to the residual it reports); p == NULL is Identity with no copies.
+ * No errors: a breakdown (nrm == 0 without convergence, a singular H) -- Inf / NaN propagate, a NaN residual never stops the
+ * loop, which ends at maxiter; a lucky breakdown -- current = 0, converged, x exact (n = 1 always ends so after one iteration);
+ * b = 0 from x = 0 -- history = [0], no iteration, x untouched.
+ * restart outside 1..ESP_GMRES_RESTART_MAX, an unknown orth_meth or maxiter < 0 -> ESP_ERR_INVALID.  n == 0 returns at once with
+ * history[0] = 0.  history: maxiter+1 host doubles or NULL: history[0] the initial norm, history[k] the norm after iteration k;
+ * *iterations = iterations run, *mv_products = mv, *reorth_passes = the DGKS correction passes of the whole solve (0 for the other
+ * methods); every out pointer is optional.  b, x: n doubles, device pointers when on_device != 0; x is updated in place.  Errors,
+ * stream use and "returns synchronised" exactly as esp_bicgstabl.  The work space (the basis block of restart+1 vectors, n more
+ * doubles in front of ILU0 / ILUAM / AMG / a permuted Block, the partial sums, a scalar block for H, nullvec, rhs, h, c, beta,
+ * acc, current and the pass counter; 2 n more for host vectors) belongs to the handle: sized on first use, released with it;
+ * ESP_ERR_NOMEM leaves the handle usable. */
+#define ESP_ORTH_MGS 0
+#define ESP_ORTH_CGS 1
+#define ESP_ORTH_DGKS 2
+#define ESP_GMRES_RESTART_MAX 64
+int32_t esp_gmres(esp_handle *h, esp_precon *p, const double *b, double *x, int32_t on_device, int32_t initially_zero,
+                  int32_t restart, int32_t orth_meth, int64_t maxiter, double abstol, double reltol, double *history,
+                  int64_t *iterations, int64_t *mv_products, int64_t *reorth_passes, int32_t *converged);
 
 /* ---- the algebra of assembled matrices on the device CSC (abstractextendablesparsematrixcsc.jl:224-280) -----------
  * The reference evaluates these through SparseArrays; the device reproduces its documented rules bit for bit:

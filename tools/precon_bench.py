@@ -30,6 +30,20 @@ restricts it to one preconditioner, --no-composed leaves the composition out (wh
 
     python tools/precon_bench.py --kind bicgstabl [--n 256] [--iters 5] [--ls 1,2,4] [--cg-only ilu0] [--no-composed]
 
+--kind gmres times restarted GMRES (esp_gmres): for Identity, Jacobi and ILU0 (--cg-only NAME: one of them) and orth_meth mgs and
+dgks (--orths), restart 20, the time of two full cycles (maxiter = 40, reltol = 0) and beside it composed_gmres, the same statements
+composed from what the package offered before esp_gmres -- A.mul, P.ldiv, torch vector operations, the scalars kept on the device,
+one read-back per iteration (two with DGKS: its decision), the small least-squares problem on the host --, in --rounds alternating
+rounds of the same call; it first asserts that the two histories agree to 1e-10 relative.  Reported: every round's time, the
+medians, the spread of the fused rounds (max - min: the margin of "the fused solve is no slower"), and the time of iteration
+k = 1, 10 and 20 of the first cycle (a run of k iterations minus a run of k - 1; k = 1 carries the first solution update).
+--kind gmres-trace is what a kernel trace wants: ONE solve of two full cycles with one preconditioner (--cg-only, default jacobi)
+and the first orth_meth of --orths, on device vectors.
+
+    python tools/precon_bench.py --kind gmres [--n 256] [--rounds 5] [--orths mgs,dgks] [--cg-only ilu0] [--no-composed]
+    rocprofv3 --kernel-trace --stats --output-format csv -d OUT -- \
+        python tools/precon_bench.py --kind gmres-trace --cg-only jacobi --orths mgs --n 256
+
 --kind block times BlockPreconditioner (esp_precon_block_create) against the unblocked preconditioner of the same kind, for Jacobi,
 ILU0 and ILUAM (--cg-only NAME: one of them): create, the values-only update! and ldiv! on device vectors for (a) the unblocked
 preconditioner, (b) odd / even unknowns, (c) 8 and (d) 64 contiguous slabs (identity path), (e) a seeded random permutation in 8
@@ -344,6 +358,149 @@ def bench_bicgstabl(a, torch, esp):
     print(json.dumps(rnd(out)))
 
 
+def composed_gmres(torch, A, P, b, restart, maxiter, orth):
+    """the statements of esp_gmres (include/esparse_hip.h) from the package's parts: `maxiter` iterations from x = 0, reltol = 0"""
+    import numpy as np
+    ldiv = (lambda v, out: P.ldiv(v, out=out)) if P is not None else (lambda v, out: out.copy_(v))
+    n = b.numel()
+    V = torch.empty((restart + 1, n), dtype=torch.float64, device=b.device)
+    H = torch.zeros((restart + 1, restart), dtype=torch.float64, device=b.device)
+    x = torch.zeros_like(b)
+    t = torch.empty_like(b)
+    eta = 1.0 / np.sqrt(2.0)
+    ldiv(b, V[0])
+    beta = torch.linalg.vector_norm(V[0])
+    V[0].div_(beta)
+    hist = [beta.item()]
+    it = 0
+    while it < maxiter:
+        nullvec = torch.ones(restart + 1, dtype=torch.float64, device=b.device)
+        acc = torch.ones((), dtype=torch.float64, device=b.device)
+        k = 0
+        while k < restart and it < maxiter:
+            w = V[k + 1]
+            ldiv(A.mul(V[k], out=t), w)
+            if orth == "mgs":
+                for i in range(k + 1):
+                    h = torch.dot(V[i], w)
+                    H[i, k] = h
+                    w.sub_(V[i] * h)
+                nrm = torch.linalg.vector_norm(w)
+            else:
+                h = V[:k + 1] @ w
+                w.sub_(h @ V[:k + 1])
+                nrm = torch.linalg.vector_norm(w)
+                if orth == "dgks":
+                    proj, passes = torch.linalg.vector_norm(h), 0
+                    while passes < 3 and bool(nrm < eta * proj):   # the decision's read-back
+                        c = V[:k + 1] @ w
+                        proj = torch.linalg.vector_norm(c)
+                        w.sub_(c @ V[:k + 1])
+                        h = h + c
+                        nrm = torch.linalg.vector_norm(w)
+                        passes += 1
+                H[:k + 1, k] = h
+            H[k + 1, k] = nrm
+            w.div_(nrm)
+            nv = -(torch.dot(nullvec[:k + 1], H[:k + 1, k]) / nrm)
+            nullvec[k + 1] = nv
+            acc = acc + nv * nv
+            hist.append((beta / torch.sqrt(acc)).item())   # the stop test's read-back
+            k += 1
+            it += 1
+        Hh = H[:k + 1, :k].cpu().numpy()                   # the small least-squares problem on the host
+        e1 = np.zeros(k + 1)
+        e1[0] = beta.item()
+        y = np.linalg.lstsq(Hh, e1, rcond=None)[0]
+        x.add_(torch.from_numpy(y).to(b.device) @ V[:k])
+        if it < maxiter:
+            torch.sub(b, A.mul(x, out=t), out=t)
+            ldiv(t, V[0])
+            beta = torch.linalg.vector_norm(V[0])
+            V[0].div_(beta)
+    return x, hist
+
+
+def bench_gmres(a, torch, esp):
+    import statistics
+    A = esp.fdrand(a.n, a.n, a.n)
+    d = A._d
+    stream = torch.cuda.current_stream()
+    d.ck(d.lib.esp_set_stream(d.h, C.c_void_p(stream.cuda_stream)))
+    N, Z = A.n, A.nnz()
+    b = torch.ones(N, dtype=torch.float64, device="cuda")
+    kinds = {"identity": lambda M: None, "jacobi": esp.JacobiPreconditioner, "ilu0": esp.ILU0Preconditioner}
+    names = [a.cg_only] if a.cg_only else list(kinds)
+    restart, maxiter = 20, 40
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    out = {"workload": "gmres_fdrand", "n": a.n, "N": N, "nnz": Z, "restart": restart, "maxiter": maxiter, "rounds": a.rounds}
+    for name in names:
+        P = kinds[name](A)
+        rec = {}
+        for orth in a.orths.split(","):
+            fused = lambda k=maxiter: esp.gmres(A, b, Pl=P, restart=restart, maxiter=k, reltol=0.0, orth_meth=orth, log=True)
+            comp = lambda: composed_gmres(torch, A, P, b, restart, maxiter, orth)
+            r = {}
+            _, log = fused()                                   # (also the warm-up: the work space is sized here)
+            r["reorth"] = log["reorth"]
+            if not a.no_composed:
+                _, hist = comp()
+                got = [log["r0"]] + list(log["resnorm"])
+                r["history_rel_diff"] = max(abs(g - w) / w for g, w in zip(got, hist))
+                assert len(got) == len(hist) == maxiter + 1 and r["history_rel_diff"] <= 1e-10, r
+            tf, tc = [], []
+            for _ in range(a.rounds):                          # the two alternate
+                tf.append(timed(fused))
+                if not a.no_composed:
+                    tc.append(timed(comp))
+            r["fused_ms"], r["fused_median_ms"], r["fused_spread_ms"] = tf, statistics.median(tf), max(tf) - min(tf)
+            if tc:
+                r["composed_ms"], r["composed_median_ms"] = tc, statistics.median(tc)
+                r["composed_over_fused"] = r["composed_median_ms"] / r["fused_median_ms"]
+                r["fused_no_slower"] = r["fused_median_ms"] <= r["composed_median_ms"] + r["fused_spread_ms"]
+            run = {k: min(timed(lambda: fused(k)) for _ in range(3)) for k in (0, 1, 9, 10, 19, 20)}
+            r["iteration_ms"] = {"k1": run[1] - run[0], "k10": run[10] - run[9], "k20": run[20] - run[19]}
+            rec[orth] = r
+        if P is not None:
+            P.close()
+        out[name] = rec
+
+    def rnd(x):
+        if isinstance(x, float):
+            return float("%.4g" % x)
+        if isinstance(x, dict):
+            return {k: rnd(y) for k, y in x.items()}
+        if isinstance(x, list):
+            return [rnd(y) for y in x]
+        return x
+
+    print(json.dumps(rnd(out)))
+
+
+def bench_gmres_trace(a, torch, esp):
+    """what a kernel trace wants: ONE solve of two full cycles (restart 20, maxiter 40, reltol 0) on device vectors with one
+    preconditioner (--cg-only, default jacobi) and one orth_meth (the first of --orths)"""
+    A = esp.fdrand(a.n, a.n, a.n)
+    b = torch.ones(A.n, dtype=torch.float64, device="cuda")
+    name, orth = a.cg_only or "jacobi", a.orths.split(",")[0]
+    P = {"identity": lambda M: None, "jacobi": esp.JacobiPreconditioner, "ilu0": esp.ILU0Preconditioner,
+         "iluam": esp.ILUAMPreconditioner}[name](A)
+    _, log = esp.gmres(A, b, Pl=P, restart=20, maxiter=40, reltol=0.0, orth_meth=orth, log=True)
+    print(json.dumps({"workload": "gmres_trace", "n": a.n, "precon": name, "orth_meth": orth, "iters": log["iters"],
+                      "mvps": log["mvps"], "reorth": log["reorth"]}))
+    if P is not None:
+        P.close()
+
+
 def block_partitioning(np, N, config):
     """1-based partitions of 1..N for the configurations b .. e of --kind block"""
     if config == "b":
@@ -561,7 +718,7 @@ def main():
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "block", "block-trace", "block-trace-diff", "amg"], default="point")
+    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "gmres", "gmres-trace", "block", "block-trace", "block-trace-diff", "amg"], default="point")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--block-config", choices=["a", "b", "c", "d", "e"], default="b")
     ap.add_argument("--dirs", nargs=2, default=None)
@@ -570,6 +727,7 @@ def main():
     ap.add_argument("--tol-maxiter", type=int, default=100000)
     ap.add_argument("--cpu-model", action="store_true")
     ap.add_argument("--ls", default="1,2,4")
+    ap.add_argument("--orths", default="mgs,dgks")
     ap.add_argument("--no-composed", action="store_true")
     a = ap.parse_args()
     if a.kind == "block-trace-diff":
@@ -584,6 +742,10 @@ def main():
         return bench_cg(a, torch, esp)
     if a.kind == "bicgstabl":
         return bench_bicgstabl(a, torch, esp)
+    if a.kind == "gmres":
+        return bench_gmres(a, torch, esp)
+    if a.kind == "gmres-trace":
+        return bench_gmres_trace(a, torch, esp)
     if a.kind == "block":
         return bench_block(a, torch, esp)
     if a.kind == "block-trace":
