@@ -18,6 +18,7 @@ ESP_OP_ADD, ESP_OP_SUB = 0, 1
 ESP_FLUSH_ROUTED, ESP_FLUSH_PLUS = 0, 1
 ESP_PRECON_JACOBI, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_BLOCK, ESP_PRECON_AMG = 0, 1, 2, 3, 4
 ESP_AMG_DENSE_MAX = 512
+ESP_AMG_COARSEN_SA, ESP_AMG_COARSEN_RS = 0, 1
 ESP_ORTH_MGS, ESP_ORTH_CGS, ESP_ORTH_DGKS = 0, 1, 2
 ESP_GMRES_RESTART_MAX = 64
 STAGES = ("append", "hist", "scan", "scatter", "local", "fold", "colptr", "merge", "copy")
@@ -112,6 +113,9 @@ SIGNATURES = {
     "esp_precon_amg_level": (i32, [vp, i32, P(vp), P(vp), P(i64), P(f64), P(i32)]),
     "esp_precon_amg_aggregates": (i32, [vp, i32, vp, i32]),
     "esp_precon_amg_coarse_inverse": (i32, [vp, vp, i32]),
+    "esp_precon_rsamg_create": (i32, [vp, i32, i32, i32, i32, f64, P(vp)]),
+    "esp_precon_amg_coarsening": (i32, [vp, P(i32)]),
+    "esp_precon_amg_splitting": (i32, [vp, i32, vp, i32]),
     "esp_simple": (i32, [vp, vp, vp, vp, i32, i64, f64, f64, vp, P(i64)]),
     "esp_cg": (i32, [vp, vp, vp, vp, i32, i32, i64, f64, f64, vp, P(i64), P(i32)]),
     "esp_bicgstabl": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i64, f64, f64, vp, P(i64), P(i64), P(i32)]),

@@ -19,6 +19,8 @@
 //                    counting sort by aggregate that keeps index order
 //   P, A_{l+1}       esp_diag_scale, esp_matmul, esp_add, esp_transpose, esp_matmul twice, on internal handles the preconditioner owns
 //   amg_gj_k         the coarsest level's dense inverse: one workgroup, Gauss-Jordan with partial pivoting on [A | I] in global memory
+// With coarsening mode ESP_AMG_COARSEN_RS (esp_precon_rsamg_create) the aggregation and the formation of P are replaced by
+// rsamg_coarsen (rsamg.hip: row-wise strength, a PMIS splitting, direct interpolation); everything else here serves both.
 // The V-cycle (esp_precon_ldiv, and inside esp_simple / esp_cg / esp_bicgstabl): launches on the handle's stream only, every buffer
 // sized at setup -- no copy, no allocation, no synchronisation.
 //   amg_scale_k      the first pre-sweep from x = 0: x = w.*b
@@ -29,29 +31,19 @@
 //   amg_row_k<PROLONG> x[i] = x[i] + (P x_c)[i] over P's row-wise index
 // The last kernel of level 0 stores straight into u (u may alias v: every lane reads its own b[i] before it stores u[i]), fused
 // with simple!'s `u .-= upd` where that is the caller.
-#include "internal.hpp"
+#include "amg.hpp"
 
-struct AmgLevel {
-    esp_handle *A = nullptr, *P = nullptr;  // A_l (n x n), P_l (n x nc; nullptr on the coarsest level)
-    i64 n = 0, nc = 0;
-    double rho = 0.0;
-    int rounds = 0;
-    bool has_agg = false;
-    DevBuf w, agg;        // f64 n: omega*dinv; i64 n: the aggregate of every unknown
-    DevBuf x0, x1, b, r;  // f64 n each: the two iterates, the right-hand side (levels > 0), the residual
-};
-struct AmgData {
-    int max_levels = 10, max_coarse = 64, pre = 1, post = 1;
-    double theta = 0.0;
-    std::vector<AmgLevel> lv;
-    DevBuf inv;  // n_L*n_L doubles, row-major
-    bool has_inv = false;
-};
+using namespace espamg;
+
+int32_t amg_make_handle(esp_handle *h, i64 m, i64 n, esp_handle **out) {
+    const int32_t st = esp_create(m, n, h->device, 0, out);
+    if (st != ESP_OK) FAIL(h, st == ESP_ERR_HIP ? ESP_ERR_NOMEM : st, "esp_precon_amg: an internal handle: %s", esp_last_error(nullptr));
+    CK(esp_set_stream(*out, (void *)h->stream));
+    return ESP_OK;
+}
 
 namespace {
 
-constexpr int AT = 256;        // threads of every kernel here but the Gauss-Jordan
-constexpr int AMG_LONG = 32;   // a column with more stored entries is folded by its whole wave (Luby rounds)
 constexpr int AMG_TLONG = 64;  // restriction: as esp_mul_transpose's MV_LONG
 constexpr int GJT = 1024;      // threads of the Gauss-Jordan workgroup
 
@@ -99,15 +91,7 @@ __global__ void amg_strength_k(espfold::Csc c, i64 n, const double *__restrict__
         strong[k] = s;
     }
 }
-__device__ __forceinline__ u64 amg_key(i64 i) {
-    u32 x = (u32)i + 1u;
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return ((u64)x << 32) | (u64)(u32)i;
-}
+__device__ __forceinline__ u64 amg_key(i64 i) { return ((u64)amg_mix(i) << 32) | (u64)(u32)i; }
 // state: 0 undecided, 1 root, 2 excluded
 __device__ __forceinline__ u64 amg_t(u32 state, i64 i) { return state == 2u ? 0ull : state == 1u ? ~0ull : amg_key(i); }
 // PH 1: out[j] = max of t over {j} and its strong neighbours; PH 2: the same max over in[] (= T1), then j's decision
@@ -353,21 +337,6 @@ __global__ void amg_finish_k(const double *__restrict__ x, double *dst, const do
     if (i < n) dst[i] = sub ? sub[i] - x[i] : x[i];
 }
 
-struct Temps {
-    DevBuf b[12];
-    ~Temps() {
-        for (DevBuf &x : b) release(x);
-    }
-};
-// internal handles of a build step: destroyed when the step ends unless taken over
-struct Handles {
-    std::vector<esp_handle *> v;
-    ~Handles() {
-        for (esp_handle *x : v)
-            if (x) (void)esp_destroy(x);
-    }
-};
-
 void release_level(AmgLevel &L) {
     if (L.A) (void)esp_destroy(L.A);
     if (L.P) (void)esp_destroy(L.P);
@@ -378,24 +347,6 @@ void release_levels(std::vector<AmgLevel> &lv) {
     for (AmgLevel &L : lv) release_level(L);
     lv.clear();
 }
-
-espfold::Csc csc_of(const esp_handle *a) {
-    return espfold::Csc{(const i64 *)a->colptr.p, (const i64 *)a->rowval.p, (double *)a->nzval.p, a->nnz};
-}
-
-// an internal m x n handle on h's device and stream
-int32_t make_handle(esp_handle *h, i64 m, i64 n, esp_handle **out) {
-    const int32_t st = esp_create(m, n, h->device, 0, out);
-    if (st != ESP_OK) FAIL(h, st == ESP_ERR_HIP ? ESP_ERR_NOMEM : st, "esp_precon_amg: an internal handle: %s", esp_last_error(nullptr));
-    CK(esp_set_stream(*out, (void *)h->stream));
-    return ESP_OK;
-}
-// a call of the library on internal handles: its message goes to h
-#define SUB(h, sub, ...)                                                                  \
-    do {                                                                                  \
-        const int32_t _st = (__VA_ARGS__);                                                \
-        if (_st != ESP_OK) FAIL(h, _st, "esp_precon_amg: %s", (sub)->err.c_str());       \
-    } while (0)
 
 // the aggregation of level L (its matrix in L.A): L.agg, L.nc, L.rounds
 int32_t aggregate(esp_handle *h, AmgLevel &L, const double *dg, double theta) {
@@ -491,7 +442,7 @@ int32_t build(esp_precon *p, std::vector<AmgLevel> &lv, DevBuf &inv, bool *has_i
         lv.emplace_back();
         AmgLevel &L = lv.back();
         L.n = n0;
-        CK(make_handle(h, n0, n0, &L.A));
+        CK(amg_make_handle(h, n0, n0, &L.A));
         Temps tmp;
         DevBuf &cp = tmp.b[0], &rv = tmp.b[1], &nz = tmp.b[2];
         const i64 nnz = h->nnz;
@@ -520,7 +471,7 @@ int32_t build(esp_precon *p, std::vector<AmgLevel> &lv, DevBuf &inv, bool *has_i
         SUB(h, A, esp_jacobi_setup(A, (double *)dinv.p, 1));
         {
             esp_handle *S = nullptr;
-            CK(make_handle(h, n, n, &S));
+            CK(amg_make_handle(h, n, n, &S));
             hs.v.push_back(S);
             SUB(h, S, esp_diag_scale(A, (const double *)dinv.p, 0, 1, S));
             SUB(h, S, esp_opnorm(S, INFINITY, &L.rho));
@@ -532,7 +483,14 @@ int32_t build(esp_precon *p, std::vector<AmgLevel> &lv, DevBuf &inv, bool *has_i
         HIPCK(h, hipGetLastError());
         SUB(h, A, csr_current(A));  // the row-wise index and values the sweeps stream
         bool coarsest = n <= (i64)D->max_coarse || l + 1 == D->max_levels;
-        if (!coarsest) {
+        esp_handle *PT = nullptr;  // transpose(P_l)
+        if (!coarsest && D->coarsen == ESP_AMG_COARSEN_RS) {
+            // the splitting and, where it leaves 0 < nc < n, P_l and its transpose (rsamg.hip)
+            const int32_t st = rsamg_coarsen(h, L, D->theta, &PT);
+            hs.v.push_back(PT);
+            CK(st);
+            if (L.nc == 0 || L.nc == n) coarsest = true;
+        } else if (!coarsest) {
             CK(aggregate(h, L, (const double *)dg.p, D->theta));
             if (L.nc == n) coarsest = true;
         }
@@ -545,43 +503,48 @@ int32_t build(esp_precon *p, std::vector<AmgLevel> &lv, DevBuf &inv, bool *has_i
             return ESP_OK;
         }
         const i64 nc = L.nc;
-        // T = transpose of the CSC one can write down
-        esp_handle *TT = nullptr, *T = nullptr, *DA = nullptr, *DAT = nullptr, *AP = nullptr, *PT = nullptr;
-        CK(make_handle(h, nc, n, &TT));
-        hs.v.push_back(TT);
-        {
-            Temps t2;
-            DevBuf &cp = t2.b[0], &rv = t2.b[1], &nz = t2.b[2];
-            CK(ensure(h, cp, sizeof(i64) * (size_t)(n + 1)));
-            CK(ensure(h, rv, sizeof(i64) * (size_t)n));
-            CK(ensure(h, nz, sizeof(double) * (size_t)n));
-            hipLaunchKernelGGL(amg_tt_k, dim3(grid_for(n + 1, AT)), dim3(AT), 0, s, (const i64 *)L.agg.p, n, (i64 *)cp.p, (i64 *)rv.p,
-                               (double *)nz.p);
-            HIPCK(h, hipGetLastError());
-            HIPCK(h, hipStreamSynchronize(s));
-            install(TT, cp, rv, nz, n);
+        esp_handle *AP = nullptr;
+        if (D->coarsen == ESP_AMG_COARSEN_SA) {
+            // T = transpose of the CSC one can write down
+            esp_handle *TT = nullptr, *T = nullptr, *DA = nullptr, *DAT = nullptr;
+            CK(amg_make_handle(h, nc, n, &TT));
+            hs.v.push_back(TT);
+            {
+                Temps t2;
+                DevBuf &cp = t2.b[0], &rv = t2.b[1], &nz = t2.b[2];
+                CK(ensure(h, cp, sizeof(i64) * (size_t)(n + 1)));
+                CK(ensure(h, rv, sizeof(i64) * (size_t)n));
+                CK(ensure(h, nz, sizeof(double) * (size_t)n));
+                hipLaunchKernelGGL(amg_tt_k, dim3(grid_for(n + 1, AT)), dim3(AT), 0, s, (const i64 *)L.agg.p, n, (i64 *)cp.p, (i64 *)rv.p,
+                                   (double *)nz.p);
+                HIPCK(h, hipGetLastError());
+                HIPCK(h, hipStreamSynchronize(s));
+                install(TT, cp, rv, nz, n);
+            }
+            CK(amg_make_handle(h, n, nc, &T));
+            hs.v.push_back(T);
+            SUB(h, T, esp_transpose(TT, T, nullptr));
+            // P = T + (Diagonal(-w)*A)*T
+            CK(amg_make_handle(h, n, n, &DA));
+            hs.v.push_back(DA);
+            SUB(h, DA, esp_diag_scale(A, (const double *)nw.p, 0, 1, DA));
+            CK(amg_make_handle(h, n, nc, &DAT));
+            hs.v.push_back(DAT);
+            SUB(h, DAT, esp_matmul(DA, T, DAT, nullptr));
+            CK(amg_make_handle(h, n, nc, &L.P));
+            SUB(h, L.P, esp_add(T, DAT, ESP_OP_ADD, L.P, nullptr));
         }
-        CK(make_handle(h, n, nc, &T));
-        hs.v.push_back(T);
-        SUB(h, T, esp_transpose(TT, T, nullptr));
-        // P = T + (Diagonal(-w)*A)*T
-        CK(make_handle(h, n, n, &DA));
-        hs.v.push_back(DA);
-        SUB(h, DA, esp_diag_scale(A, (const double *)nw.p, 0, 1, DA));
-        CK(make_handle(h, n, nc, &DAT));
-        hs.v.push_back(DAT);
-        SUB(h, DAT, esp_matmul(DA, T, DAT, nullptr));
-        CK(make_handle(h, n, nc, &L.P));
-        SUB(h, L.P, esp_add(T, DAT, ESP_OP_ADD, L.P, nullptr));
         // A_{l+1} = transpose(P)*(A*P)
-        CK(make_handle(h, n, nc, &AP));
+        CK(amg_make_handle(h, n, nc, &AP));
         hs.v.push_back(AP);
         SUB(h, AP, esp_matmul(A, L.P, AP, nullptr));
-        CK(make_handle(h, nc, n, &PT));
-        hs.v.push_back(PT);
-        SUB(h, PT, esp_transpose(L.P, PT, nullptr));
+        if (!PT) {
+            CK(amg_make_handle(h, nc, n, &PT));
+            hs.v.push_back(PT);
+            SUB(h, PT, esp_transpose(L.P, PT, nullptr));
+        }
         esp_handle *An = nullptr;
-        CK(make_handle(h, nc, nc, &An));
+        CK(amg_make_handle(h, nc, nc, &An));
         lv.emplace_back();  // (L is stale from here)
         lv.back().A = An;
         lv.back().n = nc;
@@ -701,23 +664,25 @@ int32_t amg_solve(esp_precon *p, const double *v, double *u, bool sub) {
     return ESP_OK;
 }
 
-extern "C" int32_t esp_precon_amg_create(esp_handle *h, int32_t max_levels, int32_t max_coarse, int32_t presweeps, int32_t postsweeps,
-                                         double theta, esp_precon **out) {
+namespace {
+// esp_precon_amg_create / esp_precon_rsamg_create: the same arguments and rules, another coarsening and another default of theta
+int32_t create(esp_handle *h, int32_t max_levels, int32_t max_coarse, int32_t presweeps, int32_t postsweeps, double theta, int coarsen,
+               double theta_default, const char *what, esp_precon **out) {
     if (!h || !out) return ESP_ERR_INVALID;
     *out = nullptr;
     if (max_levels == -1) max_levels = 10;
     if (max_coarse == -1) max_coarse = 64;
     if (presweeps == -1) presweeps = 1;
     if (postsweeps == -1) postsweeps = 1;
-    if (theta < 0.0) theta = 0.0;
-    if (max_levels < 1) FAIL(h, ESP_ERR_INVALID, "esp_precon_amg_create: max_levels = %d (>= 1, or -1 for the default)", max_levels);
+    if (theta < 0.0) theta = theta_default;
+    if (max_levels < 1) FAIL(h, ESP_ERR_INVALID, "%s: max_levels = %d (>= 1, or -1 for the default)", what, max_levels);
     if (max_coarse < 1 || max_coarse > ESP_AMG_DENSE_MAX)
-        FAIL(h, ESP_ERR_INVALID, "esp_precon_amg_create: max_coarse = %d (1..%d, or -1 for the default)", max_coarse, ESP_AMG_DENSE_MAX);
-    if (presweeps < 1) FAIL(h, ESP_ERR_INVALID, "esp_precon_amg_create: presweeps = %d (>= 1, or -1 for the default)", presweeps);
-    if (postsweeps < 0) FAIL(h, ESP_ERR_INVALID, "esp_precon_amg_create: postsweeps = %d (>= 0, or -1 for the default)", postsweeps);
-    if (!std::isfinite(theta)) FAIL(h, ESP_ERR_INVALID, "esp_precon_amg_create: theta is not finite");
-    CK(precon_check_handle(h, "esp_precon_amg_create"));
-    if (windowed(h) || h->shard_user) FAIL(h, ESP_ERR_UNSUPPORTED, "esp_precon_amg_create: a column window / column shard");
+        FAIL(h, ESP_ERR_INVALID, "%s: max_coarse = %d (1..%d, or -1 for the default)", what, max_coarse, ESP_AMG_DENSE_MAX);
+    if (presweeps < 1) FAIL(h, ESP_ERR_INVALID, "%s: presweeps = %d (>= 1, or -1 for the default)", what, presweeps);
+    if (postsweeps < 0) FAIL(h, ESP_ERR_INVALID, "%s: postsweeps = %d (>= 0, or -1 for the default)", what, postsweeps);
+    if (!std::isfinite(theta)) FAIL(h, ESP_ERR_INVALID, "%s: theta is not finite", what);
+    CK(precon_check_handle(h, what));
+    if (windowed(h) || h->shard_user) FAIL(h, ESP_ERR_UNSUPPORTED, "%s: a column window / column shard", what);
     esp_precon *p = new esp_precon();
     p->h = h;
     p->kind = ESP_PRECON_AMG;
@@ -728,6 +693,7 @@ extern "C" int32_t esp_precon_amg_create(esp_handle *h, int32_t max_levels, int3
     p->amg->pre = presweeps;
     p->amg->post = postsweeps;
     p->amg->theta = theta;
+    p->amg->coarsen = coarsen;
     h->live_precons++;
     p->pattern_version = 0;  // never matches: the update below builds everything
     const int32_t st = amg_update(p);
@@ -736,6 +702,23 @@ extern "C" int32_t esp_precon_amg_create(esp_handle *h, int32_t max_levels, int3
         return st;
     }
     *out = p;
+    return ESP_OK;
+}
+}  // namespace
+
+extern "C" int32_t esp_precon_amg_create(esp_handle *h, int32_t max_levels, int32_t max_coarse, int32_t presweeps, int32_t postsweeps,
+                                         double theta, esp_precon **out) {
+    return create(h, max_levels, max_coarse, presweeps, postsweeps, theta, ESP_AMG_COARSEN_SA, 0.0, "esp_precon_amg_create", out);
+}
+
+extern "C" int32_t esp_precon_rsamg_create(esp_handle *h, int32_t max_levels, int32_t max_coarse, int32_t presweeps, int32_t postsweeps,
+                                           double theta, esp_precon **out) {
+    return create(h, max_levels, max_coarse, presweeps, postsweeps, theta, ESP_AMG_COARSEN_RS, 0.25, "esp_precon_rsamg_create", out);
+}
+
+extern "C" int32_t esp_precon_amg_coarsening(esp_precon *p, int32_t *kind) {
+    if (!p || p->kind != ESP_PRECON_AMG || !kind) return ESP_ERR_INVALID;
+    *kind = p->amg->coarsen;
     return ESP_OK;
 }
 
@@ -773,11 +756,22 @@ int32_t copy_out(esp_handle *h, void *dst, const void *d_src, size_t bytes, int3
 
 extern "C" int32_t esp_precon_amg_aggregates(esp_precon *p, int32_t level, int64_t *agg, int32_t on_device) {
     if (!p || p->kind != ESP_PRECON_AMG) return ESP_ERR_INVALID;
+    if (p->amg->coarsen != ESP_AMG_COARSEN_SA) FAIL(p->h, ESP_ERR_INVALID, "esp_precon_amg_aggregates: a Ruge-Stueben hierarchy has a splitting, no aggregates");
     if (level < 0 || level >= (int32_t)p->amg->lv.size()) FAIL(p->h, ESP_ERR_INVALID, "esp_precon_amg_aggregates: no level %d", level);
     const AmgLevel &L = p->amg->lv[(size_t)level];
     if (!L.has_agg) FAIL(p->h, ESP_ERR_INVALID, "esp_precon_amg_aggregates: level %d was not aggregated", level);
     if (!agg && L.n > 0) return ESP_ERR_INVALID;
     return copy_out(p->h, agg, L.agg.p, sizeof(i64) * (size_t)L.n, on_device);
+}
+
+extern "C" int32_t esp_precon_amg_splitting(esp_precon *p, int32_t level, int64_t *cf, int32_t on_device) {
+    if (!p || p->kind != ESP_PRECON_AMG) return ESP_ERR_INVALID;
+    if (p->amg->coarsen != ESP_AMG_COARSEN_RS) FAIL(p->h, ESP_ERR_INVALID, "esp_precon_amg_splitting: a smoothed-aggregation hierarchy has aggregates, no splitting");
+    if (level < 0 || level >= (int32_t)p->amg->lv.size()) FAIL(p->h, ESP_ERR_INVALID, "esp_precon_amg_splitting: no level %d", level);
+    const AmgLevel &L = p->amg->lv[(size_t)level];
+    if (!L.has_split) FAIL(p->h, ESP_ERR_INVALID, "esp_precon_amg_splitting: level %d was not split", level);
+    if (!cf && L.n > 0) return ESP_ERR_INVALID;
+    return copy_out(p->h, cf, L.agg.p, sizeof(i64) * (size_t)L.n, on_device);
 }
 
 extern "C" int32_t esp_precon_amg_coarse_inverse(esp_precon *p, double *inv, int32_t on_device) {

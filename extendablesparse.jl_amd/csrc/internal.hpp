@@ -11,7 +11,8 @@
 //   iluam.hip      ILUAMPreconditioner: level analysis, level-scheduled ILU(0) factorization and triangular solves
 //   block.hip      BlockPreconditioner: the masked block matrix B of a partitioning (identity / permuted path) and the object around it
 //   amg.hip        AMGPreconditioner: smoothed aggregation (MIS(2) aggregates by Luby rounds, the level hierarchy from the algebra
-//                  calls on internal handles, the fused V-cycle kernels)
+//                  calls on internal handles, the fused V-cycle kernels); amg.hpp holds what it shares with rsamg.hip
+//   rsamg.hip      RS_AMGPreconditioner's coarsening: row-wise strength, the PMIS splitting, direct interpolation (the rest is amg.hip's)
 //   krylov.hip     preconditioned conjugate gradients (esp_cg): fused vector kernels, ordered dot products, scalars on the device
 //   bicgstabl.hip  BiCGStab(l) for non-symmetric systems (esp_bicgstabl): the same design with l+1 residuals and search vectors;
 //                  krylov.hpp holds what the solvers share

@@ -17,7 +17,8 @@ BlockPreconditioner(A, partitioning, factorization) (src/factorizations/blockpre
 of the three point kinds: one block matrix and one inner preconditioner on the device, bit-identical to the per-block loops.
 AMGPreconditioner(A) (= SA_AMGPreconditioner, ext/ExtendableSparseAlgebraicMultigridExt.jl) is a smoothed-aggregation V-cycle whose
 hierarchy is built on the device; the algorithm is the one include/esparse_hip.h states (esp_precon_amg_create), bit-identical to
-tests/amg_model.c.
+tests/amg_model.c.  RS_AMGPreconditioner(A) is the same V-cycle over a hierarchy coarsened the classical (Ruge-Stueben) way -- row-wise
+strength, a PMIS splitting, direct interpolation (esp_precon_rsamg_create) -- bit-identical to tests/rsamg_model.c.
 """
 import ctypes as C
 import math
@@ -214,24 +215,33 @@ class AMGPreconditioner(_PointPreconditioner):
     inverse on the coarsest level.  The stored pattern must be structurally symmetric and hold every diagonal entry.  The
     hierarchy is built from copies: a value change of A reaches ldiv only through update(), which rebuilds everything."""
     KIND = ESP_PRECON_AMG
+    CREATE = "esp_precon_amg_create"
 
     def __init__(self, A, max_levels=10, max_coarse=64, presweeps=1, postsweeps=1, theta=0.0):
+        name = type(self).__name__
         if not isinstance(A, ExtendableSparseMatrix):
-            raise TypeError("AMGPreconditioner(A): A must be an ExtendableSparseMatrix")
-        for name, v, lo in (("max_levels", max_levels, 1), ("max_coarse", max_coarse, 1), ("presweeps", presweeps, 1),
+            raise TypeError("%s(A): A must be an ExtendableSparseMatrix" % name)
+        for what, v, lo in (("max_levels", max_levels, 1), ("max_coarse", max_coarse, 1), ("presweeps", presweeps, 1),
                             ("postsweeps", postsweeps, 0)):
             if int(v) != v or v < lo:
-                raise ValueError("AMGPreconditioner: %s = %r (an integer >= %d)" % (name, v, lo))
+                raise ValueError("%s: %s = %r (an integer >= %d)" % (name, what, v, lo))
         if not (theta >= 0.0 and math.isfinite(theta)):
-            raise ValueError("AMGPreconditioner: theta = %r (finite, >= 0)" % (theta,))
+            raise ValueError("%s: theta = %r (finite, >= 0)" % (name, theta))
         self.A = A
         self._p = None
         A.flush()
         d = A._d
         p = C.c_void_p()
-        d.ck(d.lib.esp_precon_amg_create(d.h, int(max_levels), int(max_coarse), int(presweeps), int(postsweeps), float(theta),
+        d.ck(getattr(d.lib, self.CREATE)(d.h, int(max_levels), int(max_coarse), int(presweeps), int(postsweeps), float(theta),
                                          C.byref(p)))
         self._p = p
+
+    @property
+    def coarsening(self):
+        """ESP_AMG_COARSEN_SA (0, smoothed aggregation) or ESP_AMG_COARSEN_RS (1, Ruge-Stueben)"""
+        k = C.c_int32()
+        self._ck(self.A._d.lib.esp_precon_amg_coarsening(self._live(), C.byref(k)))
+        return k.value
 
     @property
     def levels(self):
@@ -280,6 +290,28 @@ class AMGPreconditioner(_PointPreconditioner):
 
 
 SA_AMGPreconditioner = AMGPreconditioner
+
+
+class RS_AMGPreconditioner(AMGPreconditioner):
+    """RS_AMGPreconditioner(A; max_levels, max_coarse, presweeps, postsweeps, theta) (the reference's RS_AMGPreconditioner,
+    ext/ExtendableSparseAlgebraicMultigridExt.jl): AMGPreconditioner's V-cycle over a hierarchy coarsened the classical way
+    (include/esparse_hip.h, esp_precon_rsamg_create): strength decided per row (|a_ij| >= theta * the row's largest off-diagonal
+    magnitude), a PMIS splitting into C and F points over a fixed hash, direct interpolation.  Made for the non-symmetric
+    M-matrices of upwind convection-diffusion schemes; the requirements on the stored pattern and update() are AMGPreconditioner's.
+    rounds in level(l) are the rounds of the splitting; aggregates() raises."""
+    CREATE = "esp_precon_rsamg_create"
+
+    def __init__(self, A, max_levels=10, max_coarse=64, presweeps=1, postsweeps=1, theta=0.25):
+        super().__init__(A, max_levels, max_coarse, presweeps, postsweeps, theta)
+
+    def splitting(self, l):
+        """the C/F splitting of level l: the 0-based coarse index of a C point, -1 for an interpolated F point, -2 for an F point
+        without interpolation (no strong dependence)"""
+        a, n = C.c_void_p(), C.c_int64()
+        self._ck(self.A._d.lib.esp_precon_amg_level(self._live(), int(l), C.byref(a), None, C.byref(n), None, None))
+        out = np.empty(n.value, np.int64)
+        self._ck(self.A._d.lib.esp_precon_amg_splitting(self._live(), int(l), _vp(out), 0))
+        return out
 
 
 def simple(A, b, u=None, Pl=None, maxiter=100, reltol=math.sqrt(np.finfo(np.float64).eps), abstol=0.0, log=False):

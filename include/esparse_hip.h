@@ -419,6 +419,39 @@ int32_t esp_precon_amg_levels(esp_precon *p, int32_t *nlevels);
 int32_t esp_precon_amg_level(esp_precon *p, int32_t level, esp_handle **a, esp_handle **prolong, int64_t *n, double *rho, int32_t *rounds);
 int32_t esp_precon_amg_aggregates(esp_precon *p, int32_t level, int64_t *agg, int32_t on_device);
 int32_t esp_precon_amg_coarse_inverse(esp_precon *p, double *inv, int32_t on_device);
+/* RS_AMGPreconditioner (ext/ExtendableSparseAlgebraicMultigridExt.jl: RS_AMGPreconditioner): the same V-cycle over a hierarchy
+ * coarsened the classical (Ruge-Stueben) way, which decides strength per row and so sees the one-directional couplings of upwind
+ * convection-diffusion matrices.  AlgebraicMultigrid.jl's splitting is a sequential sweep: the algorithm here is stated in full
+ * (DESIGN.md 5k), tests/rsamg_model.c restates it as plain loops and is normative for the order of every operation, and the device
+ * result is bit-identical to that model.  Everything of the AMG block above holds -- dinv, rho, w, the checks of level 0, the
+ * coarsest level and its dense inverse, the V-cycle -- but for the construction of P_l:
+ *   strength: m_i = the largest |a_ik| over the stored k != i; i depends on j (j in S_i) when (i,j) is stored, j != i, |a_ij| != 0
+ *     and |a_ij| >= theta*m_i (comparisons with a NaN are false); S_i^T = { j : i in S_j }, lambda_i = |S_i^T|;
+ *   splitting (PMIS over the fixed hash): key(i) = min(lambda_i, 65535) << 48 | (mix(i) >> 16) << 32 | i with the 32-bit mixer of
+ *     the aggregation's hash; a node with an empty S_i is an F point without interpolation from the start; per round, phase 1 (on
+ *     the state of the round's start): an undecided i whose key exceeds that of every undecided node of S_i + S_i^T becomes a C
+ *     point, phase 2: a node still undecided with a C point in S_i becomes an F point; until nobody is undecided (at most n
+ *     rounds).  C points are numbered in index order (cnum).  Every F point with a non-empty S_i has a C point in S_i;
+ *   direct interpolation: row i of P for a C point is P[i, cnum(i)] = 1.0.  For an F point with C_i = S_i & C non-empty, over the
+ *     stored k != i of row i in increasing k: sn / sp = the sum of the negative / positive a_ik, snc / spc the same over k in C_i;
+ *     d = a_ii; if spc == 0 then d = d + sp and beta = 0, else beta = sp/spc; alpha = snc != 0 ? sn/snc : 0;
+ *     P[i, cnum(j)] = (-(a_ij < 0 ? alpha : beta)*a_ij)/d for every j in C_i, stored whatever its value (a zero d is no error);
+ *   A_{l+1} = transpose(P_l)*(A_l*P_l) by esp_matmul's rules, P_l being esp_transpose of the transpose one can write down.
+ *   Level l is also the coarsest when the splitting leaves no C point or only C points.
+ * esp_precon_rsamg_create: the argument rules and error codes of esp_precon_amg_create; -1 / a negative theta selects 10, 64, 1, 1
+ *   and theta = 0.25.  The result has kind ESP_PRECON_AMG (esp_precon_amg_coarsening tells the two apart): esp_precon_update / _ldiv
+ *   / _destroy, esp_simple, esp_cg, esp_bicgstabl and esp_gmres take it unchanged, and the pattern requirements, the handling of
+ *   windows and shards, ESP_ERR_NOMEM and the state rules are those above.
+ * Inspection: esp_precon_amg_levels / _level / _coarse_inverse as above (rounds: the rounds of the splitting, 0 where none ran);
+ *   esp_precon_amg_splitting: n_l int64 (host or device), the 0-based coarse index of a C point, -1 for an interpolated F point, -2
+ *   for an F point without interpolation; ESP_ERR_INVALID for a smoothed-aggregation preconditioner or a level that was not split.
+ *   esp_precon_amg_aggregates -> ESP_ERR_INVALID on a Ruge-Stueben preconditioner. */
+#define ESP_AMG_COARSEN_SA 0
+#define ESP_AMG_COARSEN_RS 1
+int32_t esp_precon_rsamg_create(esp_handle *h, int32_t max_levels, int32_t max_coarse, int32_t presweeps, int32_t postsweeps,
+                                double theta, esp_precon **out);
+int32_t esp_precon_amg_coarsening(esp_precon *p, int32_t *kind);
+int32_t esp_precon_amg_splitting(esp_precon *p, int32_t level, int64_t *cf, int32_t on_device);
 /* simple!(u, A, b; abstol, reltol, maxiter, Pl = p) (src/factorizations/simple_iteration.jl:21-45) statement by
  * statement: res = A*u - b; then per step ldiv!(upd, Pl, res), u .-= upd, mul!(res, A, u), res .-= b, r = norm(res),
  * stop when (r / r0) < reltol || r < abstol (literally: r0 = 0 gives NaN or Inf there).  u (in/out) is bit-identical to

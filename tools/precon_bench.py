@@ -66,7 +66,11 @@ whole hierarchy, --rounds times: median, min, max), ldiv! on device vectors (--r
 max), the level sizes, the operator complexity (the stored entries of all A_l over those of A_0) and the Luby rounds of every
 level, and cg to reltol = 1e-8 with b = ones with AMG and with ILU0: iterations and wall time of each (the second of two solves).
 
-    python tools/precon_bench.py --kind amg [--n 64] [--iters 20] [--rounds 5] [--tol-maxiter 20000]
+--coarsen rs times RS_AMGPreconditioner (esp_precon_rsamg_create, Ruge-Stueben coarsening) the same way; "luby_rounds" are then
+the rounds of the PMIS splitting.  It adds gmres(restart = 20) to reltol = 1e-8 with RS and with ILU0 on the upwind
+convection-diffusion matrix of tests/bicgstabl_modellib.py at --cd-n cubed unknowns and Peclet number --cd-pe (b = ones).
+
+    python tools/precon_bench.py --kind amg [--coarsen sa|rs] [--n 64] [--iters 20] [--rounds 5] [--tol-maxiter 20000]
 """
 import argparse
 import ctypes as C
@@ -665,9 +669,10 @@ def bench_amg(a, torch, esp):
     def stats(xs):
         return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "runs": len(xs)}
 
-    out = {"workload": "amg_fdrand", "n": a.n, "N": N, "nnz": Z}
+    cls = esp.RS_AMGPreconditioner if a.coarsen == "rs" else esp.AMGPreconditioner
+    out = {"workload": "amg_fdrand", "coarsen": a.coarsen, "n": a.n, "N": N, "nnz": Z}
     t0 = time.perf_counter()
-    P = esp.AMGPreconditioner(A)                      # the first build (the level handles' indices included)
+    P = cls(A)                                        # the first build (the level handles' indices included)
     out["create_first_ms"] = (time.perf_counter() - t0) * 1e3
     note = lambda: print(json.dumps(out), file=sys.stderr, flush=True)   # (what is known so far, should a later phase be cut short)
     note()
@@ -700,6 +705,33 @@ def bench_amg(a, torch, esp):
         note()
     P.close()
     Q.close()
+    if a.coarsen == "rs" and a.cd_n > 0:              # a non-symmetric M-matrix: gmres with RS against ILU0
+        import numpy as np
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from bicgstabl_modellib import convdiff_triplets
+        m = a.cd_n
+        I, J, V = convdiff_triplets(m, m, m, a.cd_pe)
+        B = esp.ExtendableSparseMatrix(m ** 3, m ** 3)
+        B.append(esp.ESP_UPDATE, I, J, V)
+        B.flush()
+        ones = torch.ones(B.n, dtype=torch.float64, device="cuda")
+        rec = {"n": m, "pe": a.cd_pe, "N": B.n, "nnz": B.nnz(), "restart": 20}
+        for name, kind in (("rs", esp.RS_AMGPreconditioner), ("ilu0", esp.ILU0Preconditioner)):
+            t0 = time.perf_counter()
+            pl = kind(B)
+            r = {"create_ms": (time.perf_counter() - t0) * 1e3}
+            if name == "rs":
+                r["levels"] = pl.levels
+            for _ in range(2):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                x, log = esp.gmres(B, ones, Pl=pl, restart=20, maxiter=a.tol_maxiter, reltol=1e-8, log=True)
+                dt = time.perf_counter() - t0         # (esp_gmres returns synchronised)
+                r.update({"iterations": log["iters"], "converged": log["isconverged"], "ms": dt * 1e3})
+            r["true_residual_over_b"] = (torch.linalg.vector_norm(ones - B.mul(x)) / np.sqrt(B.n)).item()
+            rec[name] = r
+            pl.close()
+        out["gmres_convdiff"] = rec
 
     def rnd(x):
         if isinstance(x, float):
@@ -729,6 +761,9 @@ def main():
     ap.add_argument("--ls", default="1,2,4")
     ap.add_argument("--orths", default="mgs,dgks")
     ap.add_argument("--no-composed", action="store_true")
+    ap.add_argument("--coarsen", choices=["sa", "rs"], default="sa")
+    ap.add_argument("--cd-n", type=int, default=64)
+    ap.add_argument("--cd-pe", type=float, default=4.0)
     a = ap.parse_args()
     if a.kind == "block-trace-diff":
         return block_trace_diff(a)
