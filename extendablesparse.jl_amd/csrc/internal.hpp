@@ -10,6 +10,8 @@
 //   precon.hip     the point preconditioners' update! / ldiv! (esp_precon_*) and simple! (esp_simple) on the device CSC
 //   iluam.hip      ILUAMPreconditioner: level analysis, level-scheduled ILU(0) factorization and triangular solves
 //   block.hip      BlockPreconditioner: the masked block matrix B of a partitioning (identity / permuted path) and the object around it
+//   iluk.hip       ILUKPreconditioner: the level-of-fill pattern by one bounded search per column (wave / workgroup form), the filled
+//                  matrix B in an internal handle, ILUAM on it
 //   amg.hip        AMGPreconditioner: smoothed aggregation (MIS(2) aggregates by Luby rounds, the level hierarchy from the algebra
 //                  calls on internal handles, the fused V-cycle kernels); amg.hpp holds what it shares with rsamg.hip
 //   rsamg.hip      RS_AMGPreconditioner's coarsening: row-wise strength, the PMIS splitting, direct interpolation (the rest is amg.hip's)
@@ -578,9 +580,18 @@ struct esp_precon {
     // AMGPreconditioner (kind ESP_PRECON_AMG, amg.hip): the parameters and the level hierarchy (internal handles of every A_l and
     // P_l, the weights, the cycle's vectors, the dense inverse of the coarsest level)
     struct AmgData *amg = nullptr;
+    // ILUKPreconditioner (kind ESP_PRECON_ILUK, iluk.hip): h is A; the filled matrix B -- every position of level <= iluk_k, A's bits
+    // where A stores one, +0.0 elsewhere -- lives in bh, inner is the ILUAM preconditioner of bh (blk_path stays 0: ldiv! is inner's
+    // on the caller's vectors), blk_src[q] is the position in A's nzval of entry q of B (ILUK_FILL for a fill entry).
+    int iluk_k = 0;
+    esp_handle *iluk_th = nullptr;  // transpose(A), the graph of the search for the upper part
+    DevBuf iluk_lev;                // i32 nnz(B): the level of every entry of B
+    i64 iluk_stats[4] = {0, 0, 0, 0};  // nnz(B), largest stored level, columns redone by the workgroup search (L, U)
 };
-// the identity-path block preconditioner stands for its inner one in the solvers' fused branches
-static inline esp_precon *fused_precon(esp_precon *p) { return p && p->kind == ESP_PRECON_BLOCK && p->blk_path == 0 ? p->inner : p; }
+// the identity-path block preconditioner and the ILU(k) preconditioner stand for their inner one in the solvers' fused branches
+static inline esp_precon *fused_precon(esp_precon *p) {
+    return p && ((p->kind == ESP_PRECON_BLOCK && p->blk_path == 0) || p->kind == ESP_PRECON_ILUK) ? p->inner : p;
+}
 static inline bool block_permuted(const esp_precon *p) { return p && p->kind == ESP_PRECON_BLOCK && p->blk_path != 0; }
 
 #pragma GCC visibility push(hidden)
@@ -606,6 +617,10 @@ int32_t block_update(esp_precon *p);
 int32_t block_follow_stream(esp_precon *p);
 int32_t block_ldiv_launch(esp_precon *p, const double *v, double *u, bool sub);
 void block_release(esp_precon *p);
+// iluk.hip: update! (the pattern search, B and the inner ILUAM after a pattern change / the value gather and the inner values-only
+// update), release of the transpose and the level array (B, the inner preconditioner and src are block_release's)
+int32_t iluk_update(esp_precon *p);
+void iluk_release(esp_precon *p);
 // amg.hip: update! (the whole hierarchy is rebuilt every time), the V-cycle on device vectors (u may be v; sub: u[i] = u[i] - x[i],
 // simple!'s step; launches on the handle's stream only), release of the hierarchy
 int32_t amg_update(esp_precon *p);

@@ -299,7 +299,7 @@ int32_t precon_ready(esp_precon *p, const char *what) {
     if (h->pattern_version != p->pattern_version || h->nnz != p->nnz)
         FAIL(h, ESP_ERR_STATE, "%s: the matrix pattern changed since the preconditioner's last update! (update! first)", what);
     if (p->kind == ESP_PRECON_ILU0 && p->values_version != h->values_version) CK(split_scale(p, false));  // current nzval, stored xdiag
-    if (p->kind == ESP_PRECON_BLOCK) CK(block_follow_stream(p));  // (B holds copies: the values as of the last update!, ILU0 included)
+    if (p->kind == ESP_PRECON_BLOCK || p->kind == ESP_PRECON_ILUK) CK(block_follow_stream(p));  // (B holds copies: the values as of the last update!, ILU0 included)
     return ESP_OK;
 }
 
@@ -309,6 +309,7 @@ int32_t ldiv_launch(esp_precon *p, const double *v, double *u) {
     const i64 n = p->n;
     if (n == 0) return ESP_OK;
     if (p->kind == ESP_PRECON_BLOCK) return block_ldiv_launch(p, v, u, false);
+    if (p->kind == ESP_PRECON_ILUK) return ldiv_launch(p->inner, v, u);  // ILUAM of B on the caller's vectors
     if (p->kind == ESP_PRECON_ILUAM) return iluam_solve(p, v, u, false);
     if (p->kind == ESP_PRECON_AMG) return amg_solve(p, v, u, false);
     const unsigned g = grid_for(n, PT);
@@ -359,6 +360,7 @@ extern "C" int32_t esp_precon_update(esp_precon *p) {
     if (!p) return ESP_ERR_INVALID;
     if (p->kind == ESP_PRECON_BLOCK) return block_update(p);  // B and the inner preconditioner (block.hip)
     if (p->kind == ESP_PRECON_AMG) return amg_update(p);      // the whole hierarchy (amg.hip)
+    if (p->kind == ESP_PRECON_ILUK) return iluk_update(p);    // the filled matrix and the inner ILUAM (iluk.hip)
     esp_handle *h = p->h;
     CK(check_handle(h, "esp_precon_update"));
     p->n = h->n;
@@ -407,6 +409,7 @@ extern "C" int32_t esp_precon_destroy(esp_precon *p) {
     (void)hipSetDevice(h->device);
     (void)hipStreamSynchronize(h->stream);
     block_release(p);
+    iluk_release(p);
     for (DevBuf *b : {&p->diag, &p->lptr, &p->uptr, &p->lcol, &p->ucol, &p->lpos, &p->upos, &p->dpos, &p->lval, &p->uval, &p->u1, &p->res,
                       &p->partial, &p->scanws, &p->hv, &p->hu})
         release(*b);

@@ -19,13 +19,15 @@ AMGPreconditioner(A) (= SA_AMGPreconditioner, ext/ExtendableSparseAlgebraicMulti
 hierarchy is built on the device; the algorithm is the one include/esparse_hip.h states (esp_precon_amg_create), bit-identical to
 tests/amg_model.c.  RS_AMGPreconditioner(A) is the same V-cycle over a hierarchy coarsened the classical (Ruge-Stueben) way -- row-wise
 strength, a PMIS splitting, direct interpolation (esp_precon_rsamg_create) -- bit-identical to tests/rsamg_model.c.
+ILUKPreconditioner(A, k) is the level-of-fill ILU(k): the filled pattern found on the device by one bounded search per column, then
+ILUAMPreconditioner of the filled matrix (esp_precon_iluk_create) -- bit-identical to tests/iluam_model.c on the B of tests/iluk_model.c.
 """
 import ctypes as C
 import math
 
 import numpy as np
 
-from ._lib import ESP_ORTH_CGS, ESP_ORTH_DGKS, ESP_ORTH_MGS, ESP_PRECON_AMG, ESP_PRECON_BLOCK, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_JACOBI
+from ._lib import ESP_ORTH_CGS, ESP_ORTH_DGKS, ESP_ORTH_MGS, ESP_PRECON_AMG, ESP_PRECON_BLOCK, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_ILUK, ESP_PRECON_JACOBI
 from .matrix import ExtendableSparseMatrix, _vp
 
 
@@ -203,6 +205,65 @@ class BlockPreconditioner(_PointPreconditioner):
 
     def levels(self):
         """the inner preconditioner's level counts (ILUAM: the maximum over the blocks, not their sum)"""
+        out = (C.c_int64 * 3)()
+        self._ck(self.A._d.lib.esp_precon_levels(self._live(), out))
+        return tuple(int(x) for x in out)
+
+
+class ILUKPreconditioner(_PointPreconditioner):
+    """ILUKPreconditioner(A, k=1): the level-of-fill ILU(k) (include/esparse_hip.h, esp_precon_iluk_create).  The filled matrix B
+    holds every position of level <= k -- A's entries at level 0, +0.0 where elimination creates an entry -- and the
+    preconditioner is ILUAMPreconditioner of B: k = 0 is ILUAMPreconditioner(A), a larger k trades memory for fewer iterations,
+    k >= n - 2 is the complete LU without pivoting.  The pattern depends on A's structure alone; unlike the AMG kinds it needs no
+    symmetric pattern.  B holds copies: a value change of A reaches ldiv only through update(), which keeps the pattern, the
+    analysis and the schedules when only values changed."""
+    KIND = ESP_PRECON_ILUK
+
+    def __init__(self, A, k=1):
+        if not isinstance(A, ExtendableSparseMatrix):
+            raise TypeError("ILUKPreconditioner(A, k): A must be an ExtendableSparseMatrix")
+        if int(k) != k or k < 0:
+            raise ValueError("ILUKPreconditioner: k = %r (an integer >= 0)" % (k,))
+        self.A = A
+        self._p = None
+        self.k = min(int(k), 2 ** 31 - 1)     # (a level never exceeds n - 2 < 2^32 - 16)
+        A.flush()
+        d = A._d
+        p = C.c_void_p()
+        d.ck(d.lib.esp_precon_iluk_create(d.h, self.k, C.byref(p)))
+        self._p = p
+
+    def stats(self):
+        """dict: nnz (of B), max_level (the largest stored level), wide_lower / wide_upper (the columns whose search outgrew
+        the one-wave form and was redone by a workgroup)"""
+        out = (C.c_int64 * 4)()
+        self._ck(self.A._d.lib.esp_precon_iluk_stats(self._live(), out))
+        return {"nnz": int(out[0]), "max_level": int(out[1]), "wide_lower": int(out[2]), "wide_upper": int(out[3])}
+
+    def fill_matrix(self):
+        """the filled matrix B as host CSC arrays (colptr, rowval, nzval), Julia layout -- for tests and inspection"""
+        b = C.c_void_p()
+        lib = self.A._d.lib
+        self._ck(lib.esp_precon_iluk_matrix(self._live(), C.byref(b)))
+        nnz = self.stats()["nnz"]
+        cp, rv, nz = np.empty(self.A.n + 1, np.int64), np.empty(nnz, np.int64), np.empty(nnz, np.float64)
+        self._ck(lib.esp_get_csc(b, _vp(cp), _vp(rv), _vp(nz)))
+        return cp, rv, nz
+
+    def fill_levels(self):
+        """the level of every stored entry of B (int32, B's position order): 0 for A's entries"""
+        out = np.empty(self.stats()["nnz"], np.int32)
+        self._ck(self.A._d.lib.esp_precon_iluk_levels(self._live(), _vp(out), 0))
+        return out
+
+    def factor(self):
+        """the inner ILUAM factorization's values in B's position order"""
+        out = np.empty(self.stats()["nnz"], np.float64)
+        self._ck(self.A._d.lib.esp_precon_get_factor(self._live(), _vp(out), 0))
+        return out
+
+    def levels(self):
+        """the inner ILUAM's level counts: (factorization columns, forward rows, backward rows)"""
         out = (C.c_int64 * 3)()
         self._ck(self.A._d.lib.esp_precon_levels(self._live(), out))
         return tuple(int(x) for x in out)

@@ -452,6 +452,39 @@ int32_t esp_precon_rsamg_create(esp_handle *h, int32_t max_levels, int32_t max_c
                                 double theta, esp_precon **out);
 int32_t esp_precon_amg_coarsening(esp_precon *p, int32_t *kind);
 int32_t esp_precon_amg_splitting(esp_precon *p, int32_t level, int64_t *cf, int32_t on_device);
+/* ILUKPreconditioner: the level-of-fill ILU(k), the dialable member of the ILU family (the reference's own dial is the threshold
+ * ILUTPreconditioner, docs/src/iter.md, whose pattern depends on the values and whose elimination is sequential; ILU(k)'s pattern
+ * depends on the structure alone).  Indices 0-based: lev(i,j) = 0 where A stores (i,j) -- a stored 0.0, -0.0 or NaN counts -- and
+ * infinite elsewhere; for i = 0..n-1, for k < i in increasing order with lev(i,k) <= K, for j > k with lev(k,j) <= K:
+ * lev(i,j) = min(lev(i,j), lev(i,k) + lev(k,j) + 1).  B holds every position with lev <= K: A's bits where lev = 0, +0.0 elsewhere,
+ * rows ascending in every column.  esp_precon_iluk_create(h, k) is esp_precon_create(B, ESP_PRECON_ILUAM): ILU(k) of A is ILU(0) of B,
+ * so the factorization, the level-scheduled solves and their results are ILUAM's, bit-identical to tests/iluam_model.c applied to the
+ * B of tests/iluk_model.c; k = 0 is ESP_PRECON_ILUAM itself, k >= n - 2 the complete LU without pivoting.  ldiv! is ILUAM's on the
+ * caller's vectors (no further launch, copy or scratch); esp_simple, esp_cg, esp_bicgstabl and esp_gmres take it as they take ILUAM.
+ * The pattern is found on the device by one bounded breadth-first search per column over A (lower part) and over transpose(A)
+ * (upper part): one wave per column with a visited set of up to ESP_ILUK_WAVE_VISITS vertices (the column itself, every vertex enqueued
+ * and every row emitted as fill; A's own entries do not count, so k = 0 takes any matrix), a workgroup per column up to
+ * ESP_ILUK_VISIT_MAX.
+ * esp_precon_update: with A's pattern kept one gather (B.nzval[q] = A.nzval[src[q]], +0.0 for fill) and ILUAM's values-only update
+ * -- bitwise what a fresh create gives; after a pattern change everything anew.  B holds copies: a value change of A reaches ldiv!
+ * only through the update, and a pattern change of A without it is ESP_ERR_STATE.  When an update fails before B is replaced
+ * (ESP_ERR_NOMEM, ESP_ERR_UNSUPPORTED) the preconditioner stays what its last good update made it.
+ * esp_precon_get_factor and esp_precon_levels answer for the inner ILUAM (nnz(B) values in B's position order).
+ * esp_precon_iluk_matrix: B's handle, borrowed and read-only, like esp_precon_block_matrix.  esp_precon_iluk_levels: the level of every
+ * stored entry of B, nnz(B) values in B's position order.  esp_precon_iluk_stats: out = nnz(B), the largest stored level, the columns
+ * the workgroup search redid (lower part, upper part).
+ * ESP_ERR_INVALID: k < 0, a rectangular matrix, a column without a stored diagonal (ILUAM's error, which names it).
+ * ESP_ERR_STATE: pending entries.  ESP_ERR_UNSUPPORTED: a column window / column shard on h; n or nnz(B) >= 2^32 - 16; a search that
+ * visits more than ESP_ILUK_VISIT_MAX vertices (esp_last_error names the smallest such column and k; refused before B is touched).
+ * ILUK is no inner kind of esp_precon_block_create.  A live preconditioner makes h refuse esp_destroy; esp_precon_destroy releases B,
+ * the transpose and every buffer. */
+#define ESP_PRECON_ILUK 5
+#define ESP_ILUK_WAVE_VISITS 512
+#define ESP_ILUK_VISIT_MAX 8192
+int32_t esp_precon_iluk_create(esp_handle *h, int32_t k, esp_precon **out);
+int32_t esp_precon_iluk_matrix(esp_precon *p, esp_handle **b);
+int32_t esp_precon_iluk_levels(esp_precon *p, int32_t *lev, int32_t on_device);
+int32_t esp_precon_iluk_stats(esp_precon *p, int64_t out[4]);
 /* simple!(u, A, b; abstol, reltol, maxiter, Pl = p) (src/factorizations/simple_iteration.jl:21-45) statement by
  * statement: res = A*u - b; then per step ldiv!(upd, Pl, res), u .-= upd, mul!(res, A, u), res .-= b, r = norm(res),
  * stop when (r / r0) < reltol || r < abstol (literally: r0 = 0 gives NaN or Inf there).  u (in/out) is bit-identical to

@@ -71,6 +71,13 @@ the rounds of the PMIS splitting.  It adds gmres(restart = 20) to reltol = 1e-8 
 convection-diffusion matrix of tests/bicgstabl_modellib.py at --cd-n cubed unknowns and Peclet number --cd-pe (b = ones).
 
     python tools/precon_bench.py --kind amg [--coarsen sa|rs] [--n 64] [--iters 20] [--rounds 5] [--tol-maxiter 20000]
+
+--kind iluk --k K times ILUKPreconditioner (esp_precon_iluk_create) on fdrand(n,n,n) beside ILUAMPreconditioner, the yardstick, in the
+same run: the create (median over --rounds of create + close; the ILUAM analysis + factorization part is timed on a copy of B, the
+search + sort part is the rest), a values-only update!, ldiv!, nnz(B)/nnz(A), the three ILUAM level counts, the counters of the search,
+and gmres(restart = 20) / cg to reltol 1e-8 on b = ones (iterations and time).
+
+    python tools/precon_bench.py --kind iluk --k 1 [--n 64] [--iters 20] [--rounds 5]
 """
 import argparse
 import ctypes as C
@@ -745,12 +752,96 @@ def bench_amg(a, torch, esp):
     print(json.dumps(rnd(out)))
 
 
+def bench_iluk(a, torch, esp):
+    import numpy as np
+    A = esp.fdrand(a.n, a.n, a.n)
+    d = A._d
+    stream = torch.cuda.current_stream()
+    d.ck(d.lib.esp_set_stream(d.h, C.c_void_p(stream.cuda_stream)))
+    N, Z = A.n, A.nnz()
+    v = torch.randn(N, dtype=torch.float64, device="cuda")
+    u = torch.empty_like(v)
+    b = torch.ones_like(v)
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()                                   # (create, update!, ldiv! and the solvers return synchronised)
+        return (time.perf_counter() - t0) * 1e3, r
+
+    def median(xs):
+        return float(np.median(xs))
+
+    def measure(make, M=A):
+        rec = {}
+        ts = []
+        for _ in range(a.rounds):
+            t, P = wall(lambda: make(M))
+            ts.append(t)
+            P.close()
+        rec["create_ms"] = median(ts)
+        P = make(M)
+        rec["update_values_ms"] = median([wall(P.update)[0] for _ in range(a.rounds)])
+        for _ in range(3):
+            P.ldiv(v, out=u)
+        rec["ldiv_ms"] = median([wall(lambda: [P.ldiv(v, out=u) for _ in range(a.iters)])[0] / a.iters for _ in range(a.rounds)])
+        rec["levels"] = list(P.levels())
+        return rec, P
+
+    def solvers(rec, P):
+        for name, fn in (("gmres", lambda: esp.gmres(A, b, Pl=P, restart=20, reltol=1e-8, maxiter=a.tol_maxiter, log=True)),
+                         ("cg", lambda: esp.cg(A, b, Pl=P, reltol=1e-8, maxiter=a.tol_maxiter, log=True))):
+            fn()
+            ts, log = [], None
+            for _ in range(a.rounds):
+                t, (_, log) = wall(fn)
+                ts.append(t)
+            rec[name] = {"iterations": log["iters"], "converged": log["isconverged"], "ms": median(ts)}
+
+    out = {"workload": "iluk_fdrand", "n": a.n, "N": N, "nnz": Z, "k": a.k, "rounds": a.rounds}
+    Pw = esp.ILU0Preconditioner(A)     # builds the row-wise index esp_mul shares, so that the creates below are their own
+    Pw.close()
+    rec, P = measure(esp.ILUAMPreconditioner)
+    solvers(rec, P)
+    P.close()
+    out["iluam"] = rec
+    rec, P = measure(lambda M: esp.ILUKPreconditioner(M, a.k))
+    st = P.stats()
+    rec["nnz_B"] = st["nnz"]
+    rec["fill_ratio"] = st["nnz"] / Z
+    rec["stats"] = st
+    solvers(rec, P)
+    cp, rv, nz = P.fill_matrix()
+    P.close()
+    Bm = esp.ExtendableSparseMatrix(esp.SparseMatrixCSC(N, N, cp, rv, nz))      # ILUAM's analysis + factorization of B, on a copy
+    Bm.flush()
+    Pw = esp.ILU0Preconditioner(Bm)
+    Pw.close()
+    ts = []
+    for _ in range(a.rounds):
+        t, Q = wall(lambda: esp.ILUAMPreconditioner(Bm))
+        ts.append(t)
+        Q.close()
+    rec["create_iluam_of_B_ms"] = median(ts)
+    rec["create_search_sort_ms"] = rec["create_ms"] - rec["create_iluam_of_B_ms"]
+    out["iluk"] = rec
+
+    def rnd(x):
+        if isinstance(x, float):
+            return round(x, 4)
+        if isinstance(x, dict):
+            return {k: rnd(y) for k, y in x.items()}
+        return x
+    print(json.dumps(rnd(out)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "gmres", "gmres-trace", "block", "block-trace", "block-trace-diff", "amg"], default="point")
+    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "gmres", "gmres-trace", "block", "block-trace", "block-trace-diff", "amg", "iluk"], default="point")
+    ap.add_argument("--k", type=int, default=1)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--block-config", choices=["a", "b", "c", "d", "e"], default="b")
     ap.add_argument("--dirs", nargs=2, default=None)
@@ -785,6 +876,8 @@ def main():
         return bench_block(a, torch, esp)
     if a.kind == "block-trace":
         return bench_block_trace(a, torch, esp)
+    if a.kind == "iluk":
+        return bench_iluk(a, torch, esp)
     if a.kind == "amg":
         return bench_amg(a, torch, esp)
     A = esp.fdrand(a.n, a.n, a.n)
