@@ -1,5 +1,5 @@
 // bicgstabl.hip -- libesparse_hip: BiCGStab(l) for non-symmetric systems (esp_bicgstabl) on the device CSC
-// (see internal.hpp for the map of the translation units; krylov.hpp for what this shares with esp_cg)
+// (see internal.hpp for the map of the translation units; krylov.hpp for what this shares with esp_cg and esp_gmres)
 //
 // The algorithm is IterativeSolvers.jl's bicgstabl! with a left preconditioner.  That package is not part of the reference
 // tree: the statement sequence below is RESTATED from its documented behaviour, not read from its source.
@@ -44,7 +44,7 @@
 // Kernels of one outer iteration (l BiCG steps, then the minimal-residual step):
 //   bicg_dir_k      level 2 of rho and of the last sigma redone by every workgroup (j = 0: sigma = -omega*sigma from the
 //                   scalar block), beta, us[0..j] = rs[0..j] - beta*us[0..j] in one launch
-//   pmul            us[j+1] = Pl \ (A*us[j]) with level 0 of dot(rt, us[j+1]):
+//   pmul            us[j+1] = Pl \ (A*us[j]) with level 0 of dot(rt, us[j+1]) (krylov.hpp, PreconProduct::pmul):
 //                     Identity  row_dot_k<MUL_DOT>, other = rt
 //                     Jacobi    row_dot_k<MUL_JAC_DOT>: the gathered row sum times invdiag[i] before the store -- one launch,
 //                               bitwise ldiv! of mul!
@@ -80,35 +80,6 @@ constexpr int ndots(int l) { return (l + 1) * (l + 2) / 2; }
 
 __global__ void init_scalars_k(double *__restrict__ sc) {
     if (threadIdx.x < SC_COUNT) sc[threadIdx.x] = threadIdx.x <= SC_SIGMA ? 1.0 : 0.0;  // omega = sigma = 1
-}
-
-// level 1 of `gridDim.y` dot products at once: dot d has its partial0 at p0 + d*nb0 and its partial1 at p1 + d*nb1
-__global__ __launch_bounds__(KT) void fold_batch_k(const double *__restrict__ p0, i64 nb0, double *__restrict__ p1, i64 nb1) {
-    __shared__ double sred[KT];
-    p0 += (i64)blockIdx.y * nb0;
-    const i64 q = (i64)blockIdx.x * KT + threadIdx.x;
-    const double s = tree256(q < nb0 ? p0[q] : 0.0, sred);
-    if (threadIdx.x == 0) p1[(i64)blockIdx.y * nb1 + blockIdx.x] = s;
-}
-
-// ND trees of the summation shape at once: sred[d][t] holds the 256 values of dot d.  The steps w = 128 and 64 go through LDS,
-// w = 32 .. 1 pair the lanes of one wave (dot d in wave d mod 4): the same pairs in the same order as tree256.  Lane 0 of that
-// wave stores the sum to out[d*stride].  Ends with a barrier: sred is free again.
-template <int ND>
-__device__ __forceinline__ void trees(double (*sred)[KT], double *__restrict__ out, i64 stride) {
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    __syncthreads();
-    if (t < 128) {
-#pragma unroll
-        for (int d = 0; d < ND; d++) sred[d][t] = sred[d][t] + sred[d][t + 128];
-    }
-    __syncthreads();
-    for (int d = wv; d < ND; d += KT / 64) {
-        double a = sred[d][lane] + sred[d][lane + 64];
-        for (int w = 32; w > 0; w >>= 1) a = a + __shfl_down(a, w, 64);
-        if (lane == 0) out[(i64)d * stride] = a;
-    }
-    __syncthreads();
 }
 
 // rt = r_shadow (src; nullptr: a copy of rs[0]; src == rt: already there), level 0 of dot(rs[0], rs[0]) in p0[q] and of
@@ -318,64 +289,20 @@ extern "C" int32_t esp_bicgstabl(esp_handle *h, esp_precon *p, int32_t l, const 
     if (p) CK(ensure(h, w.t, vbytes));  // A*v in front of ILU0 / ILUAM, the unpreconditioned initial residual
     CK(ensure(h, w.part, sizeof(double) * (size_t)(nd * nb0 + (4 + nd) * nb1 + 8)));
     CK(ensure(h, w.sc, sizeof(double) * SC_COUNT));
-    const double *db = b;
-    double *dx = x;
-    if (!on_device) {
-        CK(ensure(h, w.hb, vbytes));
-        CK(ensure(h, w.hx, vbytes));
-        HIPCK(h, hipMemcpyAsync(w.hb.p, b, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-        HIPCK(h, hipMemcpyAsync(w.hx.p, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-        db = (const double *)w.hb.p;
-        dx = (double *)w.hx.p;
-    }
+    const double *db;
+    double *dx;
+    CK(stage_vectors(h, n, on_device != 0, b, x, &db, &dx));
     double *rs = (double *)w.bv.p, *us = rs + (l + 1) * ns, *rt = us + (l + 1) * ns, *t = (double *)w.t.p, *sc = (double *)w.sc.p;
     // the partial sums: level 0 of up to nd dots | level 1: rr, rho (neighbours: mr_k's two dots fold in one launch), two places
     // for sigma (bicg_dir_k reads the last one while the next is formed), the Gram matrix
     double *p0 = (double *)w.part.p, *p1 = p0 + nd * nb0;
     double *p1_rr = p1, *p1_rho = p1 + nb1, *p1_sig[2] = {p1 + 2 * nb1, p1 + 3 * nb1}, *p1_gram = p1 + 4 * nb1;
-    const u64 *rp = (const u64 *)h->csr_rowptr.p + 1;
     const unsigned g0 = (unsigned)std::max<i64>(nb0, 1), g1 = (unsigned)std::max<i64>(nb1, 1);
     const unsigned gv = (unsigned)std::min<i64>(std::max<i64>(nb0, 1), KGRID);
     const double *const nil = nullptr;
-    esp_precon *const blk = block_permuted(p) ? p : nullptr;  // BlockPreconditioner, permuted path: gather, inner ldiv!, scatter, dot_k
-    p = fused_precon(p);                                      // ... identity path: the inner kind's own branch on its buffers
     auto fold = [&](double *dst) { hipLaunchKernelGGL(fold_k, dim3(g1), dim3(KT), 0, h->stream, (const double *)p0, nb0, dst); };
-    // dst = A*src (mul!), level 0 of dot(dst, rt) when dot
-    auto mul = [&](const double *src, double *dst, bool dot) {
-        hipLaunchKernelGGL((row_dot_k<MUL_DOT, u64>), dim3(g0), dim3(KT), 0, h->stream, rp, (const u32 *)h->csr_col.p,
-                           (const double *)h->csr_val.p, src, (const double *)rt, dst, n, dot ? p0 : (double *)nullptr, nil);
-    };
-    // dst = Pl \ src for ILU0 / ILUAM (src != dst), level 0 of dot(dst, rt) when dot
-    auto ldiv = [&](const double *src, double *dst, bool dot) -> int32_t {
-        if (blk || p->kind == ESP_PRECON_ILUAM || p->kind == ESP_PRECON_AMG) {
-            if (blk) CK(block_ldiv_launch(blk, src, dst, false));
-            else if (p->kind == ESP_PRECON_AMG) CK(amg_solve(p, src, dst, false));
-            else CK(iluam_solve(p, src, dst, false));
-            if (dot)
-                hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, h->stream, nil, (const double *)dst, (const double *)rt,
-                                   (double *)nullptr, n, nb0, p0);
-            return ESP_OK;
-        }
-        ilu0_lower_launch(p, src);
-        hipLaunchKernelGGL((row_dot_k<UPPER_DOT, u32>), dim3(g0), dim3(KT), 0, h->stream, (const u32 *)p->uptr.p, (const u32 *)p->ucol.p,
-                           (const double *)p->uval.p, (const double *)p->u1.p, (const double *)rt, dst, n,
-                           dot ? p0 : (double *)nullptr, nil);
-        return ESP_OK;
-    };
-    // dst = Pl \ (A*src), level 0 of dot(dst, rt) when dot
-    auto pmul = [&](const double *src, double *dst, bool dot) -> int32_t {
-        if (!p) {
-            mul(src, dst, dot);
-        } else if (!blk && p->kind == ESP_PRECON_JACOBI) {
-            hipLaunchKernelGGL((row_dot_k<MUL_JAC_DOT, u64>), dim3(g0), dim3(KT), 0, h->stream, rp, (const u32 *)h->csr_col.p,
-                               (const double *)h->csr_val.p, src, (const double *)rt, dst, n, dot ? p0 : (double *)nullptr,
-                               (const double *)p->diag.p);
-        } else {
-            mul(src, t, false);
-            CK(ldiv(t, dst, dot));
-        }
-        return ESP_OK;
-    };
+    // every A*v, Pl \ v and Pl \ (A*v) below, level 0 of dot(dst, rt) when a dot product is wanted
+    const PreconProduct pp{h, fused_precon(p), block_permuted(p) ? p : nullptr, n, nb0, g0, gv, p0, t};
     // residual = norm(rs[0]) from its level 1 in p1_rr: one read-back (the stop test runs on the host)
     auto residual = [&](double *out) -> int32_t {
         if (n == 0) {
@@ -394,12 +321,10 @@ extern "C" int32_t esp_bicgstabl(esp_handle *h, esp_precon *p, int32_t l, const 
         hipLaunchKernelGGL(init_scalars_k, dim3(1), dim3(64), 0, h->stream, sc);
         HIPCK(h, hipMemsetAsync(us, 0, sizeof(double) * (size_t)ns * (size_t)(l + 1), h->stream));  // us = 0
         double *r0 = p ? t : rs;  // the unpreconditioned initial residual
-        if (!initially_zero) mul(dx, rs + ns, false);  // A*x in rs[1], which is free until the first BiCG step
+        if (!initially_zero) pp.mul(dx, rs + ns, rt, false);  // A*x in rs[1], which is free until the first BiCG step
         hipLaunchKernelGGL(start_k, dim3(gv), dim3(KT), 0, h->stream, db, initially_zero ? nil : (const double *)(rs + ns), r0, n, nb0,
                            p0);
-        if (p && !blk && p->kind == ESP_PRECON_JACOBI)  // rs[0] = invdiag .* r0
-            hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)p->diag.p, nil, (const double *)r0, rs, n, nb0, p0);
-        else if (p) CK(ldiv(r0, rs, false));
+        if (p) CK(pp.ldiv(r0, rs, rt, false));  // rs[0] = Pl \ r0
         const double *src = nullptr;
         if (r_shadow && on_device) src = r_shadow;
         else if (r_shadow) {
@@ -422,11 +347,11 @@ extern "C" int32_t esp_bicgstabl(esp_handle *h, esp_precon *p, int32_t l, const 
                 hipLaunchKernelGGL(bicg_dir_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)p1_rho,
                                    j == 0 ? nil : (const double *)p1_sig[(j - 1) & 1], (const double *)sc, nb1, j, (const double *)rs, us,
                                    ns, n);
-                CK(pmul(us + j * ns, us + (j + 1) * ns, true));  // us[j+1] = Pl \ (A*us[j]), level 0 of sigma
+                CK(pp.pmul(us + j * ns, us + (j + 1) * ns, rt, true));  // us[j+1] = Pl \ (A*us[j]), level 0 of sigma
                 fold(sig);
                 hipLaunchKernelGGL(bicg_upd_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)p1_rho, (const double *)sig, nb1, j, rs,
                                    (const double *)us, dx, ns, n);
-                CK(pmul(rs + j * ns, rs + (j + 1) * ns, j + 1 < l));  // rs[j+1] = Pl \ (A*rs[j]), level 0 of the next rho
+                CK(pp.pmul(rs + j * ns, rs + (j + 1) * ns, rt, j + 1 < l));  // rs[j+1] = Pl \ (A*rs[j]), level 0 of the next rho
                 if (j + 1 < l) fold(p1_rho);
             }
             const double *sig_last = p1_sig[(l - 1) & 1];
@@ -444,7 +369,5 @@ extern "C" int32_t esp_bicgstabl(esp_handle *h, esp_precon *p, int32_t l, const 
     if (iterations) *iterations = it;
     if (mv_products) *mv_products = mv;
     if (converged) *converged = res <= tol ? 1 : 0;
-    if (!on_device) HIPCK(h, hipMemcpyAsync(x, dx, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    return ESP_OK;
+    return return_x(h, n, on_device != 0, x, dx);
 }

@@ -46,13 +46,13 @@
 // history, the counters and the flag are bit-identical to it.
 //
 // Kernels of iteration k (w = V[k+1]):
-//   expand          w = Pl \ (A*V[k]), bicgstabl.hip's branches: Identity / Jacobi / ILU0 end in a row_dot_k that (MGS) also emits
-//                   level 0 of dot(V[1], w); ILUAM / AMG / the permuted Block end in dot_k
+//   pmul            w = Pl \ (A*V[k]) (krylov.hpp, PreconProduct::pmul: the branches esp_bicgstabl takes): Identity / Jacobi / ILU0 end
+//                   in a row_dot_k that (MGS) also emits level 0 of dot(V[1], w); ILUAM / AMG / the permuted Block end in dot_k
 //   MGS    fold_k, then k times  mgs_step_k + fold_k:  every workgroup finishes H[i,k] from the level-1 partials (workgroup 0
 //          stores it), w = w - H[i,k]*V[i] and level 0 of the NEXT dot -- dot(V[i+1], w), or dot(w, w) after the last column -- in
 //          the same pass: three streams read, one written, double2 accesses; the dots alternate between two level-1 places.
 //          2k + constant launches.
-//   CGS / DGKS   bdot_k (w[e] in a register, level 0 of all k dots, the columns in groups of 8 trees), fold_batch_k, coef_k (ONE
+//   CGS / DGKS   bdot_k (w[e] in a register, level 0 of all k dots, the columns in groups of 8 trees), gm_fold_batch_k, coef_k (ONE
 //          workgroup: h or c, proj, h += c to the scalar block), comb_k (the ordered combination, level 0 of dot(w, w)), fold;
 //          DGKS then enqueues pred_k (ONE workgroup: nrm, the predicate nrm < eta*proj AND every earlier one, to the scalar block)
 //          and the same five kernels three times, unconditionally: each reads the device predicate and returns at once when it is
@@ -90,34 +90,12 @@ __global__ __launch_bounds__(KT) void gm_scalars_k(double *__restrict__ sc) {
     for (int i = threadIdx.x; i < SC_COUNT; i += KT) sc[i] = i >= SC_NULL && i < SC_RHS ? 1.0 : 0.0;  // nullvec = 1
 }
 
-// level 1 of `gridDim.y` dot products at once (bicgstabl.hip's fold_batch_k with the DGKS predicate in front)
+// krylov.hpp's fold_batch behind the DGKS predicate
 __global__ __launch_bounds__(KT) void gm_fold_batch_k(const double *__restrict__ p0, i64 nb0, double *__restrict__ p1, i64 nb1,
                                                       const double *__restrict__ flag) {
     __shared__ double sred[KT];
     if (flag && flag[0] == 0.0) return;
-    p0 += (i64)blockIdx.y * nb0;
-    const i64 q = (i64)blockIdx.x * KT + threadIdx.x;
-    const double s = tree256(q < nb0 ? p0[q] : 0.0, sred);
-    if (threadIdx.x == 0) p1[(i64)blockIdx.y * nb1 + blockIdx.x] = s;
-}
-
-// ND trees of the summation shape at once (bicgstabl.hip's trees): sred[d][t] holds the 256 values of dot d; the same pairs in
-// the same order as tree256.  Lane 0 of wave d mod 4 stores the sum of dot d < nout to out[d*stride].  Ends with a barrier.
-template <int ND>
-__device__ __forceinline__ void gm_trees(double (*sred)[KT], double *__restrict__ out, i64 stride, int nout) {
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    __syncthreads();
-    if (t < 128) {
-#pragma unroll
-        for (int d = 0; d < ND; d++) sred[d][t] = sred[d][t] + sred[d][t + 128];
-    }
-    __syncthreads();
-    for (int d = wv; d < ND; d += KT / 64) {
-        double a = sred[d][lane] + sred[d][lane + 64];
-        for (int w = 32; w > 0; w >>= 1) a = a + __shfl_down(a, w, 64);
-        if (lane == 0 && d < nout) out[(i64)d * stride] = a;
-    }
-    __syncthreads();
+    fold_batch(p0, nb0, p1, nb1, sred);
 }
 
 // beta = norm(v) from its level 1, v = v * (1.0/beta); workgroup 0: beta, acc = 1 and (first: the start of a solve) current = beta
@@ -170,7 +148,7 @@ __global__ __launch_bounds__(KT) void mgs_step_k(const double *__restrict__ p1, 
             pr.x = (vnext ? vnext[i0] : wi) * wi;
         }
         ((double2 *)&sred[0][0])[threadIdx.x] = pr;  // element 2t + s of the round = place 2t + s of the two chunks
-        gm_trees<2>(sred, p0 + 2 * q, 1, nb0 - 2 * q < 2 ? 1 : 2);
+        trees<2>(sred, p0 + 2 * q, 1, nb0 - 2 * q < 2 ? 1 : 2);
     }
 }
 
@@ -185,7 +163,7 @@ __global__ __launch_bounds__(KT) void bdot_k(const double *__restrict__ V, i64 n
         for (int g = 0; g < k; g += GM_GROUP) {
 #pragma unroll
             for (int d = 0; d < GM_GROUP; d++) sred[d][threadIdx.x] = (g + d < k && i < n) ? V[(i64)(g + d) * ns + i] * wv : 0.0;
-            gm_trees<GM_GROUP>(sred, p0 + (i64)g * nb0 + q, nb0, k - g < GM_GROUP ? k - g : GM_GROUP);
+            trees<GM_GROUP>(sred, p0 + (i64)g * nb0 + q, nb0, k - g < GM_GROUP ? k - g : GM_GROUP);
         }
     }
 }
@@ -345,71 +323,29 @@ extern "C" int32_t esp_gmres(esp_handle *h, esp_precon *p, const double *b, doub
     if (p) CK(ensure(h, w.t, vbytes));  // A*v in front of ILU0 / ILUAM / AMG / the permuted Block, the unpreconditioned residual
     CK(ensure(h, w.part, sizeof(double) * (size_t)(restart * nb0 + (2 + restart) * nb1 + 8)));
     CK(ensure(h, w.sc, sizeof(double) * SC_COUNT));
-    const double *db = b;
-    double *dx = x;
-    if (!on_device) {
-        CK(ensure(h, w.hb, vbytes));
-        CK(ensure(h, w.hx, vbytes));
-        HIPCK(h, hipMemcpyAsync(w.hb.p, b, vbytes, hipMemcpyHostToDevice, h->stream));
-        HIPCK(h, hipMemcpyAsync(w.hx.p, x, vbytes, hipMemcpyHostToDevice, h->stream));
-        db = (const double *)w.hb.p;
-        dx = (double *)w.hx.p;
-    }
+    const double *db;
+    double *dx;
+    CK(stage_vectors(h, n, on_device != 0, b, x, &db, &dx));
     double *V = (double *)w.bv.p, *t = (double *)w.t.p, *sc = (double *)w.sc.p;
     // the partial sums: level 0 of up to `restart` dots | level 1: two places the single dots alternate between (mgs_step_k reads
     // one while the next is formed), the batch of the CGS / DGKS passes
     double *p0 = (double *)w.part.p, *p1 = p0 + (i64)restart * nb0;
     double *slot[2] = {p1, p1 + nb1}, *p1_batch = p1 + 2 * nb1;
-    const u64 *rp = (const u64 *)h->csr_rowptr.p + 1;
     const unsigned g0 = (unsigned)nb0, g1 = (unsigned)nb1;
     const unsigned gv = (unsigned)std::min<i64>(nb0, KGRID), gv2 = (unsigned)std::min<i64>((nb0 + 1) >> 1, KGRID);
     const double *const nil = nullptr;
     double *const nilw = nullptr;
     hipStream_t st = h->stream;
-    esp_precon *const blk = block_permuted(p) ? p : nullptr;  // BlockPreconditioner, permuted path: gather, inner ldiv!, scatter, dot_k
-    p = fused_precon(p);                                      // ... identity path: the inner kind's own branch on its buffers
     auto fold = [&](double *dst) { hipLaunchKernelGGL(fold_k, dim3(g1), dim3(KT), 0, st, (const double *)p0, nb0, dst); };
-    // dst = A*src (mul!), level 0 of dot(dst, V[0]) when dot
-    auto mul = [&](const double *src, double *dst, bool dot) {
-        hipLaunchKernelGGL((row_dot_k<MUL_DOT, u64>), dim3(g0), dim3(KT), 0, st, rp, (const u32 *)h->csr_col.p,
-                           (const double *)h->csr_val.p, src, (const double *)V, dst, n, dot ? p0 : nilw, nil);
-    };
-    // dst = Pl \ src for ILU0 / ILUAM / AMG / the permuted Block (src != dst), level 0 of dot(dst, V[0]) when dot
-    auto ldiv = [&](const double *src, double *dst, bool dot) -> int32_t {
-        if (blk || p->kind == ESP_PRECON_ILUAM || p->kind == ESP_PRECON_AMG) {
-            if (blk) CK(block_ldiv_launch(blk, src, dst, false));
-            else if (p->kind == ESP_PRECON_AMG) CK(amg_solve(p, src, dst, false));
-            else CK(iluam_solve(p, src, dst, false));
-            if (dot) hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, st, nil, (const double *)dst, (const double *)V, nilw, n, nb0, p0);
-            return ESP_OK;
-        }
-        ilu0_lower_launch(p, src);
-        hipLaunchKernelGGL((row_dot_k<UPPER_DOT, u32>), dim3(g0), dim3(KT), 0, st, (const u32 *)p->uptr.p, (const u32 *)p->ucol.p,
-                           (const double *)p->uval.p, (const double *)p->u1.p, (const double *)V, dst, n, dot ? p0 : nilw, nil);
-        return ESP_OK;
-    };
-    // dst = Pl \ (A*src), level 0 of dot(dst, V[0]) when dot
-    auto expand = [&](const double *src, double *dst, bool dot) -> int32_t {
-        if (!p) {
-            mul(src, dst, dot);
-        } else if (!blk && p->kind == ESP_PRECON_JACOBI) {
-            hipLaunchKernelGGL((row_dot_k<MUL_JAC_DOT, u64>), dim3(g0), dim3(KT), 0, st, rp, (const u32 *)h->csr_col.p,
-                               (const double *)h->csr_val.p, src, (const double *)V, dst, n, dot ? p0 : nilw, (const double *)p->diag.p);
-        } else {
-            mul(src, t, false);
-            CK(ldiv(t, dst, dot));
-        }
-        return ESP_OK;
-    };
+    // every A*v, Pl \ v and Pl \ (A*v) below, level 0 of dot(dst, V[0]) when a dot product is wanted
+    const PreconProduct pp{h, fused_precon(p), block_permuted(p) ? p : nullptr, n, nb0, g0, gv, p0, t};
     // V[0] = Pl \ b or Pl \ (b - A*x), normalised; beta, acc = 1 (first: current = beta) to the scalar block
     auto init = [&](bool zero, bool first) -> int32_t {
         double *r0 = p ? t : V;                // the unpreconditioned residual
-        if (!zero) mul(dx, V + ns, false);     // A*x in V[1], which is free here
+        if (!zero) pp.mul(dx, V + ns, V, false);  // A*x in V[1], which is free here
         hipLaunchKernelGGL(start_k, dim3(gv), dim3(KT), 0, st, db, zero ? nil : (const double *)(V + ns), r0, n, nb0, p0);
         if (p) {
-            if (!blk && p->kind == ESP_PRECON_JACOBI)  // V[0] = invdiag .* r0
-                hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, st, (const double *)p->diag.p, nil, (const double *)r0, V, n, nb0, p0);
-            else CK(ldiv(r0, V, false));
+            CK(pp.ldiv(r0, V, V, false));  // V[0] = Pl \ r0
             hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, st, nil, (const double *)V, (const double *)V, nilw, n, nb0, p0);
         }
         fold(slot[0]);
@@ -449,7 +385,7 @@ extern "C" int32_t esp_gmres(esp_handle *h, esp_precon *p, const double *b, doub
     int k = 1;
     while (it < maxiter && !(current <= tol)) {
         double *wv = V + (i64)k * ns;
-        CK(expand(V + (i64)(k - 1) * ns, wv, orth_meth == ESP_ORTH_MGS));
+        CK(pp.pmul(V + (i64)(k - 1) * ns, wv, V, orth_meth == ESP_ORTH_MGS));
         mv++;
         const double *nrm_p1, *hsrc;
         if (orth_meth == ESP_ORTH_MGS) {
@@ -494,7 +430,5 @@ extern "C" int32_t esp_gmres(esp_handle *h, esp_precon *p, const double *b, doub
     if (reorth_passes) *reorth_passes = passes;
     if (converged) *converged = current <= tol ? 1 : 0;
     HIPCK(h, hipGetLastError());
-    if (!on_device) HIPCK(h, hipMemcpyAsync(x, dx, vbytes, hipMemcpyDeviceToHost, st));
-    HIPCK(h, hipStreamSynchronize(st));
-    return ESP_OK;
+    return return_x(h, n, on_device != 0, x, dx);
 }

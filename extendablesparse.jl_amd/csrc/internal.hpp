@@ -17,7 +17,8 @@
 //   rsamg.hip      RS_AMGPreconditioner's coarsening: row-wise strength, the PMIS splitting, direct interpolation (the rest is amg.hip's)
 //   krylov.hip     preconditioned conjugate gradients (esp_cg): fused vector kernels, ordered dot products, scalars on the device
 //   bicgstabl.hip  BiCGStab(l) for non-symmetric systems (esp_bicgstabl): the same design with l+1 residuals and search vectors;
-//                  krylov.hpp holds what the solvers share
+//                  krylov.hpp holds what the solvers share: the summation shape's kernels, the preconditioned product
+//                  (PreconProduct) and the hand-over of host b / x
 //   gmres.hip      restarted GMRES (esp_gmres): fused modified Gram-Schmidt steps, batched classical / DGKS passes behind a device
 //                  predicate, H, the residual recurrence, the rotations and y in a scalar block on the device
 //   matops.hip     the algebra of assembled matrices on the device: A*B (esp_matmul), A+B / A-B (esp_add), Diagonal scaling
@@ -354,7 +355,9 @@ struct esp_handle {
     // esp_cg's work vectors (krylov.hip), sized on first use: residual, search direction, Pl \ r and A*u, the partial sums of the
     // three dot products, and the device copies of host b / x.  esp_bicgstabl (bicgstabl.hip) shares part, hb and hx and adds
     // bv: its 2(l+1) + 1 vectors (rs[0..l], us[0..l], the shadow residual), t: A*v in front of ILU0 / ILUAM, sc: the scalar block.
-    // esp_gmres (gmres.hip) uses the same buffers: bv holds its restart+1 basis vectors, sc its H, nullvec, rhs, h, c and scalars
+    // esp_gmres (gmres.hip) uses the same buffers: bv holds its restart+1 basis vectors, sc its H, nullvec, rhs, h, c and scalars.
+    // krylov.hpp holds what the three share on the host side too: stage_vectors / return_x fill hb and hx and copy x back, and
+    // PreconProduct issues every A*v, Pl \ v and Pl \ (A*v) of a solve (t is its scratch between the two).
     struct Krylov {
         DevBuf r, u, c, part, hb, hx, bv, t, sc;
     } kry;
@@ -604,8 +607,8 @@ int32_t split_build(esp_precon *p, bool reversed);
 int32_t iluam_update(esp_precon *p, bool rebuild);
 int32_t iluam_solve(esp_precon *p, const double *v, double *dst, bool sub);
 void iluam_release(esp_precon *p);
-// precon.hip, for krylov.hip: the checks in front of a solve (p == nullptr: those of the handle alone); pass 1 of ILU0's ldiv!
-// into the scratch p->u1 (pass 2 is krylov.hip's own: it carries the dot product)
+// precon.hip, for the Krylov solvers: the checks in front of a solve (p == nullptr: those of the handle alone); pass 1 of ILU0's
+// ldiv! into the scratch p->u1 (pass 2 is krylov.hpp's own, in PreconProduct::ldiv: it carries the dot product)
 int32_t solver_ready(esp_handle *h, esp_precon *p, const char *what);
 void ilu0_lower_launch(esp_precon *p, const double *v);
 // precon.hip, for block.hip: the checks of every preconditioner call on the handle; ldiv! on device vectors (u may be v)

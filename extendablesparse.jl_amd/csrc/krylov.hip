@@ -34,7 +34,7 @@
 // the rounding of the dot products only.  The sums of squares overflow for entries above about 1e154, where nrm2 would not.
 //
 // Kernels of one iteration (ILU0; Jacobi and Identity have one launch in place of the first two, ILUAM its level launches
-// and a dot kernel):
+// and a dot kernel -- the branches are krylov.hpp's PreconProduct::ldiv, which esp_bicgstabl and esp_gmres call as well):
 //   row_chain_k<ILU_LOWER>   pass 1 of ldiv! (precon.hip, unchanged)
 //   row_dot_k<UPPER_DOT>     pass 2, c[i] stored, level 0 of dot(c, r)
 //   fold_k                   level 1
@@ -109,27 +109,16 @@ extern "C" int32_t esp_cg(esp_handle *h, esp_precon *p, const double *b, double 
     CK(ensure(h, w.u, vbytes));
     CK(ensure(h, w.c, vbytes));
     CK(ensure(h, w.part, sizeof(double) * (size_t)(nb0 + 4 * nb1 + 8)));
-    const double *db = b;
-    double *dx = x;
-    if (!on_device) {
-        CK(ensure(h, w.hb, vbytes));
-        CK(ensure(h, w.hx, vbytes));
-        HIPCK(h, hipMemcpyAsync(w.hb.p, b, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-        HIPCK(h, hipMemcpyAsync(w.hx.p, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->stream));
-        db = (const double *)w.hb.p;
-        dx = (double *)w.hx.p;
-    }
+    const double *db;
+    double *dx;
+    CK(stage_vectors(h, n, on_device != 0, b, x, &db, &dx));
     double *r = (double *)w.r.p, *u = (double *)w.u.p, *c = (double *)w.c.p;
     double *p0 = (double *)w.part.p, *p1_rho[2] = {p0 + nb0, p0 + nb0 + nb1}, *p1_uc = p0 + nb0 + 2 * nb1, *p1_rr = p0 + nb0 + 3 * nb1;
     double *d_out = p0 + nb0 + 4 * nb1;
-    const u64 *rp = (const u64 *)h->csr_rowptr.p + 1;
     const unsigned g0 = (unsigned)std::max<i64>(nb0, 1), g1 = (unsigned)std::max<i64>(nb1, 1);
     const unsigned gv = (unsigned)std::min<i64>(std::max<i64>(nb0, 1), KGRID);
     auto fold = [&](double *p1) { hipLaunchKernelGGL(fold_k, dim3(g1), dim3(KT), 0, h->stream, (const double *)p0, nb0, p1); };
-    auto mul_dot = [&](const double *src, const double *other) {  // c = A*src, level 0 of dot(c, other)
-        hipLaunchKernelGGL((row_dot_k<MUL_DOT, u64>), dim3(g0), dim3(KT), 0, h->stream, rp, (const u32 *)h->csr_col.p,
-                           (const double *)h->csr_val.p, src, other, c, n, p0, (const double *)nullptr);
-    };
+    const PreconProduct pp{h, fused_precon(p), block_permuted(p) ? p : nullptr, n, nb0, g0, gv, p0, nullptr};
     // residual = norm(r) from level 0 in p0: one read-back (the stop test runs on the host)
     auto residual = [&](double *out) -> int32_t {
         if (n == 0) {
@@ -146,7 +135,7 @@ extern "C" int32_t esp_cg(esp_handle *h, esp_precon *p, const double *b, double 
     };
     if (n > 0) {
         HIPCK(h, hipMemsetAsync(u, 0, sizeof(double) * (size_t)n, h->stream));  // u = 0
-        if (!initially_zero) mul_dot(dx, dx);                                   // c = A*x (its partials are not used)
+        if (!initially_zero) pp.mul(dx, c, dx, true);                           // c = A*x (its partials are not used)
         hipLaunchKernelGGL(start_k, dim3(gv), dim3(KT), 0, h->stream, db, initially_zero ? (const double *)nullptr : (const double *)c, r,
                            n, nb0, p0);
     }
@@ -156,39 +145,16 @@ extern "C" int32_t esp_cg(esp_handle *h, esp_precon *p, const double *b, double 
     const double tol = std::max(reltol * res, abstol);
     int64_t it = 0;
     const double *z = p ? c : r;  // Pl \ r (Identity: r itself)
-    esp_precon *const blk = block_permuted(p) ? p : nullptr;  // BlockPreconditioner, permuted path: gather, inner ldiv!, scatter, dot_k
-    p = fused_precon(p);                                      // ... identity path: the inner kind's own branch on its buffers
     while (it < maxiter && !(res <= tol)) {
         it++;
         if (n > 0) {
             double *rho = p1_rho[it & 1];
-            // c = Pl \ r with level 0 of dot(c, r)
-            if (!p) {
-                hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)nullptr, (const double *)r, (const double *)r,
-                                   (double *)nullptr, n, nb0, p0);
-            } else if (blk) {
-                CK(block_ldiv_launch(blk, r, c, false));
-                hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)nullptr, (const double *)c, (const double *)r,
-                                   (double *)nullptr, n, nb0, p0);
-            } else if (p->kind == ESP_PRECON_JACOBI) {
-                hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)p->diag.p, (const double *)nullptr,
-                                   (const double *)r, c, n, nb0, p0);
-            } else if (p->kind == ESP_PRECON_ILUAM || p->kind == ESP_PRECON_AMG) {
-                if (p->kind == ESP_PRECON_AMG) CK(amg_solve(p, r, c, false));  // the V-cycle's launches, then dot_k
-                else CK(iluam_solve(p, r, c, false));
-                hipLaunchKernelGGL(dot_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)nullptr, (const double *)c, (const double *)r,
-                                   (double *)nullptr, n, nb0, p0);
-            } else {
-                ilu0_lower_launch(p, r);
-                hipLaunchKernelGGL((row_dot_k<UPPER_DOT, u32>), dim3(g0), dim3(KT), 0, h->stream, (const u32 *)p->uptr.p,
-                                   (const u32 *)p->ucol.p, (const double *)p->uval.p, (const double *)p->u1.p, (const double *)r, c, n, p0,
-                                   (const double *)nullptr);
-            }
+            CK(pp.ldiv(r, c, r, true));  // c = Pl \ r with level 0 of dot(c, r)
             fold(rho);
             // rho_prev = rho; rho = dot(c, r); beta = rho/rho_prev; u = c + beta*u
             hipLaunchKernelGGL(direction_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)rho,
                                it == 1 ? (const double *)nullptr : (const double *)p1_rho[(it - 1) & 1], nb1, z, u, n);
-            mul_dot(u, u);  // c = A*u with level 0 of dot(u, c)
+            pp.mul(u, c, u, true);  // c = A*u with level 0 of dot(u, c)
             fold(p1_uc);
             // alpha = rho / dot(u, c); x += alpha*u; r -= alpha*c
             hipLaunchKernelGGL(update_k, dim3(gv), dim3(KT), 0, h->stream, (const double *)rho, (const double *)p1_uc, nb1,
@@ -199,7 +165,5 @@ extern "C" int32_t esp_cg(esp_handle *h, esp_precon *p, const double *b, double 
     }
     if (iterations) *iterations = it;
     if (converged) *converged = res <= tol ? 1 : 0;
-    if (!on_device) HIPCK(h, hipMemcpyAsync(x, dx, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    return ESP_OK;
+    return return_x(h, n, on_device != 0, x, dx);
 }

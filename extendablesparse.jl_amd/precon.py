@@ -40,6 +40,47 @@ def _check_cuda(t, n):
     assert t.is_cuda and t.dtype == torch.float64 and t.numel() == n and t.is_contiguous()
 
 
+def _handover(n, b, x, what, zeros=True, r_shadow=None):
+    """The vector hand-over of every call.  b: a NumPy array (copied through the device) or a CUDA float64 tensor (used in place);
+    x: the result vector, `what` in the messages, or None for a new one where b lives (zeros, or uninitialised); r_shadow:
+    bicgstabl's.  Returns (pointer of b, of x, of r_shadow or None, on_device, x)."""
+    if _is_cuda(b):
+        import torch
+        _check_cuda(b, n)
+        if x is None:
+            x = (torch.zeros if zeros else torch.empty)(n, dtype=torch.float64, device=b.device)
+        _check_cuda(x, n)
+        if r_shadow is not None:
+            if not _is_cuda(r_shadow):
+                raise ValueError("r_shadow must live where b does")
+            if r_shadow.numel() != n:
+                raise ValueError("DimensionMismatch")
+            _check_cuda(r_shadow, n)
+        torch.cuda.current_stream(b.device).synchronize()   # the library runs on its own stream
+        return [None if t is None else C.c_void_p(t.data_ptr()) for t in (b, x, r_shadow)] + [1, x]
+    b = np.ascontiguousarray(b, np.float64)
+    if b.shape != (n,):
+        raise ValueError("DimensionMismatch")
+    if x is None:
+        x = (np.zeros if zeros else np.empty)(n, np.float64)
+    if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.shape == (n,) and x.flags.c_contiguous):
+        raise ValueError("%s must be a contiguous float64 array of length n" % what)
+    if r_shadow is not None:
+        if _is_cuda(r_shadow):
+            raise ValueError("r_shadow must live where b does")
+        r_shadow = np.ascontiguousarray(r_shadow, np.float64)
+        if r_shadow.shape != (n,):
+            raise ValueError("DimensionMismatch")
+    return [None if a is None else _vp(a) for a in (b, x, r_shadow)] + [0, x]   # (a pointer keeps its array alive)
+
+
+def _check_solver(name, A, Pl):
+    if not isinstance(A, ExtendableSparseMatrix):
+        raise TypeError("%s(A, b): A must be an ExtendableSparseMatrix" % name)
+    if Pl is not None and (not isinstance(Pl, _PointPreconditioner) or Pl.A is not A):
+        raise ValueError("%s: Pl must be a preconditioner of A, or None" % name)
+
+
 class _PointPreconditioner:
     KIND = None
 
@@ -75,24 +116,18 @@ class _PointPreconditioner:
         p = self._live()
         A = self.A
         A._push_edits()   # (a device consumer: host edits of a handed-out copy go up first, as for mul)
-        lib = A._d.lib
-        n = A.n
-        if _is_cuda(v):
-            import torch
-            _check_cuda(v, n)
-            u = out if out is not None else torch.empty(n, dtype=torch.float64, device=v.device)
-            _check_cuda(u, n)
-            torch.cuda.current_stream(v.device).synchronize()   # the library runs on its own stream
-            self._ck(lib.esp_precon_ldiv(p, C.c_void_p(v.data_ptr()), C.c_void_p(u.data_ptr()), 1))
-            return u
-        vv = np.ascontiguousarray(v, np.float64)
-        if vv.shape != (n,):
-            raise ValueError("DimensionMismatch")
-        u = out if out is not None else np.empty(n, np.float64)
-        if not (isinstance(u, np.ndarray) and u.dtype == np.float64 and u.shape == (n,) and u.flags.c_contiguous):
-            raise ValueError("out must be a contiguous float64 array of length n")
-        self._ck(lib.esp_precon_ldiv(p, _vp(vv), _vp(u), 0))
+        pv, pu, _, dev, u = _handover(A.n, v, out, "out", zeros=False)
+        self._ck(A._d.lib.esp_precon_ldiv(p, pv, pu, dev))
         return u
+
+    def _host_csc(self, h, n):
+        """the matrix of handle h (n columns) as host CSC arrays (colptr, rowval, nzval), Julia layout"""
+        lib = self.A._d.lib
+        nnz = C.c_int64()
+        self._ck(lib.esp_nnz(h, C.byref(nnz)))
+        cp, rv, nz = np.empty(n + 1, np.int64), np.empty(nnz.value, np.int64), np.empty(nnz.value, np.float64)
+        self._ck(lib.esp_get_csc(h, _vp(cp), _vp(rv), _vp(nz)))
+        return cp, rv, nz
 
     def close(self):
         if self._p is not None:
@@ -117,28 +152,41 @@ class ILU0Preconditioner(_PointPreconditioner):
     KIND = ESP_PRECON_ILU0
 
 
-class ILUAMPreconditioner(_PointPreconditioner):
-    """ILUAMPreconditioner(A) (src/experimental/ExtendableSparseMatrixParallel/iluam.jl): a real ILU(0) on A's pattern, the
-    factorization and both triangular solves level by level on the device, bit-identical to the reference's sequential
-    loops.  It owns a copy of the values: a value change of A reaches ldiv only through update()."""
-    KIND = ESP_PRECON_ILUAM
+class _ILUAMFactors:
+    """factor() and levels() of the kinds that hold an ILUAM factorization: ILUAMPreconditioner (of A itself), BlockPreconditioner
+    and ILUKPreconditioner (of their matrix B: the inner preconditioner answers)"""
+
+    def _factored(self):
+        """the handle of the matrix the factorization belongs to"""
+        self.A.flush()
+        return self.A._d.h
 
     def factor(self):
-        """the factorization's values in CSC position order (the reference's ILU.nzval): unit-lower L scaled below the
-        diagonal, U on and above it"""
+        """the factorization's values in the position order of the factored CSC (ILUAM: A's, the reference's ILU.nzval; Block and
+        ILU(k): the inner ILUAM's, B's): unit-lower L scaled below the diagonal, U on and above it"""
         p = self._live()
-        out = np.empty(self.A.nnz(), np.float64)
+        nnz = C.c_int64()
+        self._ck(self.A._d.lib.esp_nnz(self._factored(), C.byref(nnz)))
+        out = np.empty(nnz.value, np.float64)
         self._ck(self.A._d.lib.esp_precon_get_factor(p, _vp(out), 0))
         return out
 
     def levels(self):
-        """level counts of the three schedules: (factorization columns, forward rows, backward rows)"""
+        """level counts of the three schedules: (factorization columns, forward rows, backward rows); Block: the inner
+        preconditioner's (ILUAM: the maximum over the blocks, not their sum)"""
         out = (C.c_int64 * 3)()
         self._ck(self.A._d.lib.esp_precon_levels(self._live(), out))
         return tuple(int(x) for x in out)
 
 
-class BlockPreconditioner(_PointPreconditioner):
+class ILUAMPreconditioner(_ILUAMFactors, _PointPreconditioner):
+    """ILUAMPreconditioner(A) (src/experimental/ExtendableSparseMatrixParallel/iluam.jl): a real ILU(0) on A's pattern, the
+    factorization and both triangular solves level by level on the device, bit-identical to the reference's sequential
+    loops.  It owns a copy of the values: a value change of A reaches ldiv only through update()."""
+    KIND = ESP_PRECON_ILUAM
+
+
+class BlockPreconditioner(_ILUAMFactors, _PointPreconditioner):
     """BlockPreconditioner(A; partitioning, factorization) (src/factorizations/blockpreconditioner.jl, docs/src/iter.md):
     ldiv! is u[part] = factorization(A[part, part]) \\ v[part] for every partition, bit-identical to the reference's per-block
     loops (include/esparse_hip.h, esp_precon_block_create).
@@ -186,31 +234,13 @@ class BlockPreconditioner(_PointPreconditioner):
 
     def block_matrix(self):
         """the block matrix B as host CSC arrays (colptr, rowval, nzval), Julia layout -- for tests and inspection"""
-        b, _ = self._block()
-        lib = self.A._d.lib
-        nnz = C.c_int64()
-        self._ck(lib.esp_nnz(b, C.byref(nnz)))
-        cp, rv, nz = np.empty(self.A.n + 1, np.int64), np.empty(nnz.value, np.int64), np.empty(nnz.value, np.float64)
-        self._ck(lib.esp_get_csc(b, _vp(cp), _vp(rv), _vp(nz)))
-        return cp, rv, nz
+        return self._host_csc(self._factored(), self.A.n)
 
-    def factor(self):
-        """the inner ILUAM factorization's values in B's position order"""
-        b, _ = self._block()
-        nnz = C.c_int64()
-        self._ck(self.A._d.lib.esp_nnz(b, C.byref(nnz)))
-        out = np.empty(nnz.value, np.float64)
-        self._ck(self.A._d.lib.esp_precon_get_factor(self._live(), _vp(out), 0))
-        return out
-
-    def levels(self):
-        """the inner preconditioner's level counts (ILUAM: the maximum over the blocks, not their sum)"""
-        out = (C.c_int64 * 3)()
-        self._ck(self.A._d.lib.esp_precon_levels(self._live(), out))
-        return tuple(int(x) for x in out)
+    def _factored(self):
+        return self._block()[0]
 
 
-class ILUKPreconditioner(_PointPreconditioner):
+class ILUKPreconditioner(_ILUAMFactors, _PointPreconditioner):
     """ILUKPreconditioner(A, k=1): the level-of-fill ILU(k) (include/esparse_hip.h, esp_precon_iluk_create).  The filled matrix B
     holds every position of level <= k -- A's entries at level 0, +0.0 where elimination creates an entry -- and the
     preconditioner is ILUAMPreconditioner of B: k = 0 is ILUAMPreconditioner(A), a larger k trades memory for fewer iterations,
@@ -242,31 +272,18 @@ class ILUKPreconditioner(_PointPreconditioner):
 
     def fill_matrix(self):
         """the filled matrix B as host CSC arrays (colptr, rowval, nzval), Julia layout -- for tests and inspection"""
+        return self._host_csc(self._factored(), self.A.n)
+
+    def _factored(self):
         b = C.c_void_p()
-        lib = self.A._d.lib
-        self._ck(lib.esp_precon_iluk_matrix(self._live(), C.byref(b)))
-        nnz = self.stats()["nnz"]
-        cp, rv, nz = np.empty(self.A.n + 1, np.int64), np.empty(nnz, np.int64), np.empty(nnz, np.float64)
-        self._ck(lib.esp_get_csc(b, _vp(cp), _vp(rv), _vp(nz)))
-        return cp, rv, nz
+        self._ck(self.A._d.lib.esp_precon_iluk_matrix(self._live(), C.byref(b)))
+        return b
 
     def fill_levels(self):
         """the level of every stored entry of B (int32, B's position order): 0 for A's entries"""
         out = np.empty(self.stats()["nnz"], np.int32)
         self._ck(self.A._d.lib.esp_precon_iluk_levels(self._live(), _vp(out), 0))
         return out
-
-    def factor(self):
-        """the inner ILUAM factorization's values in B's position order"""
-        out = np.empty(self.stats()["nnz"], np.float64)
-        self._ck(self.A._d.lib.esp_precon_get_factor(self._live(), _vp(out), 0))
-        return out
-
-    def levels(self):
-        """the inner ILUAM's level counts: (factorization columns, forward rows, backward rows)"""
-        out = (C.c_int64 * 3)()
-        self._ck(self.A._d.lib.esp_precon_levels(self._live(), out))
-        return tuple(int(x) for x in out)
 
 
 class AMGPreconditioner(_PointPreconditioner):
@@ -311,14 +328,6 @@ class AMGPreconditioner(_PointPreconditioner):
         self._ck(self.A._d.lib.esp_precon_amg_levels(self._live(), C.byref(k)))
         return k.value
 
-    def _csc(self, h, n):
-        lib = self.A._d.lib
-        nnz = C.c_int64()
-        self._ck(lib.esp_nnz(h, C.byref(nnz)))
-        cp, rv, nz = np.empty(n + 1, np.int64), np.empty(nnz.value, np.int64), np.empty(nnz.value, np.float64)
-        self._ck(lib.esp_get_csc(h, _vp(cp), _vp(rv), _vp(nz)))
-        return cp, rv, nz
-
     def level(self, l):
         """level l as a dict: n, rho, rounds (the Luby rounds of its aggregation, 0 where none ran), A and P as host CSC arrays
         (colptr, rowval, nzval), Julia layout; P is None on the coarsest level -- for tests and inspection"""
@@ -326,11 +335,11 @@ class AMGPreconditioner(_PointPreconditioner):
         n, rho, rounds = C.c_int64(), C.c_double(), C.c_int32()
         self._ck(self.A._d.lib.esp_precon_amg_level(self._live(), int(l), C.byref(a), C.byref(pr), C.byref(n), C.byref(rho),
                                                     C.byref(rounds)))
-        out = {"n": n.value, "rho": rho.value, "rounds": rounds.value, "A": self._csc(a, n.value), "P": None}
+        out = {"n": n.value, "rho": rho.value, "rounds": rounds.value, "A": self._host_csc(a, n.value), "P": None}
         if pr.value:
             m, nc = C.c_int64(), C.c_int64()
             self._ck(self.A._d.lib.esp_size(pr, C.byref(m), C.byref(nc)))
-            out["P"] = self._csc(pr, nc.value)
+            out["P"] = self._host_csc(pr, nc.value)
         return out
 
     def aggregates(self, l):
@@ -392,24 +401,8 @@ def simple(A, b, u=None, Pl=None, maxiter=100, reltol=math.sqrt(np.finfo(np.floa
         raise ValueError("maxiter < 0")
     hist = np.empty(maxiter + 1, np.float64)
     its = C.c_int64()
-    if _is_cuda(b):
-        import torch
-        _check_cuda(b, n)
-        if u is None:
-            u = torch.zeros(n, dtype=torch.float64, device=b.device)
-        _check_cuda(u, n)
-        torch.cuda.current_stream(b.device).synchronize()
-        d.ck(d.lib.esp_simple(d.h, p, C.c_void_p(b.data_ptr()), C.c_void_p(u.data_ptr()), 1, maxiter, float(abstol),
-                              float(reltol), _vp(hist), C.byref(its)))
-    else:
-        bb = np.ascontiguousarray(b, np.float64)
-        if bb.shape != (n,):
-            raise ValueError("DimensionMismatch")
-        if u is None:
-            u = np.zeros(n, np.float64)
-        if not (isinstance(u, np.ndarray) and u.dtype == np.float64 and u.shape == (n,) and u.flags.c_contiguous):
-            raise ValueError("u must be a contiguous float64 array of length n")
-        d.ck(d.lib.esp_simple(d.h, p, _vp(bb), _vp(u), 0, maxiter, float(abstol), float(reltol), _vp(hist), C.byref(its)))
+    pb, pu, _, dev, u = _handover(n, b, u, "u")
+    d.ck(d.lib.esp_simple(d.h, p, pb, pu, dev, maxiter, float(abstol), float(reltol), _vp(hist), C.byref(its)))
     if log:
         return u, {"resnorm": hist[:its.value + 1].copy()}
     return u
@@ -420,10 +413,7 @@ def cg(A, b, Pl=None, x=None, abstol=0.0, reltol=math.sqrt(np.finfo(np.float64).
     conjugate gradients until norm(r) <= max(reltol*norm(r0), abstol) or maxiter (None: n) iterations.  x = None starts from zeros
     (cg); a given x is updated in place (cg!).  Pl: a preconditioner of A, or None (Identity).
     log=True returns (x, {"resnorm": the norm after every iteration, "r0": the initial one, "iters": k, "isconverged": bool})."""
-    if not isinstance(A, ExtendableSparseMatrix):
-        raise TypeError("cg(A, b): A must be an ExtendableSparseMatrix")
-    if Pl is not None and (not isinstance(Pl, _PointPreconditioner) or Pl.A is not A):
-        raise ValueError("cg: Pl must be a preconditioner of A, or None")
+    _check_solver("cg", A, Pl)
     p = Pl._live() if Pl is not None else None
     A.flush()
     d = A._d
@@ -435,25 +425,8 @@ def cg(A, b, Pl=None, x=None, abstol=0.0, reltol=math.sqrt(np.finfo(np.float64).
     its = C.c_int64()
     conv = C.c_int32()
     zero = 1 if x is None else 0
-    if _is_cuda(b):
-        import torch
-        _check_cuda(b, n)
-        if x is None:
-            x = torch.zeros(n, dtype=torch.float64, device=b.device)
-        _check_cuda(x, n)
-        torch.cuda.current_stream(b.device).synchronize()   # the library runs on its own stream
-        d.ck(d.lib.esp_cg(d.h, p, C.c_void_p(b.data_ptr()), C.c_void_p(x.data_ptr()), 1, zero, maxiter, float(abstol),
-                          float(reltol), _vp(hist), C.byref(its), C.byref(conv)))
-    else:
-        bb = np.ascontiguousarray(b, np.float64)
-        if bb.shape != (n,):
-            raise ValueError("DimensionMismatch")
-        if x is None:
-            x = np.zeros(n, np.float64)
-        if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.shape == (n,) and x.flags.c_contiguous):
-            raise ValueError("x must be a contiguous float64 array of length n")
-        d.ck(d.lib.esp_cg(d.h, p, _vp(bb), _vp(x), 0, zero, maxiter, float(abstol), float(reltol), _vp(hist), C.byref(its),
-                          C.byref(conv)))
+    pb, px, _, dev, x = _handover(n, b, x, "x")
+    d.ck(d.lib.esp_cg(d.h, p, pb, px, dev, zero, maxiter, float(abstol), float(reltol), _vp(hist), C.byref(its), C.byref(conv)))
     if log:
         k = its.value
         return x, {"resnorm": hist[1:k + 1].copy(), "r0": float(hist[0]), "iters": k, "isconverged": bool(conv.value)}
@@ -469,10 +442,7 @@ def bicgstabl(A, b, l=2, Pl=None, x=None, abstol=0.0, reltol=math.sqrt(np.finfo(
     or None (Identity).  r_shadow: the shadow residual (None: the initial preconditioned residual; the package draws rand(n)).
     log=True returns (x, {"resnorm": the norm after every outer iteration, "r0": the initial one, "iters": outer iterations,
     "mvps": matrix-vector products, "isconverged": bool})."""
-    if not isinstance(A, ExtendableSparseMatrix):
-        raise TypeError("bicgstabl(A, b): A must be an ExtendableSparseMatrix")
-    if Pl is not None and (not isinstance(Pl, _PointPreconditioner) or Pl.A is not A):
-        raise ValueError("bicgstabl: Pl must be a preconditioner of A, or None")
+    _check_solver("bicgstabl", A, Pl)
     p = Pl._live() if Pl is not None else None
     A.flush()
     d = A._d
@@ -485,40 +455,9 @@ def bicgstabl(A, b, l=2, Pl=None, x=None, abstol=0.0, reltol=math.sqrt(np.finfo(
     its, mvs = C.c_int64(), C.c_int64()
     conv = C.c_int32()
     zero = 1 if x is None else 0
-    if _is_cuda(b):
-        import torch
-        _check_cuda(b, n)
-        if x is None:
-            x = torch.zeros(n, dtype=torch.float64, device=b.device)
-        _check_cuda(x, n)
-        rs = None
-        if r_shadow is not None:
-            if not _is_cuda(r_shadow):
-                raise ValueError("r_shadow must live where b does")
-            if r_shadow.numel() != n:
-                raise ValueError("DimensionMismatch")
-            _check_cuda(r_shadow, n)
-            rs = C.c_void_p(r_shadow.data_ptr())
-        torch.cuda.current_stream(b.device).synchronize()   # the library runs on its own stream
-        d.ck(d.lib.esp_bicgstabl(d.h, p, l, C.c_void_p(b.data_ptr()), C.c_void_p(x.data_ptr()), rs, 1, zero, max_mv_products,
-                                 float(abstol), float(reltol), _vp(hist), C.byref(its), C.byref(mvs), C.byref(conv)))
-    else:
-        bb = np.ascontiguousarray(b, np.float64)
-        if bb.shape != (n,):
-            raise ValueError("DimensionMismatch")
-        if x is None:
-            x = np.zeros(n, np.float64)
-        if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.shape == (n,) and x.flags.c_contiguous):
-            raise ValueError("x must be a contiguous float64 array of length n")
-        rs = None
-        if r_shadow is not None:
-            if _is_cuda(r_shadow):
-                raise ValueError("r_shadow must live where b does")
-            rs = np.ascontiguousarray(r_shadow, np.float64)
-            if rs.shape != (n,):
-                raise ValueError("DimensionMismatch")
-        d.ck(d.lib.esp_bicgstabl(d.h, p, l, _vp(bb), _vp(x), _vp(rs) if rs is not None else None, 0, zero, max_mv_products,
-                                 float(abstol), float(reltol), _vp(hist), C.byref(its), C.byref(mvs), C.byref(conv)))
+    pb, px, prs, dev, x = _handover(n, b, x, "x", r_shadow=r_shadow)
+    d.ck(d.lib.esp_bicgstabl(d.h, p, l, pb, px, prs, dev, zero, max_mv_products, float(abstol), float(reltol), _vp(hist),
+                             C.byref(its), C.byref(mvs), C.byref(conv)))
     if log:
         k = its.value
         return x, {"resnorm": hist[1:k + 1].copy(), "r0": float(hist[0]), "iters": k, "mvps": mvs.value,
@@ -539,10 +478,7 @@ def gmres(A, b, Pl=None, x=None, restart=None, maxiter=None, abstol=0.0, reltol=
     preconditioner of A, or None (Identity).
     log=True returns (x, {"resnorm": the norm after every iteration, "r0": the initial one, "iters": iterations, "mvps":
     matrix-vector products, "reorth": DGKS correction passes, "isconverged": bool})."""
-    if not isinstance(A, ExtendableSparseMatrix):
-        raise TypeError("gmres(A, b): A must be an ExtendableSparseMatrix")
-    if Pl is not None and (not isinstance(Pl, _PointPreconditioner) or Pl.A is not A):
-        raise ValueError("gmres: Pl must be a preconditioner of A, or None")
+    _check_solver("gmres", A, Pl)
     if orth_meth not in _ORTH:
         raise ValueError("gmres: orth_meth = %r (one of 'mgs', 'cgs', 'dgks')" % (orth_meth,))
     p = Pl._live() if Pl is not None else None
@@ -557,25 +493,9 @@ def gmres(A, b, Pl=None, x=None, restart=None, maxiter=None, abstol=0.0, reltol=
     its, mvs, reorth = C.c_int64(), C.c_int64(), C.c_int64()
     conv = C.c_int32()
     zero = 1 if x is None else 0
-    if _is_cuda(b):
-        import torch
-        _check_cuda(b, n)
-        if x is None:
-            x = torch.zeros(n, dtype=torch.float64, device=b.device)
-        _check_cuda(x, n)
-        torch.cuda.current_stream(b.device).synchronize()   # the library runs on its own stream
-        d.ck(d.lib.esp_gmres(d.h, p, C.c_void_p(b.data_ptr()), C.c_void_p(x.data_ptr()), 1, zero, restart, _ORTH[orth_meth], maxiter,
-                             float(abstol), float(reltol), _vp(hist), C.byref(its), C.byref(mvs), C.byref(reorth), C.byref(conv)))
-    else:
-        bb = np.ascontiguousarray(b, np.float64)
-        if bb.shape != (n,):
-            raise ValueError("DimensionMismatch")
-        if x is None:
-            x = np.zeros(n, np.float64)
-        if not (isinstance(x, np.ndarray) and x.dtype == np.float64 and x.shape == (n,) and x.flags.c_contiguous):
-            raise ValueError("x must be a contiguous float64 array of length n")
-        d.ck(d.lib.esp_gmres(d.h, p, _vp(bb), _vp(x), 0, zero, restart, _ORTH[orth_meth], maxiter, float(abstol), float(reltol),
-                             _vp(hist), C.byref(its), C.byref(mvs), C.byref(reorth), C.byref(conv)))
+    pb, px, _, dev, x = _handover(n, b, x, "x")
+    d.ck(d.lib.esp_gmres(d.h, p, pb, px, dev, zero, restart, _ORTH[orth_meth], maxiter, float(abstol), float(reltol), _vp(hist),
+                         C.byref(its), C.byref(mvs), C.byref(reorth), C.byref(conv)))
     if log:
         k = its.value
         return x, {"resnorm": hist[1:k + 1].copy(), "r0": float(hist[0]), "iters": k, "mvps": mvs.value, "reorth": reorth.value,
