@@ -18,6 +18,7 @@ ESP_OP_ADD, ESP_OP_SUB = 0, 1
 ESP_FLUSH_ROUTED, ESP_FLUSH_PLUS = 0, 1
 ESP_PRECON_JACOBI, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_BLOCK, ESP_PRECON_AMG = 0, 1, 2, 3, 4
 ESP_PRECON_ILUK = 5
+ESP_PRECON_COLORED = 6
 ESP_ILUK_WAVE_VISITS, ESP_ILUK_VISIT_MAX = 512, 8192
 ESP_AMG_DENSE_MAX = 512
 ESP_AMG_COARSEN_SA, ESP_AMG_COARSEN_RS = 0, 1
@@ -122,6 +123,12 @@ SIGNATURES = {
     "esp_precon_iluk_matrix": (i32, [vp, P(vp)]),
     "esp_precon_iluk_levels": (i32, [vp, vp, i32]),
     "esp_precon_iluk_stats": (i32, [vp, P(i64)]),
+    "esp_graph_coloring": (i32, [vp, P(i64), vp, i32]),
+    "esp_precon_colored_create": (i32, [vp, i32, P(vp)]),
+    "esp_precon_colored_info": (i32, [vp, P(i64)]),
+    "esp_precon_colored_colors": (i32, [vp, vp, i32]),
+    "esp_precon_colored_perm": (i32, [vp, vp, i32]),
+    "esp_precon_colored_matrix": (i32, [vp, P(vp)]),
     "esp_simple": (i32, [vp, vp, vp, vp, i32, i64, f64, f64, vp, P(i64)]),
     "esp_cg": (i32, [vp, vp, vp, vp, i32, i32, i64, f64, f64, vp, P(i64), P(i32)]),
     "esp_bicgstabl": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i64, f64, f64, vp, P(i64), P(i64), P(i32)]),

@@ -392,7 +392,7 @@ void iluam_release(esp_precon *p) {
 extern "C" int32_t esp_precon_get_factor(esp_precon *p, double *nzval, int32_t on_device) {
     if (!p || !nzval) return ESP_ERR_INVALID;
     esp_handle *h = p->h;
-    if (p->kind == ESP_PRECON_BLOCK || p->kind == ESP_PRECON_ILUK) {  // the inner factorization: nnz(B) values in B's position order
+    if (block_built(p) || p->kind == ESP_PRECON_ILUK) {  // the inner factorization: nnz(B) values in B's position order
         if (h->pattern_version != p->pattern_version || h->nnz != p->nnz)
             FAIL(h, ESP_ERR_STATE, "esp_precon_get_factor: the matrix pattern changed since the preconditioner's last update!");
         CK(block_follow_stream(p));
@@ -416,7 +416,7 @@ extern "C" int32_t esp_precon_get_factor(esp_precon *p, double *nzval, int32_t o
 
 extern "C" int32_t esp_precon_levels(esp_precon *p, int64_t out[3]) {
     if (!p || !out) return ESP_ERR_INVALID;
-    if ((p->kind == ESP_PRECON_BLOCK || p->kind == ESP_PRECON_ILUK) && p->inner) p = p->inner;
+    if ((block_built(p) || p->kind == ESP_PRECON_ILUK) && p->inner) p = p->inner;
     for (int k = 0; k < 3; k++) out[k] = p->kind == ESP_PRECON_ILUAM ? p->sched[k].levels : 0;
     return ESP_OK;
 }

@@ -10,6 +10,8 @@
 //   precon.hip     the point preconditioners' update! / ldiv! (esp_precon_*) and simple! (esp_simple) on the device CSC
 //   iluam.hip      ILUAMPreconditioner: level analysis, level-scheduled ILU(0) factorization and triangular solves
 //   block.hip      BlockPreconditioner: the masked block matrix B of a partitioning (identity / permuted path) and the object around it
+//   color.hip      the multicolour ordering: graph colouring by rounds over a fixed hash (esp_graph_coloring), the permutation by
+//                  (colour, index), ColoredPreconditioner = block.hip's permuted path over that one partition
 //   iluk.hip       ILUKPreconditioner: the level-of-fill pattern by one bounded search per column (wave / workgroup form), the filled
 //                  matrix B in an internal handle, ILUAM on it
 //   amg.hip        AMGPreconditioner: smoothed aggregation (MIS(2) aggregates by Luby rounds, the level hierarchy from the algebra
@@ -590,12 +592,20 @@ struct esp_precon {
     esp_handle *iluk_th = nullptr;  // transpose(A), the graph of the search for the upper part
     DevBuf iluk_lev;                // i32 nnz(B): the level of every entry of B
     i64 iluk_stats[4] = {0, 0, 0, 0};  // nnz(B), largest stored level, columns redone by the workgroup search (L, U)
+    // ColoredPreconditioner (kind ESP_PRECON_COLORED, color.hip): h is A; the multicolour ordering c of A's graph -- the vertices
+    // sorted by (colour, index) -- is the one partition of a permuted-path block preconditioner: blk_new = the inverse of c, blk_part
+    // = 0 everywhere, B = A[c,c] in bh, inner (ILU0 or ILUAM) bound to bh, blk_path = 1 (0 only for n == 0).  A pattern change of A
+    // re-colours before B is rebuilt.
+    DevBuf col_color, col_perm;      // u32 n each: the colour of every vertex (1-based, as the rounds number them), c
+    std::vector<i64> col_ptr;        // ncolors + 1: colour r holds c[col_ptr[r] .. col_ptr[r + 1])
 };
+// the kinds that block.hip's builder, update! and ldiv! serve
+static inline bool block_built(const esp_precon *p) { return p->kind == ESP_PRECON_BLOCK || p->kind == ESP_PRECON_COLORED; }
 // the identity-path block preconditioner and the ILU(k) preconditioner stand for their inner one in the solvers' fused branches
 static inline esp_precon *fused_precon(esp_precon *p) {
-    return p && ((p->kind == ESP_PRECON_BLOCK && p->blk_path == 0) || p->kind == ESP_PRECON_ILUK) ? p->inner : p;
+    return p && ((block_built(p) && p->blk_path == 0) || p->kind == ESP_PRECON_ILUK) ? p->inner : p;
 }
-static inline bool block_permuted(const esp_precon *p) { return p && p->kind == ESP_PRECON_BLOCK && p->blk_path != 0; }
+static inline bool block_permuted(const esp_precon *p) { return p && block_built(p) && p->blk_path != 0; }
 
 #pragma GCC visibility push(hidden)
 // precon.hip: smallest column without a stored diagonal -> ESP_ERR_INVALID (ILU0 / ILUAM), invdiag / xdiag into p->diag;
@@ -624,6 +634,10 @@ void block_release(esp_precon *p);
 // update), release of the transpose and the level array (B, the inner preconditioner and src are block_release's)
 int32_t iluk_update(esp_precon *p);
 void iluk_release(esp_precon *p);
+// color.hip: update! (after a pattern change the colouring and the maps anew, then block_update; else block_update's value gather),
+// release of the colour arrays (B, the inner preconditioner and the maps are block_release's)
+int32_t color_update(esp_precon *p);
+void color_release(esp_precon *p);
 // amg.hip: update! (the whole hierarchy is rebuilt every time), the V-cycle on device vectors (u may be v; sub: u[i] = u[i] - x[i],
 // simple!'s step; launches on the handle's stream only), release of the hierarchy
 int32_t amg_update(esp_precon *p);

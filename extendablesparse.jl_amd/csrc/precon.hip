@@ -299,7 +299,7 @@ int32_t precon_ready(esp_precon *p, const char *what) {
     if (h->pattern_version != p->pattern_version || h->nnz != p->nnz)
         FAIL(h, ESP_ERR_STATE, "%s: the matrix pattern changed since the preconditioner's last update! (update! first)", what);
     if (p->kind == ESP_PRECON_ILU0 && p->values_version != h->values_version) CK(split_scale(p, false));  // current nzval, stored xdiag
-    if (p->kind == ESP_PRECON_BLOCK || p->kind == ESP_PRECON_ILUK) CK(block_follow_stream(p));  // (B holds copies: the values as of the last update!, ILU0 included)
+    if (block_built(p) || p->kind == ESP_PRECON_ILUK) CK(block_follow_stream(p));  // (B holds copies: the values as of the last update!, ILU0 included)
     return ESP_OK;
 }
 
@@ -308,7 +308,7 @@ int32_t ldiv_launch(esp_precon *p, const double *v, double *u) {
     esp_handle *h = p->h;
     const i64 n = p->n;
     if (n == 0) return ESP_OK;
-    if (p->kind == ESP_PRECON_BLOCK) return block_ldiv_launch(p, v, u, false);
+    if (block_built(p)) return block_ldiv_launch(p, v, u, false);
     if (p->kind == ESP_PRECON_ILUK) return ldiv_launch(p->inner, v, u);  // ILUAM of B on the caller's vectors
     if (p->kind == ESP_PRECON_ILUAM) return iluam_solve(p, v, u, false);
     if (p->kind == ESP_PRECON_AMG) return amg_solve(p, v, u, false);
@@ -361,6 +361,7 @@ extern "C" int32_t esp_precon_update(esp_precon *p) {
     if (p->kind == ESP_PRECON_BLOCK) return block_update(p);  // B and the inner preconditioner (block.hip)
     if (p->kind == ESP_PRECON_AMG) return amg_update(p);      // the whole hierarchy (amg.hip)
     if (p->kind == ESP_PRECON_ILUK) return iluk_update(p);    // the filled matrix and the inner ILUAM (iluk.hip)
+    if (p->kind == ESP_PRECON_COLORED) return color_update(p);  // the colouring, A[c,c] and the inner preconditioner (color.hip)
     esp_handle *h = p->h;
     CK(check_handle(h, "esp_precon_update"));
     p->n = h->n;
@@ -410,6 +411,7 @@ extern "C" int32_t esp_precon_destroy(esp_precon *p) {
     (void)hipStreamSynchronize(h->stream);
     block_release(p);
     iluk_release(p);
+    color_release(p);
     for (DevBuf *b : {&p->diag, &p->lptr, &p->uptr, &p->lcol, &p->ucol, &p->lpos, &p->upos, &p->dpos, &p->lval, &p->uval, &p->u1, &p->res,
                       &p->partial, &p->scanws, &p->hv, &p->hu})
         release(*b);

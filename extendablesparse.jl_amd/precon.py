@@ -21,13 +21,16 @@ tests/amg_model.c.  RS_AMGPreconditioner(A) is the same V-cycle over a hierarchy
 strength, a PMIS splitting, direct interpolation (esp_precon_rsamg_create) -- bit-identical to tests/rsamg_model.c.
 ILUKPreconditioner(A, k) is the level-of-fill ILU(k): the filled pattern found on the device by one bounded search per column, then
 ILUAMPreconditioner of the filled matrix (esp_precon_iluk_create) -- bit-identical to tests/iluam_model.c on the B of tests/iluk_model.c.
+ColoredPreconditioner(A, factorization) colours A's graph on the device (rounds over a fixed hash, esp_graph_coloring), reorders A by
+(colour, index) and runs ILU0 or ILUAM on A[c,c]: at most ncolors levels per schedule.  ParallelILU0Preconditioner(A) is the ILU0 form,
+the reference's src/factorizations/parallel_ilu0.jl acting in A's numbering; graphcol, reordermatrix and reorderlinsys are its helpers.
 """
 import ctypes as C
 import math
 
 import numpy as np
 
-from ._lib import ESP_ORTH_CGS, ESP_ORTH_DGKS, ESP_ORTH_MGS, ESP_PRECON_AMG, ESP_PRECON_BLOCK, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_ILUK, ESP_PRECON_JACOBI
+from ._lib import ESP_ORTH_CGS, ESP_ORTH_DGKS, ESP_ORTH_MGS, ESP_PRECON_AMG, ESP_PRECON_BLOCK, ESP_PRECON_COLORED, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_ILUK, ESP_PRECON_JACOBI
 from .matrix import ExtendableSparseMatrix, _vp
 
 
@@ -153,8 +156,8 @@ class ILU0Preconditioner(_PointPreconditioner):
 
 
 class _ILUAMFactors:
-    """factor() and levels() of the kinds that hold an ILUAM factorization: ILUAMPreconditioner (of A itself), BlockPreconditioner
-    and ILUKPreconditioner (of their matrix B: the inner preconditioner answers)"""
+    """factor() and levels() of the kinds that hold an ILUAM factorization: ILUAMPreconditioner (of A itself), BlockPreconditioner,
+    ILUKPreconditioner and ColoredPreconditioner (of their matrix B: the inner preconditioner answers)"""
 
     def _factored(self):
         """the handle of the matrix the factorization belongs to"""
@@ -162,8 +165,8 @@ class _ILUAMFactors:
         return self.A._d.h
 
     def factor(self):
-        """the factorization's values in the position order of the factored CSC (ILUAM: A's, the reference's ILU.nzval; Block and
-        ILU(k): the inner ILUAM's, B's): unit-lower L scaled below the diagonal, U on and above it"""
+        """the factorization's values in the position order of the factored CSC (ILUAM: A's, the reference's ILU.nzval; Block,
+        ILU(k) and Colored: the inner ILUAM's, B's): unit-lower L scaled below the diagonal, U on and above it"""
         p = self._live()
         nnz = C.c_int64()
         self._ck(self.A._d.lib.esp_nnz(self._factored(), C.byref(nnz)))
@@ -284,6 +287,129 @@ class ILUKPreconditioner(_ILUAMFactors, _PointPreconditioner):
         out = np.empty(self.stats()["nnz"], np.int32)
         self._ck(self.A._d.lib.esp_precon_iluk_levels(self._live(), _vp(out), 0))
         return out
+
+
+class ColoredPreconditioner(_ILUAMFactors, _PointPreconditioner):
+    """ColoredPreconditioner(A, factorization=ILUAMPreconditioner): the multicolour ordering (include/esparse_hip.h,
+    esp_precon_colored_create).  A's graph -- i and j are neighbours when A[i,j] or A[j,i] is stored -- is coloured on the device by
+    rounds over a fixed hash, c holds the unknowns sorted by (colour, index), and ldiv! is u[c] = factorization(A[c,c]) \\ v[c]: one
+    gather, the inner kind's launches, one scatter.  No two unknowns of one colour are coupled, so ILUAM's schedules on A[c,c] have at
+    most ncolors levels.  factorization: ILU0Preconditioner or ILUAMPreconditioner.  It acts in A's numbering (a drop-in Pl for A;
+    the reference's ParallelILU0Preconditioner wants the reordered system).  A[c,c] holds copies: a value change of A reaches ldiv
+    only through update(), which keeps the colouring and the analysis when only values changed and re-colours after a pattern change."""
+    KIND = ESP_PRECON_COLORED
+
+    def __init__(self, A, factorization=None):
+        if not isinstance(A, ExtendableSparseMatrix):
+            raise TypeError("%s(A, ...): A must be an ExtendableSparseMatrix" % type(self).__name__)
+        if factorization is None:
+            factorization = ILUAMPreconditioner
+        if not (isinstance(factorization, type) and issubclass(factorization, _PointPreconditioner)
+                and factorization.KIND in (ESP_PRECON_ILU0, ESP_PRECON_ILUAM)):
+            raise TypeError("ColoredPreconditioner: factorization must be ILU0Preconditioner or ILUAMPreconditioner")
+        self.A = A
+        self._p = None
+        self.factorization = factorization
+        A.flush()
+        d = A._d
+        p = C.c_void_p()
+        d.ck(d.lib.esp_precon_colored_create(d.h, factorization.KIND, C.byref(p)))
+        self._p = p
+
+    def _info(self):
+        out = (C.c_int64 * 2)()
+        self._ck(self.A._d.lib.esp_precon_colored_info(self._live(), out))
+        return int(out[0]), int(out[1])
+
+    @property
+    def ncolors(self):
+        """the number of colours (= the rounds of the colouring)"""
+        return self._info()[0]
+
+    def colors(self):
+        """the colour of every unknown: int64, 0-based"""
+        out = np.empty(self.A.n, np.int64)
+        if self.A.n:
+            self._ck(self.A._d.lib.esp_precon_colored_colors(self._live(), _vp(out), 0))
+        return out
+
+    def permutation(self):
+        """c, the unknowns sorted by (colour, index), in the index base of A[i, j] (1-based): flatten(coloring)"""
+        out = np.empty(self.A.n, np.int64)
+        if self.A.n:
+            self._ck(self.A._d.lib.esp_precon_colored_perm(self._live(), _vp(out), 0))
+        return out + 1
+
+    def coloring(self):
+        """the colours as a list of 1-based index arrays, each ascending: the shape of the reference's `coloring`"""
+        col, c = self.colors(), self.permutation()
+        cuts = np.cumsum(np.bincount(col, minlength=self.ncolors))[:-1] if len(col) else []
+        return [np.ascontiguousarray(a) for a in np.split(c, cuts)] if len(col) else []
+
+    def reordered_matrix(self):
+        """A[c,c] as host CSC arrays (colptr, rowval, nzval), Julia layout -- for tests and inspection"""
+        return self._host_csc(self._factored(), self.A.n)
+
+    def _factored(self):
+        b = C.c_void_p()
+        self._ck(self.A._d.lib.esp_precon_colored_matrix(self._live(), C.byref(b)))
+        return b
+
+
+class ParallelILU0Preconditioner(ColoredPreconditioner):
+    """ParallelILU0Preconditioner(A) (src/factorizations/parallel_ilu0.jl): ColoredPreconditioner(A, ILU0Preconditioner)"""
+
+    def __init__(self, A):
+        super().__init__(A, ILU0Preconditioner)
+
+
+def graphcol(A):
+    """graphcol(A) (parallel_ilu0.jl): the multicolouring of A's graph as a list of 1-based index arrays, found on the device by
+    esp_graph_coloring's rule (rounds over a fixed hash in place of the reference's rand)"""
+    if not isinstance(A, ExtendableSparseMatrix):
+        raise TypeError("graphcol(A): A must be an ExtendableSparseMatrix")
+    A.flush()
+    d = A._d
+    nc = C.c_int64()
+    col = np.empty(A.n, np.int64)
+    d.ck(d.lib.esp_graph_coloring(d.h, C.byref(nc), _vp(col) if A.n else None, 0))
+    return [np.flatnonzero(col == r).astype(np.int64) + 1 for r in range(nc.value)]
+
+
+def _flatten(coloring, n):
+    c = np.concatenate([np.asarray(a, np.int64).reshape(-1) for a in coloring]) - 1 if len(coloring) else np.empty(0, np.int64)
+    if len(c) != n or not np.array_equal(np.sort(c), np.arange(n)):
+        raise ValueError("coloring must hold every index 1..n exactly once")
+    return c
+
+
+def reordermatrix(A, coloring):
+    """reordermatrix(A, coloring) (parallel_ilu0.jl): A[c,c] with c = flatten(coloring) as a new ExtendableSparseMatrix, every column
+    sorted by row, the values bitwise A's.  A host-side helper, no hot path."""
+    if not isinstance(A, ExtendableSparseMatrix) or A.m != A.n:
+        raise TypeError("reordermatrix(A, coloring): A must be a square ExtendableSparseMatrix")
+    from .matrix import SparseMatrixCSC
+    n = A.n
+    c = _flatten(coloring, n)
+    cp, rv, nz = (np.asarray(a) for a in A.sparse().arrays())
+    new = np.empty(n, np.int64)
+    new[c] = np.arange(n)
+    lens = np.diff(cp)[c]
+    ncp = np.ones(n + 1, np.int64)
+    np.cumsum(lens, out=ncp[1:])
+    ncp[1:] += 1
+    src = np.concatenate([np.arange(cp[j] - 1, cp[j + 1] - 1) for j in c]) if n else np.empty(0, np.int64)
+    src = src.astype(np.int64)
+    rows = new[rv[src] - 1]
+    colof = np.repeat(np.arange(n), lens)
+    order = np.lexsort((rows, colof))
+    return ExtendableSparseMatrix(SparseMatrixCSC(n, n, ncp, rows[order] + 1, np.asarray(nz, np.float64)[src[order]]))
+
+
+def reorderlinsys(A, b, coloring):
+    """reorderlinsys(A, b, coloring) (parallel_ilu0.jl): (A[c,c], b[c]) with c = flatten(coloring)"""
+    b = np.asarray(b, np.float64)
+    return reordermatrix(A, coloring), np.ascontiguousarray(b[_flatten(coloring, A.n)])
 
 
 class AMGPreconditioner(_PointPreconditioner):

@@ -485,6 +485,55 @@ int32_t esp_precon_iluk_create(esp_handle *h, int32_t k, esp_precon **out);
 int32_t esp_precon_iluk_matrix(esp_precon *p, esp_handle **b);
 int32_t esp_precon_iluk_levels(esp_precon *p, int32_t *lev, int32_t on_device);
 int32_t esp_precon_iluk_stats(esp_precon *p, int64_t out[4]);
+/* Multicolour ordering (the reference's src/factorizations/parallel_ilu0.jl: graphcol, reordermatrix, reorderlinsys and
+ * ParallelILU0Preconditioner).  The reference's colouring draws rand(); the rule here replaces the draw by the fixed hash of the AMG
+ * aggregation and the PMIS splitting, which makes it parallel and reproducible.  The rule is normative, tests/coloring_model.c states it
+ * as plain loops, and the device result equals that model exactly.
+ *   graph     vertices 0..n-1; i and j (i != j) are neighbours when A[i,j] or A[j,i] is stored.  Only the pattern counts: a stored 0.0,
+ *             -0.0 or NaN is an entry.  (The pattern of A + transpose(A) in graphcol; the sum is never formed: column i of the CSC
+ *             and row i of esp_mul's row-wise index are read.)  No symmetric pattern is required.
+ *   priority  key(i) = (uint64)mix(i) << 32 | i with the 32-bit mixer of the aggregation's hash (applied to i + 1).  The keys are
+ *             distinct: every comparison is strict.
+ *   rounds    r = 1, 2, ...: U = the vertices without a colour at the start of the round; i in U receives colour r iff
+ *             key(i) > key(j) for every neighbour j in U.  The colouring ends when U is empty.  (indset / graphcol with the fixed key in
+ *             place of rand(lenW) and > in place of >=.)  The vertex with the largest key of U is always chosen: at most n rounds.
+ *   result    ncolors = the number of rounds; color[i] is 0-based; the permutation c = the vertices sorted by (colour, index), the
+ *             reference's flatten(coloring); color_ptr[0..ncolors] delimits the colours in c.
+ * On the device a round is one launch on the handle's stream and one counter read back, the Luby / PMIS shape: one lane per uncoloured
+ * vertex (a vertex whose column or row holds more than 32 entries is folded by its whole wave), the vertices a round leaves uncoloured
+ * are the next round's list.  Rounds are separated by kernel boundaries and by nothing else: no flag is polled across workgroups,
+ * there is no grid barrier and no persistent kernel.  The permutation comes from stable radix passes over the colour bits.
+ * esp_graph_coloring: the colouring of a flushed square matrix without a preconditioner: *ncolors, and color[n] (int64, 0-based; host,
+ *   or device when on_device != 0; may be NULL).  The checks are esp_precon_colored_create's.
+ * esp_precon_colored_create(h, inner_kind): inner_kind is ESP_PRECON_ILU0 or ESP_PRECON_ILUAM.  The kind colours A, builds
+ *   B = A[c,c] (B[k,l] = A[c[k],c[l]]: every column sorted by row, the values bitwise A's) in an internal handle and creates the inner
+ *   kind on B.  No two unknowns of one colour are coupled, so a row of colour r meets only rows of colours < r in B's strictly lower
+ *   part and only rows of colours > r in its strictly upper part: every level schedule of ILUAM on B has at most ncolors levels.
+ *   esp_precon_ldiv is u[c] = inner(B) \ v[c]: one gather, the inner kind's own launches, one scatter; u may alias v.  It is exactly
+ *   esp_precon_block_create's permuted path over the single partition c, whose builder, value gather and vector kernels it runs; the
+ *   permutation stays on the device.  The result is an esp_precon bound to h; esp_precon_update / _ldiv / _destroy, esp_simple, esp_cg,
+ *   esp_bicgstabl and esp_gmres take it unchanged.
+ *   DEVIATION: the reference's ParallelILU0Preconditioner(A) preconditions the REORDERED system -- its ldiv! takes vectors in the
+ *   coloured numbering and the caller runs reorderlinsys first.  This one acts in A's numbering: a drop-in Pl for A.
+ * esp_precon_update: with A's pattern kept one gather of B's values and the inner values-only update (the colouring, B's pattern and
+ *   ILUAM's analysis are kept; bitwise what a fresh create gives); after a pattern change the colouring, B and the inner preconditioner
+ *   anew.  B holds copies, for ILU0 too (the block kind's value semantics): a value change of A reaches ldiv! only through the update,
+ *   and a pattern change of A without it is ESP_ERR_STATE.  A rebuild that fails before B is replaced leaves the earlier state usable.
+ * esp_precon_get_factor and esp_precon_levels answer for the inner preconditioner (nnz(B) values in B's position order).
+ * Inspection: esp_precon_colored_info: out = ncolors, nnz(B).  esp_precon_colored_colors: color[n] (int64, 0-based).
+ *   esp_precon_colored_perm: c[n] (int64, 0-based).  Both host, or device when on_device != 0.  esp_precon_colored_matrix: B's handle,
+ *   borrowed and read-only, like esp_precon_block_matrix.
+ * ESP_ERR_INVALID: a rectangular matrix; inner_kind outside the two; a column without a stored diagonal (the inner kind's error; it names
+ *   the column of B, the position in c).  ESP_ERR_STATE: pending entries.  ESP_ERR_UNSUPPORTED: a column window / column shard on h; the
+ *   preconditioners' 32-bit limits.  n == 0 is valid.  ILU(k) and AMG are no inner kinds.  A live preconditioner makes h refuse
+ *   esp_destroy; esp_precon_destroy releases B, the inner preconditioner and every buffer. */
+#define ESP_PRECON_COLORED 6
+int32_t esp_graph_coloring(esp_handle *h, int64_t *ncolors, int64_t *color, int32_t on_device);
+int32_t esp_precon_colored_create(esp_handle *h, int32_t inner_kind, esp_precon **out);
+int32_t esp_precon_colored_info(esp_precon *p, int64_t out[2]);
+int32_t esp_precon_colored_colors(esp_precon *p, int64_t *color, int32_t on_device);
+int32_t esp_precon_colored_perm(esp_precon *p, int64_t *c, int32_t on_device);
+int32_t esp_precon_colored_matrix(esp_precon *p, esp_handle **b);
 /* simple!(u, A, b; abstol, reltol, maxiter, Pl = p) (src/factorizations/simple_iteration.jl:21-45) statement by
  * statement: res = A*u - b; then per step ldiv!(upd, Pl, res), u .-= upd, mul!(res, A, u), res .-= b, r = norm(res),
  * stop when (r / r0) < reltol || r < abstol (literally: r0 = 0 gives NaN or Inf there).  u (in/out) is bit-identical to

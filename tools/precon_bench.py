@@ -78,6 +78,13 @@ search + sort part is the rest), a values-only update!, ldiv!, nnz(B)/nnz(A), th
 and gmres(restart = 20) / cg to reltol 1e-8 on b = ones (iterations and time).
 
     python tools/precon_bench.py --kind iluk --k 1 [--n 64] [--iters 20] [--rounds 5]
+
+--kind colored [--inner ilu0|iluam] times ColoredPreconditioner (esp_precon_colored_create, the multicolour ordering) on fdrand(n,n,n)
+beside the natural-order ILUAMPreconditioner and ILU0Preconditioner, the yardsticks, in the same run: the create (median over
+--rounds of create + close) with the colouring's share split off (esp_graph_coloring alone: its rounds are the colours), a values-only
+update!, ldiv! on device vectors, the colours and the level counts, and cg to reltol 1e-8 on b = ones (iterations and time).
+
+    python tools/precon_bench.py --kind colored --inner iluam [--n 64] [--iters 20] [--rounds 5]
 """
 import argparse
 import ctypes as C
@@ -835,12 +842,84 @@ def bench_iluk(a, torch, esp):
     print(json.dumps(rnd(out)))
 
 
+def bench_colored(a, torch, esp):
+    import numpy as np
+    A = esp.fdrand(a.n, a.n, a.n)
+    d = A._d
+    stream = torch.cuda.current_stream()
+    d.ck(d.lib.esp_set_stream(d.h, C.c_void_p(stream.cuda_stream)))
+    N, Z = A.n, A.nnz()
+    v = torch.randn(N, dtype=torch.float64, device="cuda")
+    u = torch.empty_like(v)
+    b = torch.ones_like(v)
+    inner = {"ilu0": esp.ILU0Preconditioner, "iluam": esp.ILUAMPreconditioner}[a.inner]
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()                                   # (create, update!, ldiv!, the colouring and cg return synchronised)
+        return (time.perf_counter() - t0) * 1e3, r
+
+    def median(xs):
+        return float(np.median(xs))
+
+    def measure(make):
+        rec = {}
+        ts = []
+        for _ in range(a.rounds):
+            t, P = wall(lambda: make(A))
+            ts.append(t)
+            P.close()
+        rec["create_ms"] = median(ts)
+        P = make(A)
+        rec["update_values_ms"] = median([wall(P.update)[0] for _ in range(a.rounds)])
+        for _ in range(3):
+            P.ldiv(v, out=u)
+        rec["ldiv_ms"] = median([wall(lambda: [P.ldiv(v, out=u) for _ in range(a.iters)])[0] / a.iters for _ in range(a.rounds)])
+        if hasattr(P, "levels"):
+            rec["levels"] = list(P.levels())
+        fn = lambda: esp.cg(A, b, Pl=P, reltol=1e-8, maxiter=a.tol_maxiter, log=True)
+        fn()
+        ts, log = [], None
+        for _ in range(a.rounds):
+            t, (_, log) = wall(fn)
+            ts.append(t)
+        rec["cg"] = {"iterations": log["iters"], "converged": log["isconverged"], "ms": median(ts)}
+        return rec, P
+
+    out = {"workload": "colored_fdrand", "n": a.n, "N": N, "nnz": Z, "inner": a.inner, "rounds": a.rounds, "iters": a.iters}
+    Pw = esp.ILU0Preconditioner(A)     # builds the row-wise index esp_mul shares, so that the creates below are their own
+    Pw.close()
+    for name, make in (("ilu0", esp.ILU0Preconditioner), ("iluam", esp.ILUAMPreconditioner),
+                       ("colored_" + a.inner, lambda M: esp.ColoredPreconditioner(M, inner))):
+        rec, P = measure(make)
+        if name.startswith("colored"):
+            rec["ncolors"] = P.ncolors
+            rec["color_sizes"] = [len(c) for c in P.coloring()]
+            nc = C.c_int64()
+            rec["coloring_ms"] = median([wall(lambda: d.ck(d.lib.esp_graph_coloring(d.h, C.byref(nc), None, 0)))[0] for _ in range(a.rounds)])
+            rec["coloring_rounds"] = nc.value
+            rec["create_without_coloring_ms"] = rec["create_ms"] - rec["coloring_ms"]
+        P.close()
+        out[name] = rec
+        print(json.dumps({name: rec}), file=sys.stderr, flush=True)   # (what is known so far, should a later phase be cut short)
+
+    def rnd(x):
+        if isinstance(x, float):
+            return round(x, 4)
+        if isinstance(x, dict):
+            return {k: rnd(y) for k, y in x.items()}
+        return x
+    print(json.dumps(rnd(out)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "gmres", "gmres-trace", "block", "block-trace", "block-trace-diff", "amg", "iluk"], default="point")
+    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "gmres", "gmres-trace", "block", "block-trace", "block-trace-diff", "amg", "iluk", "colored"], default="point")
+    ap.add_argument("--inner", choices=["ilu0", "iluam"], default="iluam")
     ap.add_argument("--k", type=int, default=1)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--block-config", choices=["a", "b", "c", "d", "e"], default="b")
@@ -880,6 +959,8 @@ def main():
         return bench_iluk(a, torch, esp)
     if a.kind == "amg":
         return bench_amg(a, torch, esp)
+    if a.kind == "colored":
+        return bench_colored(a, torch, esp)
     A = esp.fdrand(a.n, a.n, a.n)
     d = A._d
     stream = torch.cuda.current_stream()
