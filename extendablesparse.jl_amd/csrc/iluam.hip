@@ -420,3 +420,16 @@ extern "C" int32_t esp_precon_levels(esp_precon *p, int64_t out[3]) {
     for (int k = 0; k < 3; k++) out[k] = p->kind == ESP_PRECON_ILUAM ? p->sched[k].levels : 0;
     return ESP_OK;
 }
+
+extern "C" int32_t esp_precon_launches(esp_precon *p, int64_t out[6]) {
+    if (!p || !out) return ESP_ERR_INVALID;
+    if ((block_built(p) || p->kind == ESP_PRECON_ILUK) && p->inner) p = p->inner;
+    for (int k = 0; k < 3; k++) {
+        i64 wide = 0, thin = 0;
+        if (p->kind == ESP_PRECON_ILUAM)
+            for (const IluamLaunch &L : p->sched[k].launches) (L.thin ? thin : wide)++;
+        out[2 * k] = wide;
+        out[2 * k + 1] = thin;
+    }
+    return ESP_OK;
+}

@@ -181,6 +181,13 @@ class _ILUAMFactors:
         self._ck(self.A._d.lib.esp_precon_levels(self._live(), out))
         return tuple(int(x) for x in out)
 
+    def launches(self):
+        """(wide, thin) kernel launches of the three schedules, in levels()' order: a level of more than 256 nodes is one wide
+        launch, consecutive levels that together hold at most 256 nodes share one thin, single-workgroup launch"""
+        out = (C.c_int64 * 6)()
+        self._ck(self.A._d.lib.esp_precon_launches(self._live(), out))
+        return tuple((int(out[2 * k]), int(out[2 * k + 1])) for k in range(3))
+
 
 class ILUAMPreconditioner(_ILUAMFactors, _PointPreconditioner):
     """ILUAMPreconditioner(A) (src/experimental/ExtendableSparseMatrixParallel/iluam.jl): a real ILU(0) on A's pattern, the

@@ -335,10 +335,15 @@ int32_t esp_precon_destroy(esp_precon *p);
  * esp_precon_get_factor: the factorization's nnz values in CSC position order (the reference's ILU.nzval), host doubles or,
  *   on_device != 0, device doubles; ESP_ERR_INVALID for the other kinds.
  * esp_precon_levels: out[0..2] = the level counts of the three schedules (factorization columns, forward rows, backward
- *   rows); zeros for the other kinds. */
+ *   rows); zeros for the other kinds.
+ * esp_precon_launches: read-only; out[2k], out[2k+1] = the wide and the thin kernel launches schedule k runs, in
+ *   esp_precon_levels' order.  A level of more than 256 nodes is one wide launch by itself; as many consecutive levels as
+ *   together hold at most 256 nodes share one thin, single-workgroup launch.  Block, ILU(k) and Colored answer for the inner
+ *   preconditioner; zeros for the other kinds; the errors of esp_precon_levels. */
 #define ESP_PRECON_ILUAM 2
 int32_t esp_precon_get_factor(esp_precon *p, double *nzval, int32_t on_device);
 int32_t esp_precon_levels(esp_precon *p, int64_t out[3]);
+int32_t esp_precon_launches(esp_precon *p, int64_t out[6]);
 /* BlockPreconditioner (src/factorizations/blockpreconditioner.jl, docs/src/iter.md): the unknowns are split into partitions, every
  * A[part, part] is factorized with Jacobi, ILU0 or ILUAM (inner_kind), and ldiv! solves the partitions independently:
  * u[part] = inner(A[part, part]) \ v[part].  The reference builds np submatrices and runs np factorizations and solves; the device

@@ -11,6 +11,7 @@ import pytest
 import amg_modellib as am
 from bicgstabl_modellib import convdiff_triplets
 from block_precon_modellib import BlockModel
+from edge_patterns import from_triplets, tridiagonal
 from gmres_modellib import RELTOL, Model
 from refmodel import bits
 
@@ -54,14 +55,6 @@ def history_of(log):
     return np.concatenate([[log["r0"]], log["resnorm"]])
 
 
-def from_triplets(esp, n, I, J, V):
-    A = esp.ExtendableSparseMatrix(n, n)
-    if len(I):
-        A.append(esp.ESP_UPDATE, I, J, V)
-    A.flush()
-    return A
-
-
 def convdiff(esp, nx, ny, nz, pe):
     """the upwind convection-diffusion matrix, built through append + flush"""
     return from_triplets(esp, nx * ny * nz, *convdiff_triplets(nx, ny, nz, pe))
@@ -81,15 +74,6 @@ def nonsymmetric(esp, n=3000, extra=20000, seed=5):
     A.append(esp.ESP_UPDATE, I, rng.integers(1, n + 1, 2000), rng.standard_normal(2000))
     A.flush()
     return A
-
-
-def tridiagonal(esp, n):
-    """the non-symmetric tridiagonal (4, -1.5 below, -0.5 above)"""
-    d = np.arange(1, n + 1)
-    I = np.concatenate([d, d[1:], d[:-1]])
-    J = np.concatenate([d, d[:-1], d[1:]])
-    V = np.concatenate([np.full(n, 4.0), np.full(max(n - 1, 0), -1.5), np.full(max(n - 1, 0), -0.5)])
-    return from_triplets(esp, n, I, J, V)
 
 
 MATRICES = {}   # name -> (A, arrays, b = A*ones): built once, never changed
