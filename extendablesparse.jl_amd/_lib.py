@@ -141,6 +141,7 @@ SIGNATURES = {
     "esp_device": (i32, [vp, P(i32)]),
     "esp_transpose": (i32, [vp, vp, P(i64)]),
     "esp_debug_transpose_path": (i32, [vp, i32]),
+    "esp_debug_last_transpose": (i32, [vp, P(i64)]),
     "esp_mul_transpose": (i32, [vp, vp, vp, i32]),
     "esp_issymmetric": (i32, [vp, P(i32)]),
     "esp_opnorm": (i32, [vp, f64, P(f64)]),

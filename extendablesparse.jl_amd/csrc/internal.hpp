@@ -353,6 +353,7 @@ struct esp_handle {
     DevBuf csr_rowptr, csr_perm, csr_col, csr_tmp, csr_val, mul_x, mul_r;
     int matmul_tier = 0;   // esp_debug_matmul_tier: 0 automatic, 1 fused where it fits, 2 generic only (matops.hip)
     int transpose_path = 0;  // esp_debug_transpose_path: 0 automatic, 1 the ESP_COO flush, 2 the counting sort (linalg.hip)
+    i64 last_transpose[3] = {0, 0, 0};  // esp_debug_last_transpose: path taken, columns listed for the workgroup sort, longest column
     int live_precons = 0;  // esp_precon objects bound to this handle (precon.hip): esp_destroy refuses while any is alive
     // esp_cg's work vectors (krylov.hip), sized on first use: residual, search direction, Pl \ r and A*u, the partial sums of the
     // three dot products, and the device copies of host b / x.  esp_bicgstabl (bicgstabl.hip) shares part, hb and hx and adds

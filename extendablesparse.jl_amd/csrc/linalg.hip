@@ -412,7 +412,8 @@ int32_t transpose_generic(esp_handle *c, const Csc64 &A, i64 mC, i64 nC, DevBuf 
 }
 
 // C := transpose(A) by counting sort; *done = false (nothing installed, every buffer released) when a row of A is too long
-int32_t transpose_counting(esp_handle *c, const Csc64 &A, i64 nC, Temps &tmp, bool *done) {
+// seen[0], seen[1]: the columns listed for the workgroup sort and the longest column, as tp_lens_k measured them
+int32_t transpose_counting(esp_handle *c, const Csc64 &A, i64 nC, Temps &tmp, bool *done, i64 *seen) {
     esp_handle *h = c;
     hipStream_t s = h->stream;
     DevBuf &cnt = tmp.b[0], &list = tmp.b[1], &stat = tmp.b[2], &ws = tmp.b[3], &cp = tmp.b[6], &rv = tmp.b[7], &nz = tmp.b[8];
@@ -432,6 +433,8 @@ int32_t transpose_counting(esp_handle *c, const Csc64 &A, i64 nC, Temps &tmp, bo
     HIPCK(h, hipMemcpyAsync(h->pin_scalar, stat.p, sizeof(u64) * 2, hipMemcpyDeviceToHost, s));
     HIPCK(h, hipStreamSynchronize(s));
     const i64 nlong = (i64)h->pin_scalar[0], maxlen = (i64)h->pin_scalar[1];
+    seen[0] = nlong;
+    seen[1] = maxlen;
     if (maxlen > TP_BLOCK || nlong > 0x7FFFFFFFll) {
         for (DevBuf *b : {&cnt, &list, &stat, &ws, &cp}) release(*b);
         return ESP_OK;
@@ -542,6 +545,12 @@ extern "C" int32_t esp_debug_transpose_path(esp_handle *c, int32_t path) {
     return ESP_OK;
 }
 
+extern "C" int32_t esp_debug_last_transpose(const esp_handle *c, int64_t out[3]) {
+    if (!c || !out) return ESP_ERR_INVALID;
+    for (int k = 0; k < 3; k++) out[k] = c->last_transpose[k];
+    return ESP_OK;
+}
+
 extern "C" int32_t esp_transpose(esp_handle *a, esp_handle *c, int64_t *nnz_out) {
     if (!a || !c) return ESP_ERR_INVALID;
     if (c == a) FAIL(c, ESP_ERR_INVALID, "esp_transpose: the result handle must not be the operand");
@@ -554,6 +563,7 @@ extern "C" int32_t esp_transpose(esp_handle *a, esp_handle *c, int64_t *nnz_out)
     const i64 mC = a->n, nC = a->m;
     Temps tmp;
     DevBuf &cp = tmp.b[6], &rv = tmp.b[7], &nz = tmp.b[8];
+    i64 took[3] = {0, 0, 0};  // (esp_debug_last_transpose)
     if (A.nnz == 0) {
         CK(ensure(c, cp, sizeof(i64) * (size_t)(nC + 1)));
         CK(ensure(c, rv, sizeof(i64)));
@@ -563,10 +573,12 @@ extern "C" int32_t esp_transpose(esp_handle *a, esp_handle *c, int64_t *nnz_out)
         HIPCK(c, hipStreamSynchronize(c->stream));
     } else {
         bool done = false;
-        if (c->transpose_path != 1) CK(transpose_counting(c, A, nC, tmp, &done));
+        if (c->transpose_path != 1) CK(transpose_counting(c, A, nC, tmp, &done, took + 1));
         if (!done) CK(transpose_generic(c, A, mC, nC, cp, rv, nz));
+        took[0] = done ? 2 : 1;
     }
     install(c, cp, rv, nz, A.nnz);
+    for (int k = 0; k < 3; k++) c->last_transpose[k] = took[k];
     if (nnz_out) *nnz_out = A.nnz;
     return ESP_OK;
 }

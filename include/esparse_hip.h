@@ -718,6 +718,11 @@ int32_t esp_transpose(esp_handle *a, esp_handle *c, int64_t *nnz_out);
  * keys swapped, flushed into an empty CSC of a scratch handle; an esp_debug_fail_next_bucket_stage armed on c is met by that flush),
  * 2 the counting sort (row counts, a scatter, every column sorted by row; a row of A longer than 4096 entries takes path 1) */
 int32_t esp_debug_transpose_path(esp_handle *c, int32_t path);
+/* read-only: what the last successful esp_transpose into c did.  out[0] = the path taken (1 generic, 2 counting; 0: no transpose yet,
+ * or an operand without stored entries); out[1], out[2] = the columns of C listed for the workgroup sort (longer than 32 entries) and
+ * the longest column of C, as the counting path measured them (0 where it did not run: path 1 forced).  A row of A longer than 4096
+ * entries reports path 1 with these counts.  Changes nothing. */
+int32_t esp_debug_last_transpose(const esp_handle *c, int64_t out[3]);
 /* r := transpose(A)*x (= adjoint(A)*x for real A); x: m doubles, r: n doubles; on_device != 0: device pointers (as esp_mul) */
 int32_t esp_mul_transpose(esp_handle *h, const double *x, double *r, int32_t on_device);
 /* *result = 1 if issymmetric(A) (= ishermitian(A) for real A), else 0 */

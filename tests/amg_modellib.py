@@ -290,7 +290,7 @@ def graphs(fd):
         g["path%d" % n] = (path_graph(n), 0.0)
     g["fd5x5x5"] = (fd(5, 5, 5), 0.0)
     g["fd33x31"] = (fd(33, 31, 1), 0.0)
-    for d in (33, 64, 65, 130):
+    for d in (33, 64, 65, 130, 31, 32, 63):
         g["star%d" % d] = (star_graph(d, hub=d // 2), 0.0)
     g["dirichlet"] = (dirichlet_like(fd(9, 8, 1), rows={0, 13, 14, 40}, isolated={5, 30, 71}), 0.0)
     g["dense70"] = (dense_block(70), 0.0)
@@ -300,4 +300,5 @@ def graphs(fd):
 
 
 GRAPH_NAMES = ["n0", "n1", "n2", "path3", "path5", "path200", "fd5x5x5", "fd33x31", "star33", "star64", "star65", "star130",
+               "star31", "star32", "star63",
                "dirichlet", "dense70", "convdiff_t0", "convdiff_t025"]

@@ -1,7 +1,9 @@
 """CPU: the crafted patterns of tests/edge_patterns.py are what they claim to be -- the prescribed schedule of every layered
 pattern has exactly the prescribed level widths (by iluam_modellib's NumPy restatement of the schedules), launch_list gives the
 hand-written launch counts, the capacity matrix holds its table of per-block entry counts (counted with SciPy), and the C
-models' factorizations and ldiv! on every pattern are finite."""
+models' factorizations and ldiv! on every pattern are finite.  The second half does the same for tests/algebra_patterns.py: the
+column lengths, the position of every tile border relative to the column starts, the merged positions of the A+-B pairs (by a plain
+Python merge), the tiles and columns of the model's result that are empty, and finite, non-trivial model results."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -143,3 +145,325 @@ def test_tridiagonal_triplets():
     assert np.array_equal(S, 4.0 * np.eye(5) - 1.5 * np.eye(5, k=-1) - 0.5 * np.eye(5, k=1))
     assert all(len(a) == 0 for a in ep.tridiagonal_triplets(0))
     assert [len(a) for a in ep.tridiagonal_triplets(1)] == [1, 1, 1]
+
+
+# ---- tests/algebra_patterns.py: the algebra and set-up side ---------------------------------------------------------------------
+import math  # noqa: E402
+
+import algebra_patterns as ap  # noqa: E402
+import amg_modellib as am  # noqa: E402
+import iluk_modellib  # noqa: E402
+import linalg_modellib  # noqa: E402
+import matops_modellib  # noqa: E402
+from block_precon_modellib import block_matrix  # noqa: E402
+from refmodel import bits  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def linalg(tmp_path_factory):
+    return linalg_modellib.Model(tmp_path_factory.mktemp("edge_linalg_model"))
+
+
+@pytest.fixture(scope="module")
+def matops(tmp_path_factory):
+    return matops_modellib.Model(tmp_path_factory.mktemp("edge_matops_model"))
+
+
+def check_csc(csc, m):
+    cp, rv, nz = csc
+    assert cp[0] == 1 and cp[-1] == len(rv) + 1 == len(nz) + 1 and np.all(np.diff(cp) >= 0)
+    assert len(rv) == 0 or (rv.min() >= 1 and rv.max() <= m)
+    for j in np.flatnonzero(np.diff(cp) > 1):
+        assert np.all(np.diff(rv[cp[j] - 1:cp[j + 1] - 1]) > 0)         # rows ascending and distinct
+
+
+def has_specials(nz):
+    b = bits(np.asarray(nz))
+    return all(np.any(b == bits(np.array([s]))[0]) for s in (0.0, ap.NEG_ZERO, ap.NAN_PAYLOAD))
+
+
+def test_prescribed_lengths(linalg):
+    subs = ap.sort_sublists()
+    assert sorted(subs) == ap.SORT_MAXIMA == [8, 9, 16, 17, 32, 33, 4096, 4097]
+    assert subs[4096] == ap.SORT_LENGTHS and subs[4097] == ap.SORT_LENGTHS + [4097] and subs[8] == [0, 1, 2, 7, 8]
+    assert (ap.COLSORT_LANE, ap.COLSORT_BLOCK) == (32, 4096)
+    for mx, lengths in subs.items():
+        assert max(lengths) == mx
+        csc = ap.prescribed_lengths(lengths, seed=mx)
+        check_csc(csc, ap.SORT_ROWS)
+        assert list(np.diff(csc[0])) == lengths
+        assert sum(l > ap.COLSORT_LANE for l in lengths) == {32: 0, 33: 1}.get(mx, sum(l > 32 for l in lengths))
+        assert has_specials(csc[2])
+        j = int(np.argmax(lengths))
+        col = csc[1][csc[0][j] - 1:csc[0][j + 1] - 1]
+        assert col.max() - col.min() > ap.SORT_ROWS // 2                     # spread over the row range
+        # the operand of the device transpose: its rows are the prescribed columns
+        T = ap.transpose_csc(ap.SORT_ROWS, csc)
+        check_csc(T, len(lengths))
+        back = linalg.transpose(len(lengths), T)
+        assert all(np.array_equal(bits(a) if a.dtype == np.float64 else a, bits(b) if b.dtype == np.float64 else b)
+                   for a, b in zip(back, csc))
+    # the workgroup sort's padded size S: 64 at 33, 4096 at 4096
+    for L, S in ((33, 64), (4096, 4096)):
+        s = 2
+        while s < L:
+            s <<= 1
+        assert s == S
+
+
+def test_prescribed_square_and_partitions():
+    for mx, lengths in ap.sort_sublists().items():
+        lengths = [l for l in lengths if l >= 1]
+        csc, n, where = ap.prescribed_square(lengths, seed=mx)
+        check_csc(csc, n)
+        lens = np.diff(csc[0])
+        assert [int(lens[c]) for c in where] == lengths and max(lengths) == mx      # the diagonal added, the lengths kept
+        assert np.all(np.delete(lens, where) == 1) and n >= mx + 3
+        cols = np.repeat(np.arange(n), lens)
+        assert np.count_nonzero(csc[1] - 1 == cols) == n                             # a full diagonal
+        assert np.isfinite(csc[2]).all() and np.any(bits(csc[2]) == bits(np.array([-0.0]))[0])
+        parts = ap.worst_case_partitions(n)
+        assert sorted(parts) == ["reversed", "shuffled", "zigzag"]
+        for name, p in parts.items():
+            assert np.array_equal(np.sort(np.concatenate(p)), np.arange(n))
+        # what reaches the sorts: the new rows of a column in stored order
+        new = np.empty(n, np.int64)
+        new[parts["reversed"][0]] = np.arange(n)
+        c = where[-1]
+        assert np.all(np.diff(new[csc[1][csc[0][c] - 1:csc[0][c + 1] - 1] - 1]) < 0)   # strictly descending
+        new[np.concatenate(parts["zigzag"])] = np.arange(n)
+        d = np.diff(new[csc[1][csc[0][c] - 1:csc[0][c + 1] - 1] - 1])
+        assert mx < 8 or (np.any(d < 0) and np.any(d > 0))
+    csc, n, where = ap.prescribed_square([1, 2, 7, 8], seed=8)
+    wcp = block_matrix(csc, ap.worst_case_partitions(n)["reversed"], True)[0]          # one partition keeps every entry
+    assert sorted(np.diff(wcp))[-3:] == [2, 7, 8] and wcp[-1] - 1 == len(csc[1])
+
+
+def test_compaction_edges():
+    csc, n, parts = ap.compaction_edges()
+    check_csc(csc, n)
+    assert ap.BK_LONG == 32 and n == 200
+    lens = np.diff(csc[0])
+    wcp = block_matrix(csc, parts, False)[0]
+    for t, (stored, kept) in enumerate(ap.BK_CASES):
+        assert lens[t] == stored and wcp[t + 1] - wcp[t] == kept
+        rows = csc[1][csc[0][t] - 1:csc[0][t + 1] - 1] - 1
+        mine = rows % 2 == t % 2
+        if 0 < kept < stored:
+            assert np.any(mine[1:] != mine[:-1])                    # dropped and kept entries interleave
+            assert np.count_nonzero(mine[1:] != mine[:-1]) >= 2 * min(kept, stored - kept) - 1
+    assert {s for s, _ in ap.BK_CASES} == {32, 33} and {k for s, k in ap.BK_CASES if s == 33} == {0, 1, 16, 31, 32, 33}
+    t = ap.BK_CASES.index((33, 33))
+    assert has_specials(csc[2][csc[0][t] - 1:csc[0][t + 1] - 1])
+
+
+def test_bordered():
+    cp, rv, nz = ap.bordered()
+    check_csc((cp, rv, nz), ap.BORDERED_ROWS)
+    lens = list(np.diff(cp))
+    nnz = len(rv)
+    assert len(lens) == 40 and nnz == 5 * ap.TILE + 1 and ap.TILE == 2048
+    assert lens[:2] == [0, 0] and lens[-4:] == [0, 0, 0, 0] and lens[-5] == 1
+    assert lens[2] == 2048 and cp[2] - 1 == 0 and cp[3] - 1 == 2048              # one column is exactly the first tile
+    assert 4095 in lens
+    start, end = cp[:-1] - 1, cp[1:] - 1
+    where = {}
+    for b in range(ap.TILE, nnz, ap.TILE):
+        j = ap.column_of(cp, b)
+        where[b] = (j, b - start[j], end[j] - b)                                  # (column, entries before b, entries from b on)
+    assert where[2048] == (6, 0, 1000) and lens[3:6] == [0, 0, 0]                 # a column start behind three empty columns
+    assert where[4096][0] == 8 and where[4096][1] > 0 and where[4096][2] > 1      # the middle of the column of 4095
+    assert where[6144][0] == 8 and where[6144][1] > 0 and where[6144][2] > 1
+    assert where[8192][2] == 1 and where[8192][1] == lens[where[8192][0]] - 1     # one entry before a column end
+    assert where[10240] == (35, 0, 1) and 10240 == nnz - 1                        # the last tile holds a single entry
+    assert has_specials(nz)
+
+
+def test_symmetric_bordered(linalg):
+    csc = ap.symmetric_bordered()
+    cp, rv, nz = csc
+    n = ap.SYM_N
+    check_csc(csc, n)
+    assert len(cp) == n + 1 and len(rv) == 3 * ap.TILE + 1
+    positions = ap.SYM_POSITIONS + [len(rv) - 1]
+    assert positions == [0, 2047, 2048, 4095, 4096, 6144]
+    assert linalg.issymmetric(n, csc)
+    zeros = np.flatnonzero(nz == 0.0)
+    assert len(zeros) == 5 and all(ap.mirror_position(csc, int(p)) < 0 for p in zeros)     # stored zeros without a mirror
+    for p in range(len(rv)):
+        q = ap.mirror_position(csc, p)
+        if p not in zeros:
+            assert q >= 0 and bits(nz[q:q + 1])[0] == bits(nz[p:p + 1])[0]
+    for p in positions:
+        assert rv[p] - 1 != ap.column_of(cp, p) and nz[p] != 0.0
+        P = ap.perturbed(csc, p)
+        assert np.count_nonzero(bits(P[2]) != bits(nz)) == 1 and bits(P[2])[p] != bits(nz)[p]
+        assert not linalg.issymmetric(n, P)
+        Z = ap.zero_pair(csc, p)
+        assert np.count_nonzero(bits(Z[2]) != bits(nz)) == 2 and linalg.issymmetric(n, Z)
+        q = ap.mirror_position(csc, p)
+        assert {bits(Z[2][p:p + 1])[0], bits(Z[2][q:q + 1])[0]} == {0, 1 << 63}
+
+
+def test_merge_cases(matops):
+    cases = ap.merge_cases()
+    assert ap.MM_TILE == 1024
+    for name, c in cases.items():
+        A, B, m = c["A"], c["B"], c["m"]
+        check_csc(A, m)
+        check_csc(B, m)
+        assert len(A[0]) == len(B[0]) and len(A[1]) + len(B[1]) == c["total"], name
+        st = ap.merged_stream(A, B)
+        assert len(st) == c["total"]
+        ntiles = (c["total"] + 1023) // 1024
+        for sub, op in ((False, "+"), (True, "-")):
+            kept = ap.kept_per_tile(A, B, sub)
+            got = matops.add(A, B, matops_modellib.OP_SUB if sub else matops_modellib.OP_ADD)
+            assert sum(kept) == len(got[1]) > 0 and len(kept) == ntiles, (name, op)
+            assert np.isfinite(got[2]).all()
+            empty = [t for t, k in enumerate(kept) if k == 0]
+            assert empty == c.get("empty_tiles", {}).get(op, []), (name, op)
+            gone = [int(j) for j in np.flatnonzero(np.diff(got[0]) == 0)
+                    if A[0][j + 1] > A[0][j] or B[0][j + 1] > B[0][j]]                     # stored in an operand, empty in the result
+            assert gone == c.get("empty_columns", {}).get(op, []), (name, op)
+            if "cancels" in c:                                                             # exactly the split pair of this operation
+                row = c["cancels"][op]
+                assert len(got[1]) == 1100 - 1 and row not in got[1] and c["cancels"]["-" if op == "+" else "+"] in got[1]
+        if "split_pairs" in c:
+            for (pa, pb), row in zip(c["split_pairs"], c["split_rows"]):
+                assert st[pa][:3] == (0, row, 0) and st[pb][:3] == (0, row, 1)
+                assert pa % 1024 == 1023 and pb % 1024 == 0                                # a tile border between the halves
+        if "only" in c:
+            src, tiles = c["only"]
+            for t in range(ntiles):
+                srcs = {e[2] for e in st[t * 1024:(t + 1) * 1024]}
+                assert (srcs == {src}) == (t in tiles), (name, t)
+        if "border" in c:
+            d, before, after = c["border"]
+            assert d % 1024 == 0 and st[d - 1][0] == before and st[d][0] == after
+            la, lb = np.diff(A[0]), np.diff(B[0])
+            assert [int(j) for j in np.flatnonzero(la == 0)] == c["empty_a"]
+            assert [int(j) for j in np.flatnonzero(lb == 0)] == c["empty_b"]
+            only_a = [j for j in range(8) if la[j] == 0 and lb[j] > 0]
+            only_b = [j for j in range(8) if lb[j] == 0 and la[j] > 0]
+            both = [j for j in range(8) if la[j] == 0 and lb[j] == 0]
+            for group in (only_a, only_b, both):                                           # on either side of the border
+                assert any(j <= before or before < j < after and j == 3 for j in group), group
+                assert any(j >= after or j == 4 for j in group), group
+            assert both == [3, 4] and only_a == [1, 5] and only_b == [2, 6]
+    assert [cases["total%d" % t]["total"] for t in (1024, 1025, 2048, 2049)] == [1024, 1025, 2048, 2049]
+    # a cancelled whole tile lies between tiles that keep entries
+    assert ap.kept_per_tile(cases["tile_cancels_add"]["A"], cases["tile_cancels_add"]["B"], False) == [512, 0, 512]
+    assert ap.kept_per_tile(cases["tile_cancels_sub"]["A"], cases["tile_cancels_sub"]["B"], True) == [512, 0, 512]
+    assert cases["columns_cancel_add"]["empty_columns"]["+"] == [0, 2, 4, 5, 6, 8, 11]      # first, last, a run of three
+
+
+def test_wave_columns(linalg):
+    csc, lengths = ap.wave_columns()
+    check_csc(csc, ap.WAVE_M)
+    assert (ap.WAVE_M, ap.WAVE_N, ap.MV_LONG) == (700, 357, 64) and list(np.diff(csc[0])) == lengths
+    assert set(lengths) == {0, 1, 63, 64, 65, 127, 128, 129, 192, 700}
+    long_lanes = [[j - w for j in range(w, min(w + 64, ap.WAVE_N)) if lengths[j] > 64] for w in range(0, ap.WAVE_N, 64)]
+    assert long_lanes == [[], [0], [5, 20, 63], [1, 2], [], [36]]
+    assert ap.WAVE_N - 5 * 64 == 37 and lengths[-1] == 65 and set(lengths[256:320]) == {64}
+    x = ap.wave_x()
+    assert np.isinf(x[10]) and np.isnan(x[20]) and np.count_nonzero(~np.isfinite(x)) == 2
+    stores = [set(csc[1][csc[0][j] - 1:csc[0][j + 1] - 1] - 1) for j in range(ap.WAVE_N)]
+    for r in (10, 20):
+        hit = [r in s for s in stores]
+        assert any(hit) and not all(h for h, l in zip(hit, lengths) if l > 0)        # only some columns store the row
+    r = linalg.mul_transpose(csc, x)
+    assert np.isnan(r).any() and np.isfinite(r).any() and np.count_nonzero(r[np.isfinite(r)]) > 100
+
+
+def test_new_stars_and_the_prolongation_hub_column(orc, tmp_path_factory):
+    model = am.Model(tmp_path_factory.mktemp("edge_amg_model"))
+
+    def fd(*dims):
+        O = orc.fdrand(*dims, rand_mode=1, seed=7, style=orc.KIND_UPDATE)       # (O owns what sparse() views)
+        return tuple(np.array(a) for a in O.sparse().arrays())
+    g = am.graphs(fd)
+    assert list(g) == am.GRAPH_NAMES and {"star31", "star32", "star63"} <= set(am.GRAPH_NAMES)
+    hub = {}
+    for deg in (31, 32, 63, 64):
+        csc, theta = g["star%d" % deg]
+        assert np.diff(csc[0]).max() == deg + 1                                       # the hub column of A
+        with np.errstate(all="ignore"):
+            M = am.AMGModel(model, csc, max_coarse=1, theta=theta)
+        assert [L.n for L in M.levels] == [deg + 1, 1]
+        P = M.levels[0].P
+        assert len(P[0]) == 2                                                         # one aggregate: P's only column is the hub's
+        hub[deg] = int(P[0][1] - P[0][0])
+        u = M.ldiv(np.random.default_rng(deg).standard_normal(deg + 1))
+        assert np.isfinite(u).all() and np.any(u != 0.0)
+    assert hub == {31: 32, 32: 33, 63: 64, 64: 65}                                    # AMG_LONG at 32 | 33, AMG_TLONG at 64 | 65
+
+
+def test_reduction_vectors():
+    from test_linalg_gpu import NORM_P, close
+    assert ap.RED_SIZES == [65537, 262144, 262145, 524289]
+    assert ap.RED_GRID * ap.RED_MT + 1 == 262145 and 256 * ap.RED_MT + 1 == 65537 and ap.MAX_GRID * 256 + 1 == ap.GRID_N == 524289
+    for N in ap.RED_SIZES:
+        G = min(ap.RED_GRID, -(-N // ap.RED_MT))
+        sp_ = ap.reduction_specials(N)
+        if N == 65537:
+            assert G == 257 and sp_ == [256 * ap.RED_MT]                              # the 257th partial holds this element alone
+        if N >= 262145:
+            assert G == 1024 and sp_[0] == G * ap.RED_MT                              # the first element of the second round
+        if N == 524289:
+            assert sp_[-1] == 2 * G * ap.RED_MT and sp_[1] == sp_[-1] - 1             # the second round's last, the third's only
+        for negative in (False, True):
+            v = ap.reduction_vector(N, negative)
+            rest = np.delete(np.abs(v), sp_)
+            assert len(v) == N and rest.min() >= 0.5 and rest.max() <= 1.5
+            for p in NORM_P:
+                if (p < 0) != negative:
+                    continue
+                want = linalg_modellib.norm_ref(v, p)
+                assert math.isfinite(want) and want > 0
+                for i in sp_:                                                         # the reference without that element
+                    if math.isinf(p) and i != sp_[-1]:
+                        continue                                                      # (max / min: the extreme one is the last)
+                    assert not close(linalg_modellib.norm_ref(np.delete(v, i), p), want), (N, p, i)
+
+
+def test_grid_matrix(linalg):
+    csc, n = ap.grid_matrix()
+    cp, rv, nz = csc
+    assert n == 524289 and len(rv) == 2 * n and np.all(np.diff(cp) == 2)
+    assert np.all(np.diff(rv.reshape(n, 2), axis=1) > 0)
+    rows = np.bincount(rv - 1, minlength=n)
+    assert rows[n - 1] == 33 and np.delete(rows, n - 1).max() <= 3                    # the transpose's only long column: 32 | 33
+    colsum = np.abs(nz).reshape(n, 2).sum(axis=1)
+    rowsum = np.bincount(rv - 1, weights=np.abs(nz), minlength=n)
+    assert int(np.argmax(colsum)) == n - 1 and np.sort(colsum)[-2] < colsum[n - 1] - 1
+    assert int(np.argmax(rowsum)) == n - 1 and np.sort(rowsum)[-2] < rowsum[n - 1] - 1
+    assert (n - 1) // 256 == ap.MAX_GRID                                              # segment n-1 is workgroup 0's second round
+    assert linalg.opnorm_general(n, csc, 1) == colsum[n - 1] and linalg.opnorm_general(n, csc, math.inf) > 20
+
+
+def test_frontier(tmp_path_factory):
+    model = iluk_modellib.Model(tmp_path_factory.mktemp("edge_iluk_model"))
+    assert ap.SHORT_COL == 16
+    for width in (16, 17):
+        csc, tcsc, r1, r2 = ap.frontier(width)
+        n, src, u1, u2 = ap.FRONTIER_N, ap.FRONTIER_SOURCE, ap.FRONTIER_U1, ap.FRONTIER_U2
+        check_csc(csc, n)
+        check_csc(tcsc, n)
+        lens = np.diff(csc[0])
+        assert lens[u1] == width and lens[u2] == width and u1 < u2 < src
+        assert np.delete(lens, [u1, u2]).max() <= 2                                   # every other frontier vertex is short
+        assert r1.min() > src and r2.min() > src and len(set(r2) - set(r1)) == width - 1 - (width - 1) // 2 > 0
+        back = ap.transpose_csc(n, tcsc)
+        assert all(np.array_equal(a, b) for a, b in zip(back, csc))
+        for K, want1, want2 in ((0, 0, 0), (1, width - 2, 0), (2, width - 2, len(set(r2) - set(r1))), (3, width - 2, len(set(r2) - set(r1)))):
+            for which, arrays in (("lower", csc), ("upper", tcsc)):
+                P = model.precon(arrays, K)
+                lev = iluk_modellib.levels_as_dict(P.B, P.lev)
+                mine = {k: l for k, l in lev.items() if (k[1] if which == "lower" else k[0]) == src
+                        and (k[0] if which == "lower" else k[1]) > src}
+                assert sum(l == 1 for l in mine.values()) == want1 and sum(l == 2 for l in mine.values()) == want2, (width, K, which)
+                _, vl, vu = iluk_modellib.parallel_levels(arrays[0], arrays[1], K)
+                assert max(vl + vu) <= 64                                             # the wave form serves every column
+                u = P.ldiv(np.ones(n))
+                assert np.isfinite(u).all() and np.any(u != 0.0)
