@@ -16,6 +16,7 @@ ESP_ERR_UNSUPPORTED, ESP_ERR_STATE, ESP_ERR_NODEVICE = -5, -6, -7
 ESP_SET, ESP_UPDATE, ESP_RAWUPDATE, ESP_COO = 0, 1, 2, 3
 ESP_OP_ADD, ESP_OP_SUB = 0, 1
 ESP_FLUSH_ROUTED, ESP_FLUSH_PLUS = 0, 1
+ESP_PATH_NO_KEPT_STRUCTURE = 45  # esp_debug_force_path: the fused stencil flush always stores colptr and rowval
 ESP_PRECON_JACOBI, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_BLOCK, ESP_PRECON_AMG = 0, 1, 2, 3, 4
 ESP_PRECON_ILUK = 5
 ESP_PRECON_COLORED = 6
@@ -161,6 +162,7 @@ SIGNATURES = {
     "esp_debug_spoil_predicted": (i32, [vp]),
     "esp_debug_last_lazy_items": (i32, [vp, P(i32)]),
     "esp_debug_last_lazy_stencil": (i32, [vp, P(i32)]),
+    "esp_debug_last_kept_structure": (i32, [vp, P(i32)]),
     "esp_debug_last_sum_join": (i32, [vp, P(i32)]),
     "esp_debug_last_sum_ms": (i32, [vp, P(C.c_double), P(C.c_double)]),
     "esp_debug_last_sum_batched": (i32, [vp, P(C.c_int32)]),

@@ -211,6 +211,7 @@ int32_t sort_generic(esp_precon *p, const BlkOut &fill_args, const u32 *newpos, 
     if (ft != ESP_OK) FAIL(h, ft, "esp_precon_block: %s", sc->err.c_str());
     HIPCK(h, hipStreamSynchronize(sc->stream));
     if (sc->nnz != nnzB) FAIL(h, ESP_ERR_HIP, "esp_precon_block: the flush stored %lld entries of %lld", (long long)sc->nnz, (long long)nnzB);
+    drop_kept(sc);  // (the scratch handle gives its arrays away)
     std::swap(cp, sc->colptr);
     std::swap(rv, sc->rowval);
     std::swap(pay, sc->nzval);

@@ -21,6 +21,7 @@ extern "C" int32_t esp_dropzeros(esp_handle *h, int64_t *new_nnz) {
     HIPCK(h, hipStreamSynchronize(h->stream));
     const i64 Zk = (i64) * (u32 *)h->pin_scalar;
     if (Zk != Z) {
+        drop_kept(h);  // (colptr and rowval are replaced)
         CK(ensure(h, h->rowval2, sizeof(i64) * (size_t)std::max<i64>(Zk, 1)));
         CK(ensure(h, h->nzval2, sizeof(double) * (size_t)std::max<i64>(Zk, 1)));
         hipLaunchKernelGGL(espfold::dropzeros_compact_k, dim3(grid_for(Z, 256)), dim3(256), 0, h->stream, (const i64 *)h->rowval.p,
@@ -327,6 +328,7 @@ int32_t dirichlet_call(esp_handle *h, uint8_t *marker, int32_t on_device, bool m
     (void)hipSetDevice(h->device);
     if (!h->csc_valid) CK(init_empty_csc(h));
     CK(fix_tail(h));
+    if (!mark) drop_kept(h);  // (an editor of the stored matrix: what it leaves is not what the flush wrote)
     const i64 n = h->n;
     uint8_t *dm = marker;
     if (!on_device) {

@@ -231,6 +231,22 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
     // window flag is not fetched: the batch is armed on unwindowed handles only.  The stream is idle: the handle's last flush
     // ended with a synchronise.)
     const bool fused = st.stencil && use_pred;
+    // The kernel's KEEP form (values only) when colptr and rowval still hold what the handle's last fused flush of this plan,
+    // table, grid and kind left there, and that flush emitted the grid's whole structural pattern (esp_handle::KeptStructure has
+    // the argument): the stamp esp_flush found valid on entry, the three buffers where they were, the pattern version the one
+    // reset! made from the stamp's, and reset!'s lazy fill of colptr still pending (n > 4096: a smaller matrix is filled at once).
+    // force_path 45: never.
+    const int fused_keys = st.kind == ESP_UPDATE ? 2 : 1;
+    bool keep = false;
+    if (fused) {
+        const esp_handle::KeptStructure &ks = h->kept;
+        const espgen::FdArgs &fd = st.stencil->a;
+        keep = ks.candidate && h->force_path != ESP_PATH_NO_KEPT_STRUCTURE && h->n > 4096 && direct && !windowed(h) && h->ones_pending &&
+               ks.plan_gen == h->plan_gen && ks.pred_gen == h->pred.gen && ks.nx == fd.nx && ks.ny == fd.ny && ks.nz == fd.nz &&
+               ks.keys == fused_keys && ks.colptr == h->colptr.p && ks.rowval == h->rowval.p && ks.nzval == h->nzval.p &&
+               ks.pattern_version == h->pattern_version && ks.nnz > 0;
+    }
+    h->kept.candidate = false;
     // (the predicted form reads the error / longest-run words and leaves the grand total in the last granule: nothing else to clear)
     if (fused)
         h->pin_words[0] = h->pin_words[1] = h->pin_words[2] = 0ull;
@@ -318,7 +334,7 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
                 ap.first = first;
                 const unsigned grid = (unsigned)std::min<i64>(max_grid, Sp - first);
                 if (use_pred && st.stencil) {
-                    if (!esplocal::launch_pair_gen_predicted(var, grid, h->stream, ap, st.stencil->a, (const u64 *)h->pred.tab.p, out_cap))
+                    if (!esplocal::launch_pair_gen_predicted(var, grid, h->stream, ap, st.stencil->a, (const u64 *)h->pred.tab.p, out_cap, keep))
                         return ESP_RETRY_EXPANDED;  // (a cut the fused kernel does not take: nothing has happened)
                     continue;
                 }
@@ -470,6 +486,10 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
         use_pred = false;
         h->pred.misses++;
         h->pred.last = 2;
+        // (the KEEP form stored values into the scratch array at most: colptr and rowval are as they were, and the retry writes all
+        // of them -- the stamp is gone since esp_flush's entry)
+        if (keep) h->last_kept = 2;
+        drop_kept(h);
         CK(reset_launch_state());
         if (st.stencil) return ESP_RETRY_EXPANDED;  // (the look-back form reads the entries: the held-back PART launch first)
         {
@@ -563,6 +583,17 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
     const i64 Zn = (i64)(h->pin_scalar[0] & esplocal::ST_VAL);
     *Zn_out = Zn;
     if (st.stencil) h->last_lazy_stencil = 1;  // (served: the batch was never written; the table stays as it is)
+    // ... and colptr / rowval hold this flush's structure from here on: the stamp is armed (below, behind the rotation) when the
+    // flush emitted the grid's whole structural pattern -- N diagonal entries and two per pair of neighbours
+    bool arm = false;
+    if (fused) {
+        const espgen::FdArgs &fd = st.stencil->a;
+        const i64 structural = fd.nx * fd.ny * fd.nz + 2 * ((fd.nx - 1) * fd.ny * fd.nz + fd.nx * (fd.ny - 1) * fd.nz + fd.nx * fd.ny * (fd.nz - 1));
+        if (keep && Zn != h->kept.nnz) FAIL(h, ESP_ERR_STATE, "esp_flush: internal error (a kept structure of %lld entries, a flush of %lld)", (long long)h->kept.nnz, (long long)Zn);
+        arm = h->force_path != ESP_PATH_NO_KEPT_STRUCTURE && h->n > 4096 && h->n == fd.nx * fd.ny * fd.nz && direct && !windowed(h) && Zn == structural &&
+              !a.stop_after;
+        if (keep) h->last_kept = 1;
+    }
     if (pred_batch && used_pair && !use_pred && Zn > 0 && !a.stop_after) {
         // a look-back flush of a kept plan that succeeded: its pairs' offsets, from the fresh colptr, for the next flush of the plan
         // (not once two predictions in a row have missed: the stream's zeros move every time)
@@ -585,14 +616,20 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
         // (empty) CSC arrays become the next flush's scratch pair: bring them to the same capacity
         // once, so that the rotation never shrinks the scratch pair (a 10 GB hipMalloc per flush
         // costs more than the flush itself)
-        CK(ensure(h, h->rowval, h->keys2.bytes));
+        // (the KEEP form wrote values only: rowval stays the array it is)
+        if (!keep) CK(ensure(h, h->rowval, h->keys2.bytes));
         CK(ensure(h, h->nzval, h->vals2.bytes));
-        std::swap(h->rowval, h->keys2);
+        if (!keep) std::swap(h->rowval, h->keys2);
         std::swap(h->nzval, h->vals2);
         if (direct) {  // colptr is complete (behind a column window it is refreshed lazily, as after the scan)
             if (windowed(h)) h->tail_stale = h->wc1 < h->n;
             h->nnz = Zn;
             h->pattern_version++, h->values_version++;
+            if (arm) {
+                const espgen::FdArgs &fd = st.stencil->a;
+                h->kept = esp_handle::KeptStructure{true, false, h->plan_gen, h->pred.gen, fd.nx, fd.ny, fd.nz, fused_keys, h->rowval.p, h->colptr.p, h->nzval.p,
+                                                    Zn, h->pattern_version};
+            }
             return ESP_OK;
         }
         return finish_csc(h, 0, Zn, nullptr, nullptr);
@@ -955,6 +992,11 @@ extern "C" int32_t esp_flush(esp_handle *h, int32_t mode, int64_t *new_nnz, int3
     h->last_rebuild = 0;
     h->last_pair = 0;
     h->pred.last = 0;
+    // A flush writes colptr and rowval: the kept structure (esp_handle::KeptStructure) is given up here.  What was valid is what
+    // the fused branch of flush_local may use once, and only that branch arms the stamp again.
+    h->kept.candidate = h->kept.valid;
+    h->kept.valid = false;
+    h->last_kept = 0;
     bool use_local = h->force_path != ESP_PATH_GENERAL;
     if (h->ones_pending && windowed(h)) CK(fix_tail(h));  // (cannot happen: a window is declared through fix_tail)
     if (h->pre.valid) {  // the producer's partition serves this flush if nothing changed since (appends BEHIND it may have)

@@ -14,6 +14,7 @@ thread_local std::string g_err;
 
 int32_t ensure(esp_handle *h, DevBuf &b, size_t need, bool keep) {
     if (b.bytes >= need && b.p) return ESP_OK;
+    if (h && (&b == &h->colptr || &b == &h->rowval || &b == &h->nzval)) drop_kept(h);  // (the buffer moves)
     size_t want = need;
     if (keep && b.bytes) want = std::max(need, b.bytes + b.bytes / 2);
     want = (want + 255) & ~(size_t)255;
@@ -110,6 +111,7 @@ void release(DevBuf &b) {
 }
 
 void release_all(esp_handle *h) {
+    drop_kept(h);
     for (DevBuf *b : {&h->keys, &h->vals, &h->keys2, &h->vals2, &h->hist, &h->segs, &h->colend, &h->newkey,
                       &h->newval, &h->heads, &h->misc, &h->pred.tab, &h->colptr, &h->colptr2, &h->rowval, &h->nzval, &h->rowval2,
                       &h->nzval2, &h->seg[0], &h->seg[1], &h->tilef[0], &h->tilef[1], &h->segcnt, &h->segout, &h->tseg, &h->ttile, &h->runbuf, &h->chunkbuf, &h->parttab, &h->piecetab, &h->asmwork, &h->sumrange, &h->csr_rowptr, &h->csr_perm, &h->csr_col, &h->csr_tmp, &h->csr_val, &h->mul_x, &h->mul_r, &h->kry.r, &h->kry.u, &h->kry.c, &h->kry.part, &h->kry.hb, &h->kry.hx, &h->kry.bv, &h->kry.t, &h->kry.sc, &h->lazy_hold, &h->elemplan.sorted, &h->elemplan.cellrec, &h->elemplan.segtab, &h->stage.d_rows, &h->stage.d_cols, &h->stage.d_vals, &h->stage.d_kinds, &h->bulk.d_rows, &h->bulk.d_cols, &h->bulk.d_vals, &h->bulk.d_kinds})
@@ -180,6 +182,7 @@ int32_t fix_tail(esp_handle *h) {
     if (h->ones_pending) {
         h->ones_pending = false;
         h->tail_stale = false;
+        drop_kept(h);  // (colptr is written)
         if (h->colptr.p)
             hipLaunchKernelGGL(fill_i64_k, dim3(grid_for(h->n + 1, 256)), dim3(256), 0, h->stream, (i64 *)h->colptr.p, h->n + 1, (i64)1);
         HIPCK(h, hipGetLastError());
@@ -187,6 +190,7 @@ int32_t fix_tail(esp_handle *h) {
     }
     if (!h->tail_stale) return ESP_OK;
     h->tail_stale = false;
+    drop_kept(h);
     const i64 from = h->wc1 + 1, cnt = h->n + 1 - from;
     if (cnt > 0 && h->colptr.p)
         hipLaunchKernelGGL(fill_i64_k, dim3(grid_for(cnt, 256)), dim3(256), 0, h->stream, (i64 *)h->colptr.p + from, cnt, h->nnz + 1);
@@ -196,6 +200,10 @@ int32_t fix_tail(esp_handle *h) {
 
 int32_t init_empty_csc(esp_handle *h) {
     CK(ensure(h, h->colptr, sizeof(i64) * (size_t)(h->n + 1)));
+    // A kept structure (esp_handle::KeptStructure) outlives the lazy branch alone, which writes neither colptr nor rowval: it is
+    // bound to the pattern version made below, so that a pattern change between two resets is seen by the flush that would keep.
+    const bool carry = h->kept.valid && h->kept.pattern_version == h->pattern_version && h->csc_valid && !windowed(h) && h->n > 4096;
+    if (!carry) drop_kept(h);
     if (h->csc_valid && windowed(h)) {
         // every entry was inside the window: colptr is 1 up to it already, the part behind it is refreshed lazily
         i64 c0, cnt;
@@ -213,6 +221,7 @@ int32_t init_empty_csc(esp_handle *h) {
     }
     h->nnz = 0;
     h->pattern_version++, h->values_version++;
+    if (carry) h->kept.pattern_version = h->pattern_version;
     h->csc_valid = true;
     return ESP_OK;
 }
@@ -352,6 +361,7 @@ extern "C" int32_t esp_clone(esp_handle *h, esp_handle **out) {
         return st;
     };
     int32_t st = ESP_OK;
+    drop_kept(h);  // (the copy is a fresh handle that keeps nothing; the source gives its stamp up with it: the next flush of either stores everything)
     if ((st = pending_materialize(h)) != ESP_OK) return fail(st);
     HIPCK(h, hipStreamSynchronize(h->stream));  // everything the copy reads is complete
     if (h->count > 0) {
@@ -1005,6 +1015,7 @@ extern "C" int32_t esp_set_csc(esp_handle *h, const int64_t *colptr, const int64
     if (!h || !colptr || nnz < 0 || (nnz > 0 && (!rowval || !nzval))) return ESP_ERR_INVALID;
     if (colptr[0] != 1 || colptr[h->n] != nnz + 1) FAIL(h, ESP_ERR_INVALID, "esp_set_csc: colptr[1]=%lld colptr[n+1]=%lld nnz=%lld violate the CSC invariants", (long long)colptr[0], (long long)colptr[h->n], (long long)nnz);
     (void)hipSetDevice(h->device);
+    drop_kept(h);  // (colptr and rowval are overwritten where they lie)
     CK(ensure(h, h->colptr, sizeof(i64) * (size_t)(h->n + 1)));
     CK(ensure(h, h->rowval, sizeof(i64) * (size_t)std::max<i64>(nnz, 1)));
     CK(ensure(h, h->nzval, sizeof(double) * (size_t)std::max<i64>(nnz, 1)));
@@ -1220,6 +1231,7 @@ extern "C" int32_t esp_set_csc_i32(esp_handle *h, const int32_t *colptr, const i
     if (!h || !colptr || nnz < 0 || (nnz > 0 && (!rowval || !nzval))) return ESP_ERR_INVALID;
     if (colptr[0] != 1 || (i64)colptr[h->n] != nnz + 1) FAIL(h, ESP_ERR_INVALID, "esp_set_csc_i32: colptr[1]=%d colptr[n+1]=%d nnz=%lld violate the CSC invariants", colptr[0], colptr[h->n], (long long)nnz);
     (void)hipSetDevice(h->device);
+    drop_kept(h);  // (colptr and rowval are overwritten where they lie)
     CK(ensure(h, h->colptr, sizeof(i64) * (size_t)(h->n + 1)));
     CK(ensure(h, h->rowval, sizeof(i64) * (size_t)std::max<i64>(nnz, 1)));
     CK(ensure(h, h->nzval, sizeof(double) * (size_t)std::max<i64>(nnz, 1)));
@@ -1295,6 +1307,7 @@ extern "C" int32_t esp_zero_values(esp_handle *h) {
 extern "C" int32_t esp_debug_force_path(esp_handle *h, int32_t path) {
     if (!h) return ESP_ERR_INVALID;
     h->force_path = path;
+    if (path == ESP_PATH_NO_KEPT_STRUCTURE) drop_kept(h);  // (pinned to the storing form from the next flush on)
     return ESP_OK;
 }
 extern "C" int32_t esp_debug_plan_cap(esp_handle *h, double cap) {

@@ -389,6 +389,7 @@ int32_t build_b(esp_precon *p) {
             if (ft != ESP_OK) FAIL(h, ft, "esp_precon_iluk: %s", sc->err.c_str());
             HIPCK(h, hipStreamSynchronize(sc->stream));
             if (sc->nnz != nnzB) FAIL(h, ESP_ERR_HIP, "esp_precon_iluk: the flush stored %lld entries of %lld", (long long)sc->nnz, (long long)nnzB);
+            drop_kept(sc);  // (the scratch handle gives its arrays away)
             std::swap(cp, sc->colptr);
             std::swap(rv, sc->rowval);
             std::swap(pay, sc->nzval);

@@ -161,6 +161,29 @@ struct esp_handle {
         espgen::FdArgs a;        // its argument block (part = GenPlan::out; the output arrays are filled in by lazy_expand)
     } lazyst;
     int last_lazy_stencil = 0;   // esp_debug_last_lazy_stencil: 0 not armed, 1 the fused kernel served the flush, 2 armed, then expanded
+    // The structure a served fused flush wrote stays where it is (round 16).  A time loop over a fixed grid has new values every
+    // step and the same pattern: when the next fused flush of the same plan, table, grid and kind finds colptr and rowval as that
+    // flush left them, the kernel's KEEP form stores the values alone -- 8 Z of the step's 16 Z + 8 (N + 1) bytes.
+    // Why the table's `hit` test proves the patterns equal: every step's pattern is a subset of the grid's structural pattern S
+    // (an update whose value folds to "not present" drops an entry and can never add one).  The stamp is armed only behind a
+    // flush P0 that hit the table in every pair with |P0| = |S|, so P0 = S and every pair's table count is its structural count;
+    // a step P1 that hits the table in every pair then has S's count in every pair, and a subset of S with S's count is S.
+    // The stamp describes what the buffers physically HOLD, so whatever may write colptr or rowval, or move them, drops it
+    // (drop_kept below): esp_flush on entry (only the served fused branch arms it again), ensure / release_all, the fills of
+    // colptr, esp_set_csc, the CSC editors, results installed into a handle, clones, shard calls.  Three conditions are checked
+    // where it is used as well: the three pointers, that the pattern version is the one the handle's last reset! made from the
+    // stamp's (whoever changes the pattern moves it), and that the lazy fill of colptr reset! left is still pending.
+    struct KeptStructure {
+        bool valid = false;
+        bool candidate = false;  // esp_flush moved `valid` here on entry: what its fused branch may use
+        u64 plan_gen = 0, pred_gen = 0;
+        i64 nx = 0, ny = 0, nz = 0;
+        int keys = 0;            // the kind instantiation (1 / 2)
+        const void *rowval = nullptr, *colptr = nullptr, *nzval = nullptr;
+        i64 nnz = 0;
+        unsigned long long pattern_version = 0;
+    } kept;
+    int last_kept = 0;           // esp_debug_last_kept_structure: 0 stored everything, 1 kept, 2 the kept form missed and the retry rewrote everything
     int last_rebuild = 0;        // the last flush's tail rebuilt the matrix (flush_rebuild: the stored CSC as the first piece of a fresh flush)
     int last_lazy_items = 0;     // the last flush's bucket kernel formed its updates from item records (esp_debug_last_lazy_items)
     int last_sum_join = 0;     // esp_debug_last_sum_join
@@ -385,6 +408,9 @@ static inline void drop_gen_plan(esp_handle *h) {
     if (h->genplan.valid) h->plan_gen++;
     h->genplan.valid = false;
 }
+
+// colptr / rowval may be written or moved: they are no longer known to hold what the last fused flush left (esp_handle::KeptStructure)
+static inline void drop_kept(esp_handle *h) { h->kept.valid = h->kept.candidate = false; }
 
 // the pending entries changed: whatever was derived from them is stale
 static inline void pending_changed(esp_handle *h) {
@@ -777,10 +803,10 @@ static inline unsigned grid_for(i64 n, int threads) { return (unsigned)std::max<
 
 // ---- small helpers
 // no force_path, or one that pins the bucket kernel's form alone (42: one bucket per workgroup, 43: no predicted offsets, 44: the
-// stencil batch is always written): every other choice automatic
+// stencil batch is always written, 45: the fused kernel always stores the structure): every other choice automatic
 static inline bool paths_auto(const esp_handle *h) {
     return h->force_path == ESP_PATH_AUTO || h->force_path == ESP_PATH_NO_BUCKET_PAIRS || h->force_path == ESP_PATH_NO_PREDICTED_OFFSETS ||
-           h->force_path == ESP_PATH_NO_LAZY_STENCIL;
+           h->force_path == ESP_PATH_NO_LAZY_STENCIL || h->force_path == ESP_PATH_NO_KEPT_STRUCTURE;
 }
 static inline bool windowed(const esp_handle *h) { return h->win_excl && (h->wc0 > 0 || h->wc1 < h->n); }
 

@@ -405,6 +405,7 @@ int32_t transpose_generic(esp_handle *c, const Csc64 &A, i64 mC, i64 nC, DevBuf 
     if (ft != ESP_OK) FAIL(c, ft, "esp_transpose: %s", sc->err.c_str());
     HIPCK(c, hipStreamSynchronize(sc->stream));
     if (sc->nnz != A.nnz) FAIL(c, ESP_ERR_HIP, "esp_transpose: the flush stored %lld entries of %lld", (long long)sc->nnz, (long long)A.nnz);
+    drop_kept(sc);  // (the scratch handle gives its arrays away)
     std::swap(cp, sc->colptr);
     std::swap(rv, sc->rowval);
     std::swap(nz, sc->nzval);

@@ -142,7 +142,7 @@ bool launch_pair_predicted(const Variant &v, unsigned grid, hipStream_t stream, 
 // ... and the predicted form that FORMS the pair's updates itself (pair_gen_pred_k, local_x.hip): the batch is the stencil
 // generator's over the full node range and was never written (esp_handle::LazyStencil) -- keys_in / vals_in / seg_start are not read
 bool launch_pair_gen_predicted(const Variant &v, unsigned grid, hipStream_t stream, const Args &a, const espgen::FdArgs &fd, const u64 *pred,
-                               u64 out_cap);  // local_x.hip
+                               u64 out_cap, bool keep);  // local_x.hip (keep: colptr and rowval stay as they are, values only)
 // pred[s] = colptr[first column of pair s] - 1 for s < Sp, pred[Sp] = colptr[col_end] - 1: the table a look-back flush leaves
 void launch_pair_record(hipStream_t stream, const i64 *colptr, i64 col_end, int ncl_bits, int Sp, u64 *pred);
 

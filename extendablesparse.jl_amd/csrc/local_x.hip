@@ -16,6 +16,11 @@
 // the grand total and a miss in pinned host memory (Args::host_words).  No ticket, no look-back, nothing that waits for another
 // workgroup, no memset in front of the launch and no copy behind it.
 //
+// A step that repeats the last one's structure stores the values alone (the template parameter KEEP, esp_handle::KeptStructure):
+// colptr and rowval -- 8 Z + 8 (N + 1) of the 16 Z + 8 (N + 1) bytes -- already lie where the handle's last fused flush wrote them.
+// The kernel was store-limited (393 us at 256^3, 273 without the rowval store; NOTES/round16.md); the KEEP form needs no rows in
+// LDS (28 KiB: four workgroups per CU) and takes 226 us.
+//
 // Where the values come from is the template parameter SRC (FdSource: the built-in generator's draws, the expressions and the
 // operation order of espgen::fdrand_part_k -- compiled without FMA contraction like every unit); a source that reads edge
 // coefficients from a caller's arrays fills the same StencilColumn.
@@ -38,6 +43,12 @@ struct StencilColumn {
     double vlo[3], vhi[3], vb[3];
 };
 
+// f() where some active lane of the wave has `on` (a wave-uniform branch: no lane data crosses), else 0.0 -- a value nobody reads
+template <class F>
+__device__ __forceinline__ double draw_if(bool on, F f) {
+    return __ballot(on) != 0 ? f() : 0.0;
+}
+
 // the built-in generator (espgen::FdArgs without the producer's tables)
 struct FdSource {
     i64 nx, ny, nz;
@@ -46,40 +57,46 @@ struct FdSource {
     int rand_mode;
     int fast;
     u64 magic_nx, magic_nxny;
+    u64 zsub[3];  // 6 d GOLDEN for d = nx ny, nx, 1 (wrapping u64, formed once on the host): draw 0 of node g - d has the counter z0(g) - zsub
 
     __device__ __forceinline__ void column(i64 g, StencilColumn &c) const {
         i64 i, j, k;
         espgen::fd_node(*this, g, &i, &j, &k);
         const i64 nxy = nx * ny;
         const int md = rand_mode;
-        // draw q of node gg: counter 6 gg + q (espgen::fd_rand_z)
-        auto z0 = [&](i64 gg) -> u64 { return seed + (6ull * (u64)gg + 1ull) * ESP_GOLDEN; };
-        const u64 zg = z0(g);
+        // draw q of node gg: counter 6 gg + q (espgen::fd_rand_z); z0(g - d) = z0(g) - 6 d GOLDEN exactly (the arithmetic wraps)
+        const u64 zg = seed + (6ull * (u64)g + 1ull) * ESP_GOLDEN;
         c.stride[0] = nxy, c.stride[1] = nx, c.stride[2] = 1;
         c.lo[0] = k > 1, c.lo[1] = j > 1, c.lo[2] = i > 1;
         c.hi[0] = i < nx, c.hi[1] = j < ny, c.hi[2] = k < nz;
         c.b[0] = i == 1 || i == nx;
         c.b[1] = ny > 2 && (j == 1 || j == ny);
         c.b[2] = nz > 2 && (k == 1 || k == nz);
-        // (a neighbour that does not exist: some draw nobody looks at -- every lane does the same arithmetic)
-        c.vlo[0] = espgen::fd_rand_z(md, z0(g - nxy), 4) * hx * hy / hz;
-        c.vlo[1] = espgen::fd_rand_z(md, z0(g - nx), 2) * hx * hz / hy;
-        c.vlo[2] = espgen::fd_rand_z(md, z0(g - 1), 0) * hy * hz / hx;
+        // A lower neighbour's or a boundary draw is formed only where some lane of the wave uses it (the kernel's step() does
+        // not look at a value whose flag is off: 0.0 stands there).  At 256^3 the y and z boundary draws are skipped in more than
+        // 99 % of the waves, the x boundary draw in half of them.
+        c.vlo[0] = draw_if(c.lo[0], [&] { return espgen::fd_rand_z(md, zg - zsub[0], 4) * hx * hy / hz; });
+        c.vlo[1] = draw_if(c.lo[1], [&] { return espgen::fd_rand_z(md, zg - zsub[1], 2) * hx * hz / hy; });
+        c.vlo[2] = draw_if(c.lo[2], [&] { return espgen::fd_rand_z(md, zg - zsub[2], 0) * hy * hz / hx; });
         c.vhi[0] = espgen::fd_rand_z(md, zg, 0) * hy * hz / hx;
-        c.vb[0] = espgen::fd_rand_z(md, zg, 1) * hy * hz;
+        c.vb[0] = draw_if(c.b[0], [&] { return espgen::fd_rand_z(md, zg, 1) * hy * hz; });
         c.vhi[1] = espgen::fd_rand_z(md, zg, 2) * hx * hz / hy;
-        c.vb[1] = espgen::fd_rand_z(md, zg, 3) * hx * hz;
+        c.vb[1] = draw_if(c.b[1], [&] { return espgen::fd_rand_z(md, zg, 3) * hx * hz; });
         c.vhi[2] = espgen::fd_rand_z(md, zg, 4) * hx * hy / hz;
-        c.vb[2] = espgen::fd_rand_z(md, zg, 5) * hx * hy;
+        c.vb[2] = draw_if(c.b[2], [&] { return espgen::fd_rand_z(md, zg, 5) * hx * hy; });
     }
 };
 
-template <int KEYS, class SRC>
+// KEEP: colptr and rowval hold what the handle's last fused flush of this plan, table, grid and kind wrote, and that flush emitted
+// the grid's whole structural pattern (esp_handle::KeptStructure) -- a step that hits the table in every pair then has that very
+// pattern, so the kernel stores the values alone: no srow (the LDS holds the values only), no out_row, no colptr.  Everything that
+// decides is the writing form's: the fold, the scan, the `hit` test, PRED_MISS and the grand total.
+template <int KEYS, class SRC, bool KEEP>
 __global__ __launch_bounds__(THREADS, 6) void pair_gen_pred_k(Args a, SRC src, const u64 *pred, u64 out_cap) {
     static_assert(KEYS == 1 || KEYS == 2, "one kind: 2 = every update is an UPDATE");
     constexpr bool UPD = KEYS == 2;
-    __shared__ u32 srow[G_CAP];     // the records' rows (1-based) ...
-    __shared__ double sval[G_CAP];  // ... and values
+    __shared__ u32 srow[KEEP ? 1 : G_CAP];  // the records' rows (1-based; not kept by the KEEP form) ...
+    __shared__ double sval[G_CAP];          // ... and values
     __shared__ u32 lw[WAVES];
 
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -151,7 +168,7 @@ __global__ __launch_bounds__(THREADS, 6) void pair_gen_pred_k(Args a, SRC src, c
 #pragma unroll
         for (int q = 0; q < G_ROWS; q++) {
             if (present[q]) {
-                srow[at] = row[q];
+                if constexpr (!KEEP) srow[at] = row[q];
                 sval[at] = acc[q];
                 at++;
             }
@@ -160,27 +177,36 @@ __global__ __launch_bounds__(THREADS, 6) void pair_gen_pred_k(Args a, SRC src, c
     __syncthreads();
     // ---- coalesced stores; the lane of a column writes its colptr
     for (int p = t; p < (int)total; p += THREADS) {
-        a.out_row[dst + p] = (i64)srow[p];
+        if constexpr (!KEEP) a.out_row[dst + p] = (i64)srow[p];
         a.out_val[dst + p] = sval[p];
     }
-    if (has) a.colptr_out[c_lo + t] = (i64)(dst + at0) + 1;
+    if constexpr (!KEEP) {
+        if (has) a.colptr_out[c_lo + t] = (i64)(dst + at0) + 1;
+    }
     if (s == a.S - 1 && t == 0) {
-        a.colptr_out[a.col_end] = (i64)(dst + total) + 1;
+        if constexpr (!KEEP) a.colptr_out[a.col_end] = (i64)(dst + total) + 1;
         a.host_words[0] = ST_PRE | ((dst + (u64)total) & ST_VAL);  // (the grand total, in the form of lb_complete's last granule)
     }
 }
 
 bool launch_pair_gen_predicted(const Variant &v, unsigned grid, hipStream_t stream, const Args &a, const espgen::FdArgs &fd, const u64 *pred,
-                               u64 out_cap) {
+                               u64 out_cap, bool keep) {
     // (whole columns, at most 512 of them per pair, rows that fit the records' 32 bits)
     if (!v.fresh || v.pieces || a.cl_bits < 0 || (2 << a.cl_bits) > THREADS || a.rb >= 32 || !a.colptr_out || !a.host_words) return false;
-    const FdSource src{fd.nx, fd.ny, fd.nz, fd.hx, fd.hy, fd.hz, fd.seed, fd.rand_mode, fd.fast, fd.magic_nx, fd.magic_nxny};
+    const FdSource src{fd.nx, fd.ny, fd.nz, fd.hx, fd.hy, fd.hz, fd.seed, fd.rand_mode, fd.fast, fd.magic_nx, fd.magic_nxny,
+                       {6ull * (u64)(fd.nx * fd.ny) * ESP_GOLDEN, 6ull * (u64)fd.nx * ESP_GOLDEN, 6ull * ESP_GOLDEN}};
     if (v.keys == 1) {
-        hipLaunchKernelGGL((pair_gen_pred_k<1, FdSource>), dim3(grid), dim3(THREADS), 0, stream, a, src, pred, out_cap);
+        if (keep)
+            hipLaunchKernelGGL((pair_gen_pred_k<1, FdSource, true>), dim3(grid), dim3(THREADS), 0, stream, a, src, pred, out_cap);
+        else
+            hipLaunchKernelGGL((pair_gen_pred_k<1, FdSource, false>), dim3(grid), dim3(THREADS), 0, stream, a, src, pred, out_cap);
         return true;
     }
     if (v.keys == 2) {
-        hipLaunchKernelGGL((pair_gen_pred_k<2, FdSource>), dim3(grid), dim3(THREADS), 0, stream, a, src, pred, out_cap);
+        if (keep)
+            hipLaunchKernelGGL((pair_gen_pred_k<2, FdSource, true>), dim3(grid), dim3(THREADS), 0, stream, a, src, pred, out_cap);
+        else
+            hipLaunchKernelGGL((pair_gen_pred_k<2, FdSource, false>), dim3(grid), dim3(THREADS), 0, stream, a, src, pred, out_cap);
         return true;
     }
     return false;

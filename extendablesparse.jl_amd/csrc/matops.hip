@@ -418,6 +418,7 @@ Csc64 csc_of(const esp_handle *h) {
 }  // namespace
 // c takes the new CSC (a pattern change, as a flush that rebuilds leaves it)
 void install(esp_handle *c, DevBuf &cp, DevBuf &rv, DevBuf &nz, i64 nnz) {
+    drop_kept(c);  // (other buffers from here on)
     std::swap(c->colptr, cp);
     std::swap(c->rowval, rv);
     std::swap(c->nzval, nz);

@@ -8,6 +8,7 @@
 int32_t shard_prepare(esp_handle *h, int P, espradix::Pass *out) {
     if (P < 1 || P > 256) FAIL(h, ESP_ERR_INVALID, "shards: nshards must be in 1..256");
     h->shard_user = true;
+    drop_kept(h);  // (a shard's flushes are never the fused stencil flush: nothing is kept across them)
     CK(pending_materialize(h));
     h->part_valid = h->part_assembled = false;  // (its tables share scratch arrays with this path)
     drop_gen_plan(h), drop_raw_plan(h);  // (seg[1] and the histogram arrays are rewritten: a kept producer plan would read them)
@@ -382,6 +383,7 @@ __global__ void piece_totals_k(const i64 *__restrict__ pstart, int P, i64 nb, un
 extern "C" int32_t esp_shard_plan(esp_handle *h, int32_t nshards, int32_t self, int64_t entries_per_shard) {
     if (!h) return ESP_ERR_INVALID;
     h->shard_user = true;
+    drop_kept(h);  // (a shard's flushes are never the fused stencil flush: nothing is kept across them)
     h->shard_plan.valid = nshards >= 1 && self >= 0 && self < nshards && entries_per_shard >= 0;
     h->shard_plan.P = nshards;
     h->shard_plan.me = self;
@@ -401,6 +403,11 @@ extern "C" int32_t esp_debug_last_lazy_items(const esp_handle *h, int32_t *on) {
 extern "C" int32_t esp_debug_last_lazy_stencil(const esp_handle *h, int32_t *state) {
     if (!h || !state) return ESP_ERR_INVALID;
     *state = h->last_lazy_stencil;
+    return ESP_OK;
+}
+extern "C" int32_t esp_debug_last_kept_structure(const esp_handle *h, int32_t *state) {
+    if (!h || !state) return ESP_ERR_INVALID;
+    *state = h->last_kept;
     return ESP_OK;
 }
 extern "C" int32_t esp_debug_last_sum_join(const esp_handle *h, int32_t *segments) {
@@ -456,6 +463,7 @@ extern "C" int32_t esp_shard_partition(esp_handle *h, int32_t nshards, int32_t s
     if (P < 1 || self < 0 || self >= P || entries_per_shard < 0) FAIL(h, ESP_ERR_INVALID, "esp_shard_partition: arguments");
     (void)hipSetDevice(h->device);
     h->shard_user = true;
+    drop_kept(h);  // (a shard's flushes are never the fused stencil flush: nothing is kept across them)
     const i64 E = h->count;
     // the producer already partitioned this very batch for this very call (esp_shard_plan): nothing to move
     const bool from_producer = h->pre.valid && h->pre.mw_P == nshards && h->pre.mw_me == self && h->pre.mw_eps == entries_per_shard &&

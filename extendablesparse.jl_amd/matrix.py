@@ -926,6 +926,13 @@ class ExtendableSparseMatrix:
         self._d.ck(self._d.lib.esp_debug_last_lazy_stencil(self._d.h, C.byref(p)))
         return p.value
 
+    def debug_last_kept_structure(self):
+        """What the last flush did with colptr / rowval: 0 stored everything, 1 kept them (the fused stencil flush stored the values
+        alone), 2 the kept form missed and the retry rewrote everything; debug_force_path(ESP_PATH_NO_KEPT_STRUCTURE): never 1"""
+        p = C.c_int32()
+        self._d.ck(self._d.lib.esp_debug_last_kept_structure(self._d.h, C.byref(p)))
+        return p.value
+
     def debug_last_rebuild(self):
         """1: the last flush rebuilt the matrix for the entries behind a re-assembly's batch (stored entries as a first piece)"""
         p = C.c_int32()

@@ -917,6 +917,10 @@ typedef enum {
                                         never the fused form in which a repeated full-range batch on a fresh matrix stays unwritten
                                         and the predicted pair kernel forms every column's updates itself (see
                                         esp_debug_last_lazy_stencil).  Counts as automatic for every other choice, like 42 and 43 */
+    ESP_PATH_NO_KEPT_STRUCTURE = 45, /* the fused stencil flush always stores colptr and rowval: never its KEEP form, in which a
+                                        repeated step whose structure the handle's last fused flush left in these very buffers stores
+                                        the values alone (see esp_debug_last_kept_structure).  Counts as automatic for every other
+                                        choice, like 42, 43 and 44                                                             */
     ESP_PATH_NO_PLAN_REUSE = 31     /* esp_append_device / esp_commit of one kind on an empty buffer always count their columns
                                         (never the run lists of the previous, identical-looking batch)                      */
 } esp_debug_path;
@@ -986,6 +990,14 @@ int32_t esp_debug_last_lazy_items(const esp_handle *h, int32_t *on);
  * other than that flush needed the entries -- an append behind the batch, a read of the pending buffer, a clone, a shard call, a
  * second generator call -- or the prediction missed) */
 int32_t esp_debug_last_lazy_stencil(const esp_handle *h, int32_t *state);
+/* what the last flush did with the structure (colptr, rowval): 0 it stored everything (every flush but the one below), 1 KEPT -- the
+ * fused stencil flush found colptr and rowval as the handle's last fused flush of the same plan, offset table, grid and kind left
+ * them, that flush had emitted the grid's whole structural pattern, and every pair hit the table: the pattern is the stored one and
+ * the kernel stored the values alone (n > 4096, no column window; esp_reset and esp_zero_values in between keep the structure,
+ * whatever else may write or move colptr / rowval -- a read that resolves reset!'s lazy colptr, esp_set_csc, an editor of the CSC, a
+ * result installed into the handle, esp_clone, a shard call, esp_release_buffers -- makes the next flush store everything), 2 the
+ * KEEP form missed (some pair's count differs from the table's) and the retry rewrote everything.  esp_debug_force_path(45): never 1 */
+int32_t esp_debug_last_kept_structure(const esp_handle *h, int32_t *state);
 /* how many neighbouring segments of the folds' plan the combine flush of the last esp_flush_sum of that kind (last_lazy_items 2)
  * joined into one (1, 2, 4 or 8: as many as keep the longest joined segment within the bucket kernel's capacity); 0 otherwise */
 int32_t esp_debug_last_sum_join(const esp_handle *h, int32_t *segments);
