@@ -126,515 +126,513 @@ int32_t prepare_outputs(esp_handle *h, i64 Z0, i64 Zn) {
     return ESP_OK;
 }
 
-// fast path: LDS bucket kernel over the MSD segments; writes the final arrays itself
-int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
-    const i64 Z0 = h->nnz;
-    const i64 N1 = h->n + 1;
+// ---- fast path: the LDS bucket kernel over the MSD segments writes the final arrays itself.  flush_local (below) is a choice
+// made once (choose_local), one argument block (fill_args), attempts (launch_attempt) and a ladder of retries (retry_attempt).
+
+// Everything that is decided before the first launch.  use_pred and want_wide are where the ladder STARTS (LocalTry carries them
+// on); the handle's pair_off / g3_off, which the rungs set, are read at launch time.
+struct LocalChoice {
+    int S;                   // segments launched: the table's, cut behind the last column
+    i64 total_check;         // Args::total (>= 0: S was cut)
+    i64 col_begin, col_end;  // the column range this flush can touch (all columns, or the column window of a shard)
+    int clb, cl_bits;        // rem_bits - rb; the same where the kernel counts a segment's columns in LDS, else -1
+    u64 seg_base;            // key base of the segments
+    bool stopping;           // ESP_LOCAL_STOP (experiments build only: ablation of the bucket kernel) ...
+    int stop_after;          // ... and its value
+    int no_group, late_total, kind_all;  // Args' members of these names
+    bool fresh, direct, small_variant, pair_ok, pred_batch, use_pred, fused, keep;
+    int keys, pair_keys;  // key format of the regular kernels (0 .. 7) and of pair_k and its fused form (1 / 2: what a kept structure is stamped with)
+    double longest;       // the longest column run to expect
+    bool grp, big, g3_plain, g3_k64, want_wide, try_hits;
+};
+
+static LocalChoice choose_local(const esp_handle *h, const Sorted &st, int mode) {
+    LocalChoice c;
+    const int fp = h->force_path;
+    c.fresh = h->nnz == 0;
+    c.clb = st.rem_bits - h->L.rb;
     // Segments behind the last column hold nothing (a matrix of 10^7 columns fills 60 % of the 2^24 its column bits span:
     // 40 % of the segments, each of which would still draw a ticket, resolve its offset and leave): the launch ends at
     // the segment of the last column; that segment checks that every entry lies in front of its end (Args::total).
-    int S = st.S;
-    i64 total_check = -1;
-    if (st.npieces == 0 && st.total >= 0 && st.seg_start && st.rem_bits >= h->L.rb && st.rem_bits - h->L.rb < 40 && S > 1) {
-        const int clb0 = st.rem_bits - h->L.rb;
+    c.S = st.S;
+    c.total_check = -1;
+    if (st.npieces == 0 && st.total >= 0 && st.seg_start && c.clb >= 0 && c.clb < 40 && c.S > 1) {
         // (the segments cut the key window: its first column, and the column behind its last)
         const i64 c_first = (i64)(h->win_base >> h->L.rb), c_last = (i64)((h->win_base + h->win_span) >> h->L.rb);
-        const i64 need = ceil_div<i64>(c_last - c_first, (i64)1 << clb0);
-        if (need >= 1 && need < (i64)S) {
-            S = (int)need;
-            total_check = st.total;
+        const i64 need = ceil_div<i64>(c_last - c_first, (i64)1 << c.clb);
+        if (need >= 1 && need < (i64)c.S) {
+            c.S = (int)need;
+            c.total_check = st.total;
         }
     }
-    // esp_flush normalised the buffers: data in keys/vals, scratch pair = keys2/vals2
-    u64 *tk = (u64 *)h->keys2.p;
-    double *tv = (double *)h->vals2.p;
-    // look-back granules: one per segment | error flag | longest run | one per group of 256 segments, rounded up to a 4 KiB
-    // page; behind them a page of its own for the ticket counter (every workgroup draws from it while others poll the
-    // granules: on one line with them the draws cost the headline's bucket kernel 0.18 of 1.55 ms) -- one memset clears
-    // everything
-    const i64 n_gs = ((i64)S >> 8) + 2;  // (local.hpp: LB_SHIFT = 8)
-    const i64 G = (((i64)S + 2 + n_gs + 511) & ~(i64)511) - (S + 2);  // (granules behind status[S + 1])
-    const i64 tick_at = S + 2 + G + 256;
-    CK(ensure(h, h->segout, sizeof(u64) * (size_t)(S + 2 + G + 512)));
-    u64 *status = (u64 *)h->segout.p;
-    const size_t status_bytes = sizeof(u64) * (size_t)(S + 2 + G + 512);
-    CK(ensure(h, h->colend, sizeof(u64) * (size_t)(N1 + espscan::workspace_elems(N1))));
-    esplocal::Args a;
-    memset(&a, 0, sizeof a);
-    const char *stop_env = esp_exp_env("ESP_LOCAL_STOP");  // (experiments build only: ablation of the bucket kernel)
+    const char *stop_env = esp_exp_env("ESP_LOCAL_STOP");
+    c.stopping = stop_env != nullptr;
+    c.stop_after = stop_env ? atoi(stop_env) : 0;
+    c.late_total = fp == ESP_PATH_LATE_TOTAL ? 1 : 0;  // 36: test hook, group3_k publishes a segment's total after the fold
+    c.no_group = fp == ESP_PATH_NO_GROUP_TIER ? 1 : 0;  // 24: test hook, long column runs through the radix tier
+    // (every pending entry was noted with one kind; pieces of other ranks carry kinds this handle has not seen)
+    c.kind_all = (st.npieces == 0 && h->kind_uniform >= 0 && h->kind_noted == h->count && fp != ESP_PATH_GENERIC_FOLD) ? h->kind_uniform : -1;
+    c.cl_bits = (c.clb >= 0 && c.clb <= esplocal::CL_MAX_BITS && fp != ESP_PATH_RADIX_TAIL_ONLY) ? c.clb : -1;
+    c.col_begin = windowed(h) ? h->wc0 : 0, c.col_end = windowed(h) ? h->wc1 : h->n;
+    c.seg_base = st.has_base ? st.base : st.npieces > 0 ? h->part_base : h->win_base;
     // A fresh matrix whose segments are whole blocks of <= CL_MAX columns that start at the first column of the
     // range this flush can touch (all columns, or the column window of a shard) and cover it: every segment writes
     // the colptr of its own columns (no column-end marks, no memset and no scan over the columns).
     // force_path 13: marks + scan.
-    bool direct = false;
-    const i64 col_begin = windowed(h) ? h->wc0 : 0, col_end = windowed(h) ? h->wc1 : h->n;
-    {
-        const int clb = st.rem_bits - h->L.rb;
-        const u64 seg_base = st.has_base ? st.base : st.npieces > 0 ? h->part_base : h->win_base;
-        direct = Z0 == 0 && clb >= 0 && clb <= esplocal::CL_MAX_BITS && h->force_path != ESP_PATH_RADIX_TAIL_ONLY && h->force_path != ESP_PATH_COLPTR_BY_SCAN && !stop_env &&
-                 seg_base == ((u64)col_begin << h->L.rb) && col_begin + ((i64)S << clb) >= col_end;
-    }
-    h->last_colptr_direct = direct ? 1 : 0;
-    if (!direct) {
-        i64 c0, cnt;
-        col_range(h, &c0, &cnt);
-        HIPCK(h, hipMemsetAsync((u64 *)h->colend.p + c0, 0, sizeof(u64) * (size_t)cnt, h->stream));
-    }
-    // (a failed flush must not leave a half-written colptr behind)
-    auto restore_colptr = [&]() {
-        if (direct) {
-            hipLaunchKernelGGL(fill_i64_k, dim3(grid_for(N1, 256)), dim3(256), 0, h->stream, (i64 *)h->colptr.p, N1, (i64)1);
-            h->tail_stale = false;
-            h->ones_pending = false;
-        }
-    };
+    c.direct = c.fresh && c.cl_bits >= 0 && fp != ESP_PATH_COLPTR_BY_SCAN && !c.stopping && c.seg_base == ((u64)c.col_begin << h->L.rb) &&
+               c.col_begin + ((i64)c.S << c.clb) >= c.col_end;
+    // the pending entries per column: what stands in for the handle's history where it has none
+    const double cols = (double)std::max<i64>(c.col_end - c.col_begin, 1), per_col = (double)h->count / cols;
     // The small variant of the bucket kernel (3 workgroups per CU) serves segments of at most 3072 entries over at most
     // 256 columns whose column runs the register tiers take; a segment with longer runs (it cannot know before it counts)
     // goes through the variant's slow tier, and what it reports sends the next flushes to the regular kernel.
     // force_path 18: never.
-    bool small_variant = false;
-    {
-        const int clb = st.rem_bits - h->L.rb;
-        // (what the handle's last flush saw decides; a handle without history tries it when the columns hold few entries
-        // on average -- a stencil's 12, not a 3-D FEM mesh's 120)
-        const double per_col = (double)h->count / (double)std::max<i64>(col_end - col_begin, 1);
-        // (runs of 17..24 want the 24-input network, which does not fit the variant's 80 registers: measured 4.7 against
-        // 4.0 ms on 2-D FEM)
-        const bool runs_fit = h->seen_maxrun > 0 ? h->seen_maxrun <= 16 : per_col <= 16.0;
-        small_variant = st.maxlen <= 6 * esplocal::THREADS && clb >= 0 && clb <= 8 &&
-                        st.rem_bits <= esplocal::REG_MAX_REM && runs_fit && h->force_path != ESP_PATH_RADIX_TAIL_ONLY &&
-                        h->force_path != ESP_PATH_NO_SMALL_VARIANT && !stop_env;
-    }
-    h->last_local_small = small_variant ? 1 : 0;
+    // (what the handle's last flush saw decides; a handle without history tries it when the columns hold few entries
+    // on average -- a stencil's 12, not a 3-D FEM mesh's 120)
+    // (runs of 17..24 want the 24-input network, which does not fit the variant's 80 registers: measured 4.7 against
+    // 4.0 ms on 2-D FEM)
+    const bool runs_fit = h->seen_maxrun > 0 ? h->seen_maxrun <= 16 : per_col <= 16.0;
+    c.small_variant = st.maxlen <= 6 * esplocal::THREADS && c.clb >= 0 && c.clb <= 8 && st.rem_bits <= esplocal::REG_MAX_REM && runs_fit &&
+                      fp != ESP_PATH_RADIX_TAIL_ONLY && fp != ESP_PATH_NO_SMALL_VARIANT && !c.stopping;
     // The small variant's PAIR form (pair_k, local_w.hip): one workgroup takes two neighbouring buckets of the table -- a fresh
     // matrix whose segments write colptr themselves, 4-byte keys of one kind, one bucket per segment of the table (a FINE
     // partition's segments are several buckets already), at most 12 pending entries per column.  A pair with a longer column run
     // or rows spread over 2^19 or more makes the flush run again with local_k, which then serves the handle.  force_path 42: never.
-    const bool pair_ok = small_variant && direct && Z0 == 0 && st.npieces == 0 && st.key_bytes == 4 && st.fb == 0 && !st.lazy &&
-                         !windowed(h) && h->L.rb < 32 && h->seen_maxrun == 0 &&
-                         (double)h->count <= (double)esplocal::PAIR_RUN * (double)std::max<i64>(col_end - col_begin, 1) &&
-                         h->force_path != ESP_PATH_NO_BUCKET_PAIRS && h->force_path != ESP_PATH_GENERIC_FOLD;
-    bool used_pair = false;
+    c.pair_ok = c.small_variant && c.direct && st.npieces == 0 && st.key_bytes == 4 && st.fb == 0 && !st.lazy && !windowed(h) && h->L.rb < 32 &&
+                h->seen_maxrun == 0 && (double)h->count <= (double)esplocal::PAIR_RUN * cols && fp != ESP_PATH_NO_BUCKET_PAIRS &&
+                fp != ESP_PATH_GENERIC_FOLD;
     // ... and its PREDICTED form (pair_pred_k): the batch repeats the producer plan of the handle's last flush (GenPlan / RawPlan:
     // the same buckets) and nothing lies behind it, and that flush left the offsets its look-back found (esp_handle::PredTable) --
     // every pair writes at the table's offset when it emits the table's count, no ticket and no look-back; a pair that emits
     // another count (structural zeros moved) stores nothing and the flush runs again with pair_k.  force_path 43: never.
-    const bool pred_batch = pair_ok && paths_auto(h) && h->force_path != ESP_PATH_NO_PREDICTED_OFFSETS && h->pre.valid && h->pre.tail == 0 &&
-                            h->count == h->pre.E && st.seg_start == (const i64 *)h->seg[1].p && (h->genplan.valid || h->rawplan.valid);
-    bool use_pred = pred_batch && !h->pair_off && h->last_plan_reused == 1 && h->pred.gen == h->plan_gen && h->pred.S == S && h->pred.tab.p &&
-                    h->pred.misses < 2 && h->force_path != ESP_PATH_MANY_LAUNCHES && !st.no_pred;
-    // A stencil batch that was never written (esp_handle::LazyStencil): the predicted form's fused kernel (pair_gen_pred_k) or
-    // nothing -- the caller issues the PART launch that was held back and comes again with the entries.
-    if (st.stencil && !use_pred) return ESP_RETRY_EXPANDED;
-    // The fused kernel stores its grand total and its error bits straight into pinned host memory (esp_handle::pin_words): the host
-    // clears the words here and reads them after the synchronise -- no memset in front of the kernel, no copy behind it.  (The
-    // window flag is not fetched: the batch is armed on unwindowed handles only.  The stream is idle: the handle's last flush
-    // ended with a synchronise.)
-    const bool fused = st.stencil && use_pred;
+    c.pred_batch = c.pair_ok && paths_auto(h) && fp != ESP_PATH_NO_PREDICTED_OFFSETS && h->pre.valid && h->pre.tail == 0 && h->count == h->pre.E &&
+                   st.seg_start == (const i64 *)h->seg[1].p && (h->genplan.valid || h->rawplan.valid);
+    c.use_pred = c.pred_batch && !h->pair_off && h->last_plan_reused == 1 && h->pred.gen == h->plan_gen && h->pred.S == c.S && h->pred.tab.p &&
+                 h->pred.misses < 2 && fp != ESP_PATH_MANY_LAUNCHES && !st.no_pred;
+    // The fused kernel (pair_gen_pred_k) stores its grand total and its error bits straight into pinned host memory
+    // (esp_handle::pin_words): the host clears the words and reads them after the synchronise -- no memset in front of the kernel,
+    // no copy behind it.  (The window flag is not fetched: the batch is armed on unwindowed handles only.  The stream is idle: the
+    // handle's last flush ended with a synchronise.)
+    c.fused = st.stencil && c.use_pred;
+    c.pair_keys = st.kind == ESP_UPDATE ? 2 : 1;
     // The kernel's KEEP form (values only) when colptr and rowval still hold what the handle's last fused flush of this plan,
     // table, grid and kind left there, and that flush emitted the grid's whole structural pattern (esp_handle::KeptStructure has
     // the argument): the stamp esp_flush found valid on entry, the three buffers where they were, the pattern version the one
     // reset! made from the stamp's, and reset!'s lazy fill of colptr still pending (n > 4096: a smaller matrix is filled at once).
     // force_path 45: never.
-    const int fused_keys = st.kind == ESP_UPDATE ? 2 : 1;
-    bool keep = false;
-    if (fused) {
+    c.keep = false;
+    if (c.fused) {
         const esp_handle::KeptStructure &ks = h->kept;
         const espgen::FdArgs &fd = st.stencil->a;
-        keep = ks.candidate && h->force_path != ESP_PATH_NO_KEPT_STRUCTURE && h->n > 4096 && direct && !windowed(h) && h->ones_pending &&
-               ks.plan_gen == h->plan_gen && ks.pred_gen == h->pred.gen && ks.nx == fd.nx && ks.ny == fd.ny && ks.nz == fd.nz &&
-               ks.keys == fused_keys && ks.colptr == h->colptr.p && ks.rowval == h->rowval.p && ks.nzval == h->nzval.p &&
-               ks.pattern_version == h->pattern_version && ks.nnz > 0;
+        c.keep = ks.candidate && fp != ESP_PATH_NO_KEPT_STRUCTURE && h->n > 4096 && c.direct && !windowed(h) && h->ones_pending &&
+                 ks.plan_gen == h->plan_gen && ks.pred_gen == h->pred.gen && ks.nx == fd.nx && ks.ny == fd.ny && ks.nz == fd.nz &&
+                 ks.keys == c.pair_keys && ks.colptr == h->colptr.p && ks.rowval == h->rowval.p && ks.nzval == h->nzval.p &&
+                 ks.pattern_version == h->pattern_version && ks.nnz > 0;
     }
-    h->kept.candidate = false;
-    // (the predicted form reads the error / longest-run words and leaves the grand total in the last granule: nothing else to clear)
-    if (fused)
-        h->pin_words[0] = h->pin_words[1] = h->pin_words[2] = 0ull;
-    else if (use_pred)
-        HIPCK(h, hipMemsetAsync(status + (S - 1), 0, 3 * sizeof(u64), h->stream));
-    else
-        HIPCK(h, hipMemsetAsync(status, 0, status_bytes, h->stream));
-    std::function<int32_t(bool)> launch_all;
-    bool used_g3 = false;
-    bool want_wide = h->g3_wide && h->force_path != ESP_PATH_NO_WIDE_GROUP3;
-    {
-        Span sp(h, ESP_ST_LOCAL);
-        a.kind32 = (u32)((st.key_bytes == 4 || st.p32_piece >= 0 || st.all32) ? st.kind : 0);
-        a.k32_piece = st.p32_piece;
-        a.k32_lo = st.p32_lo;
-        h->last_key_bytes = (st.p32_piece >= 0 || st.all32) ? 4 : st.key_bytes;
-        a.fb = ((st.npieces == 0 && st.key_bytes == 4) || (st.npieces > 0 && st.p32_piece >= 0 && st.own_fine)) ? st.fb : 0;
-        a.own_fine = a.fb > 0 ? st.own_fine : nullptr;
-        a.colptr_out = direct ? (i64 *)h->colptr.p : nullptr;
-        a.late_total = h->force_path == ESP_PATH_LATE_TOTAL ? 1 : 0;  // 36: test hook, group3_k publishes a segment's total after the fold
-        a.no_group = h->force_path == ESP_PATH_NO_GROUP_TIER ? 1 : 0;  // 24: test hook, long column runs through the radix tier
-        // (every pending entry was noted with one kind; pieces of other ranks carry kinds this handle has not seen)
-        a.kind_all = (st.npieces == 0 && h->kind_uniform >= 0 && h->kind_noted == h->count && h->force_path != ESP_PATH_GENERIC_FOLD) ? h->kind_uniform : -1;
-        a.expect_hits = st.expect_hits >= 0 ? st.expect_hits : (h->seen_hits ? 1 : 0);
-        a.col_end = col_end;
-        a.n_cols = h->n;
-        a.keys_in = st.sk;
-        a.vals_in = st.sv;
-        a.seg_start = st.seg_start;
-        a.S = S;
-        a.rem_bits = st.rem_bits;
-        a.base = st.has_base ? st.base : st.npieces > 0 ? h->part_base : h->win_base;
-        a.rb = h->L.rb;
-        {
-            const int clb = st.rem_bits - h->L.rb;
-            a.cl_bits = (clb >= 0 && clb <= esplocal::CL_MAX_BITS && h->force_path != ESP_PATH_RADIX_TAIL_ONLY) ? clb : -1;
-        }
-        // a segment is a whole number of columns when the prefix does not reach into the row bits
-        a.col_aligned = st.rem_bits >= h->L.rb ? 1 : 0;
-        a.csc = espfold::Csc{(const i64 *)h->colptr.p, (const i64 *)h->rowval.p, (double *)h->nzval.p, Z0};
-        a.mode = mode;
-        a.out_row = (i64 *)tk;
-        a.out_key = tk;
-        a.out_val = tv;
-        a.colend = (u64 *)h->colend.p;
-        a.status = status;
-        a.gstatus = status + S + 2;
-        a.npieces = st.npieces;
-        a.pieces_dense = st.pieces_dense ? 1 : 0;
-        a.total = total_check;
-        a.pstart = st.pstart;
-        a.ptab = st.ptab;
-        a.ticket = (u32 *)(status + tick_at);
-        a.err = (u32 *)(status + S) + 1;
-        a.maxrun_seen = (u32 *)(status + S) + 2;  // (zeroed with the granules)
-        a.host_words = fused ? (u64 *)h->pin_words_dev : nullptr;
-        {
-            a.stop_after = stop_env ? atoi(stop_env) : 0;
-            a.stamps = nullptr;
-            a.hits_out = nullptr;
-            if (esp_exp_env("ESP_LOCAL_STAMPS")) {  // diagnostics (experiments build): per-segment phase stamps, dumped to a file
-                CK(ensure(h, h->heads, sizeof(u64) * (size_t)S * 16));
-                HIPCK(h, hipMemsetAsync(h->heads.p, 0, sizeof(u64) * (size_t)S * 16, h->stream));
-                a.stamps = (unsigned long long *)h->heads.p;
-            }
-        }
-        const i64 max_grid = h->force_path == ESP_PATH_MANY_LAUNCHES ? 64 : esplocal::MAX_GRID;  // 4: test hook, many launches
-        launch_all = [&, max_grid](bool allow_g3) -> int32_t {
-        used_g3 = false;
-        used_pair = false;
-        if (pair_ok && !h->pair_off) {
-            // (S / 2 segments, rounded up; their granules end where the grand total is read back: status[S - 1])
-            const int Sp = (S + 1) / 2;
-            esplocal::Args ap = a;
-            ap.S = Sp;
-            ap.pair_buckets = S;
-            ap.status = status + (S - Sp);
-            const int keys = st.kind == ESP_UPDATE ? 2 : 1;
-            esplocal::Variant var{true, false, false, true, keys};
-            var.pair = true;
-            h->last_fold_update = keys == 2 ? 1 : 0;
-            // (what the output arrays hold: a stale table must not send a pair's stores outside them)
-            const u64 out_cap = (u64)std::min(h->keys2.bytes / sizeof(i64), h->vals2.bytes / sizeof(double));
-            for (i64 first = 0; first < Sp; first += max_grid) {
-                ap.first = first;
-                const unsigned grid = (unsigned)std::min<i64>(max_grid, Sp - first);
-                if (use_pred && st.stencil) {
-                    if (!esplocal::launch_pair_gen_predicted(var, grid, h->stream, ap, st.stencil->a, (const u64 *)h->pred.tab.p, out_cap, keep))
-                        return ESP_RETRY_EXPANDED;  // (a cut the fused kernel does not take: nothing has happened)
-                    continue;
-                }
-                if (!(use_pred ? esplocal::launch_pair_predicted(var, grid, h->stream, ap, (const u64 *)h->pred.tab.p, out_cap)
-                               : esplocal::launch(var, grid, h->stream, ap)))
-                    FAIL(h, ESP_ERR_STATE, "esp_flush: internal error (no pair kernel for this flush)");
-            }
-            used_pair = true;
-            return ESP_OK;
-        }
-        for (i64 first = 0; first < S; first += max_grid) {
-            const unsigned grid = (unsigned)std::min<i64>(max_grid, S - first);
-            a.first = first;
-            // (key format: 0 packed, 1 four-byte keys of one kind, 2 four-byte keys that are all UPDATEs)
-            // (3: packed keys whose kinds are all UPDATE -- the pieces of a shard)
-            // (4 / 5: pieces of which one -- a shard's own range -- holds 4-byte keys; 5: everything is an UPDATE)
-            // (6 / 7: pieces that all hold 4-byte keys of one kind -- a producer's batch and its tail; 7: UPDATE)
-            const bool generic = h->force_path == ESP_PATH_GENERIC_FOLD;
-            const int keys = st.npieces > 0 ? (st.all32 ? (st.kind == ESP_UPDATE && !generic ? 7 : 6)
-                                               : st.p32_piece >= 0 ? (st.all_update && !generic ? 5 : 4)
-                                                                   : (st.all_update && !generic ? 3 : 0))
-                                            : st.key_bytes != 4 ? 0 : (st.kind == ESP_UPDATE && !generic ? 2 : 1);
-            h->last_fold_update = (keys == 2 || keys == 3 || keys == 5 || keys == 7) ? 1 : 0;  // (local.hpp: UPD)
-            // the longest column run: what the handle's last flush met, or -- no history -- the pending entries per column (a
-            // P1 mesh in 2-D: 24, in 3-D: 120; a wrong guess costs that one flush the radix tier)
-            const double longest = h->seen_maxrun > 0 ? (double)h->seen_maxrun : (double)h->count / (double)std::max<i64>(col_end - col_begin, 1);
-            // (the group-tier kernel for runs of more than 16 entries -- up to 32: its four-lane form; 24: test hook, never)
-            const bool grp = st.npieces == 0 && !small_variant && keys <= 2 && longest > 16.0 && h->force_path != ESP_PATH_NO_GROUP_TIER &&
-                             h->force_path != ESP_PATH_RADIX_TAIL_ONLY;
-            // (else the variant with the 24-input register tier for runs of 17 .. 24 -- shard pieces; 26: test hook, never)
-            const bool big = longest > 16.0 && longest <= (double)esplocal::REG_RUN && h->force_path != ESP_PATH_NO_BIG_VARIANT;
-            esplocal::Variant var{Z0 == 0, st.npieces > 0, big && !small_variant && !grp, small_variant, keys};
-            var.shortg = grp && longest <= 32.0;
-            var.grp = grp;
-            // (the group tier with three workgroups per CU -- group3.hpp: a fresh matrix, 4-byte keys of one kind, segments of at
-            // most 256 whole columns whose (local column, row) fits 32 bits, runs of at most 128 entries; a segment it does not
-            // take makes the flush run again with the kernels above; 30: test hook, never)
-            var.g3 = allow_g3 && grp && st.fb == 0 && Z0 == 0 && (keys == 1 || keys == 2) && a.cl_bits >= 0 && a.cl_bits <= esplocal::G3_CL_BITS &&
-                     a.cl_bits + a.rb <= 32 && a.rb <= 30 && longest <= 128.0 && !h->g3_off && !a.no_group && !a.stop_after &&
-                     h->force_path != ESP_PATH_NO_GROUP3;
-            // (packed keys of ONE known adding kind whose bits below the prefix fit 32 -- a shuffled stream of triplets after the
-            // flush's own passes: the same kernel, the keys narrowed as they are loaded; not its wide form)
-            const bool k64_ok = keys == 0 && st.key_bytes == 8 && st.npieces == 0 && st.rem_bits <= 32 && !want_wide &&
-                                (a.kind_all == ESP_UPDATE || a.kind_all == ESP_RAWUPDATE) && paths_auto(h);
-            if (!var.g3 && k64_ok && allow_g3 && grp && Z0 == 0 && a.cl_bits >= 0 && a.cl_bits <= esplocal::G3_CL_BITS && a.cl_bits + a.rb <= 32 &&
-                a.rb <= 30 && longest <= 128.0 && !h->g3_off && !a.no_group && !a.stop_after) {
-                var.g3 = var.g3k64 = true;
-                a.kind32 = (u32)a.kind_all;
-            }
-            var.g3wide = var.g3 && want_wide;
-            used_g3 = used_g3 || var.g3;
-            if (st.lazy) {  // sorted ITEM records: group3_k's fused form (group3_items.hpp) or nothing
-                if (!var.g3 || var.g3wide || !esplocal::launch_group3_items(*st.lazy, grid, h->stream, a)) return ESP_RETRY_EXPANDED;
-                continue;
-            }
-            if (!esplocal::launch(var, grid, h->stream, a)) FAIL(h, ESP_ERR_STATE, "esp_flush: internal error (no bucket kernel for this flush)");
-        }
-        return ESP_OK;
-        };
-    }
-    auto read_back = [&]() -> int32_t {
-        if (fused) {  // (the words are in host memory already -- in the slots' layout: no longest run, no window flag on this path)
-            HIPCK(h, hipStreamSynchronize(h->stream));
-            const volatile unsigned long long *w = h->pin_words;
-            h->pin_scalar[0] = w[0];
-            h->pin_scalar[1] = w[1] << 32;
-            h->pin_scalar[2] = 0ull;
-            h->pin_scalar[3] = 0ull;
-            return ESP_OK;
-        }
-        HIPCK(h, hipMemcpyAsync(h->pin_scalar, status + (S - 1), 24, hipMemcpyDeviceToHost, h->stream));  // last granule | ticket, err | maxrun
-        HIPCK(h, hipMemcpyAsync(h->pin_scalar + 3, (u32 *)h->misc.p + 60, 4, hipMemcpyDeviceToHost, h->stream));
-        HIPCK(h, hipStreamSynchronize(h->stream));
-        return ESP_OK;
-    };
-    auto reset_launch_state = [&]() -> int32_t {
-        HIPCK(h, hipMemsetAsync(status, 0, status_bytes, h->stream));
-        if (!direct) {
-            i64 c0, cnt;
-            col_range(h, &c0, &cnt);
-            HIPCK(h, hipMemsetAsync((u64 *)h->colend.p + c0, 0, sizeof(u64) * (size_t)cnt, h->stream));
-        }
-        return ESP_OK;
-    };
+    // (key format: 0 packed, 1 four-byte keys of one kind, 2 four-byte keys that are all UPDATEs)
+    // (3: packed keys whose kinds are all UPDATE -- the pieces of a shard)
+    // (4 / 5: pieces of which one -- a shard's own range -- holds 4-byte keys; 5: everything is an UPDATE)
+    // (6 / 7: pieces that all hold 4-byte keys of one kind -- a producer's batch and its tail; 7: UPDATE)
+    const bool generic = fp == ESP_PATH_GENERIC_FOLD;
+    c.keys = st.npieces > 0 ? (st.all32 ? (st.kind == ESP_UPDATE && !generic ? 7 : 6)
+                               : st.p32_piece >= 0 ? (st.all_update && !generic ? 5 : 4)
+                                                   : (st.all_update && !generic ? 3 : 0))
+                            : st.key_bytes != 4 ? 0 : (st.kind == ESP_UPDATE && !generic ? 2 : 1);
+    // the longest column run: what the handle's last flush met, or -- no history -- the pending entries per column (a
+    // P1 mesh in 2-D: 24, in 3-D: 120; a wrong guess costs that one flush the radix tier)
+    c.longest = h->seen_maxrun > 0 ? (double)h->seen_maxrun : per_col;
+    // (the group-tier kernel for runs of more than 16 entries -- up to 32: its four-lane form; 24: test hook, never)
+    c.grp = st.npieces == 0 && !c.small_variant && c.keys <= 2 && c.longest > 16.0 && fp != ESP_PATH_NO_GROUP_TIER && fp != ESP_PATH_RADIX_TAIL_ONLY;
+    // (else the variant with the 24-input register tier for runs of 17 .. 24 -- shard pieces; 26: test hook, never)
+    c.big = c.longest > 16.0 && c.longest <= (double)esplocal::REG_RUN && fp != ESP_PATH_NO_BIG_VARIANT;
+    // The group tier with three workgroups per CU (group3.hpp) takes segments of at most 256 whole columns whose (local column,
+    // row) fits 32 bits, with runs of at most 128 entries: the shape test of all its forms.
+    const bool g3_shape = c.cl_bits >= 0 && c.cl_bits <= esplocal::G3_CL_BITS && c.cl_bits + h->L.rb <= 32 && h->L.rb <= 30 && c.longest <= 128.0 &&
+                          !c.no_group && !c.stop_after;
+    // (its plain form: a fresh matrix, 4-byte keys of one kind; a segment it does not take makes the flush run again with the
+    // kernels above; 30: test hook, never)
+    c.g3_plain = g3_shape && c.grp && c.fresh && st.fb == 0 && (c.keys == 1 || c.keys == 2) && fp != ESP_PATH_NO_GROUP3;
+    // (packed keys of ONE known adding kind whose bits below the prefix fit 32 -- a shuffled stream of triplets after the
+    // flush's own passes: the same kernel, the keys narrowed as they are loaded; not its wide form)
+    c.g3_k64 = g3_shape && c.grp && c.fresh && c.keys == 0 && st.key_bytes == 8 && st.npieces == 0 && st.rem_bits <= 32 &&
+               (c.kind_all == ESP_UPDATE || c.kind_all == ESP_RAWUPDATE) && paths_auto(h);
+    c.want_wide = h->g3_wide && fp != ESP_PATH_NO_WIDE_GROUP3;
     // A re-assembly over the pattern the same mesh built (a ROUTED flush of 4-byte-key additions with long column runs, and
     // the handle's last flush over the pattern hit): group3_k's re-assembly form -- every (col,row) of a column's sorted run
     // IS the column's stored entry of the same rank; the sums go to a second value array, swapped in when no column
-    // objected (bit 64) -- else nothing has happened and the general kernels below take the flush.  force_path 34: never.
-    {
-        const bool generic = h->force_path == ESP_PATH_GENERIC_FOLD;
-        const int keys = st.key_bytes != 4 ? 0 : (st.kind == ESP_UPDATE && !generic ? 2 : 1);
-        const double longest = h->seen_maxrun > 0 ? (double)h->seen_maxrun : (double)h->count / (double)std::max<i64>(col_end - col_begin, 1);
-        const bool hits_expected = st.expect_hits >= 0 ? st.expect_hits == 1 : h->seen_hits;
-        bool try_hits = Z0 > 0 && st.fb == 0 && mode == ESP_FLUSH_ROUTED && st.npieces == 0 && (keys == 1 || keys == 2) && (st.kind == ESP_UPDATE || st.kind == ESP_RAWUPDATE) &&
-                        a.kind_all == st.kind && a.cl_bits >= 0 && a.cl_bits <= esplocal::G3_CL_BITS && a.cl_bits + a.rb <= 32 && a.rb <= 30 &&
-                        longest > 16.0 && longest <= 128.0 && hits_expected && !h->hits_off && !a.no_group && !a.stop_after && !small_variant &&
-                        h->wc0 == 0 && h->wc1 == h->n &&  // (the segments cover every column: what they do not write into the second array would be lost)
-                        h->force_path != ESP_PATH_NO_GROUP_TIER && h->force_path != ESP_PATH_RADIX_TAIL_ONLY && h->force_path != ESP_PATH_NO_GROUP3 &&
-                        h->force_path != ESP_PATH_NO_HITS_KERNEL && h->force_path != ESP_PATH_MANY_LAUNCHES && (i64)S <= esplocal::MAX_GRID;
-        for (int attempt = 0; attempt < 2 && try_hits; attempt++) {
-            CK(ensure(h, h->nzval2, sizeof(double) * (size_t)Z0));
-            a.hits_out = (double *)h->nzval2.p;
-            a.first = 0;
-            esplocal::Variant var{false, false, false, false, keys};
-            var.grp = var.g3 = var.g3hits = true;
-            var.g3wide = want_wide;
-            {
-                Span sp(h, ESP_ST_LOCAL);
-                if (st.lazy) {  // (sorted item records: the fused form -- plain rows only -- or the caller expands them)
-                    if (want_wide || !esplocal::launch_group3_items(*st.lazy, (unsigned)S, h->stream, a, true)) return ESP_RETRY_EXPANDED;
-                } else if (!esplocal::launch(var, (unsigned)S, h->stream, a))
-                    FAIL(h, ESP_ERR_STATE, "esp_flush: internal error (no re-assembly kernel for this flush)");
-                sp.add(1);
-            }
-            CK(read_back());
-            const u32 e = (u32)(h->pin_scalar[1] >> 32);
-            // (accepted only when NOTHING objected: no refused segment (8), no column that is not the stored one (64), no look-back
-            // error (1 / 2 / 4), no entry outside a declared window -- anything else falls through to the general kernels' checks)
-            if ((e & (1u | 2u | 4u | 8u | 64u)) == 0u && (u32)h->pin_scalar[3] == 0u) {
-                std::swap(h->nzval, h->nzval2);
-                h->last_group3 = want_wide ? 4 : 3;
-                h->seen_maxrun = (int)(u32)(h->pin_scalar[2] & 0xFFFFFFFFull);
-                h->seen_hits = true;
-                h->last_lazy_items = st.lazy ? 1 : 0;
-                *Zn_out = 0;
-                return ESP_OK;
-            }
-            CK(reset_launch_state());
-            if (st.lazy) return ESP_RETRY_EXPANDED;  // (nothing has happened: the entries, then whatever form takes them)
-            if ((e & 8u) && (e & 16u) && !(e & 32u) && !(e & 64u) && !want_wide && h->force_path != ESP_PATH_NO_WIDE_GROUP3) {
-                want_wide = true;  // (refused for its rows alone: once more in the wide form)
-                h->g3_wide = true;
-                continue;
-            }
-            h->hits_off = true;  // (not a re-assembly of the stored pattern, or shapes the kernel does not take: not tried again)
-            try_hits = false;
+    // objected (bit 64) -- else nothing has happened and the general kernels take the flush.  force_path 34: never.
+    const bool hits_expected = st.expect_hits >= 0 ? st.expect_hits == 1 : h->seen_hits;
+    c.try_hits = !c.fresh && st.fb == 0 && mode == ESP_FLUSH_ROUTED && st.npieces == 0 && (c.keys == 1 || c.keys == 2) &&
+                 (st.kind == ESP_UPDATE || st.kind == ESP_RAWUPDATE) && c.kind_all == st.kind && g3_shape && c.longest > 16.0 && hits_expected &&
+                 !h->hits_off && !c.small_variant &&
+                 h->wc0 == 0 && h->wc1 == h->n &&  // (the segments cover every column: what they do not write into the second array would be lost)
+                 fp != ESP_PATH_NO_GROUP_TIER && fp != ESP_PATH_RADIX_TAIL_ONLY && fp != ESP_PATH_NO_GROUP3 && fp != ESP_PATH_NO_HITS_KERNEL &&
+                 fp != ESP_PATH_MANY_LAUNCHES && (i64)c.S <= esplocal::MAX_GRID;
+    return c;
+}
+
+static void fill_args(esplocal::Args &a, const esp_handle *h, const Sorted &st, const LocalChoice &c, int mode, const StatusLayout &lay) {
+    memset(&a, 0, sizeof a);  // (stamps, hits_out: nullptr)
+    a.kind32 = (u32)((st.key_bytes == 4 || st.p32_piece >= 0 || st.all32) ? st.kind : 0);
+    a.k32_piece = st.p32_piece;
+    a.k32_lo = st.p32_lo;
+    a.fb = ((st.npieces == 0 && st.key_bytes == 4) || (st.npieces > 0 && st.p32_piece >= 0 && st.own_fine)) ? st.fb : 0;
+    a.own_fine = a.fb > 0 ? st.own_fine : nullptr;
+    a.colptr_out = c.direct ? (i64 *)h->colptr.p : nullptr;
+    a.late_total = c.late_total;
+    a.no_group = c.no_group;
+    a.kind_all = c.kind_all;
+    a.expect_hits = st.expect_hits >= 0 ? st.expect_hits : (h->seen_hits ? 1 : 0);
+    a.col_end = c.col_end;
+    a.n_cols = h->n;
+    a.keys_in = st.sk;
+    a.vals_in = st.sv;
+    a.seg_start = st.seg_start;
+    a.S = c.S;
+    a.rem_bits = st.rem_bits;
+    a.base = c.seg_base;
+    a.rb = h->L.rb;
+    a.cl_bits = c.cl_bits;
+    // a segment is a whole number of columns when the prefix does not reach into the row bits
+    a.col_aligned = c.clb >= 0 ? 1 : 0;
+    a.csc = espfold::Csc{(const i64 *)h->colptr.p, (const i64 *)h->rowval.p, (double *)h->nzval.p, h->nnz};
+    a.mode = mode;
+    // esp_flush normalised the buffers: data in keys/vals, scratch pair = keys2/vals2
+    a.out_row = (i64 *)h->keys2.p;
+    a.out_key = (u64 *)h->keys2.p;
+    a.out_val = (double *)h->vals2.p;
+    a.colend = (u64 *)h->colend.p;
+    lay.point(a, (u64 *)h->segout.p);
+    a.npieces = st.npieces;
+    a.pieces_dense = st.pieces_dense ? 1 : 0;
+    a.total = c.total_check;
+    a.pstart = st.pstart;
+    a.ptab = st.ptab;
+    a.host_words = c.fused ? (u64 *)h->pin_words_dev : nullptr;
+    a.stop_after = c.stop_after;
+}
+
+static inline u32 err_bits(const esp_handle *h) { return (u32)(h->pin_scalar[1] >> 32); }  // (Args::err as read_back left it)
+
+static int32_t clear_colend(esp_handle *h) {
+    i64 c0, cnt;
+    col_range(h, &c0, &cnt);
+    HIPCK(h, hipMemsetAsync((u64 *)h->colend.p + c0, 0, sizeof(u64) * (size_t)cnt, h->stream));
+    return ESP_OK;
+}
+
+// (a failed flush must not leave a half-written colptr behind)
+static void restore_colptr(esp_handle *h, const LocalChoice &c) {
+    if (!c.direct) return;
+    hipLaunchKernelGGL(fill_i64_k, dim3(grid_for(h->n + 1, 256)), dim3(256), 0, h->stream, (i64 *)h->colptr.p, h->n + 1, (i64)1);
+    h->tail_stale = false;
+    h->ones_pending = false;
+}
+
+// pin_scalar: [0] last granule (the grand total) | [1] ticket, err | [2] longest run | [3] the window flag
+static int32_t read_back(esp_handle *h, const LocalChoice &c, const esplocal::Args &a) {
+    if (c.fused) {  // (the words are in host memory already -- in the slots' layout: no longest run, no window flag on this path)
+        HIPCK(h, hipStreamSynchronize(h->stream));
+        const volatile unsigned long long *w = h->pin_words;
+        h->pin_scalar[0] = w[0];
+        h->pin_scalar[1] = w[1] << 32;
+        h->pin_scalar[2] = 0ull;
+        h->pin_scalar[3] = 0ull;
+        return ESP_OK;
+    }
+    HIPCK(h, hipMemcpyAsync(h->pin_scalar, a.status + (c.S - 1), 24, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipMemcpyAsync(h->pin_scalar + 3, (u32 *)h->misc.p + 60, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    return ESP_OK;
+}
+
+// what changes from one attempt to the next, and what an attempt reports
+struct LocalTry {
+    bool use_pred, want_wide, allow_g3;
+    bool used_pair = false, used_g3 = false;
+};
+
+// The launches of one attempt -- the pair form or the regular kernels, sliced by the largest grid -- as one span of the timing.
+// `a` is the flush's one argument block: a k64 attempt's kind32 and a hits attempt's hits_out stay in it for the later attempts.
+static int32_t launch_attempt(esp_handle *h, const Sorted &st, const LocalChoice &c, esplocal::Args &a, LocalTry &t) {
+    Span sp(h, ESP_ST_LOCAL);
+    const i64 max_grid = h->force_path == ESP_PATH_MANY_LAUNCHES ? 64 : esplocal::MAX_GRID;  // 4: test hook, many launches
+    t.used_g3 = t.used_pair = false;
+    if (c.pair_ok && !h->pair_off) {
+        // (S / 2 segments, rounded up; their granules end where the grand total is read back: status[S - 1])
+        const int Sp = (c.S + 1) / 2;
+        esplocal::Args ap = a;
+        ap.S = Sp;
+        ap.pair_buckets = c.S;
+        ap.status = a.status + (c.S - Sp);
+        esplocal::Variant var{true, false, false, true, c.pair_keys};
+        var.pair = true;
+        h->last_fold_update = c.pair_keys == 2 ? 1 : 0;
+        // (what the output arrays hold: a stale table must not send a pair's stores outside them)
+        const u64 out_cap = (u64)std::min(h->keys2.bytes / sizeof(i64), h->vals2.bytes / sizeof(double));
+        const u64 *pred = (const u64 *)h->pred.tab.p;
+        for (i64 first = 0; first < Sp; first += max_grid) {
+            ap.first = first;
+            const unsigned grid = (unsigned)std::min<i64>(max_grid, Sp - first);
+            if (t.use_pred && st.stencil) {
+                if (!esplocal::launch_pair_gen_predicted(var, grid, h->stream, ap, st.stencil->a, pred, out_cap, c.keep))
+                    return ESP_RETRY_EXPANDED;  // (a cut the fused kernel does not take: nothing has happened)
+            } else if (!(t.use_pred ? esplocal::launch_pair_predicted(var, grid, h->stream, ap, pred, out_cap) : esplocal::launch(var, grid, h->stream, ap)))
+                FAIL(h, ESP_ERR_STATE, "esp_flush: internal error (no pair kernel for this flush)");
         }
-    }
-    {
-        Span sp(h, ESP_ST_LOCAL);
-        CK(launch_all(true));
+        t.used_pair = true;
         sp.add(1);
+        return ESP_OK;
     }
-    CK(read_back());
-    const bool pred_tried = use_pred && used_pair;
-    if (pred_tried && ((u32)(h->pin_scalar[1] >> 32) & (esplocal::PRED_MISS | esplocal::PAIR_REFUSED))) {
-        // a pair emitted another count than the table says (it stored nothing; the others wrote their slices): once more with the
-        // look-back form, which rewrites everything a fresh-matrix flush writes -- the pending entries are where they were
-        use_pred = false;
+    h->last_fold_update = (c.keys == 2 || c.keys == 3 || c.keys == 5 || c.keys == 7) ? 1 : 0;  // (local.hpp: UPD)
+    esplocal::Variant var{c.fresh, st.npieces > 0, c.big && !c.small_variant && !c.grp, c.small_variant, c.keys};
+    var.shortg = c.grp && c.longest <= 32.0;
+    var.grp = c.grp;
+    var.g3 = t.allow_g3 && !h->g3_off && (c.g3_plain || (c.g3_k64 && !t.want_wide));
+    var.g3k64 = var.g3 && c.g3_k64;
+    if (var.g3k64) a.kind32 = (u32)c.kind_all;
+    var.g3wide = var.g3 && t.want_wide;
+    for (i64 first = 0; first < c.S; first += max_grid) {
+        const unsigned grid = (unsigned)std::min<i64>(max_grid, c.S - first);
+        a.first = first;
+        t.used_g3 = var.g3;
+        if (st.lazy) {  // sorted ITEM records: group3_k's fused form (group3_items.hpp) or nothing
+            if (!var.g3 || var.g3wide || !esplocal::launch_group3_items(*st.lazy, grid, h->stream, a)) return ESP_RETRY_EXPANDED;
+        } else if (!esplocal::launch(var, grid, h->stream, a))
+            FAIL(h, ESP_ERR_STATE, "esp_flush: internal error (no bucket kernel for this flush)");
+    }
+    sp.add(1);
+    return ESP_OK;
+}
+
+static int32_t reset_launch_state(esp_handle *h, const LocalChoice &c, const esplocal::Args &a, const StatusLayout &lay) {
+    HIPCK(h, hipMemsetAsync(a.status, 0, lay.bytes(), h->stream));
+    return c.direct ? ESP_OK : clear_colend(h);
+}
+
+// A rung of the ladder, after it has marked the handle and `t`: clear and go again.  (Nothing of the refused attempt has taken
+// effect that the next one does not write again; the pending entries are where they were.)  The stencil return can be met in
+// the first rung only: a stencil batch runs the predicted pair form, and a refused pair goes through that rung first.
+static int32_t retry_attempt(esp_handle *h, const Sorted &st, const LocalChoice &c, const StatusLayout &lay, esplocal::Args &a, LocalTry &t) {
+    CK(reset_launch_state(h, c, a, lay));
+    if (st.stencil && !t.use_pred) return ESP_RETRY_EXPANDED;  // (the look-back form reads the entries: the held-back PART launch first)
+    CK(launch_attempt(h, st, c, a, t));
+    return read_back(h, c, a);
+}
+
+// group3_k's re-assembly form (LocalChoice::try_hits), twice at the most: plain or wide, then wide.  *done: accepted, the flush is
+// over; else (and ESP_OK) nothing has happened and the state is cleared for the general kernels.
+static int32_t try_hits_form(esp_handle *h, const Sorted &st, const LocalChoice &c, const StatusLayout &lay, esplocal::Args &a, LocalTry &t,
+                             i64 *Zn_out, bool *done) {
+    *done = false;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        CK(ensure(h, h->nzval2, sizeof(double) * (size_t)h->nnz));
+        a.hits_out = (double *)h->nzval2.p;
+        a.first = 0;
+        esplocal::Variant var{false, false, false, false, c.keys};
+        var.grp = var.g3 = var.g3hits = true;
+        var.g3wide = t.want_wide;
+        {
+            Span sp(h, ESP_ST_LOCAL);
+            if (st.lazy) {  // (sorted item records: the fused form -- plain rows only -- or the caller expands them)
+                if (t.want_wide || !esplocal::launch_group3_items(*st.lazy, (unsigned)c.S, h->stream, a, true)) return ESP_RETRY_EXPANDED;
+            } else if (!esplocal::launch(var, (unsigned)c.S, h->stream, a))
+                FAIL(h, ESP_ERR_STATE, "esp_flush: internal error (no re-assembly kernel for this flush)");
+            sp.add(1);
+        }
+        CK(read_back(h, c, a));
+        const u32 e = err_bits(h);
+        // (accepted only when NOTHING objected: no refused segment (8), no column that is not the stored one (64), no look-back
+        // error (1 / 2 / 4), no entry outside a declared window -- anything else falls through to the general kernels' checks)
+        if ((e & (1u | 2u | 4u | 8u | 64u)) == 0u && (u32)h->pin_scalar[3] == 0u) {
+            std::swap(h->nzval, h->nzval2);
+            h->last_group3 = t.want_wide ? 4 : 3;
+            h->seen_maxrun = (int)(u32)(h->pin_scalar[2] & 0xFFFFFFFFull);
+            h->seen_hits = true;
+            h->last_lazy_items = st.lazy ? 1 : 0;
+            *Zn_out = 0;
+            *done = true;
+            return ESP_OK;
+        }
+        CK(reset_launch_state(h, c, a, lay));
+        if (st.lazy) return ESP_RETRY_EXPANDED;  // (nothing has happened: the entries, then whatever form takes them)
+        if (!((e & 8u) && (e & 16u) && !(e & 32u) && !(e & 64u) && !t.want_wide && h->force_path != ESP_PATH_NO_WIDE_GROUP3)) {
+            h->hits_off = true;  // (not a re-assembly of the stored pattern, or shapes the kernel does not take: not tried again)
+            break;
+        }
+        t.want_wide = true;  // (refused for its rows alone: once more in the wide form)
+        h->g3_wide = true;
+    }
+    return ESP_OK;
+}
+
+// A look-back flush of a kept plan that succeeded: its pairs' offsets, from the fresh colptr, for the next flush of the plan
+// (not once two predictions in a row have missed: the stream's zeros move every time)
+static void record_pred_table(esp_handle *h, const LocalChoice &c) {
+    if (h->pred.gen != h->plan_gen) h->pred.misses = 0;
+    const int Sp = (c.S + 1) / 2;
+    h->pred.gen = h->plan_gen;
+    h->pred.S = c.S;
+    if (h->pred.misses >= 2) return;
+    if (ensure(h, h->pred.tab, sizeof(u64) * (size_t)(Sp + 1)) == ESP_OK)
+        esplocal::launch_pair_record(h->stream, (const i64 *)h->colptr.p, c.col_end, c.cl_bits + 1, Sp, (u64 *)h->pred.tab.p);
+    else
+        h->pred.gen = 0;  // (no memory for the table: the flush itself is done -- no prediction, that is all)
+}
+
+int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
+    const i64 Z0 = h->nnz;
+    const i64 N1 = h->n + 1;
+    // ---- the choice
+    const LocalChoice c = choose_local(h, st, mode);
+    const StatusLayout lay(c.S);
+    CK(ensure(h, h->segout, lay.bytes()));
+    CK(ensure(h, h->colend, sizeof(u64) * (size_t)(N1 + espscan::workspace_elems(N1))));
+    h->last_colptr_direct = c.direct ? 1 : 0;
+    if (!c.direct) CK(clear_colend(h));
+    h->last_local_small = c.small_variant ? 1 : 0;
+    // A stencil batch that was never written (esp_handle::LazyStencil): the predicted form's fused kernel (pair_gen_pred_k) or
+    // nothing -- the caller issues the PART launch that was held back and comes again with the entries.
+    if (st.stencil && !c.use_pred) return ESP_RETRY_EXPANDED;
+    h->kept.candidate = false;
+    // ---- the clears in front of the first attempt
+    // (the predicted form reads the error / longest-run words and leaves the grand total in the last granule: nothing else to clear)
+    u64 *status = (u64 *)h->segout.p;
+    if (c.fused)
+        h->pin_words[0] = h->pin_words[1] = h->pin_words[2] = 0ull;
+    else if (c.use_pred)
+        HIPCK(h, hipMemsetAsync(status + (c.S - 1), 0, 3 * sizeof(u64), h->stream));
+    else
+        HIPCK(h, hipMemsetAsync(status, 0, lay.bytes(), h->stream));
+    esplocal::Args a;
+    fill_args(a, h, st, c, mode, lay);
+    h->last_key_bytes = (st.p32_piece >= 0 || st.all32) ? 4 : st.key_bytes;
+    const char *stamps_file = esp_exp_env("ESP_LOCAL_STAMPS");
+    if (stamps_file) {  // diagnostics (experiments build): per-segment phase stamps, dumped to a file
+        CK(ensure(h, h->heads, sizeof(u64) * (size_t)c.S * 16));
+        HIPCK(h, hipMemsetAsync(h->heads.p, 0, sizeof(u64) * (size_t)c.S * 16, h->stream));
+        a.stamps = (unsigned long long *)h->heads.p;
+    }
+    LocalTry t{c.use_pred, c.want_wide, true};
+    // ---- the hits form
+    if (c.try_hits) {
+        bool done = false;
+        CK(try_hits_form(h, st, c, lay, a, t, Zn_out, &done));
+        if (done) return ESP_OK;
+    }
+    // ---- the first attempt
+    CK(launch_attempt(h, st, c, a, t));
+    CK(read_back(h, c, a));
+    // ---- the rungs
+    const bool pred_tried = t.use_pred && t.used_pair;
+    if (pred_tried && (err_bits(h) & (esplocal::PRED_MISS | esplocal::PAIR_REFUSED))) {
+        // 1. a pair emitted another count than the table says (it stored nothing; the others wrote their slices): once more with the
+        // look-back form, which rewrites everything a fresh-matrix flush writes
+        t.use_pred = false;
         h->pred.misses++;
         h->pred.last = 2;
         // (the KEEP form stored values into the scratch array at most: colptr and rowval are as they were, and the retry writes all
         // of them -- the stamp is gone since esp_flush's entry)
-        if (keep) h->last_kept = 2;
+        if (c.keep) h->last_kept = 2;
         drop_kept(h);
-        CK(reset_launch_state());
-        if (st.stencil) return ESP_RETRY_EXPANDED;  // (the look-back form reads the entries: the held-back PART launch first)
-        {
-            Span sp(h, ESP_ST_LOCAL);
-            CK(launch_all(true));
-            sp.add(1);
-        }
-        CK(read_back());
+        CK(retry_attempt(h, st, c, lay, a, t));
     } else if (pred_tried) {
         h->pred.misses = 0;
         h->pred.last = 1;
     }
-    if (used_pair && ((u32)(h->pin_scalar[1] >> 32) & esplocal::PAIR_REFUSED)) {
-        // a pair the kernel does not take: once more with local_k (it writes every output a fresh-matrix flush has), and it serves
+    if (t.used_pair && (err_bits(h) & esplocal::PAIR_REFUSED)) {
+        // 2. a pair the kernel does not take: once more with local_k (it writes every output a fresh-matrix flush has), and it serves
         // this handle from now on
         h->pair_off = true;
-        CK(reset_launch_state());
-        {
-            Span sp(h, ESP_ST_LOCAL);
-            CK(launch_all(true));
-            sp.add(1);
-        }
-        CK(read_back());
+        CK(retry_attempt(h, st, c, lay, a, t));
     }
-    h->last_pair = used_pair ? 1 : 0;
-    h->last_cl_bits = a.cl_bits;
-    h->last_buckets = S;
+    h->last_pair = t.used_pair ? 1 : 0;
+    h->last_cl_bits = c.cl_bits;
+    h->last_buckets = c.S;
     h->last_lazy_items = 0;
     h->last_sum_join = 0;
     if (st.lazy) {
-        // a segment the fused kernel refuses (a column run above 128, rows spread over more than 2^18): nothing of a
+        // 3. a segment the fused kernel refuses (a column run above 128, rows spread over more than 2^18): nothing of a
         // fresh-matrix flush has taken effect -- the caller expands the items and comes back with the entries
-        if ((u32)(h->pin_scalar[1] >> 32) & 8u) return ESP_RETRY_EXPANDED;
+        if (err_bits(h) & 8u) return ESP_RETRY_EXPANDED;
         h->last_lazy_items = 1;
     }
-    if (used_g3 && !want_wide && h->force_path != ESP_PATH_NO_WIDE_GROUP3) {
-        const u32 e = (u32)(h->pin_scalar[1] >> 32);
-        if ((e & 8u) && (e & 16u) && !(e & 32u)) {
-            // every segment the kernel refused, it refused for its ROWS alone (spread over more than 2^18: a mesh numbered
-            // without locality): nothing of a fresh-matrix flush has taken effect -- once more with the kernel's wide form
-            // (full rows in LDS, every run sorted twice), which serves this handle from now on
-            want_wide = true;
-            h->g3_wide = true;
-            CK(reset_launch_state());
-            {
-                Span sp(h, ESP_ST_LOCAL);
-                CK(launch_all(true));
-                sp.add(1);
-            }
-            CK(read_back());
-        }
+    if (t.used_g3 && !t.want_wide && h->force_path != ESP_PATH_NO_WIDE_GROUP3 && (err_bits(h) & (8u | 16u | 32u)) == (8u | 16u)) {
+        // 4. every segment the kernel refused, it refused for its ROWS alone (spread over more than 2^18: a mesh numbered
+        // without locality): nothing of a fresh-matrix flush has taken effect -- once more with the kernel's wide form
+        // (full rows in LDS, every run sorted twice), which serves this handle from now on
+        t.want_wide = true;
+        h->g3_wide = true;
+        CK(retry_attempt(h, st, c, lay, a, t));
     }
-    if (used_g3 && ((u32)(h->pin_scalar[1] >> 32) & 8u)) {
-        // a segment the three-workgroup group kernel does not take (a longer run, rows too far apart): nothing of a
+    if (t.used_g3 && (err_bits(h) & 8u)) {
+        // 5. a segment the three-workgroup group kernel does not take (a longer run, rows too far apart): nothing of a
         // fresh-matrix flush has taken effect -- once more with the general kernels, and they serve this handle from now on
         h->g3_off = true;
-        HIPCK(h, hipMemsetAsync(status, 0, status_bytes, h->stream));
-        if (!direct) {
-            i64 c0, cnt;
-            col_range(h, &c0, &cnt);
-            HIPCK(h, hipMemsetAsync((u64 *)h->colend.p + c0, 0, sizeof(u64) * (size_t)cnt, h->stream));
-        }
-        {
-            Span sp(h, ESP_ST_LOCAL);
-            CK(launch_all(false));
-            sp.add(1);
-        }
-        CK(read_back());
+        t.allow_g3 = false;
+        CK(retry_attempt(h, st, c, lay, a, t));
     }
-    h->last_group3 = used_g3 ? (want_wide ? 2 : 1) : 0;
-
+    h->last_group3 = t.used_g3 ? (t.want_wide ? 2 : 1) : 0;
+    // ---- the checks
     if ((u32)h->pin_scalar[3]) {
-        restore_colptr();
+        restore_colptr(h, c);
         FAIL(h, ESP_ERR_STATE, "esp_flush: a pending entry lies outside the declared column window");
     }
     if (a.stamps) {
-        std::vector<u64> st((size_t)S * 16);
-        HIPCK(h, hipMemcpy(st.data(), a.stamps, sizeof(u64) * st.size(), hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(esp_exp_env("ESP_LOCAL_STAMPS"), "wb")) {
-            fwrite(st.data(), sizeof(u64), st.size(), f);
+        std::vector<u64> stamps((size_t)c.S * 16);
+        HIPCK(h, hipMemcpy(stamps.data(), a.stamps, sizeof(u64) * stamps.size(), hipMemcpyDeviceToHost));
+        if (FILE *f = fopen(stamps_file, "wb")) {
+            fwrite(stamps.data(), sizeof(u64), stamps.size(), f);
             fclose(f);
         }
     }
-    if (direct && !windowed(h)) h->ones_pending = false;  // (the bucket kernel wrote every entry of colptr)
-    const u32 lookback_err = (u32)(h->pin_scalar[1] >> 32);
-    h->seen_maxrun = (int)(u32)(h->pin_scalar[2] >> 0 & 0xFFFFFFFFull);
-    if (lookback_err & 7u) restore_colptr();
+    if (c.direct && !windowed(h)) h->ones_pending = false;  // (the bucket kernel wrote every entry of colptr)
+    const u32 lookback_err = err_bits(h);
+    h->seen_maxrun = (int)(u32)(h->pin_scalar[2] & 0xFFFFFFFFull);
+    if (lookback_err & 7u) restore_colptr(h, c);
     if (lookback_err & 2u) FAIL(h, ESP_ERR_STATE, "esp_flush: a pending entry lies outside the declared column window (bucket)");
     if (lookback_err & 1u) FAIL(h, ESP_ERR_HIP, "esp_flush: look-back chain timed out inside the bucket kernel");
     if (lookback_err & 4u) FAIL(h, ESP_ERR_HIP, "esp_flush: internal error (early segment total differs from the folded total)");
+    // ---- the bookkeeping
     const i64 Zn = (i64)(h->pin_scalar[0] & esplocal::ST_VAL);
     *Zn_out = Zn;
     if (st.stencil) h->last_lazy_stencil = 1;  // (served: the batch was never written; the table stays as it is)
     // ... and colptr / rowval hold this flush's structure from here on: the stamp is armed (below, behind the rotation) when the
     // flush emitted the grid's whole structural pattern -- N diagonal entries and two per pair of neighbours
     bool arm = false;
-    if (fused) {
+    if (c.fused) {
         const espgen::FdArgs &fd = st.stencil->a;
         const i64 structural = fd.nx * fd.ny * fd.nz + 2 * ((fd.nx - 1) * fd.ny * fd.nz + fd.nx * (fd.ny - 1) * fd.nz + fd.nx * fd.ny * (fd.nz - 1));
-        if (keep && Zn != h->kept.nnz) FAIL(h, ESP_ERR_STATE, "esp_flush: internal error (a kept structure of %lld entries, a flush of %lld)", (long long)h->kept.nnz, (long long)Zn);
-        arm = h->force_path != ESP_PATH_NO_KEPT_STRUCTURE && h->n > 4096 && h->n == fd.nx * fd.ny * fd.nz && direct && !windowed(h) && Zn == structural &&
-              !a.stop_after;
-        if (keep) h->last_kept = 1;
+        if (c.keep && Zn != h->kept.nnz) FAIL(h, ESP_ERR_STATE, "esp_flush: internal error (a kept structure of %lld entries, a flush of %lld)", (long long)h->kept.nnz, (long long)Zn);
+        arm = h->force_path != ESP_PATH_NO_KEPT_STRUCTURE && h->n > 4096 && h->n == fd.nx * fd.ny * fd.nz && c.direct && !windowed(h) && Zn == structural &&
+              !c.stop_after;
+        if (c.keep) h->last_kept = 1;
     }
-    if (pred_batch && used_pair && !use_pred && Zn > 0 && !a.stop_after) {
-        // a look-back flush of a kept plan that succeeded: its pairs' offsets, from the fresh colptr, for the next flush of the plan
-        // (not once two predictions in a row have missed: the stream's zeros move every time)
-        if (h->pred.gen != h->plan_gen) h->pred.misses = 0;
-        const int Sp = (S + 1) / 2;
-        h->pred.gen = h->plan_gen;
-        h->pred.S = S;
-        if (h->pred.misses < 2) {
-            if (ensure(h, h->pred.tab, sizeof(u64) * (size_t)(Sp + 1)) == ESP_OK)
-                esplocal::launch_pair_record(h->stream, (const i64 *)h->colptr.p, col_end, a.cl_bits + 1, Sp, (u64 *)h->pred.tab.p);
-            else
-                h->pred.gen = 0;  // (no memory for the table: the flush itself is done -- no prediction, that is all)
-        }
-    }
+    if (c.pred_batch && t.used_pair && !t.use_pred && Zn > 0 && !c.stop_after) record_pred_table(h, c);
     // (history for the next flush over a stored pattern: fewer than a quarter of the entries opened a new position)
     if (Z0 > 0 && st.expect_hits < 0 && st.total > 0) h->seen_hits = Zn * 4 <= st.total;
-    if (a.stop_after || Zn == 0) return ESP_OK;
-    if (Z0 == 0) {
-        // the scratch pair now holds rowval/nzval: rotate the buffers instead of copying.  The old
-        // (empty) CSC arrays become the next flush's scratch pair: bring them to the same capacity
-        // once, so that the rotation never shrinks the scratch pair (a 10 GB hipMalloc per flush
-        // costs more than the flush itself)
-        // (the KEEP form wrote values only: rowval stays the array it is)
-        if (!keep) CK(ensure(h, h->rowval, h->keys2.bytes));
-        CK(ensure(h, h->nzval, h->vals2.bytes));
-        if (!keep) std::swap(h->rowval, h->keys2);
-        std::swap(h->nzval, h->vals2);
-        if (direct) {  // colptr is complete (behind a column window it is refreshed lazily, as after the scan)
-            if (windowed(h)) h->tail_stale = h->wc1 < h->n;
-            h->nnz = Zn;
-            h->pattern_version++, h->values_version++;
-            if (arm) {
-                const espgen::FdArgs &fd = st.stencil->a;
-                h->kept = esp_handle::KeptStructure{true, false, h->plan_gen, h->pred.gen, fd.nx, fd.ny, fd.nz, fused_keys, h->rowval.p, h->colptr.p, h->nzval.p,
-                                                    Zn, h->pattern_version};
-            }
-            return ESP_OK;
-        }
-        return finish_csc(h, 0, Zn, nullptr, nullptr);
+    if (c.stop_after || Zn == 0) return ESP_OK;
+    if (Z0 > 0) return finish_csc(h, Z0, Zn, (const u64 *)h->keys2.p, (const double *)h->vals2.p);
+    // the scratch pair now holds rowval/nzval: rotate the buffers instead of copying.  The old
+    // (empty) CSC arrays become the next flush's scratch pair: bring them to the same capacity
+    // once, so that the rotation never shrinks the scratch pair (a 10 GB hipMalloc per flush
+    // costs more than the flush itself)
+    // (the KEEP form wrote values only: rowval stays the array it is)
+    if (!c.keep) CK(ensure(h, h->rowval, h->keys2.bytes));
+    CK(ensure(h, h->nzval, h->vals2.bytes));
+    if (!c.keep) std::swap(h->rowval, h->keys2);
+    std::swap(h->nzval, h->vals2);
+    if (!c.direct) return finish_csc(h, 0, Zn, nullptr, nullptr);
+    // colptr is complete (behind a column window it is refreshed lazily, as after the scan)
+    if (windowed(h)) h->tail_stale = h->wc1 < h->n;
+    h->nnz = Zn;
+    h->pattern_version++, h->values_version++;
+    if (arm) {
+        const espgen::FdArgs &fd = st.stencil->a;
+        h->kept = esp_handle::KeptStructure{true, false, h->plan_gen, h->pred.gen, fd.nx, fd.ny, fd.nz, c.pair_keys, h->rowval.p, h->colptr.p, h->nzval.p,
+                                            Zn, h->pattern_version};
     }
-    return finish_csc(h, Z0, Zn, (const u64 *)tk, (const double *)tv);
+    return ESP_OK;
 }
 
 // general path: finish with a full stable LSD sort and the global fold (any run length)
@@ -972,6 +970,52 @@ int32_t flush_rebuild(esp_handle *h, const Sorted &st, int mode, i64 *Znew, bool
     return ESP_OK;
 }
 
+// The segments of a producer's bucket-ordered batch (esp_handle::PrePart), read where the producer left them.  fine: the buckets
+// of a FINE partition joined into the segments it was planned for.
+static Sorted pre_sorted(const esp_handle *h, const esp_handle::PrePart &pp, bool fine) {
+    Sorted st;
+    st.sk = (const u64 *)h->keys.p;
+    st.sv = (const double *)h->vals.p;
+    st.in_primary = true;
+    st.S = 1 << pp.pb;
+    st.total = pp.E;
+    st.seg_start = (const i64 *)h->seg[1].p;
+    st.rem_bits = pp.K - pp.pb;
+    st.local_ok = true;
+    st.key_bytes = pp.key_bytes;
+    st.kind = pp.kind;
+    st.maxlen = pp.maxlen;
+    if (fine && pp.fb > 0 && pp.key_bytes == 4 && !h->lazy.on) {
+        // a FINE partition: the bucket kernel takes 2^fb neighbouring buckets as one segment (PrePart::fb)
+        st.fb = pp.fb;
+        st.S = 1 << (pp.pb - pp.fb);
+        st.rem_bits = pp.K - pp.pb + pp.fb;
+        st.maxlen = pp.maxlen_c;
+    }
+    return st;
+}
+
+// flush_local over E pending entries of which a batch may still be held back (sorted items, a stencil's PART launch): a form that
+// does not take it as it is (ESP_RETRY_EXPANDED) gets the entries and is called again.  A failed flush leaves the batch pending
+// as it was: still held back, or expanded by the retry.  (A batch that is neither never retries: flush_local returns that code
+// with st.lazy or st.stencil only.)
+static int32_t flush_local_expanding(esp_handle *h, Sorted &st, int mode, i64 E, i64 *Zn) {
+    CK(ensure(h, h->keys2, sizeof(u64) * (size_t)E));
+    CK(ensure(h, h->vals2, sizeof(double) * (size_t)E));
+    const int32_t rc = flush_local(h, st, mode, Zn);
+    if (rc != ESP_RETRY_EXPANDED) return rc;
+    CK(lazy_expand(h));
+    // (a stencil's miss was counted: straight to the look-back form, which records the table anew)
+    if (st.stencil) st.no_pred = h->pred.last == 2;
+    st.sk = (const u64 *)h->keys.p;
+    st.sv = (const double *)h->vals.p;
+    st.lazy = nullptr;
+    st.stencil = nullptr;
+    CK(ensure(h, h->keys2, sizeof(u64) * (size_t)E));
+    CK(ensure(h, h->vals2, sizeof(double) * (size_t)E));
+    return flush_local(h, st, mode, Zn);
+}
+
 extern "C" int32_t esp_flush(esp_handle *h, int32_t mode, int64_t *new_nnz, int32_t *pattern_changed) {
     if (!h) return ESP_ERR_INVALID;
     if (mode != ESP_FLUSH_ROUTED && mode != ESP_FLUSH_PLUS) FAIL(h, ESP_ERR_INVALID, "esp_flush: mode");
@@ -1026,18 +1070,7 @@ extern "C" int32_t esp_flush(esp_handle *h, int32_t mode, int64_t *new_nnz, int3
         // buffer, which the flush adds as it is).  Not so csc + buffer (ESP_FLUSH_PLUS): the buffer is folded by itself
         // first.  force_path 22: one flush over two pieces, as on a fresh matrix.
         const esp_handle::PrePart pp = h->pre;
-        Sorted st;
-        st.sk = (const u64 *)h->keys.p;
-        st.sv = (const double *)h->vals.p;
-        st.in_primary = true;
-        st.S = 1 << pp.pb;
-        st.total = pp.E;
-        st.seg_start = (const i64 *)h->seg[1].p;
-        st.rem_bits = pp.K - pp.pb;
-        st.local_ok = true;
-        st.key_bytes = pp.key_bytes;
-        st.kind = pp.kind;
-        st.maxlen = pp.maxlen;
+        Sorted st = pre_sorted(h, pp, false);
         st.expect_hits = 1;  // (the batch repeats the stream that built the pattern; what is new comes behind it)
         CK(ensure(h, h->keys2, sizeof(u64) * (size_t)E));
         CK(ensure(h, h->vals2, sizeof(double) * (size_t)E));
@@ -1095,58 +1128,17 @@ extern "C" int32_t esp_flush(esp_handle *h, int32_t mode, int64_t *new_nnz, int3
         h->last_partition = tail_direct ? 8 : 5;
     } else if (h->pre.valid) {
         const esp_handle::PrePart &pp = h->pre;
-        Sorted st;
-        st.sk = (const u64 *)h->keys.p;
-        st.sv = (const double *)h->vals.p;
-        st.in_primary = true;
-        st.S = 1 << pp.pb;
-        st.total = pp.E;
-        st.seg_start = (const i64 *)h->seg[1].p;
-        st.rem_bits = pp.K - pp.pb;
-        st.local_ok = true;
-        st.key_bytes = pp.key_bytes;
-        st.kind = pp.kind;
-        st.maxlen = pp.maxlen;
-        if (pp.fb > 0 && pp.key_bytes == 4 && !h->lazy.on) {
-            // a FINE partition: the bucket kernel takes 2^fb neighbouring buckets as one segment (PrePart::fb)
-            st.fb = pp.fb;
-            st.S = 1 << (pp.pb - pp.fb);
-            st.rem_bits = pp.K - pp.pb + pp.fb;
-            st.maxlen = pp.maxlen_c;
-        }
-        CK(ensure(h, h->keys2, sizeof(u64) * (size_t)E));
-        CK(ensure(h, h->vals2, sizeof(double) * (size_t)E));
-        int32_t rc_local;
-        if (h->lazy.on) {
+        Sorted st = pre_sorted(h, pp, true);
+        if (h->lazy.on) {  // (sorted item records: the fused bucket kernel, or the entries and then the usual way)
             st.sk = h->lazy.src == 1 ? h->lazy.it.sorted_keys : h->lazy.el.sorted_keys;
             st.sv = nullptr;
             st.lazy = &h->lazy;
-            rc_local = flush_local(h, st, mode, &Zn);
-            if (rc_local == ESP_RETRY_EXPANDED) {  // (not the fused kernel's flush after all: the entries, then the usual way)
-                CK(lazy_expand(h));
-                st.sk = (const u64 *)h->keys.p;
-                st.sv = (const double *)h->vals.p;
-                st.lazy = nullptr;
-                CK(ensure(h, h->keys2, sizeof(u64) * (size_t)E));
-                CK(ensure(h, h->vals2, sizeof(double) * (size_t)E));
-                rc_local = flush_local(h, st, mode, &Zn);
-            }
-            // (a failed flush leaves the batch pending as it was: still items, or expanded by the retry)
         } else if (h->lazyst.on) {
-            st.stencil = &h->lazyst;  // (sk / sv: the arrays the held-back PART launch would fill -- the fused kernel reads neither)
-            rc_local = flush_local(h, st, mode, &Zn);
-            if (rc_local == ESP_RETRY_EXPANDED) {  // (no prediction at flush time, or it missed: the entries, then the parent's way)
-                CK(lazy_expand(h));
-                st.stencil = nullptr;
-                st.no_pred = h->pred.last == 2;  // (a miss was counted: straight to the look-back form, which records the table anew)
-                CK(ensure(h, h->keys2, sizeof(u64) * (size_t)E));
-                CK(ensure(h, h->vals2, sizeof(double) * (size_t)E));
-                rc_local = flush_local(h, st, mode, &Zn);
-            }
-        } else {
-            rc_local = flush_local(h, st, mode, &Zn);
+            // (sk / sv: the arrays the held-back PART launch would fill -- the fused kernel reads neither; no prediction at flush
+            // time, or it missed: the entries, then the look-back form)
+            st.stencil = &h->lazyst;
         }
-        CK(rc_local);
+        CK(flush_local_expanding(h, st, mode, E, &Zn));
         h->last_partition = 4;
         h->runs_penalty = 0;
         h->seen_spread = pp.Ee > 0.0 ? (double)pp.maxlen * std::ldexp(1.0, pp.pb) / pp.Ee : 0.0;

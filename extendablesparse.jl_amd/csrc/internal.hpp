@@ -816,6 +816,27 @@ static inline void col_range(const esp_handle *h, i64 *c0, i64 *cnt) {
     *cnt = windowed(h) ? h->wc1 - h->wc0 + 1 : h->n + 1;
 }
 
+// The look-back status area of a bucket-kernel launch over S segments (u64 words; flush.hip and sum.hip): one granule per
+// segment | error flag | longest run | one granule per group of 256 segments, rounded up to a 4 KiB page; behind them a page
+// of its own for the ticket counter (every workgroup draws from it while others poll the granules: on one line with them the
+// draws cost the headline's bucket kernel 0.18 of 1.55 ms) -- one memset of bytes() clears everything
+struct StatusLayout {
+    i64 S, G, words;
+    explicit StatusLayout(i64 S_) : S(S_) {
+        const i64 n_gs = (S >> 8) + 2;                     // (local.hpp: LB_SHIFT = 8)
+        G = ((S + 2 + n_gs + 511) & ~(i64)511) - (S + 2);  // (granules behind status[S + 1])
+        words = S + 2 + G + 512;
+    }
+    size_t bytes() const { return sizeof(u64) * (size_t)words; }
+    void point(esplocal::Args &a, u64 *status) const {
+        a.status = status;
+        a.gstatus = status + S + 2;
+        a.ticket = (u32 *)(status + S + 2 + G + 256);
+        a.err = (u32 *)(status + S) + 1;
+        a.maxrun_seen = (u32 *)(status + S) + 2;  // (zeroed with the granules)
+    }
+};
+
 // The digits of a partition cut the 2^K keys of the window's bit range, of which only `span` exist (a matrix
 // with 2^k + 1 columns fills half of it): the plan counts the entries as if the empty part were filled as well,
 // so that the occupied buckets come out at the planned fill.

@@ -268,14 +268,13 @@ static int32_t flush_sum_items(esp_handle *dst, esp_handle *const *xs, int p, in
     char *TB = (char *)dst->piecetab.p;
     i64 *pstart = (i64 *)(TB + o_ps);
     HIPCK(dst, hipMemsetAsync(pstart, 0, sizeof(i64) * (size_t)(p * (S + 1)), dst->stream));
-    const i64 n_gs = (SV >> 8) + 2;
-    const i64 G = ((SV + 2 + n_gs + 511) & ~(i64)511) - (SV + 2);
-    const i64 tick_at = SV + 2 + G + 256;
-    CK(ensure(dst, dst->segout, sizeof(u64) * (size_t)(SV + 2 + G + 512)));
+    const StatusLayout lay(SV);
+    CK(ensure(dst, dst->segout, lay.bytes()));
     u64 *status = (u64 *)dst->segout.p;
-    HIPCK(dst, hipMemsetAsync(status, 0, sizeof(u64) * (size_t)(SV + 2 + G + 512), dst->stream));
+    HIPCK(dst, hipMemsetAsync(status, 0, lay.bytes(), dst->stream));
     esplocal::Args a;
     memset(&a, 0, sizeof a);
+    lay.point(a, status);
     a.S = (int)SV;
     a.rem_bits = rem;
     a.base = dst->win_base;
@@ -285,11 +284,6 @@ static int32_t flush_sum_items(esp_handle *dst, esp_handle *const *xs, int p, in
     a.mode = ESP_FLUSH_ROUTED;
     a.out_key = (u64 *)dst->keys.p;
     a.out_val = (double *)dst->vals.p;
-    a.status = status;
-    a.gstatus = status + SV + 2;
-    a.ticket = (u32 *)(status + tick_at);
-    a.err = (u32 *)(status + SV) + 1;
-    a.maxrun_seen = (u32 *)(status + SV) + 2;
     a.total = -1;
     a.kind32 = (u32)e0.kind;
     a.k32_piece = -1;
