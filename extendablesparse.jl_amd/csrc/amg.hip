@@ -683,10 +683,7 @@ int32_t create(esp_handle *h, int32_t max_levels, int32_t max_coarse, int32_t pr
     if (!std::isfinite(theta)) FAIL(h, ESP_ERR_INVALID, "%s: theta is not finite", what);
     CK(precon_check_handle(h, what));
     if (windowed(h) || h->shard_user) FAIL(h, ESP_ERR_UNSUPPORTED, "%s: a column window / column shard", what);
-    esp_precon *p = new esp_precon();
-    p->h = h;
-    p->kind = ESP_PRECON_AMG;
-    p->n = h->n;
+    esp_precon *p = precon_new(h, ESP_PRECON_AMG);
     p->amg = new AmgData();
     p->amg->max_levels = max_levels;
     p->amg->max_coarse = max_coarse;
@@ -694,15 +691,7 @@ int32_t create(esp_handle *h, int32_t max_levels, int32_t max_coarse, int32_t pr
     p->amg->post = postsweeps;
     p->amg->theta = theta;
     p->amg->coarsen = coarsen;
-    h->live_precons++;
-    p->pattern_version = 0;  // never matches: the update below builds everything
-    const int32_t st = amg_update(p);
-    if (st != ESP_OK) {
-        (void)esp_precon_destroy(p);
-        return st;
-    }
-    *out = p;
-    return ESP_OK;
+    return precon_finish(p, amg_update(p), out);
 }
 }  // namespace
 

@@ -37,12 +37,6 @@ __device__ __forceinline__ u32 amg_mix(i64 i) {
     return x;
 }
 
-struct Temps {
-    DevBuf b[12];
-    ~Temps() {
-        for (DevBuf &x : b) release(x);
-    }
-};
 // internal handles of a build step: destroyed when the step ends unless taken over
 struct Handles {
     std::vector<esp_handle *> v;

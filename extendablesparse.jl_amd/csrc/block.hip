@@ -130,19 +130,7 @@ __global__ __launch_bounds__(BT) void blk_compact_k(const i64 *__restrict__ colp
         if (!FILL && lane == sl) o.cp[loc] = q;
     }
 }
-// columns longer than COLSORT_LANE are listed for the workgroup sort; st[0] = listed columns, st[1] = the longest column
-__global__ __launch_bounds__(BT) void blk_lens_k(const i64 *__restrict__ cp, i64 n, u32 *__restrict__ list, unsigned long long *__restrict__ st) {
-    const i64 c = (i64)blockIdx.x * BT + threadIdx.x;
-    const u32 len = c < n ? (u32)min(cp[c + 1] - cp[c], (i64)0xFFFFFFFFll) : 0u;
-    if (len > (u32)COLSORT_LANE) list[atomicAdd(&st[0], 1ull)] = (u32)c;
-    const u32 m = esp_wave_max(len);
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(&st[1], (unsigned long long)m);
-}
-__global__ void blk_add_one_k(i64 *__restrict__ p, i64 n) {
-    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] += 1;
-}
-// B.nzval[q] = A.nzval[src[q]] (the bits); pay != nullptr: src[q] is taken from the sort's payload first
+// the build's last step: B.nzval[q] = A.nzval[src[q]] (the bits); pay != nullptr: src[q] is taken from the sort's payload first
 __global__ void blk_gather_k(const u64 *__restrict__ pay, u32 *__restrict__ src, const u64 *__restrict__ nzA, u64 *__restrict__ nzB, i64 nnzB) {
     const i64 q = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= nnzB) return;
@@ -168,63 +156,20 @@ __global__ void blk_vec_scatter_k(const u32 *__restrict__ newpos, const double *
     u[i] = sub ? u[i] - x : x;
 }
 
-struct Temps {
-    DevBuf b[10];
-    ~Temps() {
-        for (DevBuf &x : b) release(x);
-    }
-};
-
-
-// the columns of (cp, rv, pay) sorted by row through an ESP_COO flush of a scratch handle: cp / rv / pay receive its CSC
-// (colptr 1-based, the payload where the values were)
-int32_t sort_generic(esp_precon *p, const BlkOut &fill_args, const u32 *newpos, i64 nnzB, DevBuf &cp, DevBuf &rv, DevBuf &pay) {
+// derived_update's builder: B from A's current CSC, installed in p->der.bh, src in p->der.src.  Everything that can fail comes in
+// front of the two, the vectors of the permuted path included: nothing of p changes when it fails
+int32_t build_b(esp_precon *p) {
     esp_handle *h = p->h;
-    const i64 n = p->n;
-    esp_handle *sc = nullptr;
-    struct ScratchGuard {
-        esp_handle **q;
-        ~ScratchGuard() {
-            if (*q) esp_destroy(*q);
-        }
-    } sguard{&sc};
-    const int32_t st = esp_create(n, n, h->device, nnzB, &sc);
-    if (st != ESP_OK) FAIL(h, st, "esp_precon_block: scratch handle: %s", esp_last_error(nullptr));
-    const int32_t rs = reserve_append(sc, nnzB);
-    if (rs != ESP_OK) FAIL(h, rs, "esp_precon_block: append buffer of the scratch handle: %s", sc->err.c_str());
-    BlkOut o = fill_args;
-    o.keys = (u64 *)sc->keys.p;
-    o.pay = (u64 *)sc->vals.p;
-    o.L = sc->L;
-    hipLaunchKernelGGL(blk_compact_k<true>, dim3(grid_for(n, BT)), dim3(BT), 0, h->stream, (const i64 *)h->colptr.p, (const i64 *)h->rowval.p, n,
-                       (const u32 *)p->blk_part.p, newpos, o);
-    HIPCK(h, hipGetLastError());
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    note_kind(sc, ESP_COO, nnzB);
-    sc->count = nnzB;
-    pending_changed(sc);
-    i64 z = 0;
-    int32_t ch = 0;
-    const int32_t fs = esp_flush(sc, ESP_FLUSH_ROUTED, &z, &ch);
-    if (fs != ESP_OK) FAIL(h, fs, "esp_precon_block: flush of the renumbered entries: %s", sc->err.c_str());
-    const int32_t ft = fix_tail(sc);
-    if (ft != ESP_OK) FAIL(h, ft, "esp_precon_block: %s", sc->err.c_str());
-    HIPCK(h, hipStreamSynchronize(sc->stream));
-    if (sc->nnz != nnzB) FAIL(h, ESP_ERR_HIP, "esp_precon_block: the flush stored %lld entries of %lld", (long long)sc->nnz, (long long)nnzB);
-    drop_kept(sc);  // (the scratch handle gives its arrays away)
-    std::swap(cp, sc->colptr);
-    std::swap(rv, sc->rowval);
-    std::swap(pay, sc->nzval);
-    return ESP_OK;
-}
-
-// B from A's current CSC: installed in p->bh, src in p->blk_src; nothing of p changes when it fails
-int32_t build_b(esp_precon *p, int path) {
-    esp_handle *h = p->h, *bh = p->bh;
     hipStream_t s = h->stream;
     const i64 n = p->n;
+    const int path = p->blk_force == 1 || !p->blk_increasing ? 1 : 0;
+    if (path) {
+        CK(ensure(h, p->blk_t, sizeof(double) * (size_t)std::max<i64>(n, 1)));
+        CK(ensure(h, p->blk_s, sizeof(double) * (size_t)std::max<i64>(n, 1)));
+    }
     Temps tmp;
-    DevBuf &cp = tmp.b[0], &rv = tmp.b[1], &nz = tmp.b[2], &src = tmp.b[3], &pay = tmp.b[4], &list = tmp.b[5], &stat = tmp.b[6], &ws = tmp.b[7];
+    DevBuf &cp = tmp.b[0], &rv = tmp.b[1], &nz = tmp.b[2], &src = tmp.b[3], &pay = tmp.b[4], &stat = tmp.b[6], &ws = tmp.b[7];
+    ColumnSort cs(h, "esp_precon_block");
     const u32 *newpos = path ? (const u32 *)p->blk_new.p : (const u32 *)nullptr;
     const u32 *part = (const u32 *)p->blk_part.p;
     const i64 *colptr = (const i64 *)h->colptr.p, *rowval = (const i64 *)h->rowval.p;
@@ -248,85 +193,33 @@ int32_t build_b(esp_precon *p, int path) {
         o.src = (u32 *)src.p;
         hipLaunchKernelGGL(blk_compact_k<true>, dim3(grid_for(n, BT)), dim3(BT), 0, s, colptr, rowval, n, part, newpos, o);
     } else if (nnzB > 0) {
-        CK(ensure(h, list, sizeof(u32) * (size_t)n));
         CK(ensure(h, stat, sizeof(u64) * 2));
         HIPCK(h, hipMemsetAsync(stat.p, 0, sizeof(u64) * 2, s));
-        hipLaunchKernelGGL(blk_lens_k, dim3(grid_for(n, BT)), dim3(BT), 0, s, (const i64 *)cp.p, n, (u32 *)list.p, (unsigned long long *)stat.p);
-        HIPCK(h, hipGetLastError());
-        HIPCK(h, hipMemcpyAsync(h->pin_scalar, stat.p, sizeof(u64) * 2, hipMemcpyDeviceToHost, s));
-        HIPCK(h, hipStreamSynchronize(s));
-        const i64 nlong = (i64)h->pin_scalar[0], maxlen = (i64)h->pin_scalar[1];
-        if (maxlen <= COLSORT_BLOCK) {
-            CK(ensure(h, rv, sizeof(i64) * (size_t)nnzB));
-            CK(ensure(h, pay, sizeof(u64) * (size_t)nnzB));
-            o.rowB = (i64 *)rv.p;
-            o.pay = (u64 *)pay.p;
-            hipLaunchKernelGGL(blk_compact_k<true>, dim3(grid_for(n, BT)), dim3(BT), 0, s, colptr, rowval, n, part, newpos, o);
-            sort_columns_launch(s, (const i64 *)cp.p, n, (i64 *)rv.p, (u64 *)pay.p, maxlen, (const u32 *)list.p, nlong);
-        } else {
-            CK(sort_generic(p, o, newpos, nnzB, cp, rv, pay));
-            one_based = true;
-        }
+        CK(cs.plan(cp, n, nnzB, (unsigned long long *)stat.p, rv, pay));
+        o.rowB = cs.rowB;
+        o.pay = cs.pay;
+        o.keys = cs.keys;
+        o.L = cs.L;
+        hipLaunchKernelGGL(blk_compact_k<true>, dim3(grid_for(n, BT)), dim3(BT), 0, s, colptr, rowval, n, part, newpos, o);
+        CK(cs.finish(&one_based));
     }
     if (nnzB == 0) CK(ensure(h, rv, sizeof(i64)));
-    if (!one_based) hipLaunchKernelGGL(blk_add_one_k, dim3(grid_for(n + 1, BT)), dim3(BT), 0, s, (i64 *)cp.p, n + 1);
+    if (!one_based) add_one_launch(s, (i64 *)cp.p, n + 1);
     if (nnzB > 0)
         hipLaunchKernelGGL(blk_gather_k, dim3(grid_for(nnzB, BT)), dim3(BT), 0, s, path ? (const u64 *)pay.p : (const u64 *)nullptr, (u32 *)src.p,
                            (const u64 *)h->nzval.p, (u64 *)nz.p, nnzB);
     HIPCK(h, hipGetLastError());
     HIPCK(h, hipStreamSynchronize(s));
-    install(bh, cp, rv, nz, nnzB);
-    std::swap(p->blk_src, src);
+    install(p->der.bh, cp, rv, nz, nnzB);
+    std::swap(p->der.src, src);
+    p->blk_path = path;
     return ESP_OK;
 }
 
 }  // namespace
 
-// B's handle runs on A's stream (which esp_set_stream may have replaced since)
-int32_t block_follow_stream(esp_precon *p) {
-    if (p->bh && p->bh->stream != p->h->stream) CK(esp_set_stream(p->bh, (void *)p->h->stream));
-    return ESP_OK;
-}
-
 int32_t block_update(esp_precon *p) {
-    esp_handle *h = p->h;
-    CK(precon_check_handle(h, "esp_precon_update"));
-    if (windowed(h) || h->shard_user) FAIL(h, ESP_ERR_UNSUPPORTED, "esp_precon_block: a column window / column shard");
-    CK(block_follow_stream(p));
-    hipStream_t s = h->stream;
-    const bool rebuild = p->blk_rebuild || p->pattern_version != h->pattern_version || p->nnz != h->nnz;
-    if (rebuild) {
-        // everything that can fail before B is replaced comes first: a failed rebuild (ESP_ERR_NOMEM) leaves p as it was -- still
-        // usable where A's pattern is the one of its last good update!
-        const int path = p->blk_force == 1 || !p->blk_increasing ? 1 : 0;
-        if (path) {
-            CK(ensure(h, p->blk_t, sizeof(double) * (size_t)std::max<i64>(p->n, 1)));
-            CK(ensure(h, p->blk_s, sizeof(double) * (size_t)std::max<i64>(p->n, 1)));
-        }
-        CK(build_b(p, path));
-        p->pattern_version = 0;  // B is new, the inner preconditioner is not yet: a failure below refuses ldiv! until the next good update!
-        p->blk_path = path;
-        p->blk_rebuild = false;
-    } else {
-        p->pattern_version = 0;  // (B's values are overwritten in place: as above)
-        const i64 nnzB = p->bh->nnz;
-        if (nnzB > 0)
-            hipLaunchKernelGGL(blk_gather_k, dim3(grid_for(nnzB, BT)), dim3(BT), 0, s, (const u64 *)nullptr, (u32 *)p->blk_src.p,
-                               (const u64 *)h->nzval.p, (u64 *)p->bh->nzval.p, nnzB);
-        HIPCK(h, hipGetLastError());
-        p->bh->values_version++;
-    }
-    int32_t st;
-    if (!p->inner) st = esp_precon_create(p->bh, p->inner_kind, &p->inner);
-    else st = esp_precon_update(p->inner);
-    if (st != ESP_OK)
-        FAIL(h, st, "esp_precon_block: %s%s", p->bh->err.c_str(),
-             st == ESP_ERR_INVALID && p->blk_path ? " (a column of B: the position in the concatenated partitions)" : "");
-    HIPCK(h, hipStreamSynchronize(s));
-    p->nnz = h->nnz;
-    p->pattern_version = h->pattern_version;
-    p->values_version = h->values_version;
-    return ESP_OK;
+    return derived_update(p, "esp_precon_block", build_b, " (a column of B: the position in the concatenated partitions)");
 }
 
 // ldiv! on device vectors (u may be v); sub: u[i] = u[i] - x[i] (simple!'s step on the permuted path)
@@ -334,26 +227,26 @@ int32_t block_ldiv_launch(esp_precon *p, const double *v, double *u, bool sub) {
     esp_handle *h = p->h;
     const i64 n = p->n;
     if (n == 0) return ESP_OK;
-    CK(block_follow_stream(p));
+    CK(derived_follow_stream(p));
     if (p->blk_path == 0) {  // (simple! fuses its `u .-= upd` into the inner kind's own kernels there)
         if (sub) FAIL(h, ESP_ERR_STATE, "esp_precon_block: the identity path has no subtracting ldiv!");
-        return precon_ldiv_launch(p->inner, v, u);
+        return precon_ldiv_launch(p->der.inner, v, u);
     }
     const u32 *newpos = (const u32 *)p->blk_new.p;
     double *t = (double *)p->blk_t.p, *sv = (double *)p->blk_s.p;
     const unsigned g = grid_for(n, BT);
     hipLaunchKernelGGL(blk_vec_gather_k, dim3(g), dim3(BT), 0, h->stream, newpos, v, t, n);
-    CK(precon_ldiv_launch(p->inner, t, sv));
+    CK(precon_ldiv_launch(p->der.inner, t, sv));
     hipLaunchKernelGGL(blk_vec_scatter_k, dim3(g), dim3(BT), 0, h->stream, newpos, (const double *)sv, u, n, sub);
     return ESP_OK;
 }
 
 void block_release(esp_precon *p) {
-    if (p->inner) (void)esp_precon_destroy(p->inner);
-    p->inner = nullptr;
-    if (p->bh) (void)esp_destroy(p->bh);
-    p->bh = nullptr;
-    for (DevBuf *b : {&p->blk_new, &p->blk_part, &p->blk_src, &p->blk_t, &p->blk_s}) release(*b);
+    if (p->der.inner) (void)esp_precon_destroy(p->der.inner);
+    p->der.inner = nullptr;
+    if (p->der.bh) (void)esp_destroy(p->der.bh);
+    p->der.bh = nullptr;
+    for (DevBuf *b : {&p->blk_new, &p->blk_part, &p->der.src, &p->blk_t, &p->blk_s}) release(*b);
 }
 
 extern "C" int32_t esp_precon_block_create(esp_handle *h, int32_t inner_kind, int64_t nparts, const int64_t *part_ptr,
@@ -388,13 +281,8 @@ extern "C" int32_t esp_precon_block_create(esp_handle *h, int32_t inner_kind, in
     if (pp[(size_t)nparts] != n)
         FAIL(h, ESP_ERR_INVALID, "esp_precon_block_create: the partitions hold %lld indices, the matrix has %lld (the reference only warns)",
              (long long)pp[(size_t)nparts], (long long)n);
-    esp_precon *p = new esp_precon();
-    p->h = h;
-    p->kind = ESP_PRECON_BLOCK;
-    p->inner_kind = inner_kind;
-    p->n = n;
-    h->live_precons++;
-    p->pattern_version = 0;  // never matches: the update below builds everything
+    esp_precon *p = precon_new(h, ESP_PRECON_BLOCK);
+    p->der.inner_kind = inner_kind;
     const int32_t st = [&]() -> int32_t {
         Temps tmp;
         DevBuf &dptr = tmp.b[0], &didx = tmp.b[1], &cnt = tmp.b[2], &stat = tmp.b[3];
@@ -434,28 +322,23 @@ extern "C" int32_t esp_precon_block_create(esp_handle *h, int32_t inner_kind, in
             if (miss != ~0ull) FAIL(h, ESP_ERR_INVALID, "esp_precon_block_create: index %llu is in no partition", miss);
             p->blk_increasing = noninc == 0;
         }
-        const int32_t cs = esp_create(n, n, h->device, 0, &p->bh);
+        const int32_t cs = esp_create(n, n, h->device, 0, &p->der.bh);
         if (cs != ESP_OK) FAIL(h, cs, "esp_precon_block_create: the handle of B: %s", esp_last_error(nullptr));
         return block_update(p);
     }();
-    if (st != ESP_OK) {
-        (void)esp_precon_destroy(p);
-        return st;
-    }
-    *out = p;
-    return ESP_OK;
+    return precon_finish(p, st, out);
 }
 
 extern "C" int32_t esp_precon_block_matrix(esp_precon *p, esp_handle **b, int32_t *path) {
     if (!p || p->kind != ESP_PRECON_BLOCK) return ESP_ERR_INVALID;
-    if (b) *b = p->bh;
+    if (b) *b = p->der.bh;
     if (path) *path = p->blk_path;
     return ESP_OK;
 }
 
 extern "C" int32_t esp_debug_block_path(esp_precon *p, int32_t path) {
     if (!p || p->kind != ESP_PRECON_BLOCK || path < 0 || path > 1) return ESP_ERR_INVALID;
-    if (p->blk_force != path) p->blk_rebuild = true;
+    if (p->blk_force != path) p->der.rebuild = true;
     p->blk_force = path;
     return ESP_OK;
 }

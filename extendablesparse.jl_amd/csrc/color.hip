@@ -224,24 +224,24 @@ int32_t color_update(esp_precon *p) {
     esp_handle *h = p->h;
     CK(precon_check_handle(h, "esp_precon_update"));
     if (windowed(h) || h->shard_user) FAIL(h, ESP_ERR_UNSUPPORTED, "esp_precon_colored: a column window / column shard");
-    CK(block_follow_stream(p));
-    if (!(p->blk_rebuild || p->pattern_version != h->pattern_version || p->nnz != h->nnz)) return block_update(p);  // the values only
+    CK(derived_follow_stream(p));
+    if (!derived_stale(p)) return block_update(p);  // the values only
     // A's pattern is new: the colouring and the maps anew, in buffers of their own until block_update has replaced B -- a rebuild that
     // fails before that leaves p as its last good update made it
     DevBuf color, perm, newpos, part;
     std::vector<i64> ptr;
-    const bool was_rebuild = p->blk_rebuild;
+    const bool was_rebuild = p->der.rebuild;
     int32_t st = color_graph(h, color, ptr);
     if (st == ESP_OK) st = color_maps(h, color, (i64)ptr.size() - 1, perm, newpos, part);
     if (st == ESP_OK) {
         std::swap(p->blk_new, newpos);
         std::swap(p->blk_part, part);
-        p->blk_rebuild = true;
+        p->der.rebuild = true;
         st = block_update(p);
-        if (st != ESP_OK && p->blk_rebuild) {  // B was not replaced: the earlier maps again
+        if (st != ESP_OK && p->der.rebuild) {  // B was not replaced: the earlier maps again
             std::swap(p->blk_new, newpos);
             std::swap(p->blk_part, part);
-            p->blk_rebuild = was_rebuild;
+            p->der.rebuild = was_rebuild;
         } else {
             std::swap(p->col_color, color);
             std::swap(p->col_perm, perm);
@@ -280,32 +280,22 @@ extern "C" int32_t esp_precon_colored_create(esp_handle *h, int32_t inner_kind, 
     CK(precon_check_handle(h, "esp_precon_colored_create"));
     if (windowed(h) || h->shard_user) FAIL(h, ESP_ERR_UNSUPPORTED, "esp_precon_colored_create: a column window / column shard");
     const i64 n = h->n;
-    esp_precon *p = new esp_precon();
-    p->h = h;
-    p->kind = ESP_PRECON_COLORED;
-    p->inner_kind = inner_kind;
-    p->n = n;
+    esp_precon *p = precon_new(h, ESP_PRECON_COLORED);
+    p->der.inner_kind = inner_kind;
     p->blk_increasing = n == 0;  // the permuted path always (an empty matrix: the identity path, nothing to permute)
-    p->blk_rebuild = true;
-    h->live_precons++;
-    p->pattern_version = 0;  // never matches: the update below builds everything
+    p->der.rebuild = true;
     const int32_t st = [&]() -> int32_t {
-        const int32_t cs = esp_create(n, n, h->device, 0, &p->bh);
+        const int32_t cs = esp_create(n, n, h->device, 0, &p->der.bh);
         if (cs != ESP_OK) FAIL(h, cs, "esp_precon_colored_create: the handle of B: %s", esp_last_error(nullptr));
         return color_update(p);
     }();
-    if (st != ESP_OK) {
-        (void)esp_precon_destroy(p);
-        return st;
-    }
-    *out = p;
-    return ESP_OK;
+    return precon_finish(p, st, out);
 }
 
 extern "C" int32_t esp_precon_colored_info(esp_precon *p, int64_t out[2]) {
     if (!p || p->kind != ESP_PRECON_COLORED || !out) return ESP_ERR_INVALID;
     out[0] = (i64)p->col_ptr.size() - 1;
-    out[1] = p->bh ? p->bh->nnz : 0;
+    out[1] = p->der.bh ? p->der.bh->nnz : 0;
     return ESP_OK;
 }
 
@@ -323,6 +313,6 @@ extern "C" int32_t esp_precon_colored_perm(esp_precon *p, int64_t *c, int32_t on
 
 extern "C" int32_t esp_precon_colored_matrix(esp_precon *p, esp_handle **b) {
     if (!p || p->kind != ESP_PRECON_COLORED) return ESP_ERR_INVALID;
-    if (b) *b = p->bh;
+    if (b) *b = p->der.bh;
     return ESP_OK;
 }

@@ -392,12 +392,12 @@ void iluam_release(esp_precon *p) {
 extern "C" int32_t esp_precon_get_factor(esp_precon *p, double *nzval, int32_t on_device) {
     if (!p || !nzval) return ESP_ERR_INVALID;
     esp_handle *h = p->h;
-    if (block_built(p) || p->kind == ESP_PRECON_ILUK) {  // the inner factorization: nnz(B) values in B's position order
+    if (holds_derived(p)) {  // the inner factorization: nnz(B) values in B's position order
         if (h->pattern_version != p->pattern_version || h->nnz != p->nnz)
             FAIL(h, ESP_ERR_STATE, "esp_precon_get_factor: the matrix pattern changed since the preconditioner's last update!");
-        CK(block_follow_stream(p));
-        const int32_t st = esp_precon_get_factor(p->inner, nzval, on_device);
-        if (st != ESP_OK) FAIL(h, st, "%s", p->bh->err.c_str());
+        CK(derived_follow_stream(p));
+        const int32_t st = esp_precon_get_factor(p->der.inner, nzval, on_device);
+        if (st != ESP_OK) FAIL(h, st, "%s", p->der.bh->err.c_str());
         return ESP_OK;
     }
     if (p->kind != ESP_PRECON_ILUAM) FAIL(h, ESP_ERR_INVALID, "esp_precon_get_factor: not an ILUAM preconditioner");
@@ -416,14 +416,14 @@ extern "C" int32_t esp_precon_get_factor(esp_precon *p, double *nzval, int32_t o
 
 extern "C" int32_t esp_precon_levels(esp_precon *p, int64_t out[3]) {
     if (!p || !out) return ESP_ERR_INVALID;
-    if ((block_built(p) || p->kind == ESP_PRECON_ILUK) && p->inner) p = p->inner;
+    if (holds_derived(p) && p->der.inner) p = p->der.inner;
     for (int k = 0; k < 3; k++) out[k] = p->kind == ESP_PRECON_ILUAM ? p->sched[k].levels : 0;
     return ESP_OK;
 }
 
 extern "C" int32_t esp_precon_launches(esp_precon *p, int64_t out[6]) {
     if (!p || !out) return ESP_ERR_INVALID;
-    if ((block_built(p) || p->kind == ESP_PRECON_ILUK) && p->inner) p = p->inner;
+    if (holds_derived(p) && p->der.inner) p = p->der.inner;
     for (int k = 0; k < 3; k++) {
         i64 wide = 0, thin = 0;
         if (p->kind == ESP_PRECON_ILUAM)

@@ -32,11 +32,9 @@
 
 namespace {
 
-constexpr int KT = 256;                 // threads of the small kernels
 constexpr int WAVE_T = 64, WIDE_T = 512;  // lanes of the two forms of the search
 constexpr int SHORT_COL = 16;           // a frontier vertex with more stored rows is expanded by the whole workgroup
 constexpr u32 ILUK_EMPTY = 0xFFFFFFFFu;  // (n < 2^32 - 16: no vertex)
-constexpr u32 ILUK_FILL = 0xFFFFFFFFu;   // src of a fill entry (nnz(A) < 2^32 - 16: no position)
 static_assert((ESP_ILUK_WAVE_VISITS & (ESP_ILUK_WAVE_VISITS - 1)) == 0 && (ESP_ILUK_VISIT_MAX & (ESP_ILUK_VISIT_MAX - 1)) == 0,
               "the visited tables hold twice the capacity, a power of two");
 static_assert(ESP_ILUK_WAVE_VISITS >= 2 * WAVE_T && ESP_ILUK_VISIT_MAX >= 2 * WIDE_T, "insertions in flight when the table is closed");
@@ -212,59 +210,17 @@ __global__ __launch_bounds__(T) void iluk_search_k(const i64 *__restrict__ gcp, 
     }
 }
 
-// columns longer than COLSORT_LANE are listed for the workgroup sort; st[0] = listed columns, st[1] = the longest column
-__global__ __launch_bounds__(KT) void iluk_lens_k(const i64 *__restrict__ cp, i64 n, u32 *__restrict__ list, unsigned long long *__restrict__ st) {
-    const i64 c = (i64)blockIdx.x * KT + threadIdx.x;
-    const u32 len = c < n ? (u32)min(cp[c + 1] - cp[c], (i64)0xFFFFFFFFll) : 0u;
-    if (len > (u32)COLSORT_LANE) list[atomicAdd(&st[0], 1ull)] = (u32)c;
-    const u32 m = esp_wave_max(len);
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(&st[1], (unsigned long long)m);
-}
-__global__ void iluk_add_one_k(i64 *__restrict__ p, i64 n) {
-    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] += 1;
-}
-// pay != nullptr: src[q] and lev[q] from the sorted payloads first (maxlev: the largest level); then
-// B.nzval[q] = src[q] == ILUK_FILL ? +0.0 : A.nzval[src[q]] (the bits)
-__global__ __launch_bounds__(KT) void iluk_gather_k(const u64 *__restrict__ pay, u32 *__restrict__ src, int32_t *__restrict__ lev,
-                                                    const u64 *__restrict__ nzA, u64 *__restrict__ nzB, i64 nnzB,
-                                                    unsigned long long *__restrict__ maxlev) {
-    const i64 q = (i64)blockIdx.x * KT + threadIdx.x;
-    u32 s = ILUK_FILL, l = 0;
-    if (q < nnzB) {
-        if (pay) {
-            const u64 w = pay[q];
-            s = (u32)w;
-            l = (u32)(w >> 32);
-            src[q] = s;
-            lev[q] = (int32_t)l;
-        } else {
-            s = src[q];
-        }
-        nzB[q] = s == ILUK_FILL ? 0ull : nzA[s];
-    }
-    if (pay) {
-        const u32 m = esp_wave_max(l);
-        if ((threadIdx.x & 63) == 0 && m) atomicMax(maxlev, (unsigned long long)m);
-    }
-}
-
-struct Temps {
-    DevBuf b[16];
-    ~Temps() {
-        for (DevBuf &x : b) release(x);
-    }
-};
-
-// B from A's current CSC: installed in p->bh, src in p->blk_src, the levels in p->iluk_lev; nothing of p changes when it fails
+// derived_update's builder: B from A's current CSC, installed in p->der.bh, src in p->der.src, the levels in p->iluk_lev; nothing of p
+// changes when it fails
 int32_t build_b(esp_precon *p) {
-    esp_handle *h = p->h, *bh = p->bh, *th = p->iluk_th;
+    esp_handle *h = p->h, *bh = p->der.bh, *th = p->iluk_th;
     hipStream_t s = h->stream;
     const i64 n = p->n;
     const int K = p->iluk_k;
     Temps tmp;
-    DevBuf &cp = tmp.b[0], &rv = tmp.b[1], &nz = tmp.b[2], &src = tmp.b[3], &pay = tmp.b[4], &list = tmp.b[5], &stat = tmp.b[6], &ws = tmp.b[7],
+    DevBuf &cp = tmp.b[0], &rv = tmp.b[1], &nz = tmp.b[2], &src = tmp.b[3], &pay = tmp.b[4], &stat = tmp.b[6], &ws = tmp.b[7],
            &lev = tmp.b[8], &cur = tmp.b[9], &wide = tmp.b[10], &wlist = tmp.b[11];
+    ColumnSort cs(h, "esp_precon_iluk");
     int l = 0;
     if (n > 0) {
         const int32_t ts = esp_transpose(h, th, nullptr);
@@ -334,80 +290,35 @@ int32_t build_b(esp_precon *p) {
     bool one_based = false;
     if (nnzB > 0) {
         CK(ensure(h, cur, sizeof(u64) * (size_t)n));
-        CK(ensure(h, list, sizeof(u32) * (size_t)n));
         HIPCK(h, hipMemsetAsync(cur.p, 0, sizeof(u64) * (size_t)n, s));
-        hipLaunchKernelGGL(iluk_lens_k, dim3(grid_for(n, KT)), dim3(KT), 0, s, (const i64 *)cp.p, n, (u32 *)list.p, st + 5);
-        HIPCK(h, hipGetLastError());
-        HIPCK(h, hipMemcpyAsync(h->pin_scalar, st + 5, sizeof(u64) * 2, hipMemcpyDeviceToHost, s));
-        HIPCK(h, hipStreamSynchronize(s));
-        const i64 nlong = (i64)h->pin_scalar[0], maxlen = (i64)h->pin_scalar[1];
+        CK(cs.plan(cp, n, nnzB, st + 5, rv, pay));
         base.cnt = nullptr;
         base.cp = (const i64 *)cp.p;
         base.cur = (unsigned long long *)cur.p;
-        auto fill = [&]() {
-            for (int u = 0; u < 2; u++) {
-                hipLaunchKernelGGL((iluk_search_k<WAVE_T, ESP_ILUK_WAVE_VISITS, true>), dim3((unsigned)n), dim3(WAVE_T), 0, s, gcp[u], grv[u], A, n, K,
-                                   u == 1, (const u32 *)nullptr, side(u));
-                if (nwide[u] > 0)
-                    hipLaunchKernelGGL((iluk_search_k<WIDE_T, ESP_ILUK_VISIT_MAX, true>), dim3((unsigned)nwide[u]), dim3(WIDE_T), 0, s, gcp[u],
-                                       grv[u], A, n, K, u == 1, (const u32 *)side(u).list, side(u));
-            }
-        };
-        if (maxlen <= COLSORT_BLOCK) {
-            CK(ensure(h, rv, sizeof(i64) * (size_t)nnzB));
-            CK(ensure(h, pay, sizeof(u64) * (size_t)nnzB));
-            base.rowB = (i64 *)rv.p;
-            base.pay = (u64 *)pay.p;
-            fill();
-            sort_columns_launch(s, (const i64 *)cp.p, n, (i64 *)rv.p, (u64 *)pay.p, maxlen, (const u32 *)list.p, nlong);
-        } else {  // the entries as ESP_COO records, the payload as the value's bits, through a flush of a scratch handle
-            esp_handle *sc = nullptr;
-            struct ScratchGuard {
-                esp_handle **q;
-                ~ScratchGuard() {
-                    if (*q) esp_destroy(*q);
-                }
-            } sguard{&sc};
-            const int32_t cs = esp_create(n, n, h->device, nnzB, &sc);
-            if (cs != ESP_OK) FAIL(h, cs, "esp_precon_iluk: scratch handle: %s", esp_last_error(nullptr));
-            const int32_t rs = reserve_append(sc, nnzB);
-            if (rs != ESP_OK) FAIL(h, rs, "esp_precon_iluk: append buffer of the scratch handle: %s", sc->err.c_str());
-            base.keys = (u64 *)sc->keys.p;
-            base.pay = (u64 *)sc->vals.p;
-            base.L = sc->L;
-            fill();
-            HIPCK(h, hipGetLastError());
-            HIPCK(h, hipStreamSynchronize(s));
-            note_kind(sc, ESP_COO, nnzB);
-            sc->count = nnzB;
-            pending_changed(sc);
-            i64 z = 0;
-            int32_t ch = 0;
-            const int32_t fs = esp_flush(sc, ESP_FLUSH_ROUTED, &z, &ch);
-            if (fs != ESP_OK) FAIL(h, fs, "esp_precon_iluk: flush of the filled pattern: %s", sc->err.c_str());
-            const int32_t ft = fix_tail(sc);
-            if (ft != ESP_OK) FAIL(h, ft, "esp_precon_iluk: %s", sc->err.c_str());
-            HIPCK(h, hipStreamSynchronize(sc->stream));
-            if (sc->nnz != nnzB) FAIL(h, ESP_ERR_HIP, "esp_precon_iluk: the flush stored %lld entries of %lld", (long long)sc->nnz, (long long)nnzB);
-            drop_kept(sc);  // (the scratch handle gives its arrays away)
-            std::swap(cp, sc->colptr);
-            std::swap(rv, sc->rowval);
-            std::swap(pay, sc->nzval);
-            one_based = true;
+        base.rowB = cs.rowB;
+        base.pay = cs.pay;
+        base.keys = cs.keys;
+        base.L = cs.L;
+        for (int u = 0; u < 2; u++) {
+            hipLaunchKernelGGL((iluk_search_k<WAVE_T, ESP_ILUK_WAVE_VISITS, true>), dim3((unsigned)n), dim3(WAVE_T), 0, s, gcp[u], grv[u], A, n, K,
+                               u == 1, (const u32 *)nullptr, side(u));
+            if (nwide[u] > 0)
+                hipLaunchKernelGGL((iluk_search_k<WIDE_T, ESP_ILUK_VISIT_MAX, true>), dim3((unsigned)nwide[u]), dim3(WIDE_T), 0, s, gcp[u],
+                                   grv[u], A, n, K, u == 1, (const u32 *)side(u).list, side(u));
         }
+        CK(cs.finish(&one_based));
     }
     if (nnzB == 0) CK(ensure(h, rv, sizeof(i64)));
-    if (!one_based) hipLaunchKernelGGL(iluk_add_one_k, dim3(grid_for(n + 1, KT)), dim3(KT), 0, s, (i64 *)cp.p, n + 1);
+    if (!one_based) add_one_launch(s, (i64 *)cp.p, n + 1);
     if (nnzB > 0)
-        hipLaunchKernelGGL(iluk_gather_k, dim3(grid_for(nnzB, KT)), dim3(KT), 0, s, (const u64 *)pay.p, (u32 *)src.p, (int32_t *)lev.p,
-                           (const u64 *)h->nzval.p, (u64 *)nz.p, nnzB, st + 4);
+        derived_gather_launch(s, (const u64 *)pay.p, (u32 *)src.p, (int32_t *)lev.p, (const u64 *)h->nzval.p, (u64 *)nz.p, nnzB, st + 4);
     HIPCK(h, hipGetLastError());
     HIPCK(h, hipMemcpyAsync(h->pin_scalar, st + 3, sizeof(u64) * 2, hipMemcpyDeviceToHost, s));
     HIPCK(h, hipStreamSynchronize(s));
     if (h->pin_scalar[0] != 0) FAIL(h, ESP_ERR_HIP, "esp_precon_iluk: the fill pass of the search disagrees with its count pass");
     const i64 maxlev = (i64)h->pin_scalar[1];
     install(bh, cp, rv, nz, nnzB);
-    std::swap(p->blk_src, src);
+    std::swap(p->der.src, src);
     std::swap(p->iluk_lev, lev);
     p->iluk_stats[0] = nnzB;
     p->iluk_stats[1] = maxlev;
@@ -416,46 +327,9 @@ int32_t build_b(esp_precon *p) {
     return ESP_OK;
 }
 
-int32_t follow_stream(esp_precon *p) {
-    CK(block_follow_stream(p));
-    if (p->iluk_th && p->iluk_th->stream != p->h->stream) CK(esp_set_stream(p->iluk_th, (void *)p->h->stream));
-    return ESP_OK;
-}
-
 }  // namespace
 
-int32_t iluk_update(esp_precon *p) {
-    esp_handle *h = p->h;
-    CK(precon_check_handle(h, "esp_precon_update"));
-    if (windowed(h) || h->shard_user) FAIL(h, ESP_ERR_UNSUPPORTED, "esp_precon_iluk: a column window / column shard");
-    CK(follow_stream(p));
-    hipStream_t s = h->stream;
-    const bool rebuild = p->blk_rebuild || p->pattern_version != h->pattern_version || p->nnz != h->nnz;
-    if (rebuild) {
-        // everything that can fail before B is replaced comes first: a failed rebuild leaves p as it was -- still usable where A's
-        // pattern is the one of its last good update!
-        CK(build_b(p));
-        p->pattern_version = 0;  // B is new, the inner preconditioner is not yet: a failure below refuses ldiv! until the next good update!
-        p->blk_rebuild = false;
-    } else {
-        p->pattern_version = 0;  // (B's values are overwritten in place: as above)
-        const i64 nnzB = p->bh->nnz;
-        if (nnzB > 0)
-            hipLaunchKernelGGL(iluk_gather_k, dim3(grid_for(nnzB, KT)), dim3(KT), 0, s, (const u64 *)nullptr, (u32 *)p->blk_src.p, (int32_t *)nullptr,
-                               (const u64 *)h->nzval.p, (u64 *)p->bh->nzval.p, nnzB, (unsigned long long *)nullptr);
-        HIPCK(h, hipGetLastError());
-        p->bh->values_version++;
-    }
-    int32_t st;
-    if (!p->inner) st = esp_precon_create(p->bh, ESP_PRECON_ILUAM, &p->inner);
-    else st = esp_precon_update(p->inner);
-    if (st != ESP_OK) FAIL(h, st, "esp_precon_iluk: %s", p->bh->err.c_str());
-    HIPCK(h, hipStreamSynchronize(s));
-    p->nnz = h->nnz;
-    p->pattern_version = h->pattern_version;
-    p->values_version = h->values_version;
-    return ESP_OK;
-}
+int32_t iluk_update(esp_precon *p) { return derived_update(p, "esp_precon_iluk", build_b, ""); }
 
 void iluk_release(esp_precon *p) {
     if (p->iluk_th) (void)esp_destroy(p->iluk_th);
@@ -469,33 +343,22 @@ extern "C" int32_t esp_precon_iluk_create(esp_handle *h, int32_t k, esp_precon *
     if (k < 0) FAIL(h, ESP_ERR_INVALID, "esp_precon_iluk_create: k = %d < 0", k);
     CK(precon_check_handle(h, "esp_precon_iluk_create"));
     if (windowed(h) || h->shard_user) FAIL(h, ESP_ERR_UNSUPPORTED, "esp_precon_iluk_create: a column window / column shard");
-    const i64 n = h->n;
-    esp_precon *p = new esp_precon();
-    p->h = h;
-    p->kind = ESP_PRECON_ILUK;
-    p->inner_kind = ESP_PRECON_ILUAM;
-    p->n = n;
+    esp_precon *p = precon_new(h, ESP_PRECON_ILUK);
+    p->der.inner_kind = ESP_PRECON_ILUAM;
     p->iluk_k = k;
-    h->live_precons++;
-    p->pattern_version = 0;  // never matches: the update below builds everything
     const int32_t st = [&]() -> int32_t {
-        for (esp_handle **q : {&p->bh, &p->iluk_th}) {
-            const int32_t cs = esp_create(n, n, h->device, 0, q);
+        for (esp_handle **q : {&p->der.bh, &p->iluk_th}) {
+            const int32_t cs = esp_create(h->n, h->n, h->device, 0, q);
             if (cs != ESP_OK) FAIL(h, cs, "esp_precon_iluk_create: an internal handle: %s", esp_last_error(nullptr));
         }
         return iluk_update(p);
     }();
-    if (st != ESP_OK) {
-        (void)esp_precon_destroy(p);
-        return st;
-    }
-    *out = p;
-    return ESP_OK;
+    return precon_finish(p, st, out);
 }
 
 extern "C" int32_t esp_precon_iluk_matrix(esp_precon *p, esp_handle **b) {
     if (!p || p->kind != ESP_PRECON_ILUK) return ESP_ERR_INVALID;
-    if (b) *b = p->bh;
+    if (b) *b = p->der.bh;
     return ESP_OK;
 }
 

@@ -9,6 +9,8 @@
 //   consumers.hip  what reads or edits the assembled CSC: getindex, dropzeros, pattern hash, mul!, Dirichlet, Jacobi / ILU0
 //   precon.hip     the point preconditioners' update! / ldiv! (esp_precon_*) and simple! (esp_simple) on the device CSC
 //   iluam.hip      ILUAMPreconditioner: level analysis, level-scheduled ILU(0) factorization and triangular solves
+//   derived.hip    what the kinds that hold a derived matrix share (Block, Colored, ILU(k)): the update! cycle, the value gather, the
+//                  stream hand-over; ScratchFlush, the sort by an ESP_COO flush of a scratch handle (also esp_transpose, esp_matmul)
 //   block.hip      BlockPreconditioner: the masked block matrix B of a partitioning (identity / permuted path) and the object around it
 //   color.hip      the multicolour ordering: graph colouring by rounds over a fixed hash (esp_graph_coloring), the permutation by
 //                  (colour, index), ColoredPreconditioner = block.hip's permuted path over that one partition
@@ -598,41 +600,54 @@ struct esp_precon {
     // t belongs to row sched[1 / 2].order[t], so a level's slice is contiguous (8.3 against 11.2 ms per ldiv! at 256^3)
     DevBuf fval;
     IluamSched sched[3];  // 0: columns of the factorization, 1: rows of the forward solve, 2: rows of the backward solve
-    // BlockPreconditioner (kind ESP_PRECON_BLOCK, block.hip): h is A; the block matrix B -- the stored A[i,j] with part(i) == part(j)
-    // -- lives in the internal handle bh (A's device and stream), inner is an ordinary preconditioner of inner_kind bound to bh.
-    // blk_path 0 (every partition increasing): B keeps A's numbering, ldiv! is inner's on the caller's vectors.  blk_path 1: B is
-    // renumbered by blk_new (position in the concatenated partitions); ldiv! gathers into blk_t, solves into blk_s, scatters.
-    esp_handle *bh = nullptr;
-    esp_precon *inner = nullptr;
-    int inner_kind = 0, blk_path = 0, blk_force = 0;
-    bool blk_increasing = false, blk_rebuild = false;
+    // The kinds that hold a derived matrix (holds_derived: Block, Colored, ILU(k)): h is A; a matrix B made from A's stored CSC --
+    // Block: the stored A[i,j] with part(i) == part(j); Colored: A[c,c]; ILU(k): every position of level <= iluk_k -- lives in the
+    // internal handle bh (A's device and stream), and inner is an ordinary preconditioner of inner_kind bound to bh.  src[q] is the
+    // position in A's nzval entry q of B came from (ILUK_FILL for a fill entry of ILU(k)): update! with the pattern kept is one gather
+    // through it and inner's values-only update (derived_update, derived.hip).  rebuild: the next update! builds B anew whatever A's
+    // versions say.
+    struct Derived {
+        esp_handle *bh = nullptr;
+        esp_precon *inner = nullptr;
+        int inner_kind = 0;
+        bool rebuild = false;
+        DevBuf src;  // u32 nnz(B)
+    } der;
+    // BlockPreconditioner (kind ESP_PRECON_BLOCK, block.hip): B is the block matrix.  blk_path 0 (every partition increasing): B keeps
+    // A's numbering, ldiv! is inner's on the caller's vectors.  blk_path 1: B is renumbered by blk_new (position in the concatenated
+    // partitions); ldiv! gathers into blk_t, solves into blk_s, scatters.
+    int blk_path = 0, blk_force = 0;
+    bool blk_increasing = false;
     DevBuf blk_new, blk_part;  // u32 n each: new(i), part(i)
-    DevBuf blk_src;            // u32 nnz(B): the position in A's nzval entry q of B came from
     DevBuf blk_t, blk_s;       // f64 n each (permuted path)
     // AMGPreconditioner (kind ESP_PRECON_AMG, amg.hip): the parameters and the level hierarchy (internal handles of every A_l and
     // P_l, the weights, the cycle's vectors, the dense inverse of the coarsest level)
     struct AmgData *amg = nullptr;
-    // ILUKPreconditioner (kind ESP_PRECON_ILUK, iluk.hip): h is A; the filled matrix B -- every position of level <= iluk_k, A's bits
-    // where A stores one, +0.0 elsewhere -- lives in bh, inner is the ILUAM preconditioner of bh (blk_path stays 0: ldiv! is inner's
-    // on the caller's vectors), blk_src[q] is the position in A's nzval of entry q of B (ILUK_FILL for a fill entry).
+    // ILUKPreconditioner (kind ESP_PRECON_ILUK, iluk.hip): B is the filled matrix -- A's bits where A stores an entry, +0.0 elsewhere --
+    // and inner its ILUAM preconditioner (blk_path stays 0: ldiv! is inner's on the caller's vectors).
     int iluk_k = 0;
     esp_handle *iluk_th = nullptr;  // transpose(A), the graph of the search for the upper part
     DevBuf iluk_lev;                // i32 nnz(B): the level of every entry of B
     i64 iluk_stats[4] = {0, 0, 0, 0};  // nnz(B), largest stored level, columns redone by the workgroup search (L, U)
-    // ColoredPreconditioner (kind ESP_PRECON_COLORED, color.hip): h is A; the multicolour ordering c of A's graph -- the vertices
-    // sorted by (colour, index) -- is the one partition of a permuted-path block preconditioner: blk_new = the inverse of c, blk_part
-    // = 0 everywhere, B = A[c,c] in bh, inner (ILU0 or ILUAM) bound to bh, blk_path = 1 (0 only for n == 0).  A pattern change of A
-    // re-colours before B is rebuilt.
+    // ColoredPreconditioner (kind ESP_PRECON_COLORED, color.hip): the multicolour ordering c of A's graph -- the vertices sorted by
+    // (colour, index) -- is the one partition of a permuted-path block preconditioner: blk_new = the inverse of c, blk_part = 0
+    // everywhere, B = A[c,c], inner ILU0 or ILUAM, blk_path = 1 (0 only for n == 0).  A pattern change of A re-colours before B is
+    // rebuilt.
     DevBuf col_color, col_perm;      // u32 n each: the colour of every vertex (1-based, as the rounds number them), c
     std::vector<i64> col_ptr;        // ncolors + 1: colour r holds c[col_ptr[r] .. col_ptr[r + 1])
 };
 // the kinds that block.hip's builder, update! and ldiv! serve
 static inline bool block_built(const esp_precon *p) { return p->kind == ESP_PRECON_BLOCK || p->kind == ESP_PRECON_COLORED; }
-// the identity-path block preconditioner and the ILU(k) preconditioner stand for their inner one in the solvers' fused branches
-static inline esp_precon *fused_precon(esp_precon *p) {
-    return p && ((block_built(p) && p->blk_path == 0) || p->kind == ESP_PRECON_ILUK) ? p->inner : p;
+// the kinds that hold a derived matrix B and an inner preconditioner of it (esp_precon::Derived)
+static inline bool holds_derived(const esp_precon *p) { return block_built(p) || p->kind == ESP_PRECON_ILUK; }
+// ... whose next update! builds B anew (else: the values only)
+static inline bool derived_stale(const esp_precon *p) {
+    return p->der.rebuild || p->pattern_version != p->h->pattern_version || p->nnz != p->h->nnz;
 }
+// the identity-path block preconditioner and the ILU(k) preconditioner stand for their inner one in the solvers' fused branches
+static inline esp_precon *fused_precon(esp_precon *p) { return p && holds_derived(p) && p->blk_path == 0 ? p->der.inner : p; }
 static inline bool block_permuted(const esp_precon *p) { return p && block_built(p) && p->blk_path != 0; }
+constexpr u32 ILUK_FILL = 0xFFFFFFFFu;  // src of a fill entry of ILU(k): no position (every update! refuses nnz(A) >= 2^32 - 16)
 
 #pragma GCC visibility push(hidden)
 // precon.hip: smallest column without a stored diagonal -> ESP_ERR_INVALID (ILU0 / ILUAM), invdiag / xdiag into p->diag;
@@ -651,14 +666,27 @@ void ilu0_lower_launch(esp_precon *p, const double *v);
 // precon.hip, for block.hip: the checks of every preconditioner call on the handle; ldiv! on device vectors (u may be v)
 int32_t precon_check_handle(esp_handle *h, const char *what);
 int32_t precon_ldiv_launch(esp_precon *p, const double *v, double *u);
-// block.hip: update! (rebuild of B and the inner preconditioner / the value gather and the inner values-only update), ldiv! on
-// device vectors (sub: u[i] = u[i] - x[i], simple!'s step), release of B, the inner preconditioner and every buffer
+// precon.hip: the frame of every esp_precon_*_create.  precon_new: an object of `kind` bound to h whose versions match nothing (the
+// first update! builds everything); precon_finish: st is what the kind's set-up and first update! returned -- the object goes to
+// *out, or is destroyed
+esp_precon *precon_new(esp_handle *h, int kind);
+int32_t precon_finish(esp_precon *p, int32_t st, esp_precon **out);
+// derived.hip: the update! of the kinds that hold a derived matrix (what: the prefix of its messages; build: B from A's current CSC
+// into p->der.bh and p->der.src, nothing of p changed when it fails; hint: appended when the inner preconditioner refuses a column
+// on the permuted path), B's handle -- and ILU(k)'s transpose -- moved to the stream A runs on (esp_set_stream may have replaced it)
+int32_t derived_update(esp_precon *p, const char *what, int32_t (*build)(esp_precon *), const char *hint);
+int32_t derived_follow_stream(esp_precon *p);
+// ... nzB[q] = src[q] == ILUK_FILL ? +0.0 : nzA[src[q]] (the bits); pay != nullptr (ILU(k)'s build): src[q] and lev[q] from the
+// sorted payloads first, the largest level into *maxlev
+void derived_gather_launch(hipStream_t s, const u64 *pay, u32 *src, int32_t *lev, const u64 *nzA, u64 *nzB, i64 nnzB,
+                           unsigned long long *maxlev);
+// block.hip: update! (derived_update over the masked extraction), ldiv! on device vectors (sub: u[i] = u[i] - x[i], simple!'s
+// step), release of B, the inner preconditioner and every buffer
 int32_t block_update(esp_precon *p);
-int32_t block_follow_stream(esp_precon *p);
 int32_t block_ldiv_launch(esp_precon *p, const double *v, double *u, bool sub);
 void block_release(esp_precon *p);
-// iluk.hip: update! (the pattern search, B and the inner ILUAM after a pattern change / the value gather and the inner values-only
-// update), release of the transpose and the level array (B, the inner preconditioner and src are block_release's)
+// iluk.hip: update! (derived_update over the pattern search), release of the transpose and the level array (B, the inner
+// preconditioner and src are block_release's)
 int32_t iluk_update(esp_precon *p);
 void iluk_release(esp_precon *p);
 // color.hip: update! (after a pattern change the colouring and the maps anew, then block_update; else block_update's value gather),
@@ -670,12 +698,69 @@ void color_release(esp_precon *p);
 int32_t amg_update(esp_precon *p);
 int32_t amg_solve(esp_precon *p, const double *v, double *u, bool sub);
 void amg_release(esp_precon *p);
-// linalg.hip, for block.hip: every column of (cp: 0-based starts, rowC, valC) sorted by row, valC carried along; the caller
-// found maxlen <= COLSORT_BLOCK and listed the nlong columns longer than COLSORT_LANE
+// linalg.hip: every column of (cp: 0-based starts, rowC, valC) sorted by row, valC carried along; the caller found
+// maxlen <= COLSORT_BLOCK and listed the nlong columns longer than COLSORT_LANE
 constexpr int COLSORT_LANE = 32, COLSORT_BLOCK = 4096;
 void sort_columns_launch(hipStream_t s, const i64 *cp, i64 nC, i64 *rowC, u64 *valC, i64 maxlen, const u32 *list, i64 nlong);
 int32_t ensure(esp_handle *h, DevBuf &b, size_t need, bool keep = false);
 void release(DevBuf &b);
+// every device buffer of a call, released on every way out
+struct Temps {
+    DevBuf b[12];
+    ~Temps() {
+        for (DevBuf &x : b) release(x);
+    }
+};
+// matops.hip: p[i] += 1 for i < n (a scanned 0-based colptr becomes Julia's)
+void add_one_launch(hipStream_t s, i64 *p, i64 n);
+// derived.hip: entries sorted (and folded) by an ESP_COO flush of a scratch handle, in two phases around the caller's own fill:
+//   ScratchFlush sf(owner, "esp_xyz");   the scratch handle is destroyed on every way out; errors go to owner under that prefix
+//   CK(sf.open(m, n, count));            an m x n scratch handle on owner's device with room for count records
+//   ... the caller's launch writes count records to sf.keys() / sf.vals() with the layout sf.L(), and synchronises its stream ...
+//   CK(sf.flush(expected));              the flush from the empty CSC, synchronised; expected >= 0: nnz it must store (unique keys)
+//   sf.take(cp, rv, nz);                 the scratch handle's CSC (colptr 1-based) against whatever the three buffers held
+class ScratchFlush {
+  public:
+    ScratchFlush(esp_handle *owner, const char *what) : owner_(owner), what_(what) {}
+    ScratchFlush(const ScratchFlush &) = delete;
+    ~ScratchFlush();
+    // fail_hook: owner's armed esp_debug_fail_next_bucket_stage moves to the scratch handle (this is the flush it meets)
+    int32_t open(i64 m, i64 n, i64 count, bool fail_hook = false);
+    u64 *keys() const { return (u64 *)sc_->keys.p; }
+    u64 *vals() const { return (u64 *)sc_->vals.p; }
+    const KeyLayout &L() const { return sc_->L; }
+    hipStream_t stream() const { return sc_->stream; }
+    int32_t flush(i64 expected);
+    i64 nnz() const { return sc_ ? sc_->nnz : 0; }
+    void take(DevBuf &cp, DevBuf &rv, DevBuf &nz);
+
+  private:
+    esp_handle *owner_, *sc_ = nullptr;
+    const char *what_;
+    i64 count_ = 0;
+};
+// linalg.hip: "every column of (cp, rows, payload) sorted by row" in two phases around the caller's fill of nnz entries:
+//   plan     cp holds the scanned 0-based column starts (n + 1), st two zeroed device words: measures the columns and picks the
+//            route; the fill then writes either rowB[q] (1-based) and pay[q] -- rv and pay, sized here -- or, keys != nullptr,
+//            the ESP_COO record keys[q] (layout L) and pay[q] of a scratch handle (a column longer than COLSORT_BLOCK)
+//   finish   behind the fill on h's stream: the lane / workgroup sorts, or h's stream synchronised and the scratch flush, whose CSC
+//            cp / rv / pay then hold (*one_based: cp is 1-based already)
+class ColumnSort {
+  public:
+    ColumnSort(esp_handle *h, const char *what) : h_(h), sf_(h, what) {}
+    ~ColumnSort() { release(list_); }
+    int32_t plan(DevBuf &cp, i64 n, i64 nnz, unsigned long long *st, DevBuf &rv, DevBuf &pay);
+    int32_t finish(bool *one_based);
+    i64 *rowB = nullptr;
+    u64 *pay = nullptr, *keys = nullptr;
+    KeyLayout L{1, 1};
+
+  private:
+    esp_handle *h_;
+    ScratchFlush sf_;
+    DevBuf list_, *cp_ = nullptr, *rv_ = nullptr, *pay_ = nullptr;
+    i64 n_ = 0, nnz_ = 0, nlong_ = 0, maxlen_ = 0;
+};
 void release_all(esp_handle *h);
 hipEvent_t ev_get(esp_handle *h);
 void timing_collect(esp_handle *h);

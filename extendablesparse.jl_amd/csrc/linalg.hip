@@ -213,9 +213,14 @@ __global__ __launch_bounds__(MT) void tp_sort_block_k(const i64 *__restrict__ cp
         valC[s + t] = sval[k & ((1u << TP_IDX_BITS) - 1)];
     }
 }
-__global__ void tp_add_one_k(i64 *__restrict__ p, i64 n) {
-    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] += 1;
+// the columns of a scanned cp: those longer than COLSORT_LANE are listed for the workgroup sort; st[0] = listed columns, st[1] = the
+// longest column
+__global__ __launch_bounds__(MT) void col_lens_k(const i64 *__restrict__ cp, i64 n, u32 *__restrict__ list, unsigned long long *__restrict__ st) {
+    const i64 c = (i64)blockIdx.x * MT + threadIdx.x;
+    const u32 len = c < n ? (u32)min(cp[c + 1] - cp[c], (i64)0xFFFFFFFFll) : 0u;
+    if (len > (u32)COLSORT_LANE) list[atomicAdd(&st[0], 1ull)] = (u32)c;
+    const u32 m = esp_wave_max(len);
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(&st[1], (unsigned long long)m);
 }
 
 }  // namespace
@@ -226,6 +231,43 @@ void sort_columns_launch(hipStream_t s, const i64 *cp, i64 nC, i64 *rowC, u64 *v
     else if (maxlen > 8 && maxlen <= 16) hipLaunchKernelGGL(tp_sort_lane_k<4>, gc, dim3(MT), 0, s, cp, nC, rowC, valC);
     else if (maxlen > 16) hipLaunchKernelGGL(tp_sort_lane_k<5>, gc, dim3(MT), 0, s, cp, nC, rowC, valC);
     if (nlong > 0) hipLaunchKernelGGL(tp_sort_block_k, dim3((unsigned)nlong), dim3(MT), 0, s, cp, list, rowC, valC);
+}
+int32_t ColumnSort::plan(DevBuf &cp, i64 n, i64 nnz, unsigned long long *st, DevBuf &rv, DevBuf &payload) {
+    esp_handle *h = h_;
+    hipStream_t s = h->stream;
+    cp_ = &cp, rv_ = &rv, pay_ = &payload, n_ = n, nnz_ = nnz;
+    CK(ensure(h, list_, sizeof(u32) * (size_t)n));
+    hipLaunchKernelGGL(col_lens_k, dim3(grid_for(n, MT)), dim3(MT), 0, s, (const i64 *)cp.p, n, (u32 *)list_.p, st);
+    HIPCK(h, hipGetLastError());
+    HIPCK(h, hipMemcpyAsync(h->pin_scalar, st, sizeof(u64) * 2, hipMemcpyDeviceToHost, s));
+    HIPCK(h, hipStreamSynchronize(s));
+    nlong_ = (i64)h->pin_scalar[0], maxlen_ = (i64)h->pin_scalar[1];
+    if (maxlen_ <= COLSORT_BLOCK) {
+        CK(ensure(h, rv, sizeof(i64) * (size_t)nnz));
+        CK(ensure(h, payload, sizeof(u64) * (size_t)nnz));
+        rowB = (i64 *)rv.p;
+        pay = (u64 *)payload.p;
+        L = h->L;
+        return ESP_OK;
+    }
+    CK(sf_.open(n, n, nnz));
+    keys = sf_.keys();
+    pay = sf_.vals();
+    L = sf_.L();
+    return ESP_OK;
+}
+int32_t ColumnSort::finish(bool *one_based) {
+    esp_handle *h = h_;
+    *one_based = keys != nullptr;
+    if (!keys) {
+        sort_columns_launch(h->stream, (const i64 *)cp_->p, n_, rowB, pay, maxlen_, (const u32 *)list_.p, nlong_);
+        return ESP_OK;
+    }
+    HIPCK(h, hipGetLastError());
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    CK(sf_.flush(nnz_));
+    sf_.take(*cp_, *rv_, *pay_);
+    return ESP_OK;
 }
 namespace {
 
@@ -362,14 +404,6 @@ __global__ __launch_bounds__(MT) void nrm_final_k(const double *__restrict__ par
     if (threadIdx.x == 0) out[0] = acc;
 }
 
-// every device buffer of a call, released on every way out
-struct Temps {
-    DevBuf b[10];
-    ~Temps() {
-        for (DevBuf &x : b) release(x);
-    }
-};
-
 double from_bits(u64 b) {
     double d;
     memcpy(&d, &b, 8);
@@ -378,37 +412,13 @@ double from_bits(u64 b) {
 
 // C := transpose(A) through an ESP_COO flush of a scratch handle; cp / rv / nz receive its CSC
 int32_t transpose_generic(esp_handle *c, const Csc64 &A, i64 mC, i64 nC, DevBuf &cp, DevBuf &rv, DevBuf &nz) {
-    esp_handle *sc = nullptr;
-    struct ScratchGuard {
-        esp_handle **p;
-        ~ScratchGuard() {
-            if (*p) esp_destroy(*p);
-        }
-    } sguard{&sc};
-    const int32_t st = esp_create(mC, nC, c->device, A.nnz, &sc);
-    if (st != ESP_OK) FAIL(c, st, "esp_transpose: scratch handle: %s", esp_last_error(nullptr));
-    sc->debug_fail_bucket = c->debug_fail_bucket;  // (esp_debug_fail_next_bucket_stage armed on c: this is the flush it meets)
-    c->debug_fail_bucket = false;
-    const int32_t rs = reserve_append(sc, A.nnz);
-    if (rs != ESP_OK) FAIL(c, rs, "esp_transpose: append buffer of the scratch handle: %s", sc->err.c_str());
-    hipLaunchKernelGGL(tp_expand_k, dim3(grid_for(A.nnz, TP_TILE)), dim3(MT), 0, sc->stream, A, sc->L, (u64 *)sc->keys.p, (u64 *)sc->vals.p);
+    ScratchFlush sf(c, "esp_transpose");
+    CK(sf.open(mC, nC, A.nnz, true));  // (esp_debug_fail_next_bucket_stage armed on c: this is the flush it meets)
+    hipLaunchKernelGGL(tp_expand_k, dim3(grid_for(A.nnz, TP_TILE)), dim3(MT), 0, sf.stream(), A, sf.L(), sf.keys(), sf.vals());
     HIPCK(c, hipGetLastError());
-    HIPCK(c, hipStreamSynchronize(sc->stream));
-    note_kind(sc, ESP_COO, A.nnz);
-    sc->count = A.nnz;
-    pending_changed(sc);
-    i64 z = 0;
-    int32_t ch = 0;
-    const int32_t fs = esp_flush(sc, ESP_FLUSH_ROUTED, &z, &ch);
-    if (fs != ESP_OK) FAIL(c, fs, "esp_transpose: flush of the transposed entries: %s", sc->err.c_str());
-    const int32_t ft = fix_tail(sc);
-    if (ft != ESP_OK) FAIL(c, ft, "esp_transpose: %s", sc->err.c_str());
-    HIPCK(c, hipStreamSynchronize(sc->stream));
-    if (sc->nnz != A.nnz) FAIL(c, ESP_ERR_HIP, "esp_transpose: the flush stored %lld entries of %lld", (long long)sc->nnz, (long long)A.nnz);
-    drop_kept(sc);  // (the scratch handle gives its arrays away)
-    std::swap(cp, sc->colptr);
-    std::swap(rv, sc->rowval);
-    std::swap(nz, sc->nzval);
+    HIPCK(c, hipStreamSynchronize(sf.stream()));
+    CK(sf.flush(A.nnz));
+    sf.take(cp, rv, nz);
     return ESP_OK;
 }
 
@@ -445,7 +455,7 @@ int32_t transpose_counting(esp_handle *c, const Csc64 &A, i64 nC, Temps &tmp, bo
     HIPCK(h, hipMemsetAsync(cnt.p, 0, sizeof(u32) * (size_t)nC, s));
     hipLaunchKernelGGL(tp_scatter_k, dim3(grid_for(A.nnz, TP_TILE)), dim3(MT), 0, s, A, (const i64 *)cp.p, (u32 *)cnt.p, (i64 *)rv.p, (u64 *)nz.p);
     sort_columns_launch(s, (const i64 *)cp.p, nC, (i64 *)rv.p, (u64 *)nz.p, maxlen, (const u32 *)list.p, nlong);
-    hipLaunchKernelGGL(tp_add_one_k, dim3(grid_for(nC + 1, MT)), dim3(MT), 0, s, (i64 *)cp.p, nC + 1);
+    add_one_launch(s, (i64 *)cp.p, nC + 1);
     HIPCK(h, hipGetLastError());
     HIPCK(h, hipStreamSynchronize(s));
     *done = true;

@@ -390,14 +390,6 @@ __global__ __launch_bounds__(MT) void diag_scale_k(Csc64 A, const double *__rest
     }
 }
 
-// every device buffer of a call, released on every way out
-struct Temps {
-    DevBuf b[10];
-    ~Temps() {
-        for (DevBuf &x : b) release(x);
-    }
-};
-
 }  // namespace
 
 // (check_operand, install and read_i64 are shared with linalg.hip: internal.hpp)
@@ -429,6 +421,7 @@ void install(esp_handle *c, DevBuf &cp, DevBuf &rv, DevBuf &nz, i64 nnz) {
     c->tail_stale = false;
     c->ones_pending = false;
 }
+void add_one_launch(hipStream_t s, i64 *p, i64 n) { hipLaunchKernelGGL(add_one_k, dim3(grid_for(n, MT)), dim3(MT), 0, s, p, n); }
 int32_t read_i64(esp_handle *h, const i64 *d_src, i64 *out) {
     HIPCK(h, hipMemcpyAsync(h->pin_scalar, d_src, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCK(h, hipStreamSynchronize(h->stream));
@@ -490,39 +483,23 @@ extern "C" int32_t esp_matmul(esp_handle *a, esp_handle *b, esp_handle *c, int64
                            (const i64 *)bins.p, (i64 *)ccount.p, (const i64 *)nullptr, (i64 *)nullptr, (double *)nullptr);
     HIPCK(h, hipGetLastError());
     // generic tier: the products as ESP_COO records of a scratch handle, folded by its flush
-    esp_handle *sc = nullptr;
-    struct ScratchGuard {
-        esp_handle **p;
-        ~ScratchGuard() {
-            if (*p) esp_destroy(*p);
-        }
-    } sguard{&sc};
-    const i64 *scp = nullptr;
+    ScratchFlush sf(h, "esp_matmul");
+    DevBuf &scp = tmp.b[9], &srv = tmp.b[10], &snz = tmp.b[11];
     if (gtot > 0) {
-        const int32_t st = esp_create(a->m, n, h->device, gtot, &sc);
-        if (st != ESP_OK) FAIL(h, st, "esp_matmul: scratch handle of the generic tier: %s", esp_last_error(nullptr));
-        CK(reserve_append(sc, gtot));
+        CK(sf.open(a->m, n, gtot));
         HIPCK(h, hipStreamSynchronize(s));
-        hipLaunchKernelGGL(mm_expand_k, dim3(grid_for(gtot, MT)), dim3(MT), 0, sc->stream, A, B, (const i64 *)poff.p, (const i64 *)G.p, n, gtot,
-                           sc->L, (u64 *)sc->keys.p, (double *)sc->vals.p);
+        hipLaunchKernelGGL(mm_expand_k, dim3(grid_for(gtot, MT)), dim3(MT), 0, sf.stream(), A, B, (const i64 *)poff.p, (const i64 *)G.p, n, gtot,
+                           sf.L(), sf.keys(), (double *)sf.vals());
         HIPCK(h, hipGetLastError());
-        HIPCK(h, hipStreamSynchronize(sc->stream));
-        note_kind(sc, ESP_COO, gtot);
-        sc->count = gtot;
-        pending_changed(sc);
-        i64 z = 0;
-        int32_t ch = 0;
-        const int32_t fs = esp_flush(sc, ESP_FLUSH_ROUTED, &z, &ch);
-        if (fs != ESP_OK) FAIL(h, fs, "esp_matmul: flush of the generic tier: %s", sc->err.c_str());
-        CK(fix_tail(sc));
-        HIPCK(h, hipStreamSynchronize(sc->stream));
-        scp = (const i64 *)sc->colptr.p;
+        HIPCK(h, hipStreamSynchronize(sf.stream()));
+        CK(sf.flush(-1));  // (products of one position fold: no count to expect)
+        sf.take(scp, srv, snz);
     }
     // colptr of C
-    hipLaunchKernelGGL(mm_count_k, dim3(grid_for(n + 1, MT)), dim3(MT), 0, s, B.colptr, (const i64 *)poff.p, (const i64 *)ccount.p, scp, n, tier,
-                       (i64 *)cp.p);
+    hipLaunchKernelGGL(mm_count_k, dim3(grid_for(n + 1, MT)), dim3(MT), 0, s, B.colptr, (const i64 *)poff.p, (const i64 *)ccount.p, (const i64 *)scp.p, n,
+                       tier, (i64 *)cp.p);
     CK(scan_inplace<i64, false>(h, (i64 *)cp.p, n + 1, ws, &l));
-    hipLaunchKernelGGL(add_one_k, dim3(grid_for(n + 1, MT)), dim3(MT), 0, s, (i64 *)cp.p, n + 1);
+    add_one_launch(s, (i64 *)cp.p, n + 1);
     HIPCK(h, hipGetLastError());
     i64 nnzC = 0;
     CK(read_i64(h, (const i64 *)cp.p + n, &nnzC));
@@ -532,9 +509,9 @@ extern "C" int32_t esp_matmul(esp_handle *a, esp_handle *b, esp_handle *c, int64
     if (nbins > 0)
         hipLaunchKernelGGL(mm_bin_k<true>, dim3((unsigned)nbins), dim3(MT), 0, s, A, B, (const i64 *)poff.p, (const i64 *)W.p,
                            (const i64 *)bins.p, (i64 *)nullptr, (const i64 *)cp.p, (i64 *)rv.p, (double *)nz.p);
-    if (sc && sc->nnz > 0)
-        hipLaunchKernelGGL(mm_place_k, dim3(grid_for(sc->nnz, MT)), dim3(MT), 0, s, scp, (const i64 *)sc->rowval.p, (const double *)sc->nzval.p,
-                           n, sc->nnz, (const i64 *)cp.p, (i64 *)rv.p, (double *)nz.p);
+    if (sf.nnz() > 0)
+        hipLaunchKernelGGL(mm_place_k, dim3(grid_for(sf.nnz(), MT)), dim3(MT), 0, s, (const i64 *)scp.p, (const i64 *)srv.p,
+                           (const double *)snz.p, n, sf.nnz(), (const i64 *)cp.p, (i64 *)rv.p, (double *)nz.p);
     HIPCK(h, hipGetLastError());
     HIPCK(h, hipStreamSynchronize(s));
     install(c, cp, rv, nz, nnzC);
@@ -582,7 +559,7 @@ extern "C" int32_t esp_add(esp_handle *a, esp_handle *b, int32_t op, esp_handle 
         hipLaunchKernelGGL(add_colend_k, dim3(grid_for(nnzC, MT)), dim3(MT), 0, s, (const u32 *)ocol.p, nnzC, (i64 *)cp.p);
         CK(scan_inplace<i64, true>(h, (i64 *)cp.p, n + 1, ws, &l));
     }
-    hipLaunchKernelGGL(add_one_k, dim3(grid_for(n + 1, MT)), dim3(MT), 0, s, (i64 *)cp.p, n + 1);
+    add_one_launch(s, (i64 *)cp.p, n + 1);
     HIPCK(h, hipGetLastError());
     HIPCK(h, hipStreamSynchronize(s));
     install(c, cp, rv, nz, nnzC);

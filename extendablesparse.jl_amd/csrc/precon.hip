@@ -299,7 +299,7 @@ int32_t precon_ready(esp_precon *p, const char *what) {
     if (h->pattern_version != p->pattern_version || h->nnz != p->nnz)
         FAIL(h, ESP_ERR_STATE, "%s: the matrix pattern changed since the preconditioner's last update! (update! first)", what);
     if (p->kind == ESP_PRECON_ILU0 && p->values_version != h->values_version) CK(split_scale(p, false));  // current nzval, stored xdiag
-    if (block_built(p) || p->kind == ESP_PRECON_ILUK) CK(block_follow_stream(p));  // (B holds copies: the values as of the last update!, ILU0 included)
+    if (holds_derived(p)) CK(derived_follow_stream(p));  // (B holds copies: the values as of the last update!, ILU0 included)
     return ESP_OK;
 }
 
@@ -309,7 +309,7 @@ int32_t ldiv_launch(esp_precon *p, const double *v, double *u) {
     const i64 n = p->n;
     if (n == 0) return ESP_OK;
     if (block_built(p)) return block_ldiv_launch(p, v, u, false);
-    if (p->kind == ESP_PRECON_ILUK) return ldiv_launch(p->inner, v, u);  // ILUAM of B on the caller's vectors
+    if (p->kind == ESP_PRECON_ILUK) return ldiv_launch(p->der.inner, v, u);  // ILUAM of B on the caller's vectors
     if (p->kind == ESP_PRECON_ILUAM) return iluam_solve(p, v, u, false);
     if (p->kind == ESP_PRECON_AMG) return amg_solve(p, v, u, false);
     const unsigned g = grid_for(n, PT);
@@ -338,22 +338,30 @@ void ilu0_lower_launch(esp_precon *p, const double *v) {
                        (double *)p->u1.p, p->n, (double *)nullptr);
 }
 
-extern "C" int32_t esp_precon_create(esp_handle *h, int32_t kind, esp_precon **out) {
-    if (!h || !out || (kind != ESP_PRECON_JACOBI && kind != ESP_PRECON_ILU0 && kind != ESP_PRECON_ILUAM)) return ESP_ERR_INVALID;
-    *out = nullptr;
-    CK(check_handle(h, "esp_precon_create"));
+esp_precon *precon_new(esp_handle *h, int kind) {
     esp_precon *p = new esp_precon();
     p->h = h;
     p->kind = kind;
+    p->n = h->n;
     h->live_precons++;
-    p->pattern_version = 0;  // never matches: the update below builds everything
-    const int32_t st = esp_precon_update(p);
+    p->pattern_version = 0;  // never matches: the first update! builds everything
+    return p;
+}
+int32_t precon_finish(esp_precon *p, int32_t st, esp_precon **out) {
     if (st != ESP_OK) {
         (void)esp_precon_destroy(p);
         return st;
     }
     *out = p;
     return ESP_OK;
+}
+
+extern "C" int32_t esp_precon_create(esp_handle *h, int32_t kind, esp_precon **out) {
+    if (!h || !out || (kind != ESP_PRECON_JACOBI && kind != ESP_PRECON_ILU0 && kind != ESP_PRECON_ILUAM)) return ESP_ERR_INVALID;
+    *out = nullptr;
+    CK(check_handle(h, "esp_precon_create"));
+    esp_precon *p = precon_new(h, kind);
+    return precon_finish(p, esp_precon_update(p), out);
 }
 
 extern "C" int32_t esp_precon_update(esp_precon *p) {

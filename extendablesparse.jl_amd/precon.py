@@ -90,12 +90,16 @@ class _PointPreconditioner:
     def __init__(self, A):
         if not isinstance(A, ExtendableSparseMatrix):
             raise TypeError("%s(A): A must be an ExtendableSparseMatrix" % type(self).__name__)
+        self._bind(A, "esp_precon_create", self.KIND)  # factorize!: jacobi(A) / ilu0(A)
+
+    def _bind(self, A, create, *args):
+        """factorize!: flush!, then the library's `create`(A's handle, *args, &p) -- the new esp_precon is bound to A"""
         self.A = A
         self._p = None
         A.flush()
         d = A._d
         p = C.c_void_p()
-        d.ck(d.lib.esp_precon_create(d.h, self.KIND, C.byref(p)))  # factorize!: jacobi(A) / ilu0(A)
+        d.ck(getattr(d.lib, create)(d.h, *args, C.byref(p)))
         self._p = p
 
     def _ck(self, rc):
@@ -217,8 +221,6 @@ class BlockPreconditioner(_ILUAMFactors, _PointPreconditioner):
                 and factorization.KIND in (ESP_PRECON_JACOBI, ESP_PRECON_ILU0, ESP_PRECON_ILUAM)):
             raise TypeError("BlockPreconditioner: factorization must be JacobiPreconditioner, ILU0Preconditioner or "
                             "ILUAMPreconditioner (the reference's default, LUFactorization, is not on the device)")
-        self.A = A
-        self._p = None
         self.factorization = factorization
         if partitioning is None:            # blockpreconditioner.jl:46-48: one partition 1:n
             partitioning = [range(1, A.n + 1)]
@@ -226,11 +228,7 @@ class BlockPreconditioner(_ILUAMFactors, _PointPreconditioner):
         ptr = np.zeros(len(parts) + 1, np.int64)
         np.cumsum([len(part) for part in parts], out=ptr[1:])
         idx = np.ascontiguousarray(np.concatenate(parts) - 1 if parts else np.empty(0, np.int64), np.int64)
-        A.flush()
-        d = A._d
-        p = C.c_void_p()
-        d.ck(d.lib.esp_precon_block_create(d.h, factorization.KIND, len(parts), _vp(ptr), _vp(idx), 0, C.byref(p)))
-        self._p = p
+        self._bind(A, "esp_precon_block_create", factorization.KIND, len(parts), _vp(ptr), _vp(idx), 0)
 
     def _block(self):
         b, path = C.c_void_p(), C.c_int32()
@@ -264,14 +262,8 @@ class ILUKPreconditioner(_ILUAMFactors, _PointPreconditioner):
             raise TypeError("ILUKPreconditioner(A, k): A must be an ExtendableSparseMatrix")
         if int(k) != k or k < 0:
             raise ValueError("ILUKPreconditioner: k = %r (an integer >= 0)" % (k,))
-        self.A = A
-        self._p = None
         self.k = min(int(k), 2 ** 31 - 1)     # (a level never exceeds n - 2 < 2^32 - 16)
-        A.flush()
-        d = A._d
-        p = C.c_void_p()
-        d.ck(d.lib.esp_precon_iluk_create(d.h, self.k, C.byref(p)))
-        self._p = p
+        self._bind(A, "esp_precon_iluk_create", self.k)
 
     def stats(self):
         """dict: nnz (of B), max_level (the largest stored level), wide_lower / wide_upper (the columns whose search outgrew
@@ -314,14 +306,8 @@ class ColoredPreconditioner(_ILUAMFactors, _PointPreconditioner):
         if not (isinstance(factorization, type) and issubclass(factorization, _PointPreconditioner)
                 and factorization.KIND in (ESP_PRECON_ILU0, ESP_PRECON_ILUAM)):
             raise TypeError("ColoredPreconditioner: factorization must be ILU0Preconditioner or ILUAMPreconditioner")
-        self.A = A
-        self._p = None
         self.factorization = factorization
-        A.flush()
-        d = A._d
-        p = C.c_void_p()
-        d.ck(d.lib.esp_precon_colored_create(d.h, factorization.KIND, C.byref(p)))
-        self._p = p
+        self._bind(A, "esp_precon_colored_create", factorization.KIND)
 
     def _info(self):
         out = (C.c_int64 * 2)()
@@ -438,14 +424,7 @@ class AMGPreconditioner(_PointPreconditioner):
                 raise ValueError("%s: %s = %r (an integer >= %d)" % (name, what, v, lo))
         if not (theta >= 0.0 and math.isfinite(theta)):
             raise ValueError("%s: theta = %r (finite, >= 0)" % (name, theta))
-        self.A = A
-        self._p = None
-        A.flush()
-        d = A._d
-        p = C.c_void_p()
-        d.ck(getattr(d.lib, self.CREATE)(d.h, int(max_levels), int(max_coarse), int(presweeps), int(postsweeps), float(theta),
-                                         C.byref(p)))
-        self._p = p
+        self._bind(A, self.CREATE, int(max_levels), int(max_coarse), int(presweeps), int(postsweeps), float(theta))
 
     @property
     def coarsening(self):

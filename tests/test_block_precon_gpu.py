@@ -227,17 +227,22 @@ def test_reversed_range_and_random_permutation(esp, orc, model, kind):
     check_all(esp, orc, model, A, [np.arange(0, 30), np.arange(59, 29, -1)], kind)
 
 
+def arrow(esp, n, rng):
+    """dense first row and column plus the diagonal"""
+    r = np.arange(1, n)
+    I = np.concatenate([np.arange(n), r, np.zeros(n - 1, np.int64)])
+    J = np.concatenate([np.arange(n), np.zeros(n - 1, np.int64), r])
+    V = np.concatenate([10.0 + rng.random(n), 0.001 * rng.standard_normal(2 * (n - 1))])
+    return from_scipy(esp, sp.csc_matrix((V, (I, J)), shape=(n, n)))
+
+
 @pytest.mark.parametrize("kind", KINDS)
 def test_arrow_matrix_beyond_the_column_sort(esp, orc, model, kind):
     """dense first row and column plus the diagonal, n = 4200, one shuffled partition: the first column holds 4200 entries,
     more than the per-column sort takes (4096)"""
     n = 4200
     rng = np.random.default_rng(9)
-    r = np.arange(1, n)
-    I = np.concatenate([np.arange(n), r, np.zeros(n - 1, np.int64)])
-    J = np.concatenate([np.arange(n), np.zeros(n - 1, np.int64), r])
-    V = np.concatenate([10.0 + rng.random(n), 0.001 * rng.standard_normal(2 * (n - 1))])
-    A = from_scipy(esp, sp.csc_matrix((V, (I, J)), shape=(n, n)))
+    A = arrow(esp, n, rng)
     parts = [np.random.default_rng(2).permutation(n)]
     arrays = host_arrays(A)
     P = make(esp, A, parts, kind)
@@ -281,6 +286,32 @@ def test_values_only_update_equals_fresh_create(esp, orc, model, kind, which):
         if kind == "iluam":
             assert same_bits(P.factor(), F.factor())
         F.close()
+    P.close()
+
+
+def test_values_only_update_after_the_scratch_route(esp, orc, model):
+    """the arrow matrix at n = 4097 in one shuffled partition: a column of B holds 4097 entries, one more than the column sorts take, so
+    B and src come from the flush of a scratch handle.  update! with the pattern kept gathers through that src: B, the ILUAM factor and
+    ldiv! are bitwise those of a preconditioner created afresh"""
+    n = 4097
+    rng = np.random.default_rng(9)
+    A = arrow(esp, n, rng)
+    parts = [np.random.default_rng(2).permutation(n)]
+    P = make(esp, A, parts, "iluam")
+    assert int(np.diff(P.block_matrix()[0]).max()) == n
+    v = rng.standard_normal(n)
+    u_old = P.ldiv(v)
+    csc = A.sparse()
+    csc.nzval[:] = csc.nzval * (1.0 + 0.01 * np.random.default_rng(8).random(len(csc.nzval)))
+    A._push_edits()
+    P.update()
+    arrays = host_arrays(A)
+    F = make(esp, A, parts, "iluam")
+    for Q in (P, F):
+        check_b(Q, arrays, parts, True)
+    u_new = P.ldiv(v)
+    assert same_bits(P.factor(), F.factor()) and same_bits(u_new, F.ldiv(v)) and not same_bits(u_new, u_old)
+    F.close()
     P.close()
 
 

@@ -206,6 +206,21 @@ def test_tiers(esp, model, n, transposed):
     assert wide == ((0, 0) if n <= W else ((0, 1) if transposed else (1, 0)))
 
 
+@pytest.mark.parametrize("transposed", [False, True])
+@pytest.mark.parametrize("n", [4096, 4097])
+def test_column_sort_limit(esp, model, n, transposed):
+    """the comb at K = 1 with the long line of B at the column sorts' limit, COLSORT_BLOCK = 4096 entries, and one above it.  As it
+    stands the line is column 1 of B: 4096 entries are sorted by one workgroup, 4097 go through the flush of a scratch handle.
+    Transposed it is row 1 of B (no column holds more than 3 entries) and row 0 of A, whose transpose -- the graph of the upper
+    search -- meets the same limit in esp_transpose"""
+    A = from_scipy(esp, comb(n, transposed))
+    st, want = check_all(esp, model, A, 1)
+    cp, rv, _ = want.B
+    longest_col, longest_row = int(np.diff(cp).max()), int(np.bincount(rv - 1).max())
+    assert (longest_row, longest_col) == ((n, 3) if transposed else (3, n))
+    assert st["nnz"] == 3 * n - 2 and st["max_level"] == 1
+
+
 def test_arrow_fills_completely(esp, model):
     """dense first row and column plus the diagonal, n = 70, K = 1: every position fills, the columns straddle 64 lanes"""
     n = 70
@@ -267,6 +282,54 @@ def test_values_only_update_equals_fresh_create(esp, model):
         assert same_bits(P.factor(), F.factor())
         F.close()
     P.close()
+
+
+def test_values_only_update_after_the_scratch_route(esp, model):
+    """the comb at n = 4097, K = 1: column 1 of B is above the column sorts' limit, so B, src and the levels come from the flush of a
+    scratch handle.  update! with the pattern kept gathers through that src: B is the model's, the factor and ldiv! are bitwise
+    those of a preconditioner created afresh"""
+    n = 4097
+    A = from_scipy(esp, comb(n))
+    P = esp.ILUKPreconditioner(A, 1)
+    assert int(np.diff(P.fill_matrix()[0]).max()) == n
+    v = np.random.default_rng(6).standard_normal(n)
+    u_old = P.ldiv(v)
+    csc = A.sparse()
+    csc.nzval[:] = csc.nzval * (1.0 + 0.01 * np.random.default_rng(8).random(len(csc.nzval)))
+    A._push_edits()
+    P.update()
+    want = model.precon(host_arrays(A), 1)
+    F = esp.ILUKPreconditioner(A, 1)
+    for Q in (P, F):
+        check_b(Q, want)
+    u_new = P.ldiv(v)
+    assert same_bits(P.factor(), F.factor()) and same_bits(u_new, F.ldiv(v)) and same_bits(u_new, want.ldiv(v))
+    assert not same_bits(u_new, u_old)
+    F.close()
+    P.close()
+
+
+def test_stream_change_between_create_and_update(esp, model):
+    """esp_set_stream on A after the create, then a pattern change: update! moves B's handle and the transpose's to A's new stream
+    before it searches, factorizes and solves on them"""
+    hip = C.CDLL("libamdhip64.so")          # (the runtime the library itself is linked against)
+    A = esp.fdrand(5, 4, 3)
+    n = A.n
+    P = esp.ILUKPreconditioner(A, 1)
+    stream = C.c_void_p()
+    assert hip.hipStreamCreate(C.byref(stream)) == 0
+    A._d.ck(A._d.lib.esp_set_stream(A._d.h, stream))
+    A.append(esp.ESP_UPDATE, [n, 1], [1, n], [0.5, 0.25])       # two corners: new entries and new fill
+    A.flush()
+    P.update()
+    want = model.precon(host_arrays(A), 1)
+    check_b(P, want)
+    check_numeric(P, want, seed=6)
+    P.close()
+    d = A._d
+    del A
+    d.close()
+    assert hip.hipStreamDestroy(stream) == 0
 
 
 def test_pattern_change_needs_update(esp, model):
