@@ -10,11 +10,12 @@
 //   rows l + 1, l + nx, l + nx ny : one update each, -v of the node's own pairs
 // -- at most 12 updates over at most 7 rows, the rows strictly increasing wherever the pairs exist (no x pair when nx = 1 ...).
 // The run is therefore born sorted: no load, no counting sort, no sorting network (dropped), and the LDS holds the dense
-// records only (512 x 7 x 12 B = 42 KiB: three workgroups per CU).  Everything from "entries the run emits" on is
-// pair_pred_k: the scan of the emitted counts, the checks against the table that raise PRED_MISS and store nothing, the fold
-// through espfold::fold_step_update / fold_step_sel, dense records in LDS, coalesced rowval / nzval stores, the lane's colptr,
-// the grand total and a miss in pinned host memory (Args::host_words).  No ticket, no look-back, nothing that waits for another
-// workgroup, no memset in front of the launch and no copy behind it.
+// records only (512 x 7 x 12 B = 42 KiB: three workgroups per CU).  The updates go through espfold::fold_step_update /
+// fold_step_sel as they are formed; from "entries the run emits" on the kernel calls the functions pair_pred_k calls (pair.hpp):
+// pair_place scans the emitted counts, pair_table_hit is the check against the table -- a miss stores nothing --, pair_store
+// the coalesced rowval / nzval stores and the lane's colptr, pair_grand_total the granule of the grand total.  Its own: the
+// grand total and a miss (PRED_MISS) go to pinned host memory (Args::host_words).  No ticket, no look-back, nothing that waits
+// for another workgroup, no memset in front of the launch and no copy behind it.
 //
 // A step that repeats the last one's structure stores the values alone (the template parameter KEEP, esp_handle::KeptStructure):
 // colptr and rowval -- 8 Z + 8 (N + 1) of the 16 Z + 8 (N + 1) bytes -- already lie where the handle's last fused flush wrote them.
@@ -26,6 +27,7 @@
 // coefficients from a caller's arrays fills the same StencilColumn.
 #include "generators.hpp"
 #include "local.hpp"
+#include "pair.hpp"
 
 namespace esplocal {
 
@@ -90,7 +92,7 @@ struct FdSource {
 // KEEP: colptr and rowval hold what the handle's last fused flush of this plan, table, grid and kind wrote, and that flush emitted
 // the grid's whole structural pattern (esp_handle::KeptStructure) -- a step that hits the table in every pair then has that very
 // pattern, so the kernel stores the values alone: no srow (the LDS holds the values only), no out_row, no colptr.  Everything that
-// decides is the writing form's: the fold, the scan, the `hit` test, PRED_MISS and the grand total.
+// decides is the writing form's: the fold, pair_place, pair_table_hit, PRED_MISS and the grand total.
 template <int KEYS, class SRC, bool KEEP>
 __global__ __launch_bounds__(THREADS, 6) void pair_gen_pred_k(Args a, SRC src, const u64 *pred, u64 out_cap) {
     static_assert(KEYS == 1 || KEYS == 2, "one kind: 2 = every update is an UPDATE");
@@ -147,24 +149,14 @@ __global__ __launch_bounds__(THREADS, 6) void pair_gen_pred_k(Args a, SRC src, c
     u32 ec = 0;
 #pragma unroll
     for (int q = 0; q < G_ROWS; q++) ec += present[q] ? 1u : 0u;
-    const u32 einc = esp_wave_scan_add(ec);
-    if (lane == 63) lw[w] = einc;
-    __syncthreads();
-    u32 at0 = einc - ec, total = 0;
-#pragma unroll
-    for (int i = 0; i < WAVES; i++) {
-        at0 += i < w ? lw[i] : 0u;
-        total += lw[i];
-    }
-    // the pair's place is the table's when it emits what the table says and ends inside the output arrays (pair_pred_k's
-    // condition, the same answer in every lane); else nothing is stored
-    const bool hit = dst_next >= dst && dst_next - dst == (u64)total && dst <= out_cap && (u64)total <= out_cap - dst && (s > 0 || dst == 0);
-    if (!hit) {
+    const PairPlace pl = pair_place(ec, lw, lane, w);
+    // ---- place: the table's, or nothing is stored
+    if (!pair_table_hit(dst, dst_next, pl.total, out_cap, s)) {
         if (t == 0) a.host_words[1] = (u64)PRED_MISS;  // (the same constant from every missing pair: a plain store)
         return;
     }
     {
-        u32 at = at0;
+        u32 at = pl.at0;
 #pragma unroll
         for (int q = 0; q < G_ROWS; q++) {
             if (present[q]) {
@@ -175,18 +167,8 @@ __global__ __launch_bounds__(THREADS, 6) void pair_gen_pred_k(Args a, SRC src, c
         }
     }
     __syncthreads();
-    // ---- coalesced stores; the lane of a column writes its colptr
-    for (int p = t; p < (int)total; p += THREADS) {
-        if constexpr (!KEEP) a.out_row[dst + p] = (i64)srow[p];
-        a.out_val[dst + p] = sval[p];
-    }
-    if constexpr (!KEEP) {
-        if (has) a.colptr_out[c_lo + t] = (i64)(dst + at0) + 1;
-    }
-    if (s == a.S - 1 && t == 0) {
-        if constexpr (!KEEP) a.colptr_out[a.col_end] = (i64)(dst + total) + 1;
-        a.host_words[0] = ST_PRE | ((dst + (u64)total) & ST_VAL);  // (the grand total, in the form of lb_complete's last granule)
-    }
+    pair_store<KEEP>(a, srow, sval, 0, dst, pl, hi, ncl, s, t);  // (srow holds 1-based rows)
+    if (s == a.S - 1 && t == 0) a.host_words[0] = pair_grand_total(dst, pl.total);
 }
 
 bool launch_pair_gen_predicted(const Variant &v, unsigned grid, hipStream_t stream, const Args &a, const espgen::FdArgs &fd, const u64 *pred,
@@ -195,21 +177,13 @@ bool launch_pair_gen_predicted(const Variant &v, unsigned grid, hipStream_t stre
     if (!v.fresh || v.pieces || a.cl_bits < 0 || (2 << a.cl_bits) > THREADS || a.rb >= 32 || !a.colptr_out || !a.host_words) return false;
     const FdSource src{fd.nx, fd.ny, fd.nz, fd.hx, fd.hy, fd.hz, fd.seed, fd.rand_mode, fd.fast, fd.magic_nx, fd.magic_nxny,
                        {6ull * (u64)(fd.nx * fd.ny) * ESP_GOLDEN, 6ull * (u64)fd.nx * ESP_GOLDEN, 6ull * ESP_GOLDEN}};
-    if (v.keys == 1) {
+    return pair_for_keys(v.keys, [&](auto K) {
+        constexpr int KEYS = decltype(K)::value;
         if (keep)
-            hipLaunchKernelGGL((pair_gen_pred_k<1, FdSource, true>), dim3(grid), dim3(THREADS), 0, stream, a, src, pred, out_cap);
+            hipLaunchKernelGGL((pair_gen_pred_k<KEYS, FdSource, true>), dim3(grid), dim3(THREADS), 0, stream, a, src, pred, out_cap);
         else
-            hipLaunchKernelGGL((pair_gen_pred_k<1, FdSource, false>), dim3(grid), dim3(THREADS), 0, stream, a, src, pred, out_cap);
-        return true;
-    }
-    if (v.keys == 2) {
-        if (keep)
-            hipLaunchKernelGGL((pair_gen_pred_k<2, FdSource, true>), dim3(grid), dim3(THREADS), 0, stream, a, src, pred, out_cap);
-        else
-            hipLaunchKernelGGL((pair_gen_pred_k<2, FdSource, false>), dim3(grid), dim3(THREADS), 0, stream, a, src, pred, out_cap);
-        return true;
-    }
-    return false;
+            hipLaunchKernelGGL((pair_gen_pred_k<KEYS, FdSource, false>), dim3(grid), dim3(THREADS), 0, stream, a, src, pred, out_cap);
+    });
 }
 
 }  // namespace esplocal

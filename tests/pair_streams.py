@@ -409,6 +409,31 @@ def repeat_e(kind=UPDATE, seed=9, n=140000):
     return m, n, kind, out, dict(maxrun=RUN, moved_pair=P, states=[0, 2, 0], pairs=[1, 0, 0])
 
 
+def repeat_g(where, kind=UPDATE, seed=11, n=140000):
+    """(g) batches 0 and 1 as in (a), but in batch 1 one column of 12 entries holds a 13th, taken from a later column of the SAME
+    bucket: every position of the stream lies in the bucket it lay in, so the producer's plan is batch 0's and the flush is tried
+    in the predicted form -- which refuses for the run length; batch 2 is batch 0 with new values.  where = "first_pair" or
+    "odd_last" (the lone bucket of the last pair: n mod 512 is between 1 and 256)"""
+    rng = np.random.default_rng([seed, 59])
+    m, L = _repeat_base(n, rng)
+    lo = {"first_pair": 0, "odd_last": PAIR * ((n - 1) // PAIR)}[where]
+    hi = min(lo + BUCKET, n)
+    assert where == "first_pair" or n - lo <= BUCKET
+    c = lo + 7 + int(np.flatnonzero(L[lo + 7:hi] == RUN)[0])      # the column that grows
+    d = c + 1 + int(np.flatnonzero(L[c + 1:hi] >= 2)[0])          # the column that gives an entry (and keeps one)
+    L1 = L.copy()
+    L1[c] += 1
+    L1[d] -= 1
+    J, _ = _expand(L)
+    J1, _ = _expand(L1)
+    I = _near_rows(J, rng, m, shift=8)
+    I1 = I + (J1 - J)                                             # (an entry that changes its column keeps its distance from the diagonal)
+    assert I1.min() >= 1
+    Z = rng.random(len(J)) < 0.10
+    out = [(I, J, _batch_values(seed, 0, len(J), Z)), (I1, J1, _batch_values(seed, 1, len(J), Z)), (I, J, _batch_values(seed, 2, len(J), Z))]
+    return m, n, kind, out, dict(maxrun=RUN + 1, long_column=c + 1, donor_column=d + 1, long_pair=c // PAIR, states=[0, 2, 0], pairs=[1, 0, 0])
+
+
 def repeat_f(seed=10, n=140000, batches=4):
     """(f) kind UPDATE, 10 % zero values drawn anew in every batch: positions whose updates are all 0.0 are not created, so every
     batch emits other counts than the one before in thousands of pairs"""

@@ -1,11 +1,12 @@
-"""The pair bucket kernels (csrc/local_w.hip: pair_k, pair_pred_k, pair_record_k) against the CPU ORACLE at their edges.
+"""The pair bucket kernels (csrc/local_w.hip: pair_k, pair_pred_k, pair_record_k, built from the phase functions there and in
+csrc/pair.hpp) against the CPU ORACLE at their edges.
 
 tests/test_bucket_pairs_gpu.py and tests/test_predicted_offsets_gpu.py compare these kernels with their sibling local_k on two
 stream shapes; here every flush -- on an automatic handle AND on one pinned to one bucket per workgroup (esp_debug_force_path 42) --
 is compared bit for bit (colptr, rowval, nzval) with the oracle, on the streams of tests/pair_streams.py: ragged run lengths
 0 .. 12 with empty buckets and pairs, sums whose bits depend on the order of their terms, pairs whose rows span up to 2^19 - 1
 (bit 31 of the sort key) or 2^19 (refused), a column run of 13 (refused), buckets narrower than 256 columns, and repeated plans
-whose rows, zeros and spans move (the predicted form).  What ran is asserted with the esp_debug_last_* queries; a precondition
+whose rows, zeros, spans and run lengths move (the predicted form).  What ran is asserted with the esp_debug_last_* queries; a precondition
 that does not hold fails the test.  tests/test_pair_streams.py checks on the CPU that the streams are what they claim to be."""
 import collections
 
@@ -276,6 +277,18 @@ def test_predicted_rows_move_beyond_the_span(esp, orc, kind):
     kernel); the next batch of the plan is not predicted and stays on local_k"""
     m, n, kind, batches, p = ps.repeat_e(kind=kind)
     ws = _repeat_on_handle(esp, orc, _matrix(esp, m, n), m, n, kind, batches, "repeat_e")
+    assert [w.predicted for w in ws] == p["states"] == [0, 2, 0], ws
+    assert [w.pairs for w in ws] == p["pairs"] == [1, 0, 0], ws
+
+
+@pytest.mark.parametrize("where", ["first_pair", "odd_last"])
+def test_predicted_run_grows_beyond_twelve(esp, orc, where):
+    """(g) a repeat in which one column holds 13 entries, bucket by bucket the stream of the batch before: the plan IS reused
+    (precondition), pair_pred_k refuses for the run length (pair_count, the phase pair_k shares), pair_k refuses, local_k serves;
+    the next batch of the plan is not predicted and stays on local_k"""
+    m, n, kind, batches, p = ps.repeat_g(where)
+    ws = _repeat_on_handle(esp, orc, _matrix(esp, m, n), m, n, kind, batches, "repeat_g " + where)
+    assert ws[1].reused == 1, ws
     assert [w.predicted for w in ws] == p["states"] == [0, 2, 0], ws
     assert [w.pairs for w in ws] == p["pairs"] == [1, 0, 0], ws
 

@@ -253,6 +253,36 @@ def test_repeat_e_and_f(orc):
         assert (x != y).mean() > 0.5
 
 
+@pytest.mark.parametrize("where", ["first_pair", "odd_last"])
+def test_repeat_g(where):
+    m, n, kind, batches, p = ps.repeat_g(where)
+    for b in batches:
+        _check_window(ps.Stream(m, n, kind, *b))
+    (I0, J0, V0), (I1, J1, V1), (I2, J2, V2) = batches
+    assert np.array_equal(I2, I0) and np.array_equal(J2, J0) and not np.array_equal(V2, V0)
+    assert np.array_equal(V1 == 0.0, V0 == 0.0) and np.array_equal(V2 == 0.0, V0 == 0.0)
+    # the producer's plan is batch 0's: every position of the stream lies in the bucket it lay in
+    assert np.array_equal((J1 - 1) // ps.BUCKET, (J0 - 1) // ps.BUCKET)
+    nb = (n + ps.BUCKET - 1) // ps.BUCKET
+    per0, per1 = (np.bincount((J - 1) // ps.BUCKET, minlength=nb) for J in (J0, J1))
+    assert np.array_equal(per1, per0) and per0.max() <= ps.BUCKET_ENTRIES
+    # exactly one column has a run of 13, no run is longer, and it took its 13th entry from a column of its own bucket
+    runs0, runs1 = (np.bincount(J - 1, minlength=n) for J in (J0, J1))
+    c, d = p["long_column"] - 1, p["donor_column"] - 1
+    assert runs0.max() == 12 and runs0[c] == 12
+    assert runs1.max() == 13 and (runs1 == 13).sum() == 1 and int(np.argmax(runs1)) == c
+    assert np.flatnonzero(runs1 != runs0).tolist() == [c, d] and runs1[d] == runs0[d] - 1 >= 1
+    assert c // ps.BUCKET == d // ps.BUCKET
+    npairs = (n + ps.PAIR - 1) // ps.PAIR
+    if where == "first_pair":
+        assert c // ps.PAIR == 0 == p["long_pair"]
+    else:
+        assert c // ps.PAIR == npairs - 1 == p["long_pair"] and 0 < n - ps.PAIR * (npairs - 1) <= ps.BUCKET
+    # (nothing else the pair kernels refuse: the rows of every pair stay close)
+    assert all(ps.describe(m, n, b[0], b[1])["pair_span"].max() < 1024 for b in batches)
+    assert p["states"] == [0, 2, 0] and p["pairs"] == [1, 0, 0]
+
+
 def _small_cases():
     nb = SMALL
     yield "ragged", ps.ragged(1, kind=ps.UPDATE, n_base=nb)[0]
@@ -269,6 +299,9 @@ def _small_cases():
         m, n, kind, batches, _ = getattr(ps, "repeat_" + name)(n=nb + 77)
         for k in (0, 1):
             yield "repeat_%s_%d" % (name, k), ps.Stream(m, n, kind, *batches[k])
+    for w, kind in (("first_pair", ps.UPDATE), ("odd_last", ps.RAWUPDATE)):
+        m, n, kind, batches, _ = ps.repeat_g(w, kind=kind, n=nb + 77)
+        yield "repeat_g_" + w, ps.Stream(m, n, kind, *batches[1])
 
 
 def test_oracle_agrees_with_dict_model(orc):
