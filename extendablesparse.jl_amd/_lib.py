@@ -20,7 +20,9 @@ ESP_PATH_NO_KEPT_STRUCTURE = 45  # esp_debug_force_path: the fused stencil flush
 ESP_PRECON_JACOBI, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_BLOCK, ESP_PRECON_AMG = 0, 1, 2, 3, 4
 ESP_PRECON_ILUK = 5
 ESP_PRECON_COLORED = 6
+ESP_PRECON_SPAI = 7
 ESP_ILUK_WAVE_VISITS, ESP_ILUK_VISIT_MAX = 512, 8192
+ESP_SPAI_WAVE_DOUBLES, ESP_SPAI_DENSE_MAX = 512, 12288
 ESP_AMG_DENSE_MAX = 512
 ESP_AMG_COARSEN_SA, ESP_AMG_COARSEN_RS = 0, 1
 ESP_ORTH_MGS, ESP_ORTH_CGS, ESP_ORTH_DGKS = 0, 1, 2
@@ -131,6 +133,9 @@ SIGNATURES = {
     "esp_precon_colored_colors": (i32, [vp, vp, i32]),
     "esp_precon_colored_perm": (i32, [vp, vp, i32]),
     "esp_precon_colored_matrix": (i32, [vp, P(vp)]),
+    "esp_precon_spai_create": (i32, [vp, i32, i32, P(vp)]),
+    "esp_precon_spai_matrix": (i32, [vp, P(vp)]),
+    "esp_precon_spai_stats": (i32, [vp, P(i64)]),
     "esp_simple": (i32, [vp, vp, vp, vp, i32, i64, f64, f64, vp, P(i64)]),
     "esp_cg": (i32, [vp, vp, vp, vp, i32, i32, i64, f64, f64, vp, P(i64), P(i32)]),
     "esp_bicgstabl": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i64, f64, f64, vp, P(i64), P(i64), P(i32)]),

@@ -197,6 +197,11 @@ __global__ __launch_bounds__(256) void spmv_rows_k(const u64 *__restrict__ rowpt
     r[i] = acc;
 }
 
+void mul_rows_launch(esp_handle *h, const double *x, double *r) {
+    hipLaunchKernelGGL(spmv_rows_k, dim3(grid_for(h->m, 256)), dim3(256), 0, h->stream, (const u64 *)h->csr_rowptr.p,
+                       (const double *)h->csr_val.p, (const u32 *)h->csr_col.p, x, h->m, r);
+}
+
 int32_t build_csr(esp_handle *h) {
     const i64 Z = h->nnz, m = h->m;
     const i64 M2 = m + 2;
@@ -288,9 +293,7 @@ extern "C" int32_t esp_mul(esp_handle *h, const double *x, double *r, int32_t on
         dx = (const double *)h->mul_x.p;
         dr = (double *)h->mul_r.p;
     }
-    if (h->m > 0)
-        hipLaunchKernelGGL(spmv_rows_k, dim3(grid_for(h->m, 256)), dim3(256), 0, h->stream, (const u64 *)h->csr_rowptr.p,
-                           (const double *)h->csr_val.p, (const u32 *)h->csr_col.p, dx, h->m, dr);
+    if (h->m > 0) mul_rows_launch(h, dx, dr);
     HIPCK(h, hipGetLastError());
     if (!on_device && h->m > 0) HIPCK(h, hipMemcpyAsync(r, dr, sizeof(double) * (size_t)h->m, hipMemcpyDeviceToHost, h->stream));
     HIPCK(h, hipStreamSynchronize(h->stream));

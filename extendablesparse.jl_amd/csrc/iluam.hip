@@ -400,18 +400,21 @@ extern "C" int32_t esp_precon_get_factor(esp_precon *p, double *nzval, int32_t o
         if (st != ESP_OK) FAIL(h, st, "%s", p->der.bh->err.c_str());
         return ESP_OK;
     }
-    if (p->kind != ESP_PRECON_ILUAM) FAIL(h, ESP_ERR_INVALID, "esp_precon_get_factor: not an ILUAM preconditioner");
+    const bool spai = p->kind == ESP_PRECON_SPAI;  // the applied M's values in its position order / the n diagonal values of SPAI-0
+    if (p->kind != ESP_PRECON_ILUAM && !spai) FAIL(h, ESP_ERR_INVALID, "esp_precon_get_factor: not an ILUAM preconditioner");
     if (h->pattern_version != p->pattern_version || h->nnz != p->nnz)  // (the caller sized nzval by the matrix's nnz)
         FAIL(h, ESP_ERR_STATE, "esp_precon_get_factor: the matrix pattern changed since the preconditioner's last update!");
     (void)hipSetDevice(h->device);
-    const size_t bytes = sizeof(double) * (size_t)p->nnz;
+    if (spai) CK(spai_follow_stream(p));
+    const void *src = !spai ? p->fval.p : p->spai_order == 0 ? p->diag.p : spai_applied(p)->nzval.p;
+    const size_t bytes = sizeof(double) * (size_t)(!spai ? p->nnz : p->spai_order == 0 ? p->n : spai_applied(p)->nnz);
     if (bytes == 0) return ESP_OK;
     if (on_device) {
-        HIPCK(h, hipMemcpyAsync(nzval, p->fval.p, bytes, hipMemcpyDeviceToDevice, h->stream));
+        HIPCK(h, hipMemcpyAsync(nzval, src, bytes, hipMemcpyDeviceToDevice, h->stream));
         HIPCK(h, hipStreamSynchronize(h->stream));
         return ESP_OK;
     }
-    return d2h_pipelined(h, nzval, p->fval.p, bytes);
+    return d2h_pipelined(h, nzval, src, bytes);
 }
 
 extern "C" int32_t esp_precon_levels(esp_precon *p, int64_t out[3]) {

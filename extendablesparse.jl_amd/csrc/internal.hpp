@@ -14,6 +14,8 @@
 //   block.hip      BlockPreconditioner: the masked block matrix B of a partitioning (identity / permuted path) and the object around it
 //   color.hip      the multicolour ordering: graph colouring by rounds over a fixed hash (esp_graph_coloring), the permutation by
 //                  (colour, index), ColoredPreconditioner = block.hip's permuted path over that one partition
+//   spai.hip       SPAIPreconditioner: the sparse approximate inverses SPAI-0 and SPAI-1 (size pass, one wave / one workgroup per
+//                  column: sorted row union, dense gather, modified Gram-Schmidt in LDS), M in an internal handle, ldiv! = esp_mul's gather
 //   iluk.hip       ILUKPreconditioner: the level-of-fill pattern by one bounded search per column (wave / workgroup form), the filled
 //                  matrix B in an internal handle, ILUAM on it
 //   amg.hip        AMGPreconditioner: smoothed aggregation (MIS(2) aggregates by Luby rounds, the level hierarchy from the algebra
@@ -635,6 +637,16 @@ struct esp_precon {
     // rebuilt.
     DevBuf col_color, col_perm;      // u32 n each: the colour of every vertex (1-based, as the rounds number them), c
     std::vector<i64> col_ptr;        // ncolors + 1: colour r holds c[col_ptr[r] .. col_ptr[r + 1])
+    // SPAIPreconditioner (kind ESP_PRECON_SPAI, spai.hip).  order 0: the n values in diag, applied as Jacobi's invdiag is.  order 1:
+    // M lives in the internal handle spai_rh on A's pattern (A's device and stream); symmetric: spai_th holds its transpose and
+    // spai_sh 0.5*(M + transpose(M)).  ldiv! is the row gather of esp_mul over the applied handle (spai_applied), through u1 when u
+    // aliases v.  Kept for the values-only update: p of every column, its tier, the columns of the workgroup tier and their scratch.
+    int spai_order = 0, spai_sym = 0;
+    esp_handle *spai_rh = nullptr, *spai_th = nullptr, *spai_sh = nullptr;
+    DevBuf spai_p, spai_tier, spai_list;  // u32 n, u8 n, u32 spai_stats[3]
+    DevBuf spai_r, spai_half, spai_stat;  // the R slots of the workgroup tier (f64 spai_rgrid * spai_rslot), n halves, 8 status words
+    i64 spai_rslot = 0, spai_rgrid = 0;
+    i64 spai_stats[4] = {0, 0, 0, 0};     // max p, max q, max p*q, columns of the workgroup tier
 };
 // the kinds that block.hip's builder, update! and ldiv! serve
 static inline bool block_built(const esp_precon *p) { return p->kind == ESP_PRECON_BLOCK || p->kind == ESP_PRECON_COLORED; }
@@ -647,6 +659,9 @@ static inline bool derived_stale(const esp_precon *p) {
 // the identity-path block preconditioner and the ILU(k) preconditioner stand for their inner one in the solvers' fused branches
 static inline esp_precon *fused_precon(esp_precon *p) { return p && holds_derived(p) && p->blk_path == 0 ? p->der.inner : p; }
 static inline bool block_permuted(const esp_precon *p) { return p && block_built(p) && p->blk_path != 0; }
+// the kinds whose ldiv! is u = diag .* v: Jacobi (invdiag) and SPAI-0 (its diagonal M) -- one branch in precon.hip and krylov.hpp
+static inline bool diag_applied(const esp_precon *p) { return p->kind == ESP_PRECON_JACOBI || (p->kind == ESP_PRECON_SPAI && p->spai_order == 0); }
+static inline esp_handle *spai_applied(const esp_precon *p) { return p->spai_sym ? p->spai_sh : p->spai_rh; }
 constexpr u32 ILUK_FILL = 0xFFFFFFFFu;  // src of a fill entry of ILU(k): no position (every update! refuses nnz(A) >= 2^32 - 16)
 
 #pragma GCC visibility push(hidden)
@@ -693,6 +708,15 @@ void iluk_release(esp_precon *p);
 // release of the colour arrays (B, the inner preconditioner and the maps are block_release's)
 int32_t color_update(esp_precon *p);
 void color_release(esp_precon *p);
+// spai.hip: update! (after a pattern change the size pass, the tiers and M anew; else the numeric kernels alone), M's handles moved
+// to the stream A runs on, ldiv! of order 1 on device vectors (u may be v; sub: u[i] = u[i] - x[i], simple!'s step; launches and at
+// most one copy on the handle's stream), release of the handles and buffers
+int32_t spai_update(esp_precon *p);
+int32_t spai_follow_stream(esp_precon *p);
+int32_t spai_apply(esp_precon *p, const double *v, double *u, bool sub);
+void spai_release(esp_precon *p);
+// consumers.hip: the row gather of esp_mul over h's current row-wise index (csr_current ran), enqueued on h's stream
+void mul_rows_launch(esp_handle *h, const double *x, double *r);
 // amg.hip: update! (the whole hierarchy is rebuilt every time), the V-cycle on device vectors (u may be v; sub: u[i] = u[i] - x[i],
 // simple!'s step; launches on the handle's stream only), release of the hierarchy
 int32_t amg_update(esp_precon *p);

@@ -201,11 +201,12 @@ struct PreconProduct {
     int32_t ldiv(const double *src, double *dst, const double *other, bool dot) const {
         if (!p) {
             if (dot) dot_launch(nullptr, src, other, nullptr);
-        } else if (!blk && p->kind == ESP_PRECON_JACOBI) {
+        } else if (!blk && diag_applied(p)) {
             dot_launch((const double *)p->diag.p, nullptr, src, dst);
-        } else if (blk || p->kind == ESP_PRECON_ILUAM || p->kind == ESP_PRECON_AMG) {
+        } else if (blk || p->kind == ESP_PRECON_ILUAM || p->kind == ESP_PRECON_AMG || p->kind == ESP_PRECON_SPAI) {
             if (blk) CK(block_ldiv_launch(blk, src, dst, false));
             else if (p->kind == ESP_PRECON_AMG) CK(amg_solve(p, src, dst, false));  // the V-cycle's launches
+            else if (p->kind == ESP_PRECON_SPAI) CK(spai_apply(p, src, dst, false));  // one product with M
             else CK(iluam_solve(p, src, dst, false));                              // the level launches
             if (dot) dot_launch(nullptr, dst, other, nullptr);
         } else {  // ILU0: pass 1 into p->u1 (precon.hip, unchanged), pass 2 carries the dot product
@@ -220,7 +221,7 @@ struct PreconProduct {
     // bitwise ldiv! of mul!), every other kind the matvec into t (no dot), then ldiv
     int32_t pmul(const double *src, double *dst, const double *other, bool dot) const {
         if (!p) mul(src, dst, other, dot);
-        else if (!blk && p->kind == ESP_PRECON_JACOBI) gather<MUL_JAC_DOT>(src, dst, other, dot, (const double *)p->diag.p);
+        else if (!blk && diag_applied(p)) gather<MUL_JAC_DOT>(src, dst, other, dot, (const double *)p->diag.p);
         else {
             mul(src, t, other, false);
             CK(ldiv(t, dst, other, dot));

@@ -300,6 +300,7 @@ int32_t precon_ready(esp_precon *p, const char *what) {
         FAIL(h, ESP_ERR_STATE, "%s: the matrix pattern changed since the preconditioner's last update! (update! first)", what);
     if (p->kind == ESP_PRECON_ILU0 && p->values_version != h->values_version) CK(split_scale(p, false));  // current nzval, stored xdiag
     if (holds_derived(p)) CK(derived_follow_stream(p));  // (B holds copies: the values as of the last update!, ILU0 included)
+    if (p->kind == ESP_PRECON_SPAI) CK(spai_follow_stream(p));
     return ESP_OK;
 }
 
@@ -312,8 +313,9 @@ int32_t ldiv_launch(esp_precon *p, const double *v, double *u) {
     if (p->kind == ESP_PRECON_ILUK) return ldiv_launch(p->der.inner, v, u);  // ILUAM of B on the caller's vectors
     if (p->kind == ESP_PRECON_ILUAM) return iluam_solve(p, v, u, false);
     if (p->kind == ESP_PRECON_AMG) return amg_solve(p, v, u, false);
+    if (p->kind == ESP_PRECON_SPAI && p->spai_order != 0) return spai_apply(p, v, u, false);  // u = M*v
     const unsigned g = grid_for(n, PT);
-    if (p->kind == ESP_PRECON_JACOBI) {
+    if (diag_applied(p)) {  // Jacobi's invdiag / SPAI-0's diagonal M
         hipLaunchKernelGGL(jacobi_ldiv_k, dim3(g), dim3(PT), 0, h->stream, (const double *)p->diag.p, v, u, n);
         return ESP_OK;
     }
@@ -370,6 +372,7 @@ extern "C" int32_t esp_precon_update(esp_precon *p) {
     if (p->kind == ESP_PRECON_AMG) return amg_update(p);      // the whole hierarchy (amg.hip)
     if (p->kind == ESP_PRECON_ILUK) return iluk_update(p);    // the filled matrix and the inner ILUAM (iluk.hip)
     if (p->kind == ESP_PRECON_COLORED) return color_update(p);  // the colouring, A[c,c] and the inner preconditioner (color.hip)
+    if (p->kind == ESP_PRECON_SPAI) return spai_update(p);      // the approximate inverse M (spai.hip)
     esp_handle *h = p->h;
     CK(check_handle(h, "esp_precon_update"));
     p->n = h->n;
@@ -420,6 +423,7 @@ extern "C" int32_t esp_precon_destroy(esp_precon *p) {
     block_release(p);
     iluk_release(p);
     color_release(p);
+    spai_release(p);
     for (DevBuf *b : {&p->diag, &p->lptr, &p->uptr, &p->lcol, &p->ucol, &p->lpos, &p->upos, &p->dpos, &p->lval, &p->uval, &p->u1, &p->res,
                       &p->partial, &p->scanws, &p->hv, &p->hu})
         release(*b);
@@ -476,13 +480,15 @@ extern "C" int32_t esp_simple(esp_handle *h, esp_precon *p, const double *b, dou
         if (n > 0) {
             if (blk) {
                 CK(block_ldiv_launch(blk, res, du, true));
-            } else if (p->kind == ESP_PRECON_JACOBI) {
+            } else if (diag_applied(p)) {
                 hipLaunchKernelGGL(jacobi_sub_k, dim3((unsigned)nb), dim3(PT), 0, h->stream, (const double *)p->diag.p,
                                    (const double *)res, du, n);
             } else if (p->kind == ESP_PRECON_ILUAM) {
                 CK(iluam_solve(p, res, du, true));
             } else if (p->kind == ESP_PRECON_AMG) {
                 CK(amg_solve(p, res, du, true));
+            } else if (p->kind == ESP_PRECON_SPAI) {
+                CK(spai_apply(p, res, du, true));
             } else {
                 double *u1 = (double *)p->u1.p;
                 hipLaunchKernelGGL((row_chain_k<ILU_LOWER, u32>), dim3((unsigned)nb), dim3(PT), 0, h->stream, (const u32 *)p->lptr.p,

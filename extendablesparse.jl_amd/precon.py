@@ -24,13 +24,16 @@ ILUAMPreconditioner of the filled matrix (esp_precon_iluk_create) -- bit-identic
 ColoredPreconditioner(A, factorization) colours A's graph on the device (rounds over a fixed hash, esp_graph_coloring), reorders A by
 (colour, index) and runs ILU0 or ILUAM on A[c,c]: at most ncolors levels per schedule.  ParallelILU0Preconditioner(A) is the ILU0 form,
 the reference's src/factorizations/parallel_ilu0.jl acting in A's numbering; graphcol, reordermatrix and reorderlinsys are its helpers.
+SPAIPreconditioner(A, order, symmetric) is the sparse approximate inverse SPAI-0 / SPAI-1 (esp_precon_spai_create): M ~ inv(A) on A's
+pattern from one small least-squares problem per column, ldiv! one sparse product -- bit-identical to tests/spai_model.c.
+AMGCL_RLXPreconditioner(A, type="spai0" | "spai1") is the reference-named constructor over it (ext/ExtendableSparseAMGCLWrapExt.jl).
 """
 import ctypes as C
 import math
 
 import numpy as np
 
-from ._lib import ESP_ORTH_CGS, ESP_ORTH_DGKS, ESP_ORTH_MGS, ESP_PRECON_AMG, ESP_PRECON_BLOCK, ESP_PRECON_COLORED, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_ILUK, ESP_PRECON_JACOBI
+from ._lib import ESP_ORTH_CGS, ESP_ORTH_DGKS, ESP_ORTH_MGS, ESP_PRECON_AMG, ESP_PRECON_BLOCK, ESP_PRECON_COLORED, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_ILUK, ESP_PRECON_JACOBI, ESP_PRECON_SPAI
 from .matrix import ExtendableSparseMatrix, _vp
 
 
@@ -403,6 +406,70 @@ def reorderlinsys(A, b, coloring):
     """reorderlinsys(A, b, coloring) (parallel_ilu0.jl): (A[c,c], b[c]) with c = flatten(coloring)"""
     b = np.asarray(b, np.float64)
     return reordermatrix(A, coloring), np.ascontiguousarray(b[_flatten(coloring, A.n)])
+
+
+class SPAIPreconditioner(_PointPreconditioner):
+    """SPAIPreconditioner(A, order=1, symmetric=False): the sparse approximate inverse (include/esparse_hip.h,
+    esp_precon_spai_create).  M minimises |I - A*M|_F over the pattern of A, column by column from independent small least-squares
+    problems (modified Gram-Schmidt on the device), and ldiv! is u = M*v: one sparse product, no triangular solve, no levels.
+    order=0 is the diagonal member SPAI-0 (ldiv! is u = m .* v).  symmetric=True (order 1) applies 0.5*(M + transpose(M)), the form
+    cg needs.  The pattern of M depends on A's pattern alone; M holds results: a value change of A reaches ldiv only through
+    update(), which keeps every index structure when only values changed."""
+    KIND = ESP_PRECON_SPAI
+
+    def __init__(self, A, order=1, symmetric=False):
+        if not isinstance(A, ExtendableSparseMatrix):
+            raise TypeError("%s(A, ...): A must be an ExtendableSparseMatrix" % type(self).__name__)
+        if order not in (0, 1):
+            raise ValueError("SPAIPreconditioner: order = %r (0: SPAI-0, 1: SPAI-1)" % (order,))
+        if symmetric and order == 0:
+            raise ValueError("SPAIPreconditioner: SPAI-0 is diagonal; symmetric belongs to order 1")
+        self.order, self.symmetric = int(order), bool(symmetric)
+        self._bind(A, "esp_precon_spai_create", self.order, int(self.symmetric))
+
+    def _applied(self):
+        m = C.c_void_p()
+        self._ck(self.A._d.lib.esp_precon_spai_matrix(self._live(), C.byref(m)))
+        return m
+
+    def matrix(self):
+        """the applied M (order 1) as host CSC arrays (colptr, rowval, nzval), Julia layout -- for tests and inspection"""
+        return self._host_csc(self._applied(), self.A.n)
+
+    def factor(self):
+        """the values of the applied M in its position order; order 0: the n diagonal values"""
+        p = self._live()
+        if self.order == 0:
+            count = self.A.n
+        else:
+            nnz = C.c_int64()
+            self._ck(self.A._d.lib.esp_nnz(self._applied(), C.byref(nnz)))
+            count = nnz.value
+        out = np.empty(count, np.float64)
+        self._ck(self.A._d.lib.esp_precon_get_factor(p, _vp(out), 0))
+        return out
+
+    def issymmetric(self):
+        """issymmetric of the applied M (order 1), on the device"""
+        r = C.c_int32()
+        self._ck(self.A._d.lib.esp_issymmetric(self._applied(), C.byref(r)))
+        return bool(r.value)
+
+    def stats(self):
+        """dict: max_p / max_q (the largest row set / column of a local problem), max_pq (its largest size in doubles), wide (the
+        columns the workgroup tier handled); zeros for order 0"""
+        out = (C.c_int64 * 4)()
+        self._ck(self.A._d.lib.esp_precon_spai_stats(self._live(), out))
+        return {"max_p": int(out[0]), "max_q": int(out[1]), "max_pq": int(out[2]), "wide": int(out[3])}
+
+
+def AMGCL_RLXPreconditioner(A, type="spai0"):
+    """AMGCL_RLXPreconditioner(A; type) (ext/ExtendableSparseAMGCLWrapExt.jl): the relaxation preconditioners of AMGCL.  On the
+    device: "spai0" and "spai1", as SPAIPreconditioner(A, order=0 / 1)."""
+    orders = {"spai0": 0, "spai1": 1}
+    if type not in orders:
+        raise NotImplementedError("AMGCL_RLXPreconditioner: type = %r is not on the device; \"spai0\" and \"spai1\" are" % (type,))
+    return SPAIPreconditioner(A, order=orders[type])
 
 
 class AMGPreconditioner(_PointPreconditioner):

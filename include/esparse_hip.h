@@ -333,7 +333,7 @@ int32_t esp_precon_destroy(esp_precon *p);
  *   The factorization owns a copy of the values: an in-place value change of A without update! does NOT change ldiv!
  *   (unlike ILU0).  A pattern change without update! -> ESP_ERR_STATE.
  * esp_precon_get_factor: the factorization's nnz values in CSC position order (the reference's ILU.nzval), host doubles or,
- *   on_device != 0, device doubles; ESP_ERR_INVALID for the other kinds.
+ *   on_device != 0, device doubles; SPAI answers with the values of M (below); ESP_ERR_INVALID for Jacobi, ILU0 and AMG.
  * esp_precon_levels: out[0..2] = the level counts of the three schedules (factorization columns, forward rows, backward
  *   rows); zeros for the other kinds.
  * esp_precon_launches: read-only; out[2k], out[2k+1] = the wide and the thin kernel launches schedule k runs, in
@@ -539,6 +539,58 @@ int32_t esp_precon_colored_info(esp_precon *p, int64_t out[2]);
 int32_t esp_precon_colored_colors(esp_precon *p, int64_t *color, int32_t on_device);
 int32_t esp_precon_colored_perm(esp_precon *p, int64_t *c, int32_t on_device);
 int32_t esp_precon_colored_matrix(esp_precon *p, esp_handle **b);
+/* SPAIPreconditioner: the sparse approximate inverses SPAI-0 and SPAI-1 (the relaxations `spai0` and `spai1` of the reference's
+ * AMGCL_RLXPreconditioner, ext/ExtendableSparseAMGCLWrapExt.jl; AMGCLWrap is not part of the reference tree, so the algorithm below
+ * is normative, tests/spai_model.c states it as plain loops, and the device equals that model bit for bit).  M ~ inv(A) minimises
+ * |I - A*M|_F over the pattern of A, one column at a time from independent small least-squares problems: no ordering, no levels, no
+ * colouring, and ldiv! is one sparse product.  Indices 0-based; no FMA contraction anywhere; sqrt and / correctly rounded.  Column k:
+ *   1. J = the stored rows of column k of A, ascending: the unknowns of column k of M, q = |J|.  M stores exactly A's positions
+ *      (a stored 0.0, -0.0 or NaN counts as an entry): colptr and rowval of M are A's.
+ *   2. I = the ascending union of the stored rows of the columns j in J, p = |I|.
+ *   3. B = A[I, J], dense p x q: A's bits where stored, +0.0 elsewhere.
+ *   4. osum, the ordered sum of p terms: part[l], l = 0..63, adds the terms with local row r = l, l + 64, ... in increasing r,
+ *      starting from the first one (+0.0 where there is none); then for s = 32, 16, 8, 4, 2, 1: part[l] = part[l] + part[l + s] for
+ *      l < s; the result is part[0].
+ *   5. modified Gram-Schmidt, c = 0..q-1 in order: R[c][c] = sqrt(osum_r B[r][c]*B[r][c]); B[r][c] = B[r][c] / R[c][c]; for every
+ *      d > c: R[c][d] = osum_r B[r][c]*B[r][d], then B[r][d] = B[r][d] - R[c][d]*B[r][c].
+ *   6. y[c] = B[pos][c] of the normalised columns where I[pos] == k; +0.0 where k is not in I.
+ *   7. back substitution, c = q-1..0: t = y[c]; for d = c+1..q-1 ascending t = t - R[c][d]*m[d]; m[c] = t / R[c][c].
+ *   8. the values of column k of M are m[0..q-1].
+ *   A zero or NaN pivot is no error: Inf and NaN propagate (a rank-deficient local problem, an empty row set, p < q).  A column
+ *   without a stored diagonal is valid; an empty column stays empty.
+ * order = 0, SPAI-0, is the diagonal member: m_k = a_kk / osum(a*a over the stored entries of column k), a_kk = +0.0 where the
+ *   diagonal is not stored; an n-vector, applied as Jacobi's invdiag is.
+ * symmetric != 0 (order 1 only) replaces M by 0.5*(M + transpose(M)), formed by esp_transpose, esp_add and esp_diag_scale on
+ *   internal handles (their rules: a sum that is zero is not stored); bitwise symmetric, the form esp_cg needs.
+ * On the device a size pass finds p of every column (the sorted union in LDS) and sorts the columns into tiers before M is touched:
+ *   one wave per column with B, R and I in LDS while p*q <= ESP_SPAI_WAVE_DOUBLES (and q*q <= ESP_SPAI_WAVE_DOUBLES, which p >= q
+ *   implies); one workgroup of eight waves per listed column with B and I in LDS and R in a scratch slot of device memory up to
+ *   p*q <= ESP_SPAI_DENSE_MAX, the waves taking the independent columns d > c in turn, each with the wave form's sum: both tiers
+ *   give the same bits.  A column with p*q > ESP_SPAI_DENSE_MAX -> ESP_ERR_UNSUPPORTED before anything of the preconditioner
+ *   changes; esp_last_error names the smallest such column with its p and q (p as a lower bound, marked ">=", where the lists of
+ *   the column hold more than 16384 rows together).
+ * esp_precon_spai_create(h, order, symmetric): the result is an esp_precon bound to h; esp_precon_update / _ldiv / _destroy,
+ *   esp_simple, esp_cg, esp_bicgstabl and esp_gmres take it unchanged.
+ * esp_precon_ldiv: u = M*v in esp_mul's order on M's internal handle, on h's stream; no allocation, no synchronisation inside the
+ *   solvers; u may alias v (one copy through an n-vector the preconditioner owns).  order 0: u = m.*v.
+ * esp_precon_update: with A's pattern kept only the numeric kernels run on the kept p, tiers and pattern of M -- bitwise what a
+ *   fresh create gives (symmetric: the three algebra calls run again); after a pattern change everything anew.  M holds results: a
+ *   value change of A reaches ldiv! only through the update; a pattern change of A without it -> ESP_ERR_STATE.  An update that is
+ *   refused (ESP_ERR_UNSUPPORTED, ESP_ERR_NOMEM in the set-up) leaves the preconditioner what its last good update made it.
+ * esp_precon_get_factor: the values of the applied M in its position order (order 0: the n diagonal values); esp_precon_levels and
+ *   esp_precon_launches give zeros.  esp_precon_spai_matrix: the applied M's handle, borrowed and read-only, like
+ *   esp_precon_block_matrix; order 0 -> ESP_ERR_INVALID.  esp_precon_spai_stats: out = max p, max q, max p*q, the columns the
+ *   workgroup tier handled (zeros for order 0).
+ * ESP_ERR_INVALID: a rectangular matrix, order outside {0, 1}, symmetric with order 0.  ESP_ERR_STATE: pending entries.
+ * ESP_ERR_UNSUPPORTED: a column window / column shard on h; n or nnz >= 2^32 - 16; a too-large column.  n == 0 and n == 1 are
+ * valid.  SPAI is no inner kind of esp_precon_block_create or esp_precon_colored_create.  A live preconditioner makes h refuse
+ * esp_destroy; esp_precon_destroy releases M, its internal handles and every buffer. */
+#define ESP_PRECON_SPAI 7
+#define ESP_SPAI_WAVE_DOUBLES 512
+#define ESP_SPAI_DENSE_MAX 12288
+int32_t esp_precon_spai_create(esp_handle *h, int32_t order, int32_t symmetric, esp_precon **out);
+int32_t esp_precon_spai_matrix(esp_precon *p, esp_handle **m);
+int32_t esp_precon_spai_stats(esp_precon *p, int64_t out[4]);
 /* simple!(u, A, b; abstol, reltol, maxiter, Pl = p) (src/factorizations/simple_iteration.jl:21-45) statement by
  * statement: res = A*u - b; then per step ldiv!(upd, Pl, res), u .-= upd, mul!(res, A, u), res .-= b, r = norm(res),
  * stop when (r / r0) < reltol || r < abstol (literally: r0 = 0 gives NaN or Inf there).  u (in/out) is bit-identical to

@@ -85,6 +85,12 @@ beside the natural-order ILUAMPreconditioner and ILU0Preconditioner, the yardsti
 update!, ldiv! on device vectors, the colours and the level counts, and cg to reltol 1e-8 on b = ones (iterations and time).
 
     python tools/precon_bench.py --kind colored --inner iluam [--n 64] [--iters 20] [--rounds 5]
+
+--kind spai0 | spai1 | spai1sym times SPAIPreconditioner (esp_precon_spai_create: SPAI-0, SPAI-1, the symmetrised SPAI-1) on
+fdrand(n,n,n): setup_ms (create), update_ms (values-only update!), ldiv_ms beside mul_ms (one mul! of A) and cg to 1e-8, with Jacobi,
+ILU0 and ColoredPreconditioner (--inner) from the same run beside it.
+
+    python tools/precon_bench.py --kind spai1sym [--n 64] [--iters 20] [--rounds 5] [--tol-maxiter 20000]
 """
 import argparse
 import ctypes as C
@@ -913,12 +919,81 @@ def bench_colored(a, torch, esp):
     print(json.dumps(rnd(out)))
 
 
+def bench_spai(a, torch, esp):
+    """--kind spai0 | spai1 | spai1sym: set-up, values-only update!, ldiv! beside one mul! of A, and cg to 1e-8 beside Jacobi, ILU0 and
+    ColoredPreconditioner (--inner) from the same run.  cg with the unsymmetrised spai1 is reported as it comes (M is not symmetric)."""
+    import numpy as np
+    A = esp.fdrand(a.n, a.n, a.n)
+    d = A._d
+    stream = torch.cuda.current_stream()
+    d.ck(d.lib.esp_set_stream(d.h, C.c_void_p(stream.cuda_stream)))
+    N, Z = A.n, A.nnz()
+    v = torch.randn(N, dtype=torch.float64, device="cuda")
+    u = torch.empty_like(v)
+    b = torch.ones_like(v)
+    inner = {"ilu0": esp.ILU0Preconditioner, "iluam": esp.ILUAMPreconditioner}[a.inner]
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()                                   # (create, update!, ldiv!, mul! and cg return synchronised)
+        return (time.perf_counter() - t0) * 1e3, r
+
+    def median(xs):
+        return float(np.median(xs))
+
+    def measure(make):
+        rec = {}
+        ts = []
+        for _ in range(a.rounds):
+            t, P = wall(lambda: make(A))
+            ts.append(t)
+            P.close()
+        rec["setup_ms"] = median(ts)
+        P = make(A)
+        rec["update_ms"] = median([wall(P.update)[0] for _ in range(a.rounds)])
+        for _ in range(3):
+            P.ldiv(v, out=u)
+        rec["ldiv_ms"] = median([wall(lambda: [P.ldiv(v, out=u) for _ in range(a.iters)])[0] / a.iters for _ in range(a.rounds)])
+        fn = lambda: esp.cg(A, b, Pl=P, reltol=1e-8, maxiter=a.tol_maxiter, log=True)
+        fn()
+        ts, log = [], None
+        for _ in range(a.rounds):
+            t, (_, log) = wall(fn)
+            ts.append(t)
+        rec["cg"] = {"iterations": log["iters"], "converged": log["isconverged"], "ms": median(ts)}
+        return rec, P
+
+    out = {"workload": "spai_fdrand", "kind": a.kind, "n": a.n, "N": N, "nnz": Z, "rounds": a.rounds, "iters": a.iters}
+    for _ in range(3):
+        A.mul(v, out=u)                            # (builds the row-wise index mul! and the creates below share)
+    out["mul_ms"] = median([wall(lambda: [A.mul(v, out=u) for _ in range(a.iters)])[0] / a.iters for _ in range(a.rounds)])
+    spai = {"spai0": lambda M: esp.SPAIPreconditioner(M, 0), "spai1": lambda M: esp.SPAIPreconditioner(M, 1),
+            "spai1sym": lambda M: esp.SPAIPreconditioner(M, 1, True)}[a.kind]
+    for name, make in (("jacobi", esp.JacobiPreconditioner), ("ilu0", esp.ILU0Preconditioner),
+                       ("colored_" + a.inner, lambda M: esp.ColoredPreconditioner(M, inner)), (a.kind, spai)):
+        rec, P = measure(make)
+        if name == a.kind:
+            rec["stats"] = P.stats()
+        P.close()
+        out[name] = rec
+        print(json.dumps({name: rec}), file=sys.stderr, flush=True)   # (what is known so far, should a later phase be cut short)
+
+    def rnd(x):
+        if isinstance(x, float):
+            return round(x, 4)
+        if isinstance(x, dict):
+            return {k: rnd(y) for k, y in x.items()}
+        return x
+    print(json.dumps(rnd(out)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "gmres", "gmres-trace", "block", "block-trace", "block-trace-diff", "amg", "iluk", "colored"], default="point")
+    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "gmres", "gmres-trace", "block", "block-trace", "block-trace-diff", "amg", "iluk", "colored", "spai0", "spai1", "spai1sym"], default="point")
     ap.add_argument("--inner", choices=["ilu0", "iluam"], default="iluam")
     ap.add_argument("--k", type=int, default=1)
     ap.add_argument("--rounds", type=int, default=5)
@@ -961,6 +1036,8 @@ def main():
         return bench_amg(a, torch, esp)
     if a.kind == "colored":
         return bench_colored(a, torch, esp)
+    if a.kind in ("spai0", "spai1", "spai1sym"):
+        return bench_spai(a, torch, esp)
     A = esp.fdrand(a.n, a.n, a.n)
     d = A._d
     stream = torch.cuda.current_stream()
