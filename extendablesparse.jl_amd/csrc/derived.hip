@@ -4,7 +4,7 @@
 //                    esp_transpose's generic path, esp_matmul's generic tier and a column above the column sorts' limit (ColumnSort,
 //                    linalg.hip: block.hip's permuted path, iluk.hip)
 //   derived_update   the update! of the kinds that hold a matrix B made from A and an inner preconditioner of it (esp_precon::Derived:
-//                    Block, Colored, ILU(k)); the kind supplies the builder of B
+//                    Block, Colored, ILU(k), ILUT); the kind supplies the builder of B
 #include "internal.hpp"
 
 namespace {
@@ -38,6 +38,7 @@ __global__ __launch_bounds__(DT) void derived_gather_k(const u64 *__restrict__ p
 
 // update! with the pattern kept: B's values anew, in place
 int32_t refresh_values(esp_precon *p) {
+    if (p->kind == ESP_PRECON_ILUT) return ilut_warm(p);  // (F is no gather of A's values: sweeps from the current F)
     esp_handle *h = p->h, *bh = p->der.bh;
     if (bh->nnz > 0)
         derived_gather_launch(h->stream, nullptr, (u32 *)p->der.src.p, nullptr, (const u64 *)h->nzval.p, (u64 *)bh->nzval.p, bh->nnz, nullptr);
@@ -54,7 +55,7 @@ void derived_gather_launch(hipStream_t s, const u64 *pay, u32 *src, int32_t *lev
 }
 
 int32_t derived_follow_stream(esp_precon *p) {
-    for (esp_handle *q : {p->der.bh, p->iluk_th})
+    for (esp_handle *q : {p->der.bh, p->iluk_th, p->ilut_h[0], p->ilut_h[1], p->ilut_h[2], p->ilut_h[3]})
         if (q && q->stream != p->h->stream) CK(esp_set_stream(q, (void *)p->h->stream));
     return ESP_OK;
 }

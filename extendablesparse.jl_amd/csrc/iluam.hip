@@ -21,6 +21,10 @@
 // level, which leaves every level's members ascending; last the row parts are permuted into that order, so that the lanes
 // of a level stream one contiguous slice (measured at 256^3: ldiv! 8.3 ms against 11.2 ms with the parts in row order, for
 // 2 ms more per factorization, whose value gather then reads the factor scattered).  A values-only update! keeps all of it.
+//
+// Prefactored mode (esp_precon::prefactored, set by ilut.hip on its inner preconditioner): the handle's values are a factorization
+// already.  The diagonal positions, the row parts and the two solve schedules are built as above; the factor schedule is not, and
+// FactorOp does not run: fval is a copy of the handle's values, and a values-only update! is that copy and the gather.
 #include "internal.hpp"
 
 namespace {
@@ -350,17 +354,19 @@ int32_t iluam_update(esp_precon *p, bool rebuild) {
         CK(diag_refresh(p));      // (refuses a missing diagonal before anything is built)
         CK(split_build(p, true));
         CK(ensure(h, p->u1, sizeof(double) * (size_t)std::max<i64>(n, 1)));
-        CK(build_schedule<S_FACTOR>(p, p->sched[S_FACTOR]));
+        if (!p->prefactored) CK(build_schedule<S_FACTOR>(p, p->sched[S_FACTOR]));
         CK(build_schedule<S_FWD>(p, p->sched[S_FWD]));
         CK(build_schedule<S_BWD>(p, p->sched[S_BWD]));
         CK(permute_part(p, p->sched[S_FWD], p->lptr, p->lcol, p->lpos));  // (the analysis above read them in row order)
         CK(permute_part(p, p->sched[S_BWD], p->uptr, p->ucol, p->upos));
     }
-    // the numeric factorization on a copy of the values
+    // the numeric factorization on a copy of the values (prefactored, ilut.hip's inner preconditioner: the values are the factorization
+    // already -- the copy and the gather alone)
     CK(ensure(h, p->fval, sizeof(double) * (size_t)std::max<i64>(h->nnz, 1)));
     if (n == 0) return ESP_OK;
     HIPCK(h, hipMemcpyAsync(p->fval.p, h->nzval.p, sizeof(double) * (size_t)h->nnz, hipMemcpyDeviceToDevice, h->stream));
-    run_schedule(p, p->sched[S_FACTOR], FactorOp{(const u32 *)p->sched[S_FACTOR].order.p, (const i64 *)h->colptr.p, (const i64 *)h->rowval.p, (const u32 *)p->dpos.p, (double *)p->fval.p});
+    if (!p->prefactored)
+        run_schedule(p, p->sched[S_FACTOR], FactorOp{(const u32 *)p->sched[S_FACTOR].order.p, (const i64 *)h->colptr.p, (const i64 *)h->rowval.p, (const u32 *)p->dpos.p, (double *)p->fval.p});
     hipLaunchKernelGGL(iluam_gather_k, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const u32 *)p->lptr.p, (const u32 *)p->lpos.p,
                        (const u32 *)p->uptr.p, (const u32 *)p->upos.p, (const u32 *)p->dpos.p, (const u32 *)p->sched[S_BWD].order.p,
                        (const double *)p->fval.p, n,

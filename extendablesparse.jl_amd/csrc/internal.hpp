@@ -18,6 +18,8 @@
 //                  column: sorted row union, dense gather, modified Gram-Schmidt in LDS), M in an internal handle, ldiv! = esp_mul's gather
 //   iluk.hip       ILUKPreconditioner: the level-of-fill pattern by one bounded search per column (wave / workgroup form), the filled
 //                  matrix B in an internal handle, ILUAM on it
+//   ilut.hip       ILUTPreconditioner: the threshold ILU by synchronous sweeps (wave / workgroup / stride tiers of the sweep kernel),
+//                  the candidate pattern from esp_matmul, drop and compaction, F in an internal handle, ILUAM's prefactored mode on it
 //   amg.hip        AMGPreconditioner: smoothed aggregation (MIS(2) aggregates by Luby rounds, the level hierarchy from the algebra
 //                  calls on internal handles, the fused V-cycle kernels); amg.hpp holds what it shares with rsamg.hip
 //   rsamg.hip      RS_AMGPreconditioner's coarsening: row-wise strength, the PMIS splitting, direct interpolation (the rest is amg.hip's)
@@ -647,11 +649,24 @@ struct esp_precon {
     DevBuf spai_r, spai_half, spai_stat;  // the R slots of the workgroup tier (f64 spai_rgrid * spai_rslot), n halves, 8 status words
     i64 spai_rslot = 0, spai_rgrid = 0;
     i64 spai_stats[4] = {0, 0, 0, 0};     // max p, max q, max p*q, columns of the workgroup tier
+    // ILUAM's prefactored mode (iluam.hip): the handle's values ARE the factorization -- no factor schedule, no FactorOp
+    bool prefactored = false;
+    // ILUTPreconditioner (kind ESP_PRECON_ILUT, ilut.hip): der.bh holds the pattern S with the values F, der.inner its prefactored
+    // ILUAM.  Kept for the warm update (keep_pattern): the second value array of the sweeps, the position in A of every entry of S
+    // (NO_POS for fill), the diagonal positions, the columns of the workgroup / stride tier.  ilut_h: the work handles of the
+    // construction (state, candidates, L+I, U), scratch between updates
+    double ilut_tau = 0.0, ilut_max_fill = 0.0;
+    int ilut_steps = 0, ilut_sweeps = 0;
+    bool ilut_keep = false;
+    esp_handle *ilut_h[4] = {nullptr, nullptr, nullptr, nullptr};
+    DevBuf ilut_alt, ilut_apos, ilut_dpos, ilut_list;  // f64 nnz(S), u32 nnz(S), u32 n, u32 2 n
+    i64 ilut_tiers[2] = {0, 0};
+    i64 ilut_stats[ESP_ILUT_STATS] = {0};  // esp_precon_ilut_stats' layout
 };
 // the kinds that block.hip's builder, update! and ldiv! serve
 static inline bool block_built(const esp_precon *p) { return p->kind == ESP_PRECON_BLOCK || p->kind == ESP_PRECON_COLORED; }
 // the kinds that hold a derived matrix B and an inner preconditioner of it (esp_precon::Derived)
-static inline bool holds_derived(const esp_precon *p) { return block_built(p) || p->kind == ESP_PRECON_ILUK; }
+static inline bool holds_derived(const esp_precon *p) { return block_built(p) || p->kind == ESP_PRECON_ILUK || p->kind == ESP_PRECON_ILUT; }
 // ... whose next update! builds B anew (else: the values only)
 static inline bool derived_stale(const esp_precon *p) {
     return p->der.rebuild || p->pattern_version != p->h->pattern_version || p->nnz != p->h->nnz;
@@ -704,6 +719,11 @@ void block_release(esp_precon *p);
 // preconditioner and src are block_release's)
 int32_t iluk_update(esp_precon *p);
 void iluk_release(esp_precon *p);
+// ilut.hip: update! (derived_update over the construction; keep_pattern: its values-only branch is ilut_warm, s sweeps on the kept
+// pattern), release of the work handles and the sweep's buffers (F, the inner preconditioner: block_release's)
+int32_t ilut_update(esp_precon *p);
+int32_t ilut_warm(esp_precon *p);
+void ilut_release(esp_precon *p);
 // color.hip: update! (after a pattern change the colouring and the maps anew, then block_update; else block_update's value gather),
 // release of the colour arrays (B, the inner preconditioner and the maps are block_release's)
 int32_t color_update(esp_precon *p);

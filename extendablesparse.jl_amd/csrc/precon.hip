@@ -310,7 +310,7 @@ int32_t ldiv_launch(esp_precon *p, const double *v, double *u) {
     const i64 n = p->n;
     if (n == 0) return ESP_OK;
     if (block_built(p)) return block_ldiv_launch(p, v, u, false);
-    if (p->kind == ESP_PRECON_ILUK) return ldiv_launch(p->der.inner, v, u);  // ILUAM of B on the caller's vectors
+    if (p->kind == ESP_PRECON_ILUK || p->kind == ESP_PRECON_ILUT) return ldiv_launch(p->der.inner, v, u);  // ILUAM of B / over F on the caller's vectors
     if (p->kind == ESP_PRECON_ILUAM) return iluam_solve(p, v, u, false);
     if (p->kind == ESP_PRECON_AMG) return amg_solve(p, v, u, false);
     if (p->kind == ESP_PRECON_SPAI && p->spai_order != 0) return spai_apply(p, v, u, false);  // u = M*v
@@ -371,6 +371,7 @@ extern "C" int32_t esp_precon_update(esp_precon *p) {
     if (p->kind == ESP_PRECON_BLOCK) return block_update(p);  // B and the inner preconditioner (block.hip)
     if (p->kind == ESP_PRECON_AMG) return amg_update(p);      // the whole hierarchy (amg.hip)
     if (p->kind == ESP_PRECON_ILUK) return iluk_update(p);    // the filled matrix and the inner ILUAM (iluk.hip)
+    if (p->kind == ESP_PRECON_ILUT) return ilut_update(p);    // the pattern S, the values F and the inner prefactored ILUAM (ilut.hip)
     if (p->kind == ESP_PRECON_COLORED) return color_update(p);  // the colouring, A[c,c] and the inner preconditioner (color.hip)
     if (p->kind == ESP_PRECON_SPAI) return spai_update(p);      // the approximate inverse M (spai.hip)
     esp_handle *h = p->h;
@@ -422,6 +423,7 @@ extern "C" int32_t esp_precon_destroy(esp_precon *p) {
     (void)hipStreamSynchronize(h->stream);
     block_release(p);
     iluk_release(p);
+    ilut_release(p);
     color_release(p);
     spai_release(p);
     for (DevBuf *b : {&p->diag, &p->lptr, &p->uptr, &p->lcol, &p->ucol, &p->lpos, &p->upos, &p->dpos, &p->lval, &p->uval, &p->u1, &p->res,

@@ -26,14 +26,17 @@ ColoredPreconditioner(A, factorization) colours A's graph on the device (rounds 
 the reference's src/factorizations/parallel_ilu0.jl acting in A's numbering; graphcol, reordermatrix and reorderlinsys are its helpers.
 SPAIPreconditioner(A, order, symmetric) is the sparse approximate inverse SPAI-0 / SPAI-1 (esp_precon_spai_create): M ~ inv(A) on A's
 pattern from one small least-squares problem per column, ldiv! one sparse product -- bit-identical to tests/spai_model.c.
-AMGCL_RLXPreconditioner(A, type="spai0" | "spai1") is the reference-named constructor over it (ext/ExtendableSparseAMGCLWrapExt.jl).
+AMGCL_RLXPreconditioner(A, type="spai0" | "spai1" | "ilut") is the reference-named constructor over it (ext/ExtendableSparseAMGCLWrapExt.jl).
+ILUTPreconditioner(A, droptol, steps, sweeps, max_fill, keep_pattern) is the threshold ILU (ext/ExtendableSparseIncompleteLUExt.jl) as
+synchronous sweeps with candidates and drops between them (esp_precon_ilut_create), applied by ILUAM's solves -- bit-identical to
+tests/ilut_model.c.
 """
 import ctypes as C
 import math
 
 import numpy as np
 
-from ._lib import ESP_ORTH_CGS, ESP_ORTH_DGKS, ESP_ORTH_MGS, ESP_PRECON_AMG, ESP_PRECON_BLOCK, ESP_PRECON_COLORED, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_ILUK, ESP_PRECON_JACOBI, ESP_PRECON_SPAI
+from ._lib import ESP_ORTH_CGS, ESP_ORTH_DGKS, ESP_ORTH_MGS, ESP_PRECON_AMG, ESP_PRECON_BLOCK, ESP_PRECON_COLORED, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_ILUK, ESP_PRECON_ILUT, ESP_PRECON_JACOBI, ESP_PRECON_SPAI
 from .matrix import ExtendableSparseMatrix, _vp
 
 
@@ -463,12 +466,64 @@ class SPAIPreconditioner(_PointPreconditioner):
         return {"max_p": int(out[0]), "max_q": int(out[1]), "max_pq": int(out[2]), "wide": int(out[3])}
 
 
+class ILUTPreconditioner(_ILUAMFactors, _PointPreconditioner):
+    """ILUTPreconditioner(A, droptol=1e-3, steps=3, sweeps=3, max_fill=32.0, keep_pattern=False): the threshold ILU
+    (ext/ExtendableSparseIncompleteLUExt.jl; include/esparse_hip.h, esp_precon_ilut_create).  The factorization is the fixed point of
+    l_ij = (a_ij - sum l_ik u_kj)/u_jj, u_ij = a_ij - sum l_ik u_kj; every entry is updated at once from the previous values
+    (`sweeps` sweeps per phase), and each of the `steps` rounds adds the positions of pattern(L*U) as candidates, sweeps, drops every
+    l_ij with |l_ij| < droptol and every u_ij with |u_ij| < droptol*|u_ii|, and sweeps again.  The set-up has no sequential dependency;
+    ldiv is ILUAMPreconditioner's level-scheduled solves over the result.  max_fill bounds the candidates (times nnz(A)): beyond it
+    the update raises and the previous factorization stays.  update() repeats the construction -- the pattern depends on the values --
+    unless keep_pattern is set and A's pattern is unchanged: then the pattern and every index stay, and `sweeps` sweeps start from
+    the current factors and A's new values (a Newton step's update).  DEVIATION from IncompleteLU.jl: its drop rule measures against
+    the norms of A's rows and columns inside a sequential elimination."""
+    KIND = ESP_PRECON_ILUT
+
+    def __init__(self, A, droptol=1e-3, steps=3, sweeps=3, max_fill=32.0, keep_pattern=False):
+        if not isinstance(A, ExtendableSparseMatrix):
+            raise TypeError("ILUTPreconditioner(A, ...): A must be an ExtendableSparseMatrix")
+        if not float(droptol) >= 0.0:
+            raise ValueError("ILUTPreconditioner: droptol = %r (>= 0)" % (droptol,))
+        if int(steps) != steps or not 0 <= steps <= 16:
+            raise ValueError("ILUTPreconditioner: steps = %r (an integer in 0..16)" % (steps,))
+        if int(sweeps) != sweeps or not 1 <= sweeps < 2 ** 31:
+            raise ValueError("ILUTPreconditioner: sweeps = %r (an integer >= 1)" % (sweeps,))
+        if not float(max_fill) >= 1.0:
+            raise ValueError("ILUTPreconditioner: max_fill = %r (>= 1)" % (max_fill,))
+        self.droptol, self.steps, self.sweeps = float(droptol), int(steps), int(sweeps)
+        self.max_fill, self.keep_pattern = float(max_fill), bool(keep_pattern)
+        self._bind(A, "esp_precon_ilut_create", C.c_double(self.droptol), self.steps, self.sweeps, C.c_double(self.max_fill),
+                   int(self.keep_pattern))
+
+    def _factored(self):
+        f = C.c_void_p()
+        self._ck(self.A._d.lib.esp_precon_ilut_matrix(self._live(), C.byref(f)))
+        return f
+
+    def matrix(self):
+        """the pattern S with the factors F as host CSC arrays (colptr, rowval, nzval), Julia layout: the scaled unit-lower L below
+        the diagonal, U on and above it -- for tests and inspection"""
+        return self._host_csc(self._factored(), self.A.n)
+
+    def stats(self):
+        """dict: nnz (of S), sweeps (run by the last update), steps: [(nnz(C), nnz(S)) of every step], wave / group / stride: the
+        columns of S each tier of the sweep kernel serves"""
+        out = (C.c_int64 * 40)()
+        self._ck(self.A._d.lib.esp_precon_ilut_stats(self._live(), out))
+        return {"nnz": int(out[5]), "sweeps": int(out[1]), "steps": [(int(out[8 + 2 * t]), int(out[9 + 2 * t])) for t in range(int(out[0]))],
+                "wave": int(out[2]), "group": int(out[3]), "stride": int(out[4])}
+
+
 def AMGCL_RLXPreconditioner(A, type="spai0"):
     """AMGCL_RLXPreconditioner(A; type) (ext/ExtendableSparseAMGCLWrapExt.jl): the relaxation preconditioners of AMGCL.  On the
-    device: "spai0" and "spai1", as SPAIPreconditioner(A, order=0 / 1)."""
+    device: "spai0" and "spai1", as SPAIPreconditioner(A, order=0 / 1), and "ilut", as ILUTPreconditioner(A) with its defaults --
+    whose drop rule (|l_ij| < droptol, |u_ij| < droptol*|u_ii|, between parallel sweeps) is not AMGCL's (the p largest entries of a
+    row above tau times the row's norm, inside a sequential elimination)."""
     orders = {"spai0": 0, "spai1": 1}
+    if type == "ilut" and isinstance(A, ExtendableSparseMatrix):
+        return ILUTPreconditioner(A)
     if type not in orders:
-        raise NotImplementedError("AMGCL_RLXPreconditioner: type = %r is not on the device; \"spai0\" and \"spai1\" are" % (type,))
+        raise NotImplementedError("AMGCL_RLXPreconditioner: type = %r is not on the device; \"spai0\", \"spai1\" and \"ilut\" are" % (type,))
     return SPAIPreconditioner(A, order=orders[type])
 
 

@@ -458,8 +458,8 @@ int32_t esp_precon_rsamg_create(esp_handle *h, int32_t max_levels, int32_t max_c
 int32_t esp_precon_amg_coarsening(esp_precon *p, int32_t *kind);
 int32_t esp_precon_amg_splitting(esp_precon *p, int32_t level, int64_t *cf, int32_t on_device);
 /* ILUKPreconditioner: the level-of-fill ILU(k), the dialable member of the ILU family (the reference's own dial is the threshold
- * ILUTPreconditioner, docs/src/iter.md, whose pattern depends on the values and whose elimination is sequential; ILU(k)'s pattern
- * depends on the structure alone).  Indices 0-based: lev(i,j) = 0 where A stores (i,j) -- a stored 0.0, -0.0 or NaN counts -- and
+ * ILUTPreconditioner, docs/src/iter.md, whose pattern depends on the values and whose elimination is sequential -- see
+ * esp_precon_ilut_create below for its form by parallel sweeps; ILU(k)'s pattern depends on the structure alone).  Indices 0-based: lev(i,j) = 0 where A stores (i,j) -- a stored 0.0, -0.0 or NaN counts -- and
  * infinite elsewhere; for i = 0..n-1, for k < i in increasing order with lev(i,k) <= K, for j > k with lev(k,j) <= K:
  * lev(i,j) = min(lev(i,j), lev(i,k) + lev(k,j) + 1).  B holds every position with lev <= K: A's bits where lev = 0, +0.0 elsewhere,
  * rows ascending in every column.  esp_precon_iluk_create(h, k) is esp_precon_create(B, ESP_PRECON_ILUAM): ILU(k) of A is ILU(0) of B,
@@ -591,6 +591,56 @@ int32_t esp_precon_colored_matrix(esp_precon *p, esp_handle **b);
 int32_t esp_precon_spai_create(esp_handle *h, int32_t order, int32_t symmetric, esp_precon **out);
 int32_t esp_precon_spai_matrix(esp_precon *p, esp_handle **m);
 int32_t esp_precon_spai_stats(esp_precon *p, int64_t out[4]);
+/* ILUTPreconditioner (ext/ExtendableSparseIncompleteLUExt.jl; docs/src/iter.md builds ILUTPreconditioner(; droptol = 1.0e-2)): a
+ * threshold ILU.  IncompleteLU.jl is not part of the reference tree and its row-by-row elimination is sequential with a pattern that
+ * depends on the values, so the algorithm here is stated in full: the ParILUT family of Anzt, Chow and Dongarra --
+ * the factorization as the fixed point of l_ij = (a_ij - sum_{k<j} l_ik u_kj)/u_jj, u_ij = a_ij - sum_{k<i} l_ik u_kj, every entry
+ * updated at once from the previous values, candidates added and small entries dropped between sweeps.  tests/ilut_model.c restates
+ * it entry by entry and is normative; the device result is bit-identical to it.
+ *   state   A is n x n and stores every diagonal entry (a stored 0.0, -0.0 or NaN counts).  A pattern S containing the diagonal and
+ *           values F on it: strictly below the diagonal the unit-lower L, scaled; on and above it U; rows ascending in every column.
+ *   init    S = pattern(A); u_ij = a_ij for i <= j, l_ij = a_ij / a_jj for i > j.
+ *   sweep   on a pattern P, synchronous (F_old read, F_new written): for every (i,j) in P, r = a_ij (+0.0 where A stores nothing);
+ *           for every k < min(i,j) with (i,k) and (k,j) in P, k increasing: r = r - l_ik*u_kj (the product rounded first, no fused
+ *           multiply-add); then l_ij = r / u_jj(old) for i > j, u_ij = r for i <= j.
+ *   step    1. C = pattern((L+I)*U), structural (it contains S); 2. F carried to C, +0.0 at the new positions; 3. nnz(C) >
+ *           (int64)(max_fill*nnz(A)) -> ESP_ERR_UNSUPPORTED (esp_last_error names the step and both counts; the preconditioner stays
+ *           as its last good update! made it); 4. `sweeps` sweeps on C; 5. every off-diagonal (i,j) is dropped for which
+ *           fabs(l_ij) < droptol is true (i > j) or fabs(u_ij) < droptol*fabs(u_ii) is true (i < j) -- a NaN is kept, positions A
+ *           stores are droppable like any other, the diagonal never goes; 6. S = what is left; 7. `sweeps` sweeps on S.
+ *   esp_precon_ilut_create runs init and `steps` steps (steps = 0: `sweeps` sweeps on pattern(A)).  The upper part is measured against
+ *   its row's pivot so that for symmetric A the rule is symmetric (u_ij/u_ii = l_ji at the fixed point).  On a fixed pattern the
+ *   values stop changing after at most 2n sweeps, and the fixed point is bit for bit ILUAM's factorization of the matrix holding A's
+ *   values on the pattern and +0.0 elsewhere (the subtraction order is iluAM's).  DEVIATION from IncompleteLU.jl's ilu(A; tau):
+ *   that rule drops against tau times the norm of A's column or row during a sequential elimination.
+ * ldiv! is ILUAM's forward and backward level-scheduled solve over (S, F) on the caller's vectors (u may be v; no further launch,
+ * copy or scratch); esp_simple, esp_cg, esp_bicgstabl and esp_gmres take it as they take ILUAM.  esp_precon_get_factor gives F
+ * (nnz(S) values in S's position order), esp_precon_levels the forward and backward level counts (the factor schedule does not
+ * exist: 0).
+ * esp_precon_update: after a pattern change of A, and with keep_pattern == 0 always (S depends on the values), the whole
+ * construction.  With A's pattern kept and keep_pattern != 0: S and every index structure stay, F starts from its CURRENT values,
+ * A's new values are read and `sweeps` sweeps run on S (the state is carried by the model too, so any sequence of updates is
+ * defined).  A pattern change of A without update! -> ESP_ERR_STATE from ldiv! and the solvers.
+ * The sweep kernel serves a column with one wave while at most ESP_ILUT_WAVE_UPPER rows lie above its diagonal (they are staged in
+ * LDS), with one workgroup up to ESP_ILUT_GROUP_UPPER, and by lanes striding the column in global memory beyond: no column is
+ * refused.  esp_precon_ilut_limits: out = ESP_ILUT_WAVE_UPPER, ESP_ILUT_GROUP_UPPER, ESP_ILUT_STEPS_MAX, ESP_ILUT_STATS.
+ * esp_precon_ilut_matrix: the internal handle holding S with F as its values, borrowed and read-only (esp_get_csc / esp_nnz).
+ * esp_precon_ilut_stats: out[0] = steps, out[1] = the sweeps the last update! ran, out[2..4] = the columns of S the wave / workgroup /
+ * stride tier serves, out[5] = nnz(S), out[8 + 2 t], out[9 + 2 t] = nnz(C), nnz(S) of step t (the rest 0).
+ * ESP_ERR_INVALID: droptol < 0 or NaN, steps < 0 or > ESP_ILUT_STEPS_MAX, sweeps < 1, max_fill < 1 or NaN, a rectangular matrix, a
+ * column without a stored diagonal.  ESP_ERR_STATE: pending entries.  ESP_ERR_UNSUPPORTED: a column window / column shard on h; the
+ * fill guard; n or nnz >= 2^32 - 16.  ILUT is no inner kind of esp_precon_block_create or esp_precon_colored_create.  A live
+ * preconditioner makes h refuse esp_destroy; esp_precon_destroy releases F, the work handles and every buffer. */
+#define ESP_PRECON_ILUT 8
+#define ESP_ILUT_WAVE_UPPER 256
+#define ESP_ILUT_GROUP_UPPER 4096
+#define ESP_ILUT_STEPS_MAX 16
+#define ESP_ILUT_STATS 40
+int32_t esp_precon_ilut_create(esp_handle *h, double droptol, int32_t steps, int32_t sweeps, double max_fill, int32_t keep_pattern,
+                               esp_precon **out);
+int32_t esp_precon_ilut_matrix(esp_precon *p, esp_handle **f);
+int32_t esp_precon_ilut_stats(esp_precon *p, int64_t out[ESP_ILUT_STATS]);
+int32_t esp_precon_ilut_limits(int64_t out[4]);
 /* simple!(u, A, b; abstol, reltol, maxiter, Pl = p) (src/factorizations/simple_iteration.jl:21-45) statement by
  * statement: res = A*u - b; then per step ldiv!(upd, Pl, res), u .-= upd, mul!(res, A, u), res .-= b, r = norm(res),
  * stop when (r / r0) < reltol || r < abstol (literally: r0 = 0 gives NaN or Inf there).  u (in/out) is bit-identical to

@@ -91,6 +91,14 @@ fdrand(n,n,n): setup_ms (create), update_ms (values-only update!), ldiv_ms besid
 ILU0 and ColoredPreconditioner (--inner) from the same run beside it.
 
     python tools/precon_bench.py --kind spai1sym [--n 64] [--iters 20] [--rounds 5] [--tol-maxiter 20000]
+
+--kind ilut [--droptol T --steps S --sweeps W] times ILUTPreconditioner (esp_precon_ilut_create) on fdrand(n,n,n) beside ILU0, ILUAM
+and ILU(1) from the same run, the creates alternated round by round: set-up (create), update (update! without keep_pattern: the
+construction again), warm update (keep_pattern: the sweeps alone) and one sweep (the difference of two warm updates that differ by
+four sweeps, beside the bytes the sweep must move at least), nnz(F)/nnz(A), the level counts, ldiv!, and cg / gmres(restart = 20) to
+reltol 1e-8 on b = ones (iterations and time).
+
+    python tools/precon_bench.py --kind ilut --droptol 1e-2 [--n 64] [--iters 20] [--rounds 5] [--tol-maxiter 20000]
 """
 import argparse
 import ctypes as C
@@ -848,6 +856,89 @@ def bench_iluk(a, torch, esp):
     print(json.dumps(rnd(out)))
 
 
+def bench_ilut(a, torch, esp):
+    import numpy as np
+    A = esp.fdrand(a.n, a.n, a.n)
+    d = A._d
+    stream = torch.cuda.current_stream()
+    d.ck(d.lib.esp_set_stream(d.h, C.c_void_p(stream.cuda_stream)))
+    N, Z = A.n, A.nnz()
+    v = torch.randn(N, dtype=torch.float64, device="cuda")
+    u = torch.empty_like(v)
+    b = torch.ones_like(v)
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()                                   # (create, update!, ldiv! and the solvers return synchronised)
+        return (time.perf_counter() - t0) * 1e3, r
+
+    def median(xs):
+        return float(np.median(xs))
+
+    par = dict(droptol=a.droptol, steps=a.steps, sweeps=a.sweeps)
+    makes = {"ilu0": esp.ILU0Preconditioner, "iluam": esp.ILUAMPreconditioner, "iluk1": lambda M: esp.ILUKPreconditioner(M, 1),
+             "ilut": lambda M: esp.ILUTPreconditioner(M, **par)}
+    Pw = esp.ILU0Preconditioner(A)     # builds the row-wise index esp_mul shares, so that the creates below are their own
+    Pw.close()
+    creates = {k: [] for k in makes}
+    for _ in range(a.rounds):          # alternated: one create of every kind per round
+        for k, make in makes.items():
+            t, P = wall(lambda: make(A))
+            creates[k].append(t)
+            P.close()
+    out = {"workload": "ilut_fdrand", "n": a.n, "N": N, "nnz": Z, "rounds": a.rounds, **par}
+    for k, make in makes.items():
+        P = make(A)
+        rec = {"create_ms": median(creates[k]), "create_min_max": [min(creates[k]), max(creates[k])]}
+        rec["update_ms"] = median([wall(P.update)[0] for _ in range(a.rounds)])
+        for _ in range(3):
+            P.ldiv(v, out=u)
+        rec["ldiv_ms"] = median([wall(lambda: [P.ldiv(v, out=u) for _ in range(a.iters)])[0] / a.iters for _ in range(a.rounds)])
+        if hasattr(P, "levels"):
+            rec["levels"] = list(P.levels())
+        for name, fn in (("gmres", lambda: esp.gmres(A, b, Pl=P, restart=20, reltol=1e-8, maxiter=a.tol_maxiter, log=True)),
+                         ("cg", lambda: esp.cg(A, b, Pl=P, reltol=1e-8, maxiter=a.tol_maxiter, log=True))):
+            fn()
+            ts, log = [], None
+            for _ in range(a.rounds):
+                t, (_, log) = wall(fn)
+                ts.append(t)
+            rec[name] = {"iterations": log["iters"], "converged": log["isconverged"], "ms": median(ts)}
+        if k == "iluk1":
+            rec["fill_ratio"] = P.stats()["nnz"] / Z
+        if k == "ilut":
+            st = P.stats()
+            rec["stats"] = st
+            rec["fill_ratio"] = st["nnz"] / Z
+            rec["candidate_ratio"] = max([c for c, _ in st["steps"]] + [Z]) / Z
+            # every array of the sweep once: rows, apos, old and new values, the row-wise index; A's values; per column pointers
+            rec["sweep_bytes_min"] = st["nnz"] * (8 + 4 + 8 + 8 + 4 + 4) + Z * 8 + N * (8 + 4 + 8)
+        P.close()
+        out[k] = rec
+    W1 = esp.ILUTPreconditioner(A, keep_pattern=True, **par)
+    W5 = esp.ILUTPreconditioner(A, keep_pattern=True, **dict(par, sweeps=a.sweeps + 4))
+    t1, t5 = [], []
+    for _ in range(a.rounds):          # alternated as well
+        t1.append(wall(W1.update)[0])
+        t5.append(wall(W5.update)[0])
+    out["ilut"]["warm_update_ms"] = median(t1)
+    out["ilut"]["sweep_ms"] = (median(t5) - median(t1)) / 4
+    out["ilut"]["sweep_nnz"] = W5.stats()["nnz"]
+    W1.close()
+    W5.close()
+
+    def rnd(x):
+        if isinstance(x, float):
+            return round(x, 4)
+        if isinstance(x, dict):
+            return {k: rnd(y) for k, y in x.items()}
+        if isinstance(x, list):
+            return [rnd(y) for y in x]
+        return x
+    print(json.dumps(rnd(out)))
+
+
 def bench_colored(a, torch, esp):
     import numpy as np
     A = esp.fdrand(a.n, a.n, a.n)
@@ -993,7 +1084,10 @@ def main():
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "gmres", "gmres-trace", "block", "block-trace", "block-trace-diff", "amg", "iluk", "colored", "spai0", "spai1", "spai1sym"], default="point")
+    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "gmres", "gmres-trace", "block", "block-trace", "block-trace-diff", "amg", "iluk", "colored", "spai0", "spai1", "spai1sym", "ilut"], default="point")
+    ap.add_argument("--droptol", type=float, default=1e-3)
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--sweeps", type=int, default=3)
     ap.add_argument("--inner", choices=["ilu0", "iluam"], default="iluam")
     ap.add_argument("--k", type=int, default=1)
     ap.add_argument("--rounds", type=int, default=5)
@@ -1032,6 +1126,8 @@ def main():
         return bench_block_trace(a, torch, esp)
     if a.kind == "iluk":
         return bench_iluk(a, torch, esp)
+    if a.kind == "ilut":
+        return bench_ilut(a, torch, esp)
     if a.kind == "amg":
         return bench_amg(a, torch, esp)
     if a.kind == "colored":
