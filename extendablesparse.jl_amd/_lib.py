@@ -22,6 +22,7 @@ ESP_PRECON_ILUK = 5
 ESP_PRECON_COLORED = 6
 ESP_PRECON_SPAI = 7
 ESP_PRECON_ILUT = 8
+ESP_PRECON_LU = 9
 ESP_ILUT_WAVE_UPPER, ESP_ILUT_GROUP_UPPER, ESP_ILUT_STEPS_MAX, ESP_ILUT_STATS = 256, 4096, 16, 40
 ESP_ILUK_WAVE_VISITS, ESP_ILUK_VISIT_MAX = 512, 8192
 ESP_SPAI_WAVE_DOUBLES, ESP_SPAI_DENSE_MAX = 512, 12288
@@ -142,6 +143,13 @@ SIGNATURES = {
     "esp_precon_ilut_matrix": (i32, [vp, P(vp)]),
     "esp_precon_ilut_stats": (i32, [vp, P(i64)]),
     "esp_precon_ilut_limits": (i32, [P(i64)]),
+    "esp_precon_lu_create": (i32, [vp, i32, i32, P(vp)]),
+    "esp_precon_lu_perm": (i32, [vp, vp, i32]),
+    "esp_precon_lu_tree": (i32, [vp, vp, vp, i32]),
+    "esp_precon_lu_matrix": (i32, [vp, P(vp)]),
+    "esp_precon_lu_stats": (i32, [vp, P(i64)]),
+    "esp_nested_dissection": (i32, [vp, i32, i32, vp, vp, i32]),
+    "esp_debug_lu_fill_cap": (i32, [vp, i64]),
     "esp_simple": (i32, [vp, vp, vp, vp, i32, i64, f64, f64, vp, P(i64)]),
     "esp_cg": (i32, [vp, vp, vp, vp, i32, i32, i64, f64, f64, vp, P(i64), P(i32)]),
     "esp_bicgstabl": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i64, f64, f64, vp, P(i64), P(i64), P(i32)]),

@@ -121,6 +121,53 @@ struct FactorOp {
         for (i64 v = d + 1; v < ce; v++) fval[v] = fval[v] / piv;
     }
 };
+// The same column by a whole wave, for matrices whose columns are long (the filled matrices of ILU(k) and LUFactorization: a dense
+// front of m columns costs one lane m*m*m/3 dependent steps).  The positions v above the diagonal stay one after the other -- a
+// later one may read what an earlier one wrote --, but the updates of one v go to distinct positions k of column j: the lanes take
+// the rows w of column i below its diagonal 64 at a time and find k by bisection among the rows of column j behind v (staged in LDS
+// while the column holds at most FW_ROWS rows).  Every fval[k] meets the same operands in the same order as in FactorOp: the same
+// bits.  Between two v the wave's stores are made visible to its own lanes by a workgroup-scope fence.
+constexpr int FW_ROWS = 2048;   // rows of column j a wave stages in LDS (as u32: 8 KiB per wave)
+constexpr int FW_MIN_AVG = 24;  // the wave form serves a matrix with at least this many entries per column on average
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+struct FactorWaveOp {
+    const u32 *order;
+    const i64 *colptr, *rowval;
+    const u32 *dpos;
+    double *fval;
+    __device__ __forceinline__ void operator()(u32 slot, u32 *srow) const {
+        const int lane = threadIdx.x & 63;
+        const u32 j = order[slot];
+        const i64 cb = colptr[j] - 1, ce = colptr[j + 1] - 1, d = dpos[j], len = ce - cb;
+        const bool staged = len <= (i64)FW_ROWS;
+        if (staged)
+            for (i64 t = lane; t < len; t += 64) srow[t] = (u32)rowval[cb + t];
+        wave_sync();
+        for (i64 v = cb; v < d; v++) {
+            const i64 i = rowval[v] - 1;
+            const double a = fval[v];
+            const i64 we = colptr[i + 1] - 1;
+            for (i64 w = (i64)dpos[i] + 1 + lane; w < we; w += 64) {
+                const i64 r = rowval[w];
+                i64 lo = v + 1 - cb, hi = len;  // the first row of column j behind v that is not below r
+                while (lo < hi) {
+                    const i64 mid = lo + ((hi - lo) >> 1);
+                    const i64 rm = staged ? (i64)srow[mid] : rowval[cb + mid];
+                    if (rm < r) lo = mid + 1;
+                    else hi = mid;
+                }
+                if (lo < len && (staged ? (i64)srow[lo] : rowval[cb + lo]) == r) fval[cb + lo] = fval[cb + lo] - a * fval[w];
+            }
+            wave_sync();
+        }
+        const double piv = fval[d];
+        for (i64 v = d + 1 + lane; v < ce; v += 64) fval[v] = fval[v] / piv;
+    }
+};
 // forward row: y[i] = ((0 - l*y[j1]) - l*y[j2] - ...) + b[i].  The row parts lie in SLOT order (permute_part): the lanes
 // of a level read one contiguous slice of pointers, columns and values.
 struct ForwardOp {
@@ -167,6 +214,29 @@ __global__ __launch_bounds__(LT) void level_thin_k(Op op, const u32 *__restrict_
         const u32 b = loff[l], e = loff[l + 1];
         if (b + threadIdx.x < e) op(b + threadIdx.x);
         __syncthreads();
+    }
+}
+// the wave form: a wave per member (a wide level: LT / 64 members per workgroup; a thin launch: the waves of the one workgroup take
+// the members of a level in turn)
+__global__ __launch_bounds__(LT) void factor_wave_wide_k(FactorWaveOp op, u32 first, u32 count) {
+    __shared__ u32 srow[LT / 64][FW_ROWS];
+    const u32 w = blockIdx.x * (LT / 64) + (threadIdx.x >> 6);
+    if (w < count) op(first + w, srow[threadIdx.x >> 6]);
+}
+__global__ __launch_bounds__(LT) void factor_wave_thin_k(FactorWaveOp op, const u32 *__restrict__ loff, u32 l0, u32 l1) {
+    __shared__ u32 srow[LT / 64][FW_ROWS];
+    for (u32 l = l0; l < l1; l++) {
+        const u32 b = loff[l], e = loff[l + 1];
+        for (u32 m = b + (threadIdx.x >> 6); m < e; m += LT / 64) op(m, srow[threadIdx.x >> 6]);
+        __syncthreads();
+    }
+}
+void run_factor_waves(const esp_precon *p, const IluamSched &s, const FactorWaveOp &op) {
+    for (const IluamLaunch &L : s.launches) {
+        if (L.thin)
+            hipLaunchKernelGGL(factor_wave_thin_k, dim3(1), dim3(LT), 0, p->h->stream, op, (const u32 *)s.loff.p, L.l0, L.l1);
+        else
+            hipLaunchKernelGGL(factor_wave_wide_k, dim3(grid_for(L.count, LT / 64)), dim3(LT), 0, p->h->stream, op, L.first, L.count);
     }
 }
 template <class Op>
@@ -365,7 +435,9 @@ int32_t iluam_update(esp_precon *p, bool rebuild) {
     CK(ensure(h, p->fval, sizeof(double) * (size_t)std::max<i64>(h->nnz, 1)));
     if (n == 0) return ESP_OK;
     HIPCK(h, hipMemcpyAsync(p->fval.p, h->nzval.p, sizeof(double) * (size_t)h->nnz, hipMemcpyDeviceToDevice, h->stream));
-    if (!p->prefactored)
+    if (!p->prefactored && h->nnz >= (i64)FW_MIN_AVG * n)
+        run_factor_waves(p, p->sched[S_FACTOR], FactorWaveOp{(const u32 *)p->sched[S_FACTOR].order.p, (const i64 *)h->colptr.p, (const i64 *)h->rowval.p, (const u32 *)p->dpos.p, (double *)p->fval.p});
+    else if (!p->prefactored)
         run_schedule(p, p->sched[S_FACTOR], FactorOp{(const u32 *)p->sched[S_FACTOR].order.p, (const i64 *)h->colptr.p, (const i64 *)h->rowval.p, (const u32 *)p->dpos.p, (double *)p->fval.p});
     hipLaunchKernelGGL(iluam_gather_k, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const u32 *)p->lptr.p, (const u32 *)p->lpos.p,
                        (const u32 *)p->uptr.p, (const u32 *)p->upos.p, (const u32 *)p->dpos.p, (const u32 *)p->sched[S_BWD].order.p,

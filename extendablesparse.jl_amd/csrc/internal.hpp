@@ -18,6 +18,8 @@
 //                  column: sorted row union, dense gather, modified Gram-Schmidt in LDS), M in an internal handle, ldiv! = esp_mul's gather
 //   iluk.hip       ILUKPreconditioner: the level-of-fill pattern by one bounded search per column (wave / workgroup form), the filled
 //                  matrix B in an internal handle, ILUAM on it
+//   lu.hip         LUFactorization: the nested-dissection ordering by level-synchronous component and search launches, the supernodal
+//                  symbolic fill from the dissection tree, the filled reordered matrix B with ILUAM as the inner kind
 //   ilut.hip       ILUTPreconditioner: the threshold ILU by synchronous sweeps (wave / workgroup / stride tiers of the sweep kernel),
 //                  the candidate pattern from esp_matmul, drop and compaction, F in an internal handle, ILUAM's prefactored mode on it
 //   amg.hip        AMGPreconditioner: smoothed aggregation (MIS(2) aggregates by Luby rounds, the level hierarchy from the algebra
@@ -93,6 +95,7 @@ struct esp_handle {
     bool hits_off = false;                // the re-assembly form of the group kernel met a batch that was no re-assembly of the stored pattern: not tried again (until reset!)
     bool g3_wide = false;                 // ... for its rows alone (spread over more than 2^18): the kernel's wide form serves this handle
     bool debug_fail_bucket = false;       // esp_debug_fail_next_bucket_stage (test hook, one shot)
+    i64 debug_lu_cap = 0;                 // esp_debug_lu_fill_cap: LUFactorization refuses nnz(B) >= this (test hook; 0: the 32-bit limit)
     double debug_plan_cap = 0.0;          // esp_debug_plan_cap: plan as if the bucket kernel took segments of this many entries (test hook)
     int last_group3 = 0;                  // the last flush's bucket kernel was group3_k (esp_debug_last_local_small reports 2)
     bool seen_hits = true;                // the last flush over a stored pattern mostly hit stored positions (re-assembly)
@@ -662,9 +665,18 @@ struct esp_precon {
     DevBuf ilut_alt, ilut_apos, ilut_dpos, ilut_list;  // f64 nnz(S), u32 nnz(S), u32 n, u32 2 n
     i64 ilut_tiers[2] = {0, 0};
     i64 ilut_stats[ESP_ILUT_STATS] = {0};  // esp_precon_ilut_stats' layout
+    // LUFactorization (kind ESP_PRECON_LU, lu.hip): the nested-dissection ordering c of A's graph, B = the reordered matrix with the
+    // complete fill of its elimination tree (A's bits where stored, +0.0 elsewhere: der.src holds ILUK_FILL there), inner its ILUAM
+    // preconditioner -- the exact LU without pivoting.  ldiv! is the permuted path of block.hip: blk_new = the inverse of c, blk_path = 1
+    // (0 only for n == 0).  A pattern change of A orders anew before B is rebuilt.
+    int lu_leaf = 32, lu_depth = 48;
+    DevBuf lu_perm, lu_level, lu_root;  // u32 n each: c, the depth every vertex was placed at, the root vertex naming its tree node
+    i64 lu_stats[6] = {0, 0, 0, 0, 0, 0};  // esp_precon_lu_stats' layout
 };
-// the kinds that block.hip's builder, update! and ldiv! serve
-static inline bool block_built(const esp_precon *p) { return p->kind == ESP_PRECON_BLOCK || p->kind == ESP_PRECON_COLORED; }
+// the kinds that block.hip's ldiv! serves (Block and Colored: its builder and update! too; LU builds B itself)
+static inline bool block_built(const esp_precon *p) {
+    return p->kind == ESP_PRECON_BLOCK || p->kind == ESP_PRECON_COLORED || p->kind == ESP_PRECON_LU;
+}
 // the kinds that hold a derived matrix B and an inner preconditioner of it (esp_precon::Derived)
 static inline bool holds_derived(const esp_precon *p) { return block_built(p) || p->kind == ESP_PRECON_ILUK || p->kind == ESP_PRECON_ILUT; }
 // ... whose next update! builds B anew (else: the values only)
@@ -728,6 +740,10 @@ void ilut_release(esp_precon *p);
 // release of the colour arrays (B, the inner preconditioner and the maps are block_release's)
 int32_t color_update(esp_precon *p);
 void color_release(esp_precon *p);
+// lu.hip: update! (derived_update over the ordering, the tree and the filled matrix), release of the ordering's arrays (B, the inner
+// preconditioner, src and the inverse permutation are block_release's)
+int32_t lu_update(esp_precon *p);
+void lu_release(esp_precon *p);
 // spai.hip: update! (after a pattern change the size pass, the tiers and M anew; else the numeric kernels alone), M's handles moved
 // to the stream A runs on, ldiv! of order 1 on device vectors (u may be v; sub: u[i] = u[i] - x[i], simple!'s step; launches and at
 // most one copy on the handle's stream), release of the handles and buffers

@@ -374,6 +374,7 @@ extern "C" int32_t esp_precon_update(esp_precon *p) {
     if (p->kind == ESP_PRECON_ILUT) return ilut_update(p);    // the pattern S, the values F and the inner prefactored ILUAM (ilut.hip)
     if (p->kind == ESP_PRECON_COLORED) return color_update(p);  // the colouring, A[c,c] and the inner preconditioner (color.hip)
     if (p->kind == ESP_PRECON_SPAI) return spai_update(p);      // the approximate inverse M (spai.hip)
+    if (p->kind == ESP_PRECON_LU) return lu_update(p);          // the ordering, the filled matrix and the inner ILUAM (lu.hip)
     esp_handle *h = p->h;
     CK(check_handle(h, "esp_precon_update"));
     p->n = h->n;
@@ -426,6 +427,7 @@ extern "C" int32_t esp_precon_destroy(esp_precon *p) {
     ilut_release(p);
     color_release(p);
     spai_release(p);
+    lu_release(p);
     for (DevBuf *b : {&p->diag, &p->lptr, &p->uptr, &p->lcol, &p->ucol, &p->lpos, &p->upos, &p->dpos, &p->lval, &p->uval, &p->u1, &p->res,
                       &p->partial, &p->scanws, &p->hv, &p->hu})
         release(*b);

@@ -620,6 +620,17 @@ class ExtendableSparseMatrix:
         d.ck(d.lib.esp_mul(d.h, _vp(x), _vp(r), 0))
         return r
 
+    def solve(self, b):
+        """A \\ b (abstractextendablesparsematrixcsc.jl: `\\` of a square matrix; test/test_backslash.jl): a one-shot
+        LUFactorization(A).solve(b) on the device, closed afterwards.  b: a NumPy array or a CUDA torch tensor; the result lives
+        where b does."""
+        from .precon import LUFactorization   # (precon.py imports this module)
+        f = LUFactorization(self)
+        try:
+            return f.solve(b)
+        finally:
+            f.close()
+
     def copy(self):
         """Base.copy(ext) (extendable.jl:279-285): CSC, pending entries and phash are copied."""
         self._push_edits()

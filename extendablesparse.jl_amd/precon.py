@@ -30,13 +30,17 @@ AMGCL_RLXPreconditioner(A, type="spai0" | "spai1" | "ilut") is the reference-nam
 ILUTPreconditioner(A, droptol, steps, sweeps, max_fill, keep_pattern) is the threshold ILU (ext/ExtendableSparseIncompleteLUExt.jl) as
 synchronous sweeps with candidates and drops between them (esp_precon_ilut_create), applied by ILUAM's solves -- bit-identical to
 tests/ilut_model.c.
+LUFactorization(A, leaf_size, max_depth) (= SparspakLU; lu, lu_, factorize_, issolver, and A.solve(b) for `A \\ b`) is the direct solver:
+a nested-dissection ordering found on the device, a supernodal symbolic fill from the dissection tree and ILUAM's factorization and
+solves on the filled, reordered matrix (esp_precon_lu_create) -- no pivoting; bit-identical to tests/iluam_model.c on the B of
+tests/lu_model.c.  nested_dissection(A) gives the ordering alone.
 """
 import ctypes as C
 import math
 
 import numpy as np
 
-from ._lib import ESP_ORTH_CGS, ESP_ORTH_DGKS, ESP_ORTH_MGS, ESP_PRECON_AMG, ESP_PRECON_BLOCK, ESP_PRECON_COLORED, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_ILUK, ESP_PRECON_ILUT, ESP_PRECON_JACOBI, ESP_PRECON_SPAI
+from ._lib import ESP_ORTH_CGS, ESP_ORTH_DGKS, ESP_ORTH_MGS, ESP_PRECON_AMG, ESP_PRECON_BLOCK, ESP_PRECON_COLORED, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_ILUK, ESP_PRECON_ILUT, ESP_PRECON_JACOBI, ESP_PRECON_LU, ESP_PRECON_SPAI
 from .matrix import ExtendableSparseMatrix, _vp
 
 
@@ -512,6 +516,123 @@ class ILUTPreconditioner(_ILUAMFactors, _PointPreconditioner):
         self._ck(self.A._d.lib.esp_precon_ilut_stats(self._live(), out))
         return {"nnz": int(out[5]), "sweeps": int(out[1]), "steps": [(int(out[8 + 2 * t]), int(out[9 + 2 * t])) for t in range(int(out[0]))],
                 "wave": int(out[2]), "group": int(out[3]), "stride": int(out[4])}
+
+
+class LUFactorization(_ILUAMFactors, _PointPreconditioner):
+    """LUFactorization(A, leaf_size=32, max_depth=48) (src/factorizations/umfpack_lu.jl, sparspak.jl; docs/src/linearsolve.md): a
+    sparse LU without pivoting (include/esparse_hip.h, esp_precon_lu_create).  A's graph is ordered by nested dissection on the device
+    -- components, two breadth-first searches and a middle level set as the separator, round by round --, the dissection tree predicts
+    a superset of the fill (a dense block per node plus the ancestors next to its subtree), and the factorization is
+    ILUAMPreconditioner of the filled, reordered matrix B: the exact LU of A[c,c].  solve(b) = ldiv is u[c] = ILUAM(B) \\ v[c], the
+    mirror of `lufact \\ b`; as Pl of simple it is iterative refinement.  A smaller leaf_size gives a deeper tree and less fill;
+    max_depth caps the rounds (what is left becomes dense leaves).  B holds copies: a value change of A reaches solve only through
+    update(), which keeps the ordering, the tree, B's pattern and the schedules when only values changed and orders anew after a
+    pattern change.  DEVIATIONS from UMFPACK / Sparspak: no pivoting -- a zero or NaN pivot propagates as in ILUAM --, and the
+    ordering is the one above, not AMD / MMD."""
+    KIND = ESP_PRECON_LU
+
+    def __init__(self, A, leaf_size=32, max_depth=48):
+        if not isinstance(A, ExtendableSparseMatrix):
+            raise TypeError("LUFactorization(A, ...): A must be an ExtendableSparseMatrix")
+        if int(leaf_size) != leaf_size or not 1 <= leaf_size < 2 ** 31:
+            raise ValueError("LUFactorization: leaf_size = %r (an integer >= 1)" % (leaf_size,))
+        if int(max_depth) != max_depth or not 0 <= max_depth <= 64:
+            raise ValueError("LUFactorization: max_depth = %r (an integer in 0..64)" % (max_depth,))
+        self.leaf_size, self.max_depth = int(leaf_size), int(max_depth)
+        self._bind(A, "esp_precon_lu_create", self.leaf_size, self.max_depth)
+
+    def _factored(self):
+        b = C.c_void_p()
+        self._ck(self.A._d.lib.esp_precon_lu_matrix(self._live(), C.byref(b)))
+        return b
+
+    def permutation(self):
+        """c, the unknowns sorted by (level descending, node, index), in the index base of A[i, j] (1-based)"""
+        out = np.empty(self.A.n, np.int64)
+        if self.A.n:
+            self._ck(self.A._d.lib.esp_precon_lu_perm(self._live(), _vp(out), 0))
+        return out + 1
+
+    def tree(self):
+        """(level, node_root) per unknown: the depth it was placed at (int32) and the 1-based unknown naming its tree node -- the
+        root of its component in that round (int64); the node of v is the pair (level[v], node_root[v])"""
+        level, root = np.empty(self.A.n, np.int32), np.empty(self.A.n, np.int64)
+        if self.A.n:
+            self._ck(self.A._d.lib.esp_precon_lu_tree(self._live(), _vp(level), _vp(root), 0))
+        return level, root + 1
+
+    def fill_matrix(self):
+        """the filled, reordered matrix B as host CSC arrays (colptr, rowval, nzval), Julia layout -- for tests and inspection"""
+        return self._host_csc(self._factored(), self.A.n)
+
+    def stats(self):
+        """dict: nnz (of B), rounds, deepest (level), nodes (of the tree), launches (component and search launches since the create:
+        an update() with the pattern kept adds none), largest_node"""
+        out = (C.c_int64 * 6)()
+        self._ck(self.A._d.lib.esp_precon_lu_stats(self._live(), out))
+        return dict(zip(("nnz", "rounds", "deepest", "nodes", "launches", "largest_node"), (int(x) for x in out)))
+
+    def solve(self, b, out=None):
+        """lufact \\ b: an alias of ldiv"""
+        return self.ldiv(b, out)
+
+
+SparspakLU = LUFactorization
+
+
+def lu(A, **kw):
+    """lu(A) (docs/src/linearsolve.md): LUFactorization(A, **kw)"""
+    return LUFactorization(A, **kw)
+
+
+def lu_(fact, A):
+    """lu!(fact, A): the factorization of A in fact -- bound anew when A is another matrix, else update()"""
+    if not isinstance(fact, LUFactorization):
+        raise TypeError("lu_(fact, A): fact must be an LUFactorization")
+    if not isinstance(A, ExtendableSparseMatrix):
+        raise TypeError("lu_(fact, A): A must be an ExtendableSparseMatrix")
+    if A is fact.A and fact._p is not None:
+        return fact.update()
+    fact.close()
+    fact._bind(A, "esp_precon_lu_create", fact.leaf_size, fact.max_depth)
+    return fact
+
+
+def factorize_(fact, A):
+    """factorize!(fact, A) (src/factorizations/factorizations.jl): lu_ for an LUFactorization; a preconditioner is bound to its
+    matrix and takes update()"""
+    if isinstance(fact, LUFactorization):
+        return lu_(fact, A)
+    if not isinstance(fact, _PointPreconditioner):
+        raise TypeError("factorize_(fact, A): fact must be a factorization or a preconditioner")
+    if A is not fact.A:
+        raise ValueError("factorize_: a preconditioner is bound to its matrix; create a new one for another matrix")
+    return fact.update()
+
+
+def issolver(f):
+    """issolver(f) (factorizations.jl): True for the direct solver LUFactorization (an instance or the class), False for every
+    preconditioner"""
+    return isinstance(f, LUFactorization) or (isinstance(f, type) and issubclass(f, LUFactorization))
+
+
+def nested_dissection(A, leaf_size=32, max_depth=48):
+    """the nested-dissection ordering of A's graph alone (esp_nested_dissection) -> (perm, level): the 1-based permutation c and the
+    depth every unknown was placed at (int32)"""
+    if not isinstance(A, ExtendableSparseMatrix):
+        raise TypeError("nested_dissection(A): A must be an ExtendableSparseMatrix")
+    A.flush()
+    d = A._d
+    c, level = np.empty(A.n, np.int64), np.empty(A.n, np.int32)
+    d.ck(d.lib.esp_nested_dissection(d.h, int(leaf_size), int(max_depth), _vp(c) if A.n else None, _vp(level) if A.n else None, 0))
+    return c + 1, level
+
+
+def solve(A, b):
+    """A \\ b: A.solve(b)"""
+    if not isinstance(A, ExtendableSparseMatrix):
+        raise TypeError("solve(A, b): A must be an ExtendableSparseMatrix")
+    return A.solve(b)
 
 
 def AMGCL_RLXPreconditioner(A, type="spai0"):

@@ -641,6 +641,67 @@ int32_t esp_precon_ilut_create(esp_handle *h, double droptol, int32_t steps, int
 int32_t esp_precon_ilut_matrix(esp_precon *p, esp_handle **f);
 int32_t esp_precon_ilut_stats(esp_precon *p, int64_t out[ESP_ILUT_STATS]);
 int32_t esp_precon_ilut_limits(int64_t out[4]);
+/* LUFactorization and `A \ b` (src/factorizations/umfpack_lu.jl, sparspak.jl; docs/src/linearsolve.md): a sparse LU WITHOUT pivoting.
+ * The reference wraps UMFPACK / Sparspak, which are not part of its tree, so the algorithm is stated in full here and in DESIGN.md 5q:
+ * a nested-dissection ordering found on the device, a supernodal symbolic factorization that predicts a superset of the fill from the
+ * dissection tree alone, and ILUAM's factorization and level-scheduled solves on the filled, reordered matrix B.  tests/lu_model.c
+ * restates it as plain loops and is normative; the device equals it bit for bit.  Indices 0-based.
+ *   graph       i and j (i != j) are neighbours when A[i,j] or A[j,i] is stored: the colouring's graph (a stored 0.0, -0.0 or NaN is an
+ *               entry, the sum A + transpose(A) is never formed, no symmetric pattern is required).  key(i) is the colouring's key:
+ *               distinct, every comparison strict.
+ *   dissection  d = 0, one remaining part holding every vertex.  A round: 1. the connected components of every remaining part; the
+ *               root of a component is its vertex with the largest key; anc[v][d] = the root of v's component for every vertex still
+ *               unplaced.  2. a component C is a leaf of depth d when |C| <= leaf_size, or d == max_depth, or the eccentricity of
+ *               step 3 is below 2; every vertex of a leaf gets level[v] = d.  3. every other component: dist0 = the breadth-first
+ *               distances inside C from its root, e0 their maximum, r1 = the vertex with dist0 == e0 of the largest key, dist = the
+ *               distances inside C from r1, ecc their maximum; with ecc >= 2 and mid = (ecc + 1) div 2 the vertices with dist == mid
+ *               are C's separator and get level[v] = d, {dist < mid} and {dist > mid} are remaining parts of depth d + 1 (an edge joins
+ *               equal or adjacent distances only: the separator separates).  4. d = d + 1; stop when no part remains.
+ *   tree        a node is a pair (d, root): the vertices with level == d and anc[.][d] == root -- a leaf, or the separator of a split
+ *               component.  The nodes (e, anc[v][e]), e < level[v], are v's ancestors.  c = the vertices sorted by (level descending,
+ *               anc[v][level[v]] ascending, index ascending): every node is contiguous in c, every ancestor behind its descendants.
+ *   fill        for an edge (u, v) with level[v] < level[u], v belongs to struct of the node (e, anc[u][e]) for every e with
+ *               level[v] < e <= level[u]: struct(K) = the vertices of K's ancestors next to K or to a descendant of K.  In positions of
+ *               c, column u of L holds the vertices of u's node from u on (a dense diagonal block) and struct(node(u)).  B's pattern
+ *               is L + transpose(L); B[k,l] = A[c[k],c[l]] bitwise where stored, +0.0 elsewhere, rows ascending.  The pattern contains
+ *               the fill of P*A*transpose(P), so ILU(0) of B is the exact LU; entries outside the true fill stay +-0.0.
+ *   numerics    esp_precon_create(B, ESP_PRECON_ILUAM), unchanged.  esp_precon_ldiv is u[c] = ILUAM(B) \ v[c]: the coloured kind's gather,
+ *               inner solve and scatter; u may alias v.  No pivoting (a zero or NaN pivot propagates as in ILUAM), no refinement;
+ *               esp_simple with this kind is iterative refinement.  DEVIATION: the order is the one above, not AMD / MMD / COLAMD.
+ * On the device the components (the largest key spreads, every vertex at once from the labels of the launch before) and the searches
+ * (an unplaced vertex without a distance that has a neighbour at distance step - 1 takes distance step) run over all components at
+ * once, one lane per vertex, a vertex whose column or row holds more than 32 entries folded by its whole wave; the maxima per
+ * component go through atomics on arrays indexed by the root vertex.  A step is one launch on the handle's stream and one counter
+ * read back; steps are separated by kernel boundaries and by nothing else.  c comes from stable radix passes; the struct lists from
+ * an ESP_COO flush of a scratch handle (the nodes as columns) and its transpose; B's columns are written in order by one wave each.
+ * esp_nested_dissection: the ordering of a flushed square matrix without a factorization: c[n] (int64) and level[n] (int32), host, or
+ *   device when on_device != 0; either may be NULL.  The checks are esp_precon_lu_create's.
+ * esp_precon_lu_create(h, leaf_size, max_depth): the result is an esp_precon bound to h; esp_precon_update / _ldiv / _destroy,
+ *   esp_simple, esp_cg, esp_bicgstabl and esp_gmres take it unchanged; esp_precon_get_factor / _levels / _launches answer for the inner
+ *   ILUAM (nnz(B) values in B's position order).
+ * esp_precon_update: with A's pattern kept one gather of B's values and ILUAM's values-only update (the ordering, the tree, B's pattern
+ *   and the schedules are kept; bitwise what a fresh create gives); after a pattern change everything anew.  B holds copies: a value
+ *   change of A reaches ldiv! only through the update, a pattern change of A without it is ESP_ERR_STATE.  A rebuild that fails before
+ *   B is replaced leaves the earlier state usable.
+ * Inspection: esp_precon_lu_perm: c[n] (int64).  esp_precon_lu_tree: level[n] (int32) and node_root[n] (int64, anc[v][level[v]]), per
+ *   vertex; either may be NULL.  All host, or device when on_device != 0.  esp_precon_lu_matrix: B's handle, borrowed and read-only.
+ *   esp_precon_lu_stats: out = nnz(B), the rounds, the deepest level, the nodes, the component and search launches this object has
+ *   run since its create (an update! with the pattern kept adds none), the largest node.
+ * ESP_ERR_INVALID: a rectangular matrix; leaf_size < 1; max_depth outside 0..64; a column of B whose diagonal A does not store
+ *   (ILUAM's condition; the message names the column of B, the position in c, and A's column).  ESP_ERR_STATE: pending entries.
+ *   ESP_ERR_UNSUPPORTED: a column window / column shard on h; n or nnz(B) >= 2^32 - 16 -- nnz(B) is known from the count pass: refused
+ *   before B is allocated, esp_last_error gives nnz(B) (esp_debug_lu_fill_cap(h, cap) lowers that limit for the factorizations created
+ *   on h afterwards, a test hook; 0 restores it).  n == 0 is valid.  LU is no inner kind of esp_precon_block_create or
+ *   esp_precon_colored_create.  A live factorization makes h refuse esp_destroy; esp_precon_destroy releases B, the inner
+ *   preconditioner and every buffer. */
+#define ESP_PRECON_LU 9
+int32_t esp_precon_lu_create(esp_handle *h, int32_t leaf_size, int32_t max_depth, esp_precon **out);
+int32_t esp_precon_lu_perm(esp_precon *p, int64_t *c, int32_t on_device);
+int32_t esp_precon_lu_tree(esp_precon *p, int32_t *level, int64_t *node_root, int32_t on_device);
+int32_t esp_precon_lu_matrix(esp_precon *p, esp_handle **b);
+int32_t esp_precon_lu_stats(esp_precon *p, int64_t out[6]);
+int32_t esp_nested_dissection(esp_handle *h, int32_t leaf_size, int32_t max_depth, int64_t *c, int32_t *level, int32_t on_device);
+int32_t esp_debug_lu_fill_cap(esp_handle *h, int64_t cap);
 /* simple!(u, A, b; abstol, reltol, maxiter, Pl = p) (src/factorizations/simple_iteration.jl:21-45) statement by
  * statement: res = A*u - b; then per step ldiv!(upd, Pl, res), u .-= upd, mul!(res, A, u), res .-= b, r = norm(res),
  * stop when (r / r0) < reltol || r < abstol (literally: r0 = 0 gives NaN or Inf there).  u (in/out) is bit-identical to

@@ -99,6 +99,12 @@ four sweeps, beside the bytes the sweep must move at least), nnz(F)/nnz(A), the 
 reltol 1e-8 on b = ones (iterations and time).
 
     python tools/precon_bench.py --kind ilut --droptol 1e-2 [--n 64] [--iters 20] [--rounds 5] [--tol-maxiter 20000]
+
+--kind lu [--leaf-size L] times LUFactorization (esp_precon_lu_create) on fdrand(n,n,n): the create and its parts (the ordering alone
+through esp_nested_dissection, ILUAM's analysis + factorization of a copy of B, the fill as what is left), a values-only update!,
+ldiv!, nnz(B)/nnz(A), the rounds and launches of the ordering, ILUAM's level counts, and one solve of A x = 1 to 1e-8: A.solve(b)
+(create + solve) against cg with ILU0 and with ILUAM (create + cg) in the same run.  Medians over --rounds.
+    python tools/precon_bench.py --kind lu [--n 32] [--leaf-size 32] [--iters 5] [--rounds 5]
 """
 import argparse
 import ctypes as C
@@ -856,6 +862,102 @@ def bench_iluk(a, torch, esp):
     print(json.dumps(rnd(out)))
 
 
+def bench_lu(a, torch, esp):
+    """LUFactorization on fdrand n^3: the create split into ordering / fill / ILUAM's analysis + factorization of B, the values-only
+    update, ldiv!, the fill, the rounds and launches of the ordering, ILUAM's level counts, and one solve to 1e-8 -- A.solve(b)
+    against cg with ILU0 and with ILUAM in the same run.  Medians over --rounds."""
+    import numpy as np
+    A = esp.fdrand(a.n, a.n, a.n)
+    d = A._d
+    stream = torch.cuda.current_stream()
+    d.ck(d.lib.esp_set_stream(d.h, C.c_void_p(stream.cuda_stream)))
+    N, Z = A.n, A.nnz()
+    v = torch.randn(N, dtype=torch.float64, device="cuda")
+    u = torch.empty_like(v)
+    b = torch.ones_like(v)
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()                                   # (create, update!, ldiv! and the solvers return synchronised)
+        return (time.perf_counter() - t0) * 1e3, r
+
+    def median(xs):
+        return float(np.median(xs))
+
+    out = {"workload": "lu_fdrand", "n": a.n, "N": N, "nnz": Z, "leaf_size": a.leaf_size, "rounds": a.rounds}
+    Pw = esp.ILU0Preconditioner(A)     # builds the row-wise index the ordering shares, so that the creates below are their own
+    Pw.close()
+    rec = {}
+
+    def note(what):                                # (a phase is done: a line on stderr, so that a run cut short still reports)
+        print("lu n=%d: %s: %s" % (a.n, what, json.dumps({k: v for k, v in rec.items() if k != "stats"})), file=sys.stderr, flush=True)
+    rec["ordering_ms"] = median([wall(lambda: esp.nested_dissection(A, a.leaf_size))[0] for _ in range(a.rounds)])
+    ts = []
+    for _ in range(a.rounds):
+        t, P = wall(lambda: esp.LUFactorization(A, a.leaf_size))
+        ts.append(t)
+        P.close()
+    rec["create_ms"] = median(ts)
+    note("create")
+    P = esp.LUFactorization(A, a.leaf_size)
+    st = P.stats()
+    rec["stats"] = st
+    rec["nnz_B"] = st["nnz"]
+    rec["fill_ratio"] = st["nnz"] / Z
+    rec["levels"] = list(P.levels())
+    rec["update_values_ms"] = median([wall(P.update)[0] for _ in range(a.rounds)])
+    note("update")
+    for _ in range(2):
+        P.ldiv(v, out=u)
+    rec["ldiv_ms"] = median([wall(lambda: [P.ldiv(v, out=u) for _ in range(a.iters)])[0] / a.iters for _ in range(a.rounds)])
+    x = P.solve(b)
+    r = A.mul(x) - b
+    rec["solve_residual"] = float(torch.linalg.norm(r) / torch.linalg.norm(b))
+    note("ldiv and solve")
+    cp, rv, nz = P.fill_matrix()
+    P.close()
+    Bm = esp.ExtendableSparseMatrix(esp.SparseMatrixCSC(N, N, cp, rv, nz))      # ILUAM's analysis + factorization of B, on a copy
+    Bm.flush()
+    Pw = esp.ILU0Preconditioner(Bm)
+    Pw.close()
+    ts = []
+    for _ in range(a.rounds):
+        t, Q = wall(lambda: esp.ILUAMPreconditioner(Bm))
+        ts.append(t)
+        Q.close()
+    del Bm
+    rec["create_iluam_of_B_ms"] = median(ts)
+    rec["create_fill_ms"] = rec["create_ms"] - rec["ordering_ms"] - rec["create_iluam_of_B_ms"]
+    out["lu"] = rec
+    note("parts")
+    # one solve to 1e-8: the direct solve (create + solve, what A.solve(b) does) against cg with ILU0 and ILUAM (create + cg)
+    sol = {}
+    sol["A.solve"] = {"ms": median([wall(lambda: A.solve(b))[0] for _ in range(a.rounds)]), "residual": rec["solve_residual"]}
+    for name, make in (("cg+ilu0", esp.ILU0Preconditioner), ("cg+iluam", esp.ILUAMPreconditioner)):
+        def run():
+            Q = make(A)
+            try:
+                return esp.cg(A, b, Pl=Q, reltol=1e-8, maxiter=a.tol_maxiter, log=True)
+            finally:
+                Q.close()
+        run()
+        ts, log = [], None
+        for _ in range(a.rounds):
+            t, (_, log) = wall(run)
+            ts.append(t)
+        sol[name] = {"ms": median(ts), "iterations": log["iters"], "converged": log["isconverged"]}
+    out["solve_1e-8"] = sol
+
+    def rnd(x):
+        if isinstance(x, float):
+            return round(x, 4) if abs(x) >= 1e-3 else float("%.3e" % x)
+        if isinstance(x, dict):
+            return {k: rnd(y) for k, y in x.items()}
+        return x
+    print(json.dumps(rnd(out)))
+
+
 def bench_ilut(a, torch, esp):
     import numpy as np
     A = esp.fdrand(a.n, a.n, a.n)
@@ -1084,7 +1186,8 @@ def main():
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "gmres", "gmres-trace", "block", "block-trace", "block-trace-diff", "amg", "iluk", "colored", "spai0", "spai1", "spai1sym", "ilut"], default="point")
+    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "gmres", "gmres-trace", "block", "block-trace", "block-trace-diff", "amg", "iluk", "colored", "spai0", "spai1", "spai1sym", "ilut", "lu"], default="point")
+    ap.add_argument("--leaf-size", type=int, default=32)
     ap.add_argument("--droptol", type=float, default=1e-3)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--sweeps", type=int, default=3)
@@ -1128,6 +1231,8 @@ def main():
         return bench_iluk(a, torch, esp)
     if a.kind == "ilut":
         return bench_ilut(a, torch, esp)
+    if a.kind == "lu":
+        return bench_lu(a, torch, esp)
     if a.kind == "amg":
         return bench_amg(a, torch, esp)
     if a.kind == "colored":
