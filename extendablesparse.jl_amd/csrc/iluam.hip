@@ -25,6 +25,8 @@
 // Prefactored mode (esp_precon::prefactored, set by ilut.hip on its inner preconditioner): the handle's values are a factorization
 // already.  The diagonal positions, the row parts and the two solve schedules are built as above; the factor schedule is not, and
 // FactorOp does not run: fval is a copy of the handle's values, and a values-only update! is that copy and the gather.
+//
+// esp_debug_iluam_form (a test hook) forces FactorOp or FactorWaveOp at the next update!, and esp_debug_last_iluam_form tells which ran.
 #include "internal.hpp"
 
 namespace {
@@ -432,12 +434,14 @@ int32_t iluam_update(esp_precon *p, bool rebuild) {
     }
     // the numeric factorization on a copy of the values (prefactored, ilut.hip's inner preconditioner: the values are the factorization
     // already -- the copy and the gather alone)
+    p->iluam_form = 0;
     CK(ensure(h, p->fval, sizeof(double) * (size_t)std::max<i64>(h->nnz, 1)));
     if (n == 0) return ESP_OK;
     HIPCK(h, hipMemcpyAsync(p->fval.p, h->nzval.p, sizeof(double) * (size_t)h->nnz, hipMemcpyDeviceToDevice, h->stream));
-    if (!p->prefactored && h->nnz >= (i64)FW_MIN_AVG * n)
+    if (!p->prefactored) p->iluam_form = p->iluam_force ? p->iluam_force : h->nnz >= (i64)FW_MIN_AVG * n ? 2 : 1;
+    if (p->iluam_form == 2)
         run_factor_waves(p, p->sched[S_FACTOR], FactorWaveOp{(const u32 *)p->sched[S_FACTOR].order.p, (const i64 *)h->colptr.p, (const i64 *)h->rowval.p, (const u32 *)p->dpos.p, (double *)p->fval.p});
-    else if (!p->prefactored)
+    else if (p->iluam_form == 1)
         run_schedule(p, p->sched[S_FACTOR], FactorOp{(const u32 *)p->sched[S_FACTOR].order.p, (const i64 *)h->colptr.p, (const i64 *)h->rowval.p, (const u32 *)p->dpos.p, (double *)p->fval.p});
     hipLaunchKernelGGL(iluam_gather_k, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const u32 *)p->lptr.p, (const u32 *)p->lpos.p,
                        (const u32 *)p->uptr.p, (const u32 *)p->upos.p, (const u32 *)p->dpos.p, (const u32 *)p->sched[S_BWD].order.p,
@@ -499,6 +503,26 @@ extern "C" int32_t esp_precon_levels(esp_precon *p, int64_t out[3]) {
     if (!p || !out) return ESP_ERR_INVALID;
     if (holds_derived(p) && p->der.inner) p = p->der.inner;
     for (int k = 0; k < 3; k++) out[k] = p->kind == ESP_PRECON_ILUAM ? p->sched[k].levels : 0;
+    return ESP_OK;
+}
+
+// the ILUAM preconditioner the two calls below speak to: p itself, or the inner one of a kind that holds a derived matrix
+static esp_precon *iluam_of(esp_precon *p) {
+    if (p && holds_derived(p)) p = p->der.inner;
+    return p && p->kind == ESP_PRECON_ILUAM ? p : nullptr;
+}
+
+extern "C" int32_t esp_debug_iluam_form(esp_precon *p, int32_t form) {
+    esp_precon *q = iluam_of(p);
+    if (!q || form < 0 || form > 2) return ESP_ERR_INVALID;
+    q->iluam_force = form;
+    return ESP_OK;
+}
+
+extern "C" int32_t esp_debug_last_iluam_form(esp_precon *p, int32_t *form) {
+    esp_precon *q = iluam_of(p);
+    if (!q || !form) return ESP_ERR_INVALID;
+    *form = q->iluam_form;
     return ESP_OK;
 }
 

@@ -607,6 +607,7 @@ struct esp_precon {
     // t belongs to row sched[1 / 2].order[t], so a level's slice is contiguous (8.3 against 11.2 ms per ldiv! at 256^3)
     DevBuf fval;
     IluamSched sched[3];  // 0: columns of the factorization, 1: rows of the forward solve, 2: rows of the backward solve
+    int iluam_force = 0, iluam_form = 0;  // esp_debug_iluam_form's choice; the form of the last numeric factorization (0 none, 1 lane, 2 wave)
     // The kinds that hold a derived matrix (holds_derived: Block, Colored, ILU(k)): h is A; a matrix B made from A's stored CSC --
     // Block: the stored A[i,j] with part(i) == part(j); Colored: A[c,c]; ILU(k): every position of level <= iluk_k -- lives in the
     // internal handle bh (A's device and stream), and inner is an ordinary preconditioner of inner_kind bound to bh.  src[q] is the

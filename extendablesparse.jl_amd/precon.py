@@ -202,6 +202,18 @@ class _ILUAMFactors:
         self._ck(self.A._d.lib.esp_precon_launches(self._live(), out))
         return tuple((int(out[2 * k]), int(out[2 * k + 1])) for k in range(3))
 
+    def debug_factor_form(self, form):
+        """test hook (esp_debug_iluam_form), takes effect at the next update(): 0 the automatic choice between the two forms of the
+        column factorization, 1 always a lane per column, 2 always a wave per column -- the results never change"""
+        self._ck(self.A._d.lib.esp_debug_iluam_form(self._live(), int(form)))
+        return self
+
+    def last_factor_form(self):
+        """the form the last numeric factorization ran (esp_debug_last_iluam_form): 0 none, 1 lane, 2 wave"""
+        form = C.c_int32()
+        self._ck(self.A._d.lib.esp_debug_last_iluam_form(self._live(), C.byref(form)))
+        return form.value
+
 
 class ILUAMPreconditioner(_ILUAMFactors, _PointPreconditioner):
     """ILUAMPreconditioner(A) (src/experimental/ExtendableSparseMatrixParallel/iluam.jl): a real ILU(0) on A's pattern, the

@@ -344,6 +344,14 @@ int32_t esp_precon_destroy(esp_precon *p);
 int32_t esp_precon_get_factor(esp_precon *p, double *nzval, int32_t on_device);
 int32_t esp_precon_levels(esp_precon *p, int64_t out[3]);
 int32_t esp_precon_launches(esp_precon *p, int64_t out[6]);
+/* test hook, takes effect at the next esp_precon_update (a values-only one is enough: the form is chosen in the numeric phase): which
+ * of the two implementations of the column factorization runs -- 0 automatic (the wave form from 24 stored entries per column on
+ * average), 1 always a lane per column, 2 always a wave per column.  Results never change, timings do.  Block, ILU(k), Colored, ILUT
+ * and LU forward it to their inner ILUAM.  ESP_ERR_INVALID: p == NULL, a form outside 0..2, a kind without an (inner) ILUAM. */
+int32_t esp_debug_iluam_form(esp_precon *p, int32_t form);
+/* test / inspection, read-only: the form the last numeric factorization ran -- 0 none (n == 0; the prefactored inner ILUAM of ILUT,
+ * whatever was forced), 1 lane, 2 wave.  Forwards as esp_debug_iluam_form does, with its errors (and form == NULL). */
+int32_t esp_debug_last_iluam_form(esp_precon *p, int32_t *form);
 /* BlockPreconditioner (src/factorizations/blockpreconditioner.jl, docs/src/iter.md): the unknowns are split into partitions, every
  * A[part, part] is factorized with Jacobi, ILU0 or ILUAM (inner_kind), and ldiv! solves the partitions independently:
  * u[part] = inner(A[part, part]) \ v[part].  The reference builds np submatrices and runs np factorizations and solves; the device

@@ -467,3 +467,204 @@ def test_frontier(tmp_path_factory):
                 assert max(vl + vu) <= 64                                             # the wave form serves every column
                 u = P.ldiv(np.ones(n))
                 assert np.isfinite(u).all() and np.any(u != 0.0)
+
+
+# =================================================================================================================================
+# the factorization side: tests/factor_patterns.py
+# =================================================================================================================================
+import factor_patterns as fp  # noqa: E402
+import lu_modellib  # noqa: E402
+
+
+def factor_csc(case):
+    """the CSC arrays of a factor_patterns case, after the checks every case must pass: unique triplets in range, off-diagonals in
+    (-1, 1), every diagonal 1 + max(row abs sum, column abs sum)"""
+    I, J, V, n = case
+    assert len(I) == len(J) == len(V) and len(np.unique((I - 1) * n + (J - 1))) == len(I)
+    assert I.min() >= 1 and I.max() <= n and J.min() >= 1 and J.max() <= n
+    assert np.all(np.abs(V[I != J]) < 1.0)
+    arrays = ep.csc_arrays(n, I, J, V)
+    S = sp.csc_matrix((arrays[2], arrays[1] - 1, arrays[0] - 1), shape=(n, n))
+    d = S.diagonal()
+    rows = np.asarray(abs(S).sum(axis=1)).ravel() - d
+    cols = np.asarray(abs(S).sum(axis=0)).ravel() - d
+    np.testing.assert_allclose(d, 1.0 + np.maximum(rows, cols), rtol=1e-13, atol=0)
+    return arrays
+
+
+def automatic_wave(arrays):
+    """iluam_update's automatic rule"""
+    return len(arrays[1]) >= fp.FW_MIN_AVG * (len(arrays[0]) - 1)
+
+
+def factor_widths(arrays):
+    return ep.widths_of(level_schedules(arrays[0], arrays[1])[0])
+
+
+def test_factor_constants():
+    assert (fp.FW_ROWS, fp.FW_MIN_AVG, fp.WAVE, fp.LT, fp.AMG_LONG) == (2048, 24, 64, 256, 32) and fp.LT == ep.LT
+
+
+def test_exact_nnz_sits_on_the_switch(model):
+    n = 100
+    on, below = fp.exact_nnz(n, 24 * n, seed=5), fp.exact_nnz(n, 24 * n - 1, seed=5)
+    a, b = factor_csc(on), factor_csc(below)
+    assert len(a[1]) == 2400 == fp.FW_MIN_AVG * n and len(b[1]) == 2399
+    assert automatic_wave(a) and not automatic_wave(b)
+    # the second is the first minus its last off-diagonal entry
+    assert np.array_equal(on[0][n:-1], below[0][n:]) and np.array_equal(on[1][n:-1], below[1][n:]) and np.array_equal(on[2][n:-1], below[2][n:])
+    for arrays in (a, b):
+        assert np.all(np.diff(arrays[0]) >= 1) and np.isfinite(model.factor(arrays)[0]).all()
+
+
+@pytest.mark.parametrize("n,nnz", [(2047, 55087), (2048, 55114), (2049, 55141)])
+def test_arrowband_columns_at_the_staging_edge(model, n, nnz):
+    case = fp.arrowband(n)
+    arrays = factor_csc(case)
+    cp, rv, _ = arrays
+    lens = np.diff(cp)
+    assert len(rv) == nnz == 27 * n - 182 and automatic_wave(arrays) and fp.FW_MIN_AVG * n == {2047: 49128, 2048: 49152, 2049: 49176}[n]
+    assert int(lens.argmax()) == n - 1 and lens[n - 1] == n and np.delete(lens, n - 1).max() == 26
+    assert (lens[n - 1] <= fp.FW_ROWS) == (n <= 2048)                       # two staged sizes and the first unstaged one
+    assert np.all(rv[cp[1:n] - 2] == n)                                    # every other column ends with the last row ...
+    hit, inside, beyond = fp.search_outcomes(cp, rv)
+    assert hit > 0 and beyond == 0                                         # ... so no search runs beyond a column's end
+    assert factor_widths(arrays) == [1] * n                                 # n levels of one column
+    f, diag = model.factor(arrays)
+    assert np.isfinite(f).all()
+    assert np.isfinite(model.ldiv(arrays, f, diag, np.ones(n))).all()
+    t = factor_csc(fp.transposed(case))                                     # the transpose: the same pattern, other values
+    assert np.array_equal(t[0], cp) and np.array_equal(t[1], rv) and not np.array_equal(t[2], arrays[2])
+    assert np.isfinite(model.factor(t)[0]).all()
+
+
+def test_arrowband_with_the_long_column_in_the_middle(model):
+    n, hub = 2049, 1024
+    arrays = factor_csc(fp.arrowband(n, hub=hub))
+    cp, rv, _ = arrays
+    lens = np.diff(cp)
+    assert int(lens.argmax()) == hub != n - 1 and lens[hub] == n > fp.FW_ROWS and np.delete(lens, hub).max() == 26
+    assert automatic_wave(arrays) and len(rv) == 55141
+    # the columns behind the hub store row `hub` above their diagonal: they read the long column as their column i, whose rows below
+    # its diagonal take (n - 1 - hub) / 64 = 16 rounds of the lane stride
+    assert all(hub + 1 in rv[cp[j] - 1:cp[j + 1] - 1] for j in range(hub + 1, n)) and (n - 1 - hub) == 16 * fp.WAVE
+    base = ep.csc_arrays(n, *fp.arrowband(n)[:3])
+    inv = np.concatenate([np.arange(hub), [n - 1], np.arange(hub, n - 1)])   # new index -> old index
+    B = sp.csc_matrix((np.ones(len(base[1])), base[1] - 1, base[0] - 1), shape=(n, n))[inv][:, inv]
+    M = sp.csc_matrix((np.ones(len(rv)), rv - 1, cp - 1), shape=(n, n))
+    assert (B != M).nnz == 0                                                # a symmetric permutation of arrowband(n)
+    hit, inside, beyond = fp.search_outcomes(cp, rv)
+    assert hit > 0 and inside > 0 and beyond > 0
+    assert np.isfinite(model.factor(arrays)[0]).all()
+
+
+@pytest.mark.parametrize("copies,launches", [(5, (0, 1)), (256, (0, 25)), (257, (25, 0)), (258, (25, 0)), (259, (25, 0)), (260, (25, 0))])
+def test_cliques_level_widths_and_launches(copies, launches):
+    """m = 25 levels of `copies` columns: one thin launch (5: wave 0 takes members 0 and 4), a thin launch per level (256: 64 members
+    per wave), wide launches whose last workgroup has copies - 256 = 1, 2, 3, 4 live waves"""
+    arrays = factor_csc(fp.cliques(copies, 25))
+    assert np.all(np.diff(arrays[0]) == 25) and len(arrays[1]) == 625 * copies and automatic_wave(arrays)
+    widths = factor_widths(arrays)
+    assert widths == [copies] * 25 and ep.launch_list(widths) == launches
+    if copies > fp.LT:
+        per_group = fp.LT // fp.WAVE
+        assert copies - (copies - 1) // per_group * per_group == copies - 256
+    if copies == 260:
+        assert (len(arrays[0]) - 1, len(arrays[1])) == (6500, 162500)
+
+
+@pytest.mark.parametrize("m,rounds", [(64, 1), (65, 1), (66, 2), (131, 3)])
+def test_single_clique_rows_below_the_first_diagonal(model, m, rounds):
+    arrays = factor_csc(fp.cliques(1, m))
+    cp, rv, _ = arrays
+    below = int((rv[cp[0] - 1:cp[1] - 1] > 1).sum())
+    assert below == m - 1 and -(-below // fp.WAVE) == rounds and automatic_wave(arrays)
+    assert factor_widths(arrays) == [1] * m
+    assert np.isfinite(model.factor(arrays)[0]).all()
+
+
+def test_sparse_dense_enough_search_outcomes(model):
+    arrays = factor_csc(fp.sparse_dense_enough(seed=3))
+    cp, rv, nz = arrays
+    assert len(rv) == 9270 >= fp.FW_MIN_AVG * 300 == 7200 and automatic_wave(arrays)
+    S = sp.csc_matrix((nz, rv - 1, cp - 1), shape=(300, 300))
+    assert ((S != 0) != (S != 0).T).nnz > 0                                 # non-symmetric
+    hit, inside, beyond = fp.search_outcomes(cp, rv)
+    print("hits %d, misses inside column j %d, beyond its last row %d" % (hit, inside, beyond))
+    assert (hit, inside, beyond) == (9404, 76903, 3719) and min(hit, inside, beyond) > 0
+    assert np.isfinite(model.factor(arrays)[0]).all()
+
+
+def test_search_outcomes_by_hand():
+    """column 2 = rows {0, 2, 5}, column 0 = rows {0, 1, 2, 4, 9} (0-based): from v = 0 of column 2, row 1 falls before row 2 and
+    row 4 between rows 2 and 5 (inside), row 2 hits, row 9 lies beyond the last row"""
+    n = 10
+    I = np.concatenate([np.arange(n), [1, 2, 4, 9, 0, 5]])
+    J = np.concatenate([np.arange(n), [0, 0, 0, 0, 2, 2]])
+    cp, rv, _ = ep.csc_arrays(n, I + 1, J + 1, np.ones(len(I)))
+    assert fp.search_outcomes(cp, rv) == (1, 2, 1)
+
+
+def test_forced_cases_need_the_hook():
+    """the layered patterns of the launch-list tests hold 3-5 entries per column: only the hook brings them to the wave form"""
+    for name in sorted(ep.WIDTHS):
+        for form in ("upper", "symmetric"):
+            I, J, V, n = ep.layered(ep.WIDTHS[name], form, seed=3)
+            assert len(I) < fp.FW_MIN_AVG * n and len(I) <= 5 * n
+            assert 0 in ep.PRESCRIBED[form]
+
+
+@pytest.mark.parametrize("hubs,entries,by", fp.MULTI_HUB_CASES)
+def test_multi_hub_long_vertices(hubs, entries, by):
+    n = fp.MULTI_HUB_N
+    arrays = factor_csc(fp.multi_hub(n, hubs, entries, by))
+    cp, rv, _ = arrays
+    bycol, byrow = fp.long_vertices(cp, rv)
+    assert list(bycol) == (hubs if by in ("col", "both") else []) and list(byrow) == (hubs if by in ("row", "both") else [])
+    percol, perrow = np.diff(cp), np.bincount(rv - 1, minlength=n)
+    for h in hubs:
+        path = 2 - (h in (0, n - 1))
+        assert percol[h] == 1 + path + (entries if by != "row" else 0) and perrow[h] == 1 + path + (entries if by != "col" else 0)
+    others = np.setdiff1d(np.arange(n), hubs)
+    assert max(percol[others].max(), perrow[others].max()) <= 3 + len(hubs) <= fp.AMG_LONG
+    S = sp.csc_matrix((np.ones(len(rv)), rv - 1, cp - 1), shape=(n, n))
+    assert sp.csgraph.connected_components(S, directed=False)[0] == 1
+
+
+def test_multi_hub_lanes():
+    """which lanes of which waves fold: lane 0, lane 63, both, two neighbours, three in wave 1, lane 43 of the ragged wave 4"""
+    n = fp.MULTI_HUB_N
+    assert n == 300 and n - 4 * fp.WAVE == 44 and (n - 1) // fp.LT == 1
+    where = [[(h // fp.WAVE, h % fp.WAVE) for h in hubs] for hubs in fp.HUB_SETS]
+    assert where == [[(0, 0)], [(0, 63)], [(0, 0), (0, 63)], [(0, 10), (0, 11)], [(1, 0), (1, 36), (1, 63)], [(4, 43)]]
+    assert len(fp.MULTI_HUB_CASES) == 14
+    assert {(e, by) for _, e, by in fp.MULTI_HUB_CASES} == {(33, "col"), (65, "row"), (33, "both"), (65, "both")}
+    assert 33 == fp.AMG_LONG + 1 and 65 == fp.WAVE + 1                     # one and two rounds of the fold
+
+
+def test_clique_components_node_sizes(tmp_path_factory):
+    """what the LU model makes of them with leaf_size 70.  Separate cliques of 63, 64, 65: three dense leaves of exactly those sizes,
+    no struct.  With a path of 10 behind each the separator is a vertex of the path (the middle level set of the search), and the
+    leaf beside it holds the clique and the three path vertices next to it: nodes of 66, 67, 68 for cliques of 63, 64, 65.  Cliques of
+    59, 60, 61 with a path of 12 (four path vertices stay with the clique) give nodes of exactly 63, 64, 65 -- each with the separator
+    as its struct, so the separator's column lists a node of that size"""
+    lm = lu_modellib.Model(tmp_path_factory.mktemp("edge_lu_model"))
+
+    def nodes(sizes, tail):
+        arrays = factor_csc(fp.clique_components(sizes, tail))
+        F = lm.lu(arrays, 70)
+        bcp, brv, _ = F.B
+        out = []
+        for s in np.unique(F.nstart):
+            struct = int((brv[bcp[s] - 1:bcp[s + 1] - 1] - 1 >= s + F.nsize[s]).sum())
+            out.append((int(F.nsize[s]), struct))
+        assert np.isfinite(F.fval).all()
+        return out, F.stats
+
+    got, st = nodes([63, 64, 65], 0)
+    assert got == [(63, 0), (64, 0), (65, 0)] and (st["rounds"], st["nodes"], st["largest_node"]) == (1, 3, 65)
+    got, st = nodes([63, 64, 65], 10)
+    assert [g for g in got if g[0] > 60] == [(66, 1), (67, 1), (68, 1)] and st["rounds"] == 2
+    got, st = nodes(*fp.CLIQUE_TAILS_AT_THE_EDGE)
+    assert [g for g in got if g[0] > 59] == [(63, 1), (64, 1), (65, 1)] and st["rounds"] == 2
+    assert sorted(g for g in got if g[0] <= 59) == [(1, 0)] * 3 + [(7, 1)] * 3   # the separators and the far ends of the paths

@@ -2,6 +2,7 @@
 iluam_model.c's over the filled matrix) is held to the properties the rule promises -- a permutation, contiguous nodes, ancestors
 behind descendants, separators that separate, a pattern containing the fill of a dense elimination without pivoting -- to recorded
 counts, to numpy.linalg.solve, and to the reference's own acceptance tests (test/test_backslash.jl, test/test_lu.jl).  No GPU."""
+import ctypes as C
 import os
 import re
 
@@ -262,3 +263,20 @@ def test_lu_entry_points_declared_and_exported(esp):
     for call in (esp.lu, esp.nested_dissection, lambda A: esp.lu_(A, A), lambda A: esp.factorize_(A, A), lambda A: esp.solve(A, None)):
         with pytest.raises(TypeError):
             call("not a matrix")
+
+
+def test_factor_form_entry_points_declared_and_exported(esp):
+    """the hook and the read-out of ILUAM's two forms: declared in the header, bound, exported, and on every class with .launches()"""
+    text = open(os.path.join(ROOT, "include", "esparse_hip.h")).read()
+    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    lib = esp._lib.load()
+    for name in ("esp_debug_iluam_form", "esp_debug_last_iluam_form"):
+        assert re.search(r"\bint32_t\s+%s\s*\(" % name, code) and name in esp._lib.SIGNATURES and hasattr(lib, name)
+    form = C.c_int32(7)
+    assert lib.esp_debug_iluam_form(None, 1) == -1 and lib.esp_debug_last_iluam_form(None, C.byref(form)) == -1 and form.value == 7
+    with_launches = [cls for cls in (esp.ILUAMPreconditioner, esp.BlockPreconditioner, esp.ILUKPreconditioner, esp.ColoredPreconditioner,
+                                     esp.ParallelILU0Preconditioner, esp.ILUTPreconditioner, esp.LUFactorization)]
+    for cls in with_launches:
+        assert callable(cls.launches) and callable(cls.debug_factor_form) and callable(cls.last_factor_form)
+    for cls in (esp.JacobiPreconditioner, esp.ILU0Preconditioner, esp.AMGPreconditioner, esp.SPAIPreconditioner):
+        assert not hasattr(cls, "launches") and not hasattr(cls, "debug_factor_form") and not hasattr(cls, "last_factor_form")
