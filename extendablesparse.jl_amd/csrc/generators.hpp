@@ -438,12 +438,14 @@ struct SharedDiv {
         const double e1 = fma(-den, r1, 1.0);
         r = fma(r1, e1, r1);
     }
+    // the three operations alone, for a caller that knows d and n to lie in the range (n = 0 gives 0: every step is exact)
+    __device__ __forceinline__ double quot_mid(double n) const {
+        const double q0 = n * r;
+        const double rem = fma(-d, q0, n);
+        return fma(rem, r, q0);
+    }
     __device__ __forceinline__ double quot(double n) const {
-        if (fast && (n == 0.0 || mid(n))) {
-            const double q0 = n * r;
-            const double rem = fma(-d, q0, n);
-            return fma(rem, r, q0);
-        }
+        if (fast && (n == 0.0 || mid(n))) return quot_mid(n);
         return n / d;
     }
 };

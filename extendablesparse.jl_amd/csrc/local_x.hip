@@ -20,11 +20,15 @@
 // A step that repeats the last one's structure stores the values alone (the template parameter KEEP, esp_handle::KeptStructure):
 // colptr and rowval -- 8 Z + 8 (N + 1) of the 16 Z + 8 (N + 1) bytes -- already lie where the handle's last fused flush wrote them.
 // The kernel was store-limited (393 us at 256^3, 273 without the rowval store; NOTES/round16.md); the KEEP form needs no rows in
-// LDS (28 KiB: four workgroups per CU) and takes 226 us.
+// LDS (28 KiB: four workgroups per CU) and took 233 us -- 181 us of them the stores (the kernel with constant values), the rest
+// the issue of the draws' arithmetic (NOTES/round20.md).  Two cuts in that arithmetic leave 205 us: a quotient by hx, hy or hz
+// goes through a reciprocal the thread forms once, and the x and y pair values of a column's lower neighbours come from the
+// lanes that formed them, through 8 KiB of LDS (36 KiB and 50 KiB: still four and three workgroups per CU) and one barrier.
 //
 // Where the values come from is the template parameter SRC (FdSource: the built-in generator's draws, the expressions and the
 // operation order of espgen::fdrand_part_k -- compiled without FMA contraction like every unit); a source that reads edge
-// coefficients from a caller's arrays fills the same StencilColumn.
+// coefficients from a caller's arrays fills the same StencilColumn in the same two steps: Consts (what a thread forms once),
+// upper() (the flags and the node's own pairs, vhi), then -- behind the barrier that publishes vhi[0] and vhi[1] -- lower().
 #include "generators.hpp"
 #include "local.hpp"
 #include "pair.hpp"
@@ -52,39 +56,74 @@ __device__ __forceinline__ double draw_if(bool on, F f) {
 }
 
 // the built-in generator (espgen::FdArgs without the producer's tables)
+//
+// The division.  A pair's value is u h h' / h'' with h'' one of the kernel's three arguments hx, hy, hz, so the reciprocal and its
+// refinement -- the part of the compiler's division that depends on the denominator alone -- are formed once per thread
+// (espgen::SharedDiv, Consts below) and a quotient is quot_mid()'s product, exact remainder and final fma: the bits of `/` whenever
+// denominator and numerator lie in SharedDiv::mid's range [2^-400, 2^400] or the numerator is 0.  u is 1, 0.1 + u' or u' with u' = 0
+// or in [2^-53, 1), so a numerator is 0 or lies in [2^-53 h h', 1.1 h h']: with every h in [2^-100, 2^100] that is inside
+// [2^-253, 2^201], and no product on the way is subnormal.  The launcher tests the three h once on the host (div_mid); the kernel
+// branches on the flag alone, no lane looks at an operand.  h = 1 / n for a grid the API accepts (1 <= n < 2^63): the flag is
+// always on there, and the plain division behind it serves a caller that hands other spacings to launch_pair_gen_predicted.
+//
+// Pair values through LDS.  The x pair towards l - 1 is the pair node l - 1 starts towards l -- the vhi[0] lane t - 1 forms, the
+// same expression on the same counter, the same bits --, the y pair towards l - nx the vhi[1] of lane t - nx.  upper() forms the
+// lane's own three pairs, the kernel leaves vhi[0] and vhi[1] in LDS at slot t, and behind one barrier lower() takes vlo[2] from
+// slot t - 1 (t >= 1) and vlo[1] from slot t - nx (t >= nx): the slot's lane owns a lower column of the same pair of buckets, so
+// it has a column and wrote.  The first lane's x value, the first nx lanes' y values and every z value are drawn as before.
 struct FdSource {
     i64 nx, ny, nz;
     double hx, hy, hz;
     u64 seed;
     int rand_mode;
     int fast;
+    int div_mid;  // every h in [2^-100, 2^100]: quot_mid() is the division (above)
     u64 magic_nx, magic_nxny;
     u64 zsub[3];  // 6 d GOLDEN for d = nx ny, nx, 1 (wrapping u64, formed once on the host): draw 0 of node g - d has the counter z0(g) - zsub
 
-    __device__ __forceinline__ void column(i64 g, StencilColumn &c) const {
-        i64 i, j, k;
-        espgen::fd_node(*this, g, &i, &j, &k);
-        const i64 nxy = nx * ny;
+    // what a thread forms once, whatever its column: the three denominators' reciprocals
+    struct Consts {
+        espgen::SharedDiv x, y, z;
+        __device__ __forceinline__ explicit Consts(const FdSource &s) : x(s.hx), y(s.hy), z(s.hz) {}
+    };
+    __device__ __forceinline__ double over(double n, const espgen::SharedDiv &by) const {
+        return div_mid ? by.quot_mid(n) : n / by.d;
+    }
+    // draw q of node gg: counter 6 gg + q (espgen::fd_rand_z); z0(g - d) = z0(g) - 6 d GOLDEN exactly (the arithmetic wraps)
+    __device__ __forceinline__ u64 z0(i64 g) const { return seed + (6ull * (u64)g + 1ull) * ESP_GOLDEN; }
+
+    // the column's flags and the three pairs its node starts (vhi[0], vhi[1]: what the lanes above take from LDS)
+    __device__ __forceinline__ void upper(const Consts &k, i64 g, StencilColumn &c) const {
+        i64 i, j, kk;
+        espgen::fd_node(*this, g, &i, &j, &kk);
         const int md = rand_mode;
-        // draw q of node gg: counter 6 gg + q (espgen::fd_rand_z); z0(g - d) = z0(g) - 6 d GOLDEN exactly (the arithmetic wraps)
-        const u64 zg = seed + (6ull * (u64)g + 1ull) * ESP_GOLDEN;
-        c.stride[0] = nxy, c.stride[1] = nx, c.stride[2] = 1;
-        c.lo[0] = k > 1, c.lo[1] = j > 1, c.lo[2] = i > 1;
-        c.hi[0] = i < nx, c.hi[1] = j < ny, c.hi[2] = k < nz;
+        const u64 zg = z0(g);
+        c.stride[0] = nx * ny, c.stride[1] = nx, c.stride[2] = 1;
+        c.lo[0] = kk > 1, c.lo[1] = j > 1, c.lo[2] = i > 1;
+        c.hi[0] = i < nx, c.hi[1] = j < ny, c.hi[2] = kk < nz;
         c.b[0] = i == 1 || i == nx;
         c.b[1] = ny > 2 && (j == 1 || j == ny);
-        c.b[2] = nz > 2 && (k == 1 || k == nz);
-        // A lower neighbour's or a boundary draw is formed only where some lane of the wave uses it (the kernel's step() does
-        // not look at a value whose flag is off: 0.0 stands there).  At 256^3 the y and z boundary draws are skipped in more than
-        // 99 % of the waves, the x boundary draw in half of them.
-        c.vlo[0] = draw_if(c.lo[0], [&] { return espgen::fd_rand_z(md, zg - zsub[0], 4) * hx * hy / hz; });
-        c.vlo[1] = draw_if(c.lo[1], [&] { return espgen::fd_rand_z(md, zg - zsub[1], 2) * hx * hz / hy; });
-        c.vlo[2] = draw_if(c.lo[2], [&] { return espgen::fd_rand_z(md, zg - zsub[2], 0) * hy * hz / hx; });
-        c.vhi[0] = espgen::fd_rand_z(md, zg, 0) * hy * hz / hx;
+        c.b[2] = nz > 2 && (kk == 1 || kk == nz);
+        c.vhi[0] = over(espgen::fd_rand_z(md, zg, 0) * hy * hz, k.x);
+        c.vhi[1] = over(espgen::fd_rand_z(md, zg, 2) * hx * hz, k.y);
+        c.vhi[2] = over(espgen::fd_rand_z(md, zg, 4) * hx * hy, k.z);
+    }
+    // the lower neighbours' pairs and the boundary terms; sx / sy: vhi[0] / vhi[1] of the workgroup's lanes, slot = lane.
+    // A draw is formed only where some lane of the wave uses it (the kernel's step() does not look at a value whose flag is off:
+    // 0.0 stands there).  At 256^3 the y and z boundary draws are skipped in more than 99 % of the waves, the x boundary draw in
+    // half of them, the x draw in all but a pair's first wave and the y draw in its upper four.
+    __device__ __forceinline__ void lower(const Consts &k, i64 g, int t, const double *sx, const double *sy, StencilColumn &c) const {
+        const int md = rand_mode;
+        const u64 zg = z0(g);
+        const bool x_in = c.lo[2] && t >= 1, y_in = c.lo[1] && (i64)t >= nx;
+        const double x_lds = sx[x_in ? t - 1 : 0], y_lds = sy[y_in ? t - (int)nx : 0];  // (slots 0 .. t - 1)
+        c.vlo[0] = draw_if(c.lo[0], [&] { return over(espgen::fd_rand_z(md, zg - zsub[0], 4) * hx * hy, k.z); });
+        const double y_drawn = draw_if(c.lo[1] && !y_in, [&] { return over(espgen::fd_rand_z(md, zg - zsub[1], 2) * hx * hz, k.y); });
+        const double x_drawn = draw_if(c.lo[2] && !x_in, [&] { return over(espgen::fd_rand_z(md, zg - zsub[2], 0) * hy * hz, k.x); });
+        c.vlo[1] = y_in ? y_lds : y_drawn;
+        c.vlo[2] = x_in ? x_lds : x_drawn;
         c.vb[0] = draw_if(c.b[0], [&] { return espgen::fd_rand_z(md, zg, 1) * hy * hz; });
-        c.vhi[1] = espgen::fd_rand_z(md, zg, 2) * hx * hz / hy;
         c.vb[1] = draw_if(c.b[1], [&] { return espgen::fd_rand_z(md, zg, 3) * hx * hz; });
-        c.vhi[2] = espgen::fd_rand_z(md, zg, 4) * hx * hy / hz;
         c.vb[2] = draw_if(c.b[2], [&] { return espgen::fd_rand_z(md, zg, 5) * hx * hy; });
     }
 };
@@ -99,6 +138,7 @@ __global__ __launch_bounds__(THREADS, 6) void pair_gen_pred_k(Args a, SRC src, c
     constexpr bool UPD = KEYS == 2;
     __shared__ u32 srow[KEEP ? 1 : G_CAP];  // the records' rows (1-based; not kept by the KEEP form) ...
     __shared__ double sval[G_CAP];          // ... and values
+    __shared__ double shx[THREADS], shy[THREADS];  // the lanes' vhi[0] / vhi[1] (FdSource: pair values through LDS)
     __shared__ u32 lw[WAVES];
 
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -117,9 +157,18 @@ __global__ __launch_bounds__(THREADS, 6) void pair_gen_pred_k(Args a, SRC src, c
     u32 row[G_ROWS];
 #pragma unroll
     for (int q = 0; q < G_ROWS; q++) present[q] = false, acc[q] = 0.0, row[q] = 0u;
+    // the node's own pairs first; the x and y ones go through LDS to the lanes whose columns they end in.  The barrier stands
+    // outside `has`: every lane of a workgroup that got past the uniform return above reaches it.
+    const typename SRC::Consts k(src);
+    StencilColumn c;
     if (has) {
-        StencilColumn c;
-        src.column(c_lo + t, c);
+        src.upper(k, c_lo + t, c);
+        shx[t] = c.vhi[0];
+        shy[t] = c.vhi[1];
+    }
+    __syncthreads();
+    if (has) {
+        src.lower(k, c_lo + t, t, shx, shy, c);
         const i64 l = c_lo + t + 1;
         auto step = [&](int q, bool on, double v) {
             if (!on) return;
@@ -175,7 +224,9 @@ bool launch_pair_gen_predicted(const Variant &v, unsigned grid, hipStream_t stre
                                u64 out_cap, bool keep) {
     // (whole columns, at most 512 of them per pair, rows that fit the records' 32 bits)
     if (!v.fresh || v.pieces || a.cl_bits < 0 || (2 << a.cl_bits) > THREADS || a.rb >= 32 || !a.colptr_out || !a.host_words) return false;
-    const FdSource src{fd.nx, fd.ny, fd.nz, fd.hx, fd.hy, fd.hz, fd.seed, fd.rand_mode, fd.fast, fd.magic_nx, fd.magic_nxny,
+    auto mid = [](double h) { return h >= 0x1.0p-100 && h <= 0x1.0p100; };  // (FdSource: the division)
+    const FdSource src{fd.nx, fd.ny, fd.nz, fd.hx, fd.hy, fd.hz, fd.seed, fd.rand_mode, fd.fast, mid(fd.hx) && mid(fd.hy) && mid(fd.hz),
+                       fd.magic_nx, fd.magic_nxny,
                        {6ull * (u64)(fd.nx * fd.ny) * ESP_GOLDEN, 6ull * (u64)fd.nx * ESP_GOLDEN, 6ull * ESP_GOLDEN}};
     return pair_for_keys(v.keys, [&](auto K) {
         constexpr int KEYS = decltype(K)::value;
