@@ -730,19 +730,6 @@ extern "C" int32_t esp_precon_amg_level(esp_precon *p, int32_t level, esp_handle
     return ESP_OK;
 }
 
-namespace {
-int32_t copy_out(esp_handle *h, void *dst, const void *d_src, size_t bytes, int32_t on_device) {
-    if (bytes == 0) return ESP_OK;
-    (void)hipSetDevice(h->device);
-    if (on_device) {
-        HIPCK(h, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToDevice, h->stream));
-        HIPCK(h, hipStreamSynchronize(h->stream));
-        return ESP_OK;
-    }
-    return d2h_pipelined(h, dst, d_src, bytes);
-}
-}  // namespace
-
 extern "C" int32_t esp_precon_amg_aggregates(esp_precon *p, int32_t level, int64_t *agg, int32_t on_device) {
     if (!p || p->kind != ESP_PRECON_AMG) return ESP_ERR_INVALID;
     if (p->amg->coarsen != ESP_AMG_COARSEN_SA) FAIL(p->h, ESP_ERR_INVALID, "esp_precon_amg_aggregates: a Ruge-Stueben hierarchy has a splitting, no aggregates");

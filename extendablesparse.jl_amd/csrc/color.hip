@@ -105,11 +105,6 @@ __global__ void color_maps_k(const double *__restrict__ spayload, i64 n, u32 *__
     newpos[i] = (u32)k;
     part[k] = 0u;
 }
-// out[i] = in[i] - sub as int64
-__global__ void color_widen_k(const u32 *__restrict__ in, i64 n, u32 sub, i64 *__restrict__ out) {
-    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (i64)(in[i] - sub);
-}
 
 // the colouring of h's stored pattern (checked, square, flushed): color (u32 n, 1-based colours), ptr = the colours' offsets in c
 int32_t color_graph(esp_handle *h, DevBuf &color, std::vector<i64> &ptr) {
@@ -155,59 +150,16 @@ int32_t color_maps(esp_handle *h, const DevBuf &color, i64 ncolors, DevBuf &perm
     if (n == 0) return ESP_OK;
     Temps tmp;
     CK(ensure(h, tmp.b[0], (size_t)n * 4 * 8));
-    u64 *ki = (u64 *)tmp.b[0].p, *ko = ki + n;
-    double *vi = (double *)(ko + n), *vo = vi + n;
+    const PingPong d = carve_pingpong(tmp.b[0].p, n);
     const unsigned g = grid_for(n, CT);
-    hipLaunchKernelGGL(color_keys_k, dim3(g), dim3(CT), 0, s, (const u32 *)color.p, n, ki, vi);
-    CK(ensure(h, h->segs, sizeof(i64) * 8));
-    CK(ensure(h, h->misc, 256));
-    i64 *segs = (i64 *)h->segs.p;
-    const i64 T = ceil_div<i64>(n, espradix::TILE);
-    hipLaunchKernelGGL(set_i64_k, dim3(1), dim3(1), 0, s, segs, (i64)0, n, (i64)0, T);
+    hipLaunchKernelGGL(color_keys_k, dim3(g), dim3(CT), 0, s, (const u32 *)color.p, n, d.k[0], d.v[0]);
     int B = 1;
     while (((i64)1 << B) < ncolors) B++;
-    for (int done = 0; done < B; done += 8) {
-        espradix::Pass ps;
-        ps.keys_in = ki;
-        ps.vals_in = vi;
-        ps.keys_out = ko;
-        ps.vals_out = vo;
-        ps.seg_start = segs;
-        ps.tile_first = segs + 2;
-        ps.S = 1;
-        ps.owner_P = 0;
-        ps.owner_n = 1;
-        ps.colshift = 0;
-        ps.base = 0;
-        ps.span = ~0ull;
-        ps.err = (u32 *)h->misc.p + 62;
-        ps.shift = done;
-        ps.bits = std::min(8, B - done);
-        CK(partition_pass(h, ps, T));
-        std::swap(ki, ko);
-        std::swap(vi, vo);
-    }
-    hipLaunchKernelGGL(color_maps_k, dim3(g), dim3(CT), 0, s, (const double *)vi, n, (u32 *)perm.p, (u32 *)newpos.p, (u32 *)part.p);
+    SortPair r;
+    CK(sort_segment_lsd(h, d.half(0), d, n, 0, B, 62, &r));
+    hipLaunchKernelGGL(color_maps_k, dim3(g), dim3(CT), 0, s, r.v, n, (u32 *)perm.p, (u32 *)newpos.p, (u32 *)part.p);
     HIPCK(h, hipGetLastError());
     HIPCK(h, hipStreamSynchronize(s));
-    return ESP_OK;
-}
-
-// n values of a u32 device array as int64 (minus sub) into the caller's host or device array
-int32_t color_export(esp_handle *h, const DevBuf &src, u32 sub, int64_t *out, int32_t on_device) {
-    const i64 n = h->n;
-    if (n == 0) return ESP_OK;
-    (void)hipSetDevice(h->device);
-    Temps tmp;
-    i64 *dst = out;
-    if (!on_device) {
-        CK(ensure(h, tmp.b[0], sizeof(i64) * (size_t)n));
-        dst = (i64 *)tmp.b[0].p;
-    }
-    hipLaunchKernelGGL(color_widen_k, dim3(grid_for(n, CT)), dim3(CT), 0, h->stream, (const u32 *)src.p, n, sub, dst);
-    HIPCK(h, hipGetLastError());
-    if (!on_device) CK(d2h_pipelined(h, out, dst, sizeof(i64) * (size_t)n));
-    HIPCK(h, hipStreamSynchronize(h->stream));
     return ESP_OK;
 }
 
@@ -265,7 +217,7 @@ extern "C" int32_t esp_graph_coloring(esp_handle *h, int64_t *ncolors, int64_t *
     DevBuf col;
     std::vector<i64> ptr;
     int32_t st = color_graph(h, col, ptr);
-    if (st == ESP_OK && color) st = color_export(h, col, 1u, color, on_device);
+    if (st == ESP_OK && color) st = export_u32_as_i64(h, col.p, h->n, 1u, color, on_device);
     (void)hipStreamSynchronize(h->stream);
     release(col);
     if (st == ESP_OK) *ncolors = (i64)ptr.size() - 1;
@@ -302,13 +254,13 @@ extern "C" int32_t esp_precon_colored_info(esp_precon *p, int64_t out[2]) {
 extern "C" int32_t esp_precon_colored_colors(esp_precon *p, int64_t *color, int32_t on_device) {
     if (!p || p->kind != ESP_PRECON_COLORED || !color) return ESP_ERR_INVALID;
     CK(colored_current(p, "esp_precon_colored_colors"));
-    return color_export(p->h, p->col_color, 1u, color, on_device);
+    return export_u32_as_i64(p->h, p->col_color.p, p->h->n, 1u, color, on_device);
 }
 
 extern "C" int32_t esp_precon_colored_perm(esp_precon *p, int64_t *c, int32_t on_device) {
     if (!p || p->kind != ESP_PRECON_COLORED || !c) return ESP_ERR_INVALID;
     CK(colored_current(p, "esp_precon_colored_perm"));
-    return color_export(p->h, p->col_perm, 0u, c, on_device);
+    return export_u32_as_i64(p->h, p->col_perm.p, p->h->n, 0u, c, on_device);
 }
 
 extern "C" int32_t esp_precon_colored_matrix(esp_precon *p, esp_handle **b) {

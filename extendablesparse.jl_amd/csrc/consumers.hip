@@ -214,41 +214,14 @@ int32_t build_csr(esp_handle *h) {
         CK(ensure(h, h->csr_col, sizeof(u32) * (size_t)Z));
         // scratch: keys A/B, payload A/B, colidx
         CK(ensure(h, h->csr_tmp, sizeof(u64) * (size_t)Z * 5));
-        u64 *kA = (u64 *)h->csr_tmp.p, *kB = kA + Z;
-        double *vA = (double *)(kB + Z), *vB = vA + Z;
-        u64 *colidx = (u64 *)(vB + Z);
+        void *colidx;
+        const PingPong d = carve_pingpong(h->csr_tmp.p, Z, &colidx);
         hipLaunchKernelGGL(csr_keys_k, dim3(grid_for(h->n, 256)), dim3(256), 0, h->stream, (const i64 *)h->colptr.p, (const i64 *)h->rowval.p,
-                           h->n, kA, vA, colidx);
-        CK(ensure(h, h->segs, sizeof(i64) * 8));
-        CK(ensure(h, h->misc, 256));
-        i64 *segs = (i64 *)h->segs.p;
-        const i64 T = ceil_div<i64>(Z, espradix::TILE);
-        hipLaunchKernelGGL(set_i64_k, dim3(1), dim3(1), 0, h->stream, segs, (i64)0, Z, (i64)0, T);
-        u64 *ki = kA, *ko = kB;
-        double *vi = vA, *vo = vB;
-        for (int done = 0; done < h->L.rb; done += 8) {  // stable LSD sort by row: columns stay ascending
-            espradix::Pass p;
-            p.keys_in = ki;
-            p.vals_in = vi;
-            p.keys_out = ko;
-            p.vals_out = vo;
-            p.seg_start = segs;
-            p.tile_first = segs + 2;
-            p.S = 1;
-            p.owner_P = 0;
-            p.owner_n = 1;
-            p.colshift = 0;
-            p.base = 0;
-            p.span = ~0ull;
-            p.err = (u32 *)h->misc.p + 62;
-            p.shift = done;
-            p.bits = std::min(8, h->L.rb - done);
-            CK(partition_pass(h, p, T));
-            std::swap(ki, ko);
-            std::swap(vi, vo);
-        }
-        hipLaunchKernelGGL(csr_finish_k, dim3(grid_for(Z, 256)), dim3(256), 0, h->stream, (const u64 *)ki, (const double *)vi,
-                           (const u64 *)colidx, Z, (u32 *)h->csr_perm.p, (u32 *)h->csr_col.p, rowptr);
+                           h->n, d.k[0], d.v[0], (u64 *)colidx);
+        SortPair r;
+        CK(sort_segment_lsd(h, d.half(0), d, Z, 0, h->L.rb, 62, &r));  // stable LSD sort by row: columns stay ascending
+        hipLaunchKernelGGL(csr_finish_k, dim3(grid_for(Z, 256)), dim3(256), 0, h->stream, r.k, r.v, (const u64 *)colidx, Z,
+                           (u32 *)h->csr_perm.p, (u32 *)h->csr_col.p, rowptr);
     }
     // rowptr[i+1] holds the end of row i (0 for empty rows): running maximum = start of the next row
     espscan::exclusive<u64, true>(h->stream, rowptr, rowptr, M2, rowptr + M2);

@@ -749,37 +749,11 @@ int32_t flush_pre_tail(esp_handle *h, int mode, i64 *Zn, bool *served) {
         // output, serve as the other half of the ping-pong until then)
         CK(ensure(h, h->keys2, sizeof(u64) * (size_t)(E0 + T)));
         CK(ensure(h, h->vals2, sizeof(double) * (size_t)(E0 + T)));
-        CK(ensure(h, h->segs, sizeof(i64) * 8));
-        i64 *segs = (i64 *)h->segs.p;
-        const i64 TR = ceil_div<i64>(T, espradix::TILE);
-        hipLaunchKernelGGL(set_i64_k, dim3(1), dim3(1), 0, h->stream, segs, (i64)0, T, (i64)0, TR);
         HIPCK(h, hipMemsetAsync(d_maxlen, 0, 64, h->stream));
-        const int npass = (pp.pb + 7) / 8;
-        const u64 *ki = (const u64 *)h->keys.p + E0;
-        const double *vi = (const double *)h->vals.p + E0;
-        bool to_new = (npass & 1) != 0;
-        for (int done = 0; done < pp.pb; done += 8) {
-            espradix::Pass p;
-            p.keys_in = ki;
-            p.vals_in = vi;
-            p.keys_out = to_new ? (u64 *)h->newkey.p : (u64 *)h->keys2.p;
-            p.vals_out = to_new ? (double *)h->newval.p : (double *)h->vals2.p;
-            p.seg_start = segs;
-            p.tile_first = segs + 2;
-            p.S = 1;
-            p.owner_P = 0;
-            p.owner_n = 1;
-            p.colshift = 0;
-            p.base = h->win_base;
-            p.span = h->win_span;
-            p.err = (u32 *)h->misc.p + 60;
-            p.shift = pp.K - pp.pb + done;
-            p.bits = std::min(8, pp.pb - done);
-            CK(partition_pass(h, p, TR));
-            ki = p.keys_out;
-            vi = p.vals_out;
-            to_new = !to_new;
-        }
+        const PingPong d{{(u64 *)h->newkey.p, (u64 *)h->keys2.p}, {(double *)h->newval.p, (double *)h->vals2.p}};
+        SortPair r;
+        CK(sort_segment_lsd(h, SortPair{(const u64 *)h->keys.p + E0, (const double *)h->vals.p + E0}, d, T, pp.K - pp.pb, pp.pb, 60, &r,
+                            h->win_base, h->win_span));
         {
             Span sp(h, ESP_ST_SCAN);
             hipLaunchKernelGGL(tail_bucket_starts_k, dim3(grid_for(NB + 1, 256)), dim3(256), 0, h->stream, (const u64 *)h->newkey.p, T,

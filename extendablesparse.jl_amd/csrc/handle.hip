@@ -1101,6 +1101,41 @@ int32_t d2h_pipelined(esp_handle *h, void *dst, const void *d_src, size_t bytes)
     return ESP_OK;
 }
 
+// a device array into the caller's host or device array; the copy is over when this returns
+int32_t copy_out(esp_handle *h, void *dst, const void *d_src, size_t bytes, int32_t on_device) {
+    if (bytes == 0) return ESP_OK;
+    (void)hipSetDevice(h->device);
+    if (on_device) {
+        HIPCK(h, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToDevice, h->stream));
+        HIPCK(h, hipStreamSynchronize(h->stream));
+        return ESP_OK;
+    }
+    return d2h_pipelined(h, dst, d_src, bytes);
+}
+
+// out[i] = in[i] - sub as int64
+static __global__ void widen_u32_k(const u32 *__restrict__ in, i64 n, u32 sub, i64 *__restrict__ out) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (i64)(in[i] - sub);
+}
+// n values of a u32 device array as int64 (minus sub) into the caller's host or device array (the readouts of colours, permutations
+// and tree nodes: once per call, through a temporary when the caller's array is on the host)
+int32_t export_u32_as_i64(esp_handle *h, const void *d_src, i64 n, u32 sub, int64_t *out, int32_t on_device) {
+    if (n == 0) return ESP_OK;
+    (void)hipSetDevice(h->device);
+    Temps tmp;
+    i64 *dst = out;
+    if (!on_device) {
+        CK(ensure(h, tmp.b[0], sizeof(i64) * (size_t)n));
+        dst = (i64 *)tmp.b[0].p;
+    }
+    hipLaunchKernelGGL(widen_u32_k, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const u32 *)d_src, n, sub, dst);
+    HIPCK(h, hipGetLastError());
+    if (!on_device) CK(d2h_pipelined(h, out, dst, sizeof(i64) * (size_t)n));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    return ESP_OK;
+}
+
 // Pageable host memory -> device: the (multi-threaded) host copy of chunk i+1 into one pinned half overlaps the PCIe transfer
 // of chunk i out of the other.  A plain hipMemcpy from pageable memory stages through the runtime's own buffer on one thread
 // (the values of a 7 10^7-entry matrix: 560 MB in ~30 ms; this: ~13).  Returns when the device holds the data.

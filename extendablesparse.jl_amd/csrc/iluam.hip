@@ -306,9 +306,9 @@ int32_t build_schedule(esp_precon *p, IluamSched &s) {
     // scratch: sort keys and payloads (two of each), level, in-degree, two frontiers, two counters
     Scratch tmp{h};
     CK(ensure(h, tmp.b, (size_t)n * (4 * 8 + 4 * 4) + 16));
-    u64 *kA = (u64 *)tmp.b.p, *kB = kA + n;
-    double *vA = (double *)(kB + n), *vB = vA + n;
-    u32 *level = (u32 *)(vB + n), *indeg = level + n, *front[2] = {indeg + n, indeg + 2 * n}, *cnt = indeg + 3 * n;
+    void *rest;
+    const PingPong d = carve_pingpong(tmp.b.p, n, &rest);
+    u32 *level = (u32 *)rest, *indeg = level + n, *front[2] = {indeg + n, indeg + 2 * n}, *cnt = indeg + 3 * n;
     const Pattern g = pattern_of(p);
     std::vector<u32> loff(1, 0u);
     HIPCK(h, hipMemsetAsync(cnt, 0, 8, h->stream));
@@ -327,40 +327,14 @@ int32_t build_schedule(esp_precon *p, IluamSched &s) {
         FAIL(h, ESP_ERR_HIP, "iluam: the level analysis reached %lld of %lld nodes", (long long)loff.back(), (long long)n);
     s.levels = (i64)loff.size() - 1;
     // nodes sorted by (level, index): a stable LSD sort on the level bits of the nodes in index order
-    hipLaunchKernelGGL(level_keys_k, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const u32 *)level, n, kA, vA);
-    CK(ensure(h, h->segs, sizeof(i64) * 8));
-    CK(ensure(h, h->misc, 256));
-    i64 *segs = (i64 *)h->segs.p;
-    const i64 T = ceil_div<i64>(n, espradix::TILE);
-    hipLaunchKernelGGL(set_i64_k, dim3(1), dim3(1), 0, h->stream, segs, (i64)0, n, (i64)0, T);
+    hipLaunchKernelGGL(level_keys_k, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const u32 *)level, n, d.k[0], d.v[0]);
     int B = 1;
     while (((i64)1 << B) < s.levels) B++;
-    u64 *ki = kA, *ko = kB;
-    double *vi = vA, *vo = vB;
-    for (int done = 0; done < B; done += 8) {
-        espradix::Pass ps;
-        ps.keys_in = ki;
-        ps.vals_in = vi;
-        ps.keys_out = ko;
-        ps.vals_out = vo;
-        ps.seg_start = segs;
-        ps.tile_first = segs + 2;
-        ps.S = 1;
-        ps.owner_P = 0;
-        ps.owner_n = 1;
-        ps.colshift = 0;
-        ps.base = 0;
-        ps.span = ~0ull;
-        ps.err = (u32 *)h->misc.p + 62;
-        ps.shift = done;
-        ps.bits = std::min(8, B - done);
-        CK(partition_pass(h, ps, T));
-        std::swap(ki, ko);
-        std::swap(vi, vo);
-    }
+    SortPair r;
+    CK(sort_segment_lsd(h, d.half(0), d, n, 0, B, 62, &r));
     CK(ensure(h, s.order, sizeof(u32) * (size_t)n));
     CK(ensure(h, s.loff, sizeof(u32) * loff.size()));
-    hipLaunchKernelGGL(level_order_k, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, (const double *)vi, n, (u32 *)s.order.p);
+    hipLaunchKernelGGL(level_order_k, dim3(grid_for(n, 256)), dim3(256), 0, h->stream, r.v, n, (u32 *)s.order.p);
     HIPCK(h, hipMemcpyAsync(s.loff.p, loff.data(), sizeof(u32) * loff.size(), hipMemcpyHostToDevice, h->stream));
     HIPCK(h, hipGetLastError());
     HIPCK(h, hipStreamSynchronize(h->stream));
@@ -490,13 +464,7 @@ extern "C" int32_t esp_precon_get_factor(esp_precon *p, double *nzval, int32_t o
     if (spai) CK(spai_follow_stream(p));
     const void *src = !spai ? p->fval.p : p->spai_order == 0 ? p->diag.p : spai_applied(p)->nzval.p;
     const size_t bytes = sizeof(double) * (size_t)(!spai ? p->nnz : p->spai_order == 0 ? p->n : spai_applied(p)->nnz);
-    if (bytes == 0) return ESP_OK;
-    if (on_device) {
-        HIPCK(h, hipMemcpyAsync(nzval, src, bytes, hipMemcpyDeviceToDevice, h->stream));
-        HIPCK(h, hipStreamSynchronize(h->stream));
-        return ESP_OK;
-    }
-    return d2h_pipelined(h, nzval, src, bytes);
+    return copy_out(h, nzval, src, bytes, on_device);
 }
 
 extern "C" int32_t esp_precon_levels(esp_precon *p, int64_t out[3]) {

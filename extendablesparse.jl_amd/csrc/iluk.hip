@@ -364,16 +364,7 @@ extern "C" int32_t esp_precon_iluk_matrix(esp_precon *p, esp_handle **b) {
 
 extern "C" int32_t esp_precon_iluk_levels(esp_precon *p, int32_t *lev, int32_t on_device) {
     if (!p || p->kind != ESP_PRECON_ILUK || !lev) return ESP_ERR_INVALID;
-    esp_handle *h = p->h;
-    (void)hipSetDevice(h->device);
-    const size_t bytes = sizeof(int32_t) * (size_t)p->iluk_stats[0];
-    if (bytes == 0) return ESP_OK;
-    if (on_device) {
-        HIPCK(h, hipMemcpyAsync(lev, p->iluk_lev.p, bytes, hipMemcpyDeviceToDevice, h->stream));
-        HIPCK(h, hipStreamSynchronize(h->stream));
-        return ESP_OK;
-    }
-    return d2h_pipelined(h, lev, p->iluk_lev.p, bytes);
+    return copy_out(p->h, lev, p->iluk_lev.p, sizeof(int32_t) * (size_t)p->iluk_stats[0], on_device);
 }
 
 extern "C" int32_t esp_precon_iluk_stats(esp_precon *p, int64_t out[4]) {

@@ -1,9 +1,11 @@
 // internal.hpp -- what the translation units of libesparse_hip share: the handle, the error / timing helpers, the plan
 // and partition records, and the prototypes of the functions that cross file boundaries (hidden visibility: nothing
 // of this is part of the C ABI, which is include/esparse_hip.h).
-//   handle.hip     lifetime, buffers, append (esp_stage_begin / esp_commit / esp_append_*), CSC in and out, timing, debug
+//   handle.hip     lifetime, buffers, append (esp_stage_begin / esp_commit / esp_append_*), CSC in and out, timing, debug;
+//                  the readouts into a caller's host or device array (copy_out, export_u32_as_i64)
 //   produce.hip    device-side producers (esp_generate_*): plain, producer-side partition (run lists), item partition
-//   partition.hip  the plan (prefix bits, back-off), radix passes, run-based single pass, sort_msd
+//   partition.hip  the plan (prefix bits, back-off), radix passes, run-based single pass, sort_msd;
+//                  sort_segment_lsd, the one driver of every single-segment LSD sort (pending buffer, run list, tail, rows, levels, colours)
 //   flush.hip      esp_flush: bucket kernel launch, join with a stored CSC, batch + tail, general path
 //   shard.hip      column shards (esp_shard_*) and the group API (group.hpp: exchange policy + RCCL transport)
 //   consumers.hip  what reads or edits the assembled CSC: getindex, dropzeros, pattern hash, mul!, Dirichlet, Jacobi / ILU0
@@ -835,6 +837,9 @@ int32_t ensure_bounce(esp_handle *h);
 void par_memcpy(void *dst, const void *src, size_t bytes);
 void host_run_parts(int parts, const std::function<void(int)> &fn);
 int32_t d2h_pipelined(esp_handle *h, void *dst, const void *d_src, size_t bytes);
+// a device array into the caller's host or device array, synchronised / n values of a u32 device array as int64 minus sub likewise
+int32_t copy_out(esp_handle *h, void *dst, const void *d_src, size_t bytes, int32_t on_device);
+int32_t export_u32_as_i64(esp_handle *h, const void *d_src, i64 n, u32 sub, int64_t *out, int32_t on_device);
 // pageable host memory -> device through the same two pinned bounce buffers (the host copy of chunk i+1 overlaps the transfer
 // of chunk i); returns when the device holds the data
 int32_t h2d_pipelined(esp_handle *h, void *d_dst, const void *src, size_t bytes);
@@ -856,6 +861,32 @@ bool lazy_items_wanted(const esp_handle *h, int kind);
 int32_t settle_offset(esp_handle *h);
 int32_t item_produce_fem(esp_handle *h, const espgen::FemArgs &fa, i64 E, bool *took);
 int32_t partition_pass(esp_handle *h, espradix::Pass &p, i64 max_tiles);
+// partition.hip: the stable LSD sort of ONE segment of count (key, payload) pairs on the key bits [shift0, shift0 + bits), 8 bits per
+// pass (the last one: what is left).  The passes alternate between the two halves of d.  A source that is one of the halves sends
+// the first pass to the other one; a source of its own (read only) is left alone and the last pass lands in half 0.  *out: the pair
+// that holds the result (src itself when bits == 0).  err_slot: the u32 word of h->misc that a key outside [base, base + span) sets.
+struct SortPair {
+    const u64 *k;
+    const double *v;
+};
+struct PingPong {
+    u64 *k[2];
+    double *v[2];
+    SortPair half(int i) const { return SortPair{k[i], v[i]}; }
+};
+int32_t sort_segment_lsd(esp_handle *h, SortPair src, const PingPong &d, i64 count, int shift0, int bits, int err_slot, SortPair *out,
+                         u64 base = 0, u64 span = ~0ull);
+// the two halves of n pairs each at the front of one allocation of at least 4 * n * 8 bytes: keys 0, keys 1, payloads 0, payloads 1;
+// *rest: where the caller's further arrays begin
+static inline PingPong carve_pingpong(void *p, i64 n, void **rest = nullptr) {
+    PingPong d;
+    d.k[0] = (u64 *)p;
+    d.k[1] = d.k[0] + n;
+    d.v[0] = (double *)(d.k[1] + n);
+    d.v[1] = d.v[0] + n;
+    if (rest) *rest = d.v[1] + n;
+    return d;
+}
 int32_t sort_pending_lsd(esp_handle *h, const u64 **sk, const double **sv);
 int32_t chunk_arrays(esp_handle *h, i64 Ccap, int pb, ChunkArrays *out, bool keep_plan = false);
 double plan_entries(i64 E, int K, u64 span);

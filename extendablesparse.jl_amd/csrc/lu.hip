@@ -337,12 +337,6 @@ __global__ __launch_bounds__(LT) void lu_bfill_k(Struct x, espfold::Csc A, const
     if (lane == 0 && q != end) atomicMax(&st[3], 1ull);
 }
 
-// out[i] = in[i] as int64
-__global__ __launch_bounds__(LT) void lu_widen_k(const u32 *__restrict__ in, i64 n, i64 *__restrict__ out) {
-    const i64 i = (i64)blockIdx.x * LT + threadIdx.x;
-    if (i < n) out[i] = (i64)in[i];
-}
-
 // ---- the host side -----------------------------------------------------------------------------------------------------------------
 // what an ordering leaves: u32 n each but anc (one u32 n per round), released on every way out unless taken over
 struct Order {
@@ -459,47 +453,21 @@ int32_t lu_order(esp_handle *h, Order &o) {
     CK(ensure(h, sortb, (size_t)n * 4 * 8));
     CK(ensure(h, head, sizeof(u32) * (size_t)n));
     CK(ensure(h, st, sizeof(u64)));
-    u64 *ki = (u64 *)sortb.p, *ko = ki + n;
-    double *vi = (double *)(ko + n), *vo = vi + n;
+    const PingPong d = carve_pingpong(sortb.p, n);
     const unsigned g = grid_for(n, LT);
     int nb = 1, db = 1;
     while (((i64)1 << nb) < n) nb++;
     while (((i64)1 << db) < o.rounds) db++;
     hipLaunchKernelGGL(lu_keys_k, dim3(g), dim3(LT), 0, s, (const u32 *)o.level.p, (const u32 *const *)o.ancptr.p, n, (u32)o.deepest, nb,
-                       (u32 *)o.root.p, ki, vi);
-    CK(ensure(h, h->segs, sizeof(i64) * 8));
-    CK(ensure(h, h->misc, 256));
-    i64 *segs = (i64 *)h->segs.p;
-    const i64 T = ceil_div<i64>(n, espradix::TILE);
-    hipLaunchKernelGGL(set_i64_k, dim3(1), dim3(1), 0, s, segs, (i64)0, n, (i64)0, T);
-    const int B = nb + db;
-    for (int done = 0; done < B; done += 8) {
-        espradix::Pass ps;
-        ps.keys_in = ki;
-        ps.vals_in = vi;
-        ps.keys_out = ko;
-        ps.vals_out = vo;
-        ps.seg_start = segs;
-        ps.tile_first = segs + 2;
-        ps.S = 1;
-        ps.owner_P = 0;
-        ps.owner_n = 1;
-        ps.colshift = 0;
-        ps.base = 0;
-        ps.span = ~0ull;
-        ps.err = (u32 *)h->misc.p + 62;
-        ps.shift = done;
-        ps.bits = std::min(8, B - done);
-        CK(partition_pass(h, ps, T));
-        std::swap(ki, ko);
-        std::swap(vi, vo);
-    }
-    hipLaunchKernelGGL(lu_maps_k, dim3(g), dim3(LT), 0, s, (const u64 *)ki, (const double *)vi, n, (u32 *)o.perm.p, (u32 *)o.newpos.p, (u32 *)head.p);
+                       (u32 *)o.root.p, d.k[0], d.v[0]);
+    SortPair r;
+    CK(sort_segment_lsd(h, d.half(0), d, n, 0, nb + db, 62, &r));
+    hipLaunchKernelGGL(lu_maps_k, dim3(g), dim3(LT), 0, s, r.k, r.v, n, (u32 *)o.perm.p, (u32 *)o.newpos.p, (u32 *)head.p);
     int l = 0;
     CK(scan_inplace<u32, true>(h, (u32 *)head.p, n, ws, &l));
     HIPCK(h, hipMemsetAsync(o.nsize.p, 0, sizeof(u32) * (size_t)n, s));
     HIPCK(h, hipMemsetAsync(st.p, 0, sizeof(u64), s));
-    hipLaunchKernelGGL(lu_nodes_k, dim3(g), dim3(LT), 0, s, (const u64 *)ki, (const u32 *)head.p, n, (u32 *)o.nstart.p, (u32 *)o.nsize.p,
+    hipLaunchKernelGGL(lu_nodes_k, dim3(g), dim3(LT), 0, s, r.k, (const u32 *)head.p, n, (u32 *)o.nstart.p, (u32 *)o.nsize.p,
                        (unsigned long long *)st.p);
     HIPCK(h, hipGetLastError());
     HIPCK(h, hipMemcpyAsync(h->pin_scalar, st.p, sizeof(u64), hipMemcpyDeviceToHost, s));
@@ -510,26 +478,8 @@ int32_t lu_order(esp_handle *h, Order &o) {
 
 // n values of a u32 device array into the caller's host or device array: as int64 (wide) or as they are (int32)
 int32_t lu_export(esp_handle *h, const DevBuf &src, void *out, bool wide, int32_t on_device) {
-    const i64 n = h->n;
-    if (n == 0) return ESP_OK;
-    (void)hipSetDevice(h->device);
-    if (!wide) {
-        if (!on_device) return d2h_pipelined(h, out, src.p, sizeof(u32) * (size_t)n);
-        HIPCK(h, hipMemcpyAsync(out, src.p, sizeof(u32) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
-        HIPCK(h, hipStreamSynchronize(h->stream));
-        return ESP_OK;
-    }
-    Temps tmp;
-    i64 *dst = (i64 *)out;
-    if (!on_device) {
-        CK(ensure(h, tmp.b[0], sizeof(i64) * (size_t)n));
-        dst = (i64 *)tmp.b[0].p;
-    }
-    hipLaunchKernelGGL(lu_widen_k, dim3(grid_for(n, LT)), dim3(LT), 0, h->stream, (const u32 *)src.p, n, dst);
-    HIPCK(h, hipGetLastError());
-    if (!on_device) CK(d2h_pipelined(h, out, dst, sizeof(i64) * (size_t)n));
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    return ESP_OK;
+    if (wide) return export_u32_as_i64(h, src.p, h->n, 0u, (int64_t *)out, on_device);
+    return copy_out(h, out, src.p, sizeof(u32) * (size_t)h->n, on_device);
 }
 
 // derived_update's builder: the ordering, the tree and B from A's current CSC; B installed in p->der.bh, src in p->der.src, the maps

@@ -52,46 +52,55 @@ int32_t partition_pass(esp_handle *h, espradix::Pass &p, i64 max_tiles) {
     return ESP_OK;
 }
 
+// The stable LSD sort of one segment (internal.hpp): every single-segment sort of the library fills its Pass here.
+int32_t sort_segment_lsd(esp_handle *h, SortPair src, const PingPong &d, i64 count, int shift0, int bits, int err_slot, SortPair *out,
+                         u64 base, u64 span) {
+    CK(ensure(h, h->segs, sizeof(i64) * 8));
+    CK(ensure(h, h->misc, 256));
+    i64 *segs = (i64 *)h->segs.p;
+    const i64 T = ceil_div<i64>(count, espradix::TILE);
+    hipLaunchKernelGGL(set_i64_k, dim3(1), dim3(1), 0, h->stream, segs, (i64)0, count, (i64)0, T);
+    const int npass = (bits + 7) / 8;
+    int to = src.k == d.k[0] ? 1 : src.k == d.k[1] ? 0 : (npass - 1) & 1;
+    for (int done = 0; done < bits; done += 8, to ^= 1) {
+        espradix::Pass p{};  // (raw_*, k32_* and hist: zero; partition_pass points hist)
+        p.keys_in = src.k;
+        p.vals_in = src.v;
+        p.keys_out = d.k[to];
+        p.vals_out = d.v[to];
+        p.seg_start = segs;
+        p.tile_first = segs + 2;
+        p.S = 1;
+        p.shift = shift0 + done;
+        p.base = base;
+        p.span = span;
+        p.err = (u32 *)h->misc.p + err_slot;
+        p.bits = std::min(8, bits - done);
+        p.owner_P = 0;
+        p.owner_n = 1;
+        p.colshift = 0;
+        p.keys_only = 0;
+        CK(partition_pass(h, p, T));
+        src = d.half(to);
+    }
+    *out = src;
+    return ESP_OK;
+}
+
 // full stable LSD sort of the pending entries on their (col,row) bits.  Result in *sk/*sv.
 int32_t sort_pending_lsd(esp_handle *h, const u64 **sk, const double **sv) {
     const i64 E = h->count;
     CK(ensure(h, h->keys2, sizeof(u64) * (size_t)E));
     CK(ensure(h, h->vals2, sizeof(double) * (size_t)E));
-    CK(ensure(h, h->segs, sizeof(i64) * 8));
-    CK(ensure(h, h->misc, 256));
-    const i64 T = ceil_div<i64>(E, espradix::TILE);
-    i64 *segs = (i64 *)h->segs.p;
-    hipLaunchKernelGGL(set_i64_k, dim3(1), dim3(1), 0, h->stream, segs, (i64)0, E, (i64)0, T);
-    u64 *kin = (u64 *)h->keys.p, *kout = (u64 *)h->keys2.p;
-    double *vin = (double *)h->vals.p, *vout = (double *)h->vals2.p;
-    const int K = h->L.sort_bits();
-    for (int done = 0; done < K; done += 8) {
-        espradix::Pass p;
-        p.keys_in = kin;
-        p.vals_in = vin;
-        p.keys_out = kout;
-        p.vals_out = vout;
-        p.seg_start = segs;
-        p.tile_first = segs + 2;
-        p.S = 1;
-        p.owner_P = 0;
-        p.owner_n = 1;
-        p.colshift = 0;
-        p.base = 0;
-        p.span = ~0ull;
-        p.err = (u32 *)h->misc.p + 60;
-        p.shift = done;
-        p.bits = std::min(8, K - done);
-        CK(partition_pass(h, p, T));
-        std::swap(kin, kout);
-        std::swap(vin, vout);
-    }
+    const PingPong d{{(u64 *)h->keys.p, (u64 *)h->keys2.p}, {(double *)h->vals.p, (double *)h->vals2.p}};
+    SortPair r;
+    CK(sort_segment_lsd(h, d.half(0), d, E, 0, h->L.sort_bits(), 60, &r));
     HIPCK(h, hipGetLastError());
-    *sk = kin;
-    *sv = vin;
+    *sk = r.k;
+    *sv = r.v;
     // make keys/vals the scratch pair for the caller: after an odd number of passes the sorted
     // data lives in keys2/vals2
-    if (kin != (u64 *)h->keys.p) {
+    if (r.k != (u64 *)h->keys.p) {
         std::swap(h->keys, h->keys2);
         std::swap(h->vals, h->vals2);
         // capacities may differ: keep cap consistent with the smaller of the two
@@ -412,44 +421,16 @@ int32_t run_partition(esp_handle *h, const u64 *kin, const double *vin, u64 *kou
         sp.add(1);
     }
     // stable sort of the run list by digit with the ordinary 8-bit passes (chunk order is kept)
-    {
-        CK(ensure(h, h->segs, sizeof(i64) * 8));
-        i64 *segs = (i64 *)h->segs.p;
-        const i64 TR = ceil_div<i64>(R, espradix::TILE);
-        hipLaunchKernelGGL(set_i64_k, dim3(1), dim3(1), 0, h->stream, segs, (i64)0, R, (i64)0, TR);
-        u64 *ki = lk, *ko = lk2;
-        double *vi = lv, *vo = lv2;
-        for (int done = 0; done < pb; done += 8) {
-            espradix::Pass p;
-            p.keys_in = ki;
-            p.vals_in = vi;
-            p.keys_out = ko;
-            p.vals_out = vo;
-            p.seg_start = segs;
-            p.tile_first = segs + 2;
-            p.S = 1;
-            p.owner_P = 0;
-            p.owner_n = 1;
-            p.colshift = 0;
-            p.base = 0;
-            p.span = ~0ull;
-            p.err = (u32 *)h->misc.p + 62;
-            p.shift = done;
-            p.bits = std::min(8, pb - done);
-            CK(partition_pass(h, p, TR));
-            std::swap(ki, ko);
-            std::swap(vi, vo);
-        }
-        lk = ki;
-        lv = vi;
-    }
+    const PingPong lists{{lk, lk2}, {lv, lv2}};
+    SortPair sl;
+    CK(sort_segment_lsd(h, lists.half(0), lists, R, 0, pb, 62, &sl));
     {
         Span sp(h, ESP_ST_SCAN);
-        hipLaunchKernelGGL(esprun::run_counts_k, dim3(grid_for(R + 1, 256)), dim3(256), 0, h->stream, (const double *)lv, R, sc);
+        hipLaunchKernelGGL(esprun::run_counts_k, dim3(grid_for(R + 1, 256)), dim3(256), 0, h->stream, sl.v, R, sc);
         sp.add(1 + espscan::exclusive<u64, false>(h->stream, sc, sc, R + 1, sc + R + 1));
-        hipLaunchKernelGGL(esprun::run_heads_k, dim3(grid_for(R, 256)), dim3(256), 0, h->stream, (const u64 *)lk, (const u64 *)sc, R, head);
-        hipLaunchKernelGGL(esprun::run_offsets_k, dim3(grid_for(R, 256)), dim3(256), 0, h->stream, (const u64 *)lk, (const double *)lv,
-                           (const u64 *)sc, (const u64 *)head, (const u64 *)bstart, R, a.runs_off);
+        hipLaunchKernelGGL(esprun::run_heads_k, dim3(grid_for(R, 256)), dim3(256), 0, h->stream, sl.k, (const u64 *)sc, R, head);
+        hipLaunchKernelGGL(esprun::run_offsets_k, dim3(grid_for(R, 256)), dim3(256), 0, h->stream, sl.k, sl.v, (const u64 *)sc,
+                           (const u64 *)head, (const u64 *)bstart, R, a.runs_off);
         sp.add(2);
     }
     {

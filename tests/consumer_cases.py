@@ -18,7 +18,7 @@ import numpy as np
 SET, UPDATE, RAWUPDATE = 0, 1, 2
 SCAN_CHUNK = 2048          # flags per workgroup of the scan behind dropzeros! (scan.hpp: THREADS * ITEMS)
 SORT_TILE = 4096           # entries per tile of the row sort of build_csr (radix.hpp: THREADS * ITEMS)
-SORT_PASS_BITS = 8         # row bits per pass of that sort (consumers.hip: done += 8)
+SORT_PASS_BITS = 8         # row bits per pass of that sort (partition.hip, sort_segment_lsd: done += 8)
 PENDING_MATCH_CAP = 2048   # matches esp_pending_getindex folds (consumers.hip)
 PENDING_FOLD_THREADS = 256  # stride of the rank sort of pending_fold_k
 PENDING_MAX_GROUPS = 4096  # workgroups of pending_matches_k, 256 threads each
@@ -41,11 +41,13 @@ def source_constants():
     def read(f):
         with open(os.path.join(_CSRC, f)) as fh:
             return fh.read()
-    scan, radix, cons, handle = read("scan.hpp"), read("radix.hpp"), read("consumers.hip"), read("handle.hip")
+    scan, radix, cons, handle, part = read("scan.hpp"), read("radix.hpp"), read("consumers.hip"), read("handle.hip"), read("partition.hip")
+    # build_csr sorts its Z entries on the h->L.rb row bits by the one driver of partition.hip: the pass width read below is its loop's
+    assert re.search(r"sort_segment_lsd\(h, [^;]*, Z, 0, h->L\.rb, ", cons), "build_csr no longer sorts by sort_segment_lsd"
     return dict(
         SCAN_CHUNK=_const(scan, "THREADS", "espscan") * _const(scan, "ITEMS", "espscan"),
         SORT_TILE=_const(radix, "THREADS", "espradix") * _const(radix, "ITEMS", "espradix"),
-        SORT_PASS_BITS=int(re.search(r"done < h->L\.rb; done \+= (\d+)\)", cons).group(1)),
+        SORT_PASS_BITS=int(re.search(r"done < bits; done \+= (\d+),", part).group(1)),
         PENDING_MATCH_CAP=_const(cons, "PENDING_MATCH_CAP"),
         PENDING_FOLD_THREADS=int(re.search(r"q < n; q \+= (\d+)\)", cons).group(1)),
         PENDING_MAX_GROUPS=int(re.search(r"std::min<i64>\((\d+), std::max<i64>\(1, ceil_div<i64>\(h->count, 256\)\)\)", cons).group(1)),
