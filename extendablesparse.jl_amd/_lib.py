@@ -13,6 +13,7 @@ SO = os.path.join(HERE, "libesparse_hip.so")
 ESP_OK = 0
 ESP_ERR_INVALID, ESP_ERR_BOUNDS, ESP_ERR_HIP, ESP_ERR_NOMEM = -1, -2, -3, -4
 ESP_ERR_UNSUPPORTED, ESP_ERR_STATE, ESP_ERR_NODEVICE = -5, -6, -7
+ESP_ERR_NOTPOSDEF = -8
 ESP_SET, ESP_UPDATE, ESP_RAWUPDATE, ESP_COO = 0, 1, 2, 3
 ESP_OP_ADD, ESP_OP_SUB = 0, 1
 ESP_FLUSH_ROUTED, ESP_FLUSH_PLUS = 0, 1
@@ -23,6 +24,8 @@ ESP_PRECON_COLORED = 6
 ESP_PRECON_SPAI = 7
 ESP_PRECON_ILUT = 8
 ESP_PRECON_LU = 9
+ESP_PRECON_CHOLESKY = 10
+ESP_CHOL_STATS = 12
 ESP_ILUT_WAVE_UPPER, ESP_ILUT_GROUP_UPPER, ESP_ILUT_STEPS_MAX, ESP_ILUT_STATS = 256, 4096, 16, 40
 ESP_ILUK_WAVE_VISITS, ESP_ILUK_VISIT_MAX = 512, 8192
 ESP_SPAI_WAVE_DOUBLES, ESP_SPAI_DENSE_MAX = 512, 12288
@@ -42,6 +45,10 @@ class EspError(RuntimeError):
 
 class NoDeviceError(EspError):
     pass
+
+
+class PosDefError(EspError):
+    """ESP_ERR_NOTPOSDEF: CholeskyFactorization met a pivot that is not positive (Julia's PosDefException)"""
 
 
 class BoundsError(IndexError):
@@ -152,6 +159,12 @@ SIGNATURES = {
     "esp_precon_lu_stats": (i32, [vp, P(i64)]),
     "esp_nested_dissection": (i32, [vp, i32, i32, vp, vp, i32]),
     "esp_debug_lu_fill_cap": (i32, [vp, i64]),
+    "esp_precon_cholesky_create": (i32, [vp, i32, i32, P(vp)]),
+    "esp_precon_cholesky_perm": (i32, [vp, vp, i32]),
+    "esp_precon_cholesky_tree": (i32, [vp, vp, vp, i32]),
+    "esp_precon_cholesky_factor": (i32, [vp, vp, vp, vp, i32]),
+    "esp_precon_cholesky_stats": (i32, [vp, P(i64)]),
+    "esp_debug_cholesky_wide_from": (i32, [vp, i64]),
     "esp_simple": (i32, [vp, vp, vp, vp, i32, i64, f64, f64, vp, P(i64)]),
     "esp_cg": (i32, [vp, vp, vp, vp, i32, i32, i64, f64, f64, vp, P(i64), P(i32)]),
     "esp_bicgstabl": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i64, f64, f64, vp, P(i64), P(i64), P(i32)]),
@@ -253,4 +266,6 @@ def check(h, rc):
         raise BoundsError(msg)
     if rc == ESP_ERR_NODEVICE:
         raise NoDeviceError(rc, msg)
+    if rc == ESP_ERR_NOTPOSDEF:
+        raise PosDefError(rc, msg)
     raise EspError(rc, msg)

@@ -22,6 +22,8 @@
 //                  matrix B in an internal handle, ILUAM on it
 //   lu.hip         LUFactorization: the nested-dissection ordering by level-synchronous component and search launches, the supernodal
 //                  symbolic fill from the dissection tree, the filled reordered matrix B with ILUAM as the inner kind
+//   cholesky.hip   CholeskyFactorization: lu.hip's ordering and tree (lu.hpp), dense column-major panels per node, the numeric
+//                  factorization and the solves depth by depth (small form: a workgroup per node; wide form: tiles over the grid)
 //   ilut.hip       ILUTPreconditioner: the threshold ILU by synchronous sweeps (wave / workgroup / stride tiers of the sweep kernel),
 //                  the candidate pattern from esp_matmul, drop and compaction, F in an internal handle, ILUAM's prefactored mode on it
 //   amg.hip        AMGPreconditioner: smoothed aggregation (MIS(2) aggregates by Luby rounds, the level hierarchy from the algebra
@@ -97,6 +99,7 @@ struct esp_handle {
     bool hits_off = false;                // the re-assembly form of the group kernel met a batch that was no re-assembly of the stored pattern: not tried again (until reset!)
     bool g3_wide = false;                 // ... for its rows alone (spread over more than 2^18): the kernel's wide form serves this handle
     bool debug_fail_bucket = false;       // esp_debug_fail_next_bucket_stage (test hook, one shot)
+    i64 debug_chol_wide = 0;              // esp_debug_cholesky_wide_from: the width from which CholeskyFactorization uses its wide form (test hook; 0: the default)
     i64 debug_lu_cap = 0;                 // esp_debug_lu_fill_cap: LUFactorization refuses nnz(B) >= this (test hook; 0: the 32-bit limit)
     double debug_plan_cap = 0.0;          // esp_debug_plan_cap: plan as if the bucket kernel took segments of this many entries (test hook)
     int last_group3 = 0;                  // the last flush's bucket kernel was group3_k (esp_debug_last_local_small reports 2)
@@ -675,6 +678,9 @@ struct esp_precon {
     int lu_leaf = 32, lu_depth = 48;
     DevBuf lu_perm, lu_level, lu_root;  // u32 n each: c, the depth every vertex was placed at, the root vertex naming its tree node
     i64 lu_stats[6] = {0, 0, 0, 0, 0, 0};  // esp_precon_lu_stats' layout
+    // CholeskyFactorization (kind ESP_PRECON_CHOLESKY, cholesky.hip): lu_leaf / lu_depth, lu_perm / lu_level / lu_root and blk_new (the
+    // inverse of c) as above; the node table, the update lists, the schedule and the panels in chol
+    struct CholData *chol = nullptr;
 };
 // the kinds that block.hip's ldiv! serves (Block and Colored: its builder and update! too; LU builds B itself)
 static inline bool block_built(const esp_precon *p) {
@@ -747,6 +753,12 @@ void color_release(esp_precon *p);
 // preconditioner, src and the inverse permutation are block_release's)
 int32_t lu_update(esp_precon *p);
 void lu_release(esp_precon *p);
+// cholesky.hip: update! (after a pattern change the ordering, the tables and the panels anew; else the load and the numeric
+// factorization), ldiv! on device vectors (u may be v; sub: u[i] = u[i] - x[i], simple!'s step; launches on the handle's stream only),
+// release of everything
+int32_t chol_update(esp_precon *p);
+int32_t chol_solve(esp_precon *p, const double *v, double *u, bool sub);
+void chol_release(esp_precon *p);
 // spai.hip: update! (after a pattern change the size pass, the tiers and M anew; else the numeric kernels alone), M's handles moved
 // to the stream A runs on, ldiv! of order 1 on device vectors (u may be v; sub: u[i] = u[i] - x[i], simple!'s step; launches and at
 // most one copy on the handle's stream), release of the handles and buffers

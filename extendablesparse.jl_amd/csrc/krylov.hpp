@@ -203,10 +203,12 @@ struct PreconProduct {
             if (dot) dot_launch(nullptr, src, other, nullptr);
         } else if (!blk && diag_applied(p)) {
             dot_launch((const double *)p->diag.p, nullptr, src, dst);
-        } else if (blk || p->kind == ESP_PRECON_ILUAM || p->kind == ESP_PRECON_AMG || p->kind == ESP_PRECON_SPAI) {
+        } else if (blk || p->kind == ESP_PRECON_ILUAM || p->kind == ESP_PRECON_AMG || p->kind == ESP_PRECON_SPAI ||
+                   p->kind == ESP_PRECON_CHOLESKY) {
             if (blk) CK(block_ldiv_launch(blk, src, dst, false));
             else if (p->kind == ESP_PRECON_AMG) CK(amg_solve(p, src, dst, false));  // the V-cycle's launches
             else if (p->kind == ESP_PRECON_SPAI) CK(spai_apply(p, src, dst, false));  // one product with M
+            else if (p->kind == ESP_PRECON_CHOLESKY) CK(chol_solve(p, src, dst, false));  // the depth launches
             else CK(iluam_solve(p, src, dst, false));                              // the level launches
             if (dot) dot_launch(nullptr, dst, other, nullptr);
         } else {  // ILU0: pass 1 into p->u1 (precon.hip, unchanged), pass 2 carries the dot product

@@ -31,14 +31,14 @@
 //                src[q], the position in A's nzval of A[c[row], c[k]] by bisection or ILUK_FILL.
 //   the kind     update!, the value gather and the inner ILUAM are derived.hip's; ldiv! is block.hip's gather / inner ldiv! /
 //                scatter over blk_new = the inverse of c (block_built holds for this kind).
-#include "amg.hpp"
+#include "lu.hpp"
 
 using namespace espamg;
+using namespace esplu;
 
 namespace {
 
 constexpr int LT = 256;                   // threads of every kernel here
-constexpr u32 LU_NONE = 0xFFFFFFFFu;      // level: not placed yet; dist: not reached yet; a table without a node (n < 2^32 - 16)
 
 __device__ __forceinline__ u64 lu_key(i64 i) { return ((u64)amg_mix(i) << 32) | (u64)(u32)i; }
 __device__ __forceinline__ u64 lu_max(u64 a, u64 b) { return a > b ? a : b; }
@@ -281,10 +281,6 @@ __global__ __launch_bounds__(LT) void lu_pair_k(Graph g, const u32 *__restrict__
     else if (q != qend) atomicMax(err, 1ull);
 }
 
-// S: struct of the node that starts at s is column s; T = transpose(S).  Both 1-based CSC arrays, nullptr when no record exists
-struct Struct {
-    const i64 *scp, *srv, *tcp, *trv;
-};
 // cp[k] = the entries of column k of B; st[1] = the largest node
 __global__ __launch_bounds__(LT) void lu_bcount_k(Struct x, const u32 *__restrict__ nstart, const u32 *__restrict__ nsize, i64 n, i64 *__restrict__ cp,
                                                   unsigned long long *__restrict__ st) {
@@ -338,17 +334,6 @@ __global__ __launch_bounds__(LT) void lu_bfill_k(Struct x, espfold::Csc A, const
 }
 
 // ---- the host side -----------------------------------------------------------------------------------------------------------------
-// what an ordering leaves: u32 n each but anc (one u32 n per round), released on every way out unless taken over
-struct Order {
-    DevBuf level, root, perm, newpos, nstart, nsize, ancptr;
-    std::vector<DevBuf> anc;
-    i64 rounds = 0, deepest = 0, nodes = 0, launches = 0;
-    ~Order() {
-        for (DevBuf *b : {&level, &root, &perm, &newpos, &nstart, &nsize, &ancptr}) release(*b);
-        for (DevBuf &b : anc) release(b);
-    }
-};
-
 Graph graph_of(const esp_handle *h) {
     return Graph{(const i64 *)h->colptr.p, (const i64 *)h->rowval.p, (const u64 *)h->csr_rowptr.p + 1, (const u32 *)h->csr_col.p};
 }
@@ -362,6 +347,8 @@ int32_t read_cnt(esp_handle *h, const DevBuf &cnt, u32 out[2]) {
     out[1] = ((const u32 *)h->pin_scalar)[1];
     return ESP_OK;
 }
+
+}  // namespace
 
 // the rounds of h's stored pattern (checked, square, flushed): o.level, o.anc, o.rounds, o.launches
 int32_t lu_dissect(esp_handle *h, int leaf_size, int max_depth, Order &o) {
@@ -482,6 +469,61 @@ int32_t lu_export(esp_handle *h, const DevBuf &src, void *out, bool wide, int32_
     return copy_out(h, out, src.p, sizeof(u32) * (size_t)h->n, on_device);
 }
 
+// the struct lists of the ordered tree (n > 0): anc as node starts, the records of the rule, S by an ESP_COO flush, T its transpose
+int32_t lu_structs(esp_handle *h, Order &o, const char *what, Handles &hs, Struct &x) {
+    hipStream_t s = h->stream;
+    const i64 n = h->n;
+    x = Struct{nullptr, nullptr, nullptr, nullptr};
+    if (n == 0) return ESP_OK;
+    Temps tmp;
+    DevBuf &st = tmp.b[0], &ws = tmp.b[1], &tab = tmp.b[2], &off = tmp.b[3], &scp = tmp.b[4], &srv = tmp.b[5], &snz = tmp.b[6];
+    CK(ensure(h, st, sizeof(u64)));
+    HIPCK(h, hipMemsetAsync(st.p, 0, sizeof(u64), s));
+    unsigned long long *stp = (unsigned long long *)st.p;  // a record or node error
+    const unsigned g = grid_for(n, LT);
+    int l = 0;
+    // the ancestors as node starts
+    CK(ensure(h, tab, sizeof(u32) * (size_t)n));
+    for (i64 e = 0; e < o.rounds; e++) {
+        HIPCK(h, hipMemsetAsync(tab.p, 0xFF, sizeof(u32) * (size_t)n, s));
+        hipLaunchKernelGGL(lu_tab_k, dim3(g), dim3(LT), 0, s, (const u32 *)o.level.p, (const u32 *)o.root.p, (const u32 *)o.newpos.p,
+                           (const u32 *)o.nstart.p, n, (u32)e, (u32 *)tab.p);
+        hipLaunchKernelGGL(lu_anc_k, dim3(g), dim3(LT), 0, s, (const u32 *)o.level.p, (const u32 *)tab.p, n, (u32)e, (u32 *)o.anc[(size_t)e].p);
+    }
+    // the records of struct
+    const Graph gr = graph_of(h);
+    CK(ensure(h, off, sizeof(i64) * (size_t)(n + 1)));
+    HIPCK(h, hipMemsetAsync(off.p, 0, sizeof(i64) * (size_t)(n + 1), s));
+    hipLaunchKernelGGL(lu_pair_k<false>, dim3(g), dim3(LT), 0, s, gr, (const u32 *)o.level.p, (const u32 *const *)o.ancptr.p,
+                       (const u32 *)o.newpos.p, n, (i64 *)off.p, (const i64 *)nullptr, (u64 *)nullptr, (u64 *)nullptr, h->L, stp);
+    CK(scan_inplace<i64, false>(h, (i64 *)off.p, n + 1, ws, &l));
+    HIPCK(h, hipGetLastError());
+    i64 npairs = 0;
+    CK(read_i64(h, (const i64 *)off.p + n, &npairs));
+    if (npairs == 0) return ESP_OK;
+    ScratchFlush sf(h, what);
+    CK(sf.open(n, n, npairs));
+    hipLaunchKernelGGL(lu_pair_k<true>, dim3(g), dim3(LT), 0, s, gr, (const u32 *)o.level.p, (const u32 *const *)o.ancptr.p,
+                       (const u32 *)o.newpos.p, n, (i64 *)nullptr, (const i64 *)off.p, sf.keys(), sf.vals(), sf.L(), stp);
+    HIPCK(h, hipGetLastError());
+    HIPCK(h, hipMemcpyAsync(h->pin_scalar, stp, sizeof(u64), hipMemcpyDeviceToHost, s));
+    HIPCK(h, hipStreamSynchronize(s));
+    if (h->pin_scalar[0] != 0) FAIL(h, ESP_ERR_HIP, "%s: the record pass of struct disagrees with its count pass", what);
+    CK(sf.flush(-1));
+    const i64 nnzS = sf.nnz();
+    sf.take(scp, srv, snz);
+    hs.v.assign(2, nullptr);
+    for (esp_handle *&q : hs.v) CK(amg_make_handle(h, n, n, &q));
+    install(hs.v[0], scp, srv, snz, nnzS);
+    const int32_t ts = esp_transpose(hs.v[0], hs.v[1], nullptr);
+    if (ts != ESP_OK) FAIL(h, ts, "%s: transpose of the struct lists: %s", what, hs.v[1]->err.c_str());
+    x = Struct{(const i64 *)hs.v[0]->colptr.p, (const i64 *)hs.v[0]->rowval.p, (const i64 *)hs.v[1]->colptr.p,
+               (const i64 *)hs.v[1]->rowval.p};
+    return ESP_OK;
+}
+
+namespace {
+
 // derived_update's builder: the ordering, the tree and B from A's current CSC; B installed in p->der.bh, src in p->der.src, the maps
 // in p.  Everything that can fail comes in front of that: nothing of p changes when it fails
 int32_t build_b(esp_precon *p) {
@@ -494,57 +536,19 @@ int32_t build_b(esp_precon *p) {
     CK(lu_dissect(h, p->lu_leaf, p->lu_depth, o));
     CK(lu_order(h, o));
     Temps tmp;
-    DevBuf &cp = tmp.b[0], &rv = tmp.b[1], &nz = tmp.b[2], &src = tmp.b[3], &st = tmp.b[4], &ws = tmp.b[5], &tab = tmp.b[6], &off = tmp.b[7],
-           &scp = tmp.b[8], &srv = tmp.b[9], &snz = tmp.b[10];
+    DevBuf &cp = tmp.b[0], &rv = tmp.b[1], &nz = tmp.b[2], &src = tmp.b[3], &st = tmp.b[4], &ws = tmp.b[5];
     Handles hs;  // S and transpose(S)
     CK(ensure(h, cp, sizeof(i64) * (size_t)(n + 1)));
     CK(ensure(h, st, sizeof(u64) * 4));
     HIPCK(h, hipMemsetAsync(cp.p, 0, sizeof(i64) * (size_t)(n + 1), s));
     hipLaunchKernelGGL(set_i64_k, dim3(1), dim3(1), 0, s, (i64 *)st.p, (i64)0, (i64)0, (i64)-1, (i64)0);
-    unsigned long long *stp = (unsigned long long *)st.p;  // 0: a record or node error, 1: the largest node, 2: smallest column without a
+    unsigned long long *stp = (unsigned long long *)st.p;  // 0: spare, 1: the largest node, 2: smallest column without a
                                                             // stored diagonal, 3: count and fill of B disagree
     const unsigned g = grid_for(n, LT);
     Struct x{nullptr, nullptr, nullptr, nullptr};
     int l = 0;
     if (n > 0) {
-        // the ancestors as node starts
-        CK(ensure(h, tab, sizeof(u32) * (size_t)n));
-        for (i64 e = 0; e < o.rounds; e++) {
-            HIPCK(h, hipMemsetAsync(tab.p, 0xFF, sizeof(u32) * (size_t)n, s));
-            hipLaunchKernelGGL(lu_tab_k, dim3(g), dim3(LT), 0, s, (const u32 *)o.level.p, (const u32 *)o.root.p, (const u32 *)o.newpos.p,
-                               (const u32 *)o.nstart.p, n, (u32)e, (u32 *)tab.p);
-            hipLaunchKernelGGL(lu_anc_k, dim3(g), dim3(LT), 0, s, (const u32 *)o.level.p, (const u32 *)tab.p, n, (u32)e, (u32 *)o.anc[(size_t)e].p);
-        }
-        // the records of struct
-        const Graph gr = graph_of(h);
-        CK(ensure(h, off, sizeof(i64) * (size_t)(n + 1)));
-        HIPCK(h, hipMemsetAsync(off.p, 0, sizeof(i64) * (size_t)(n + 1), s));
-        hipLaunchKernelGGL(lu_pair_k<false>, dim3(g), dim3(LT), 0, s, gr, (const u32 *)o.level.p, (const u32 *const *)o.ancptr.p,
-                           (const u32 *)o.newpos.p, n, (i64 *)off.p, (const i64 *)nullptr, (u64 *)nullptr, (u64 *)nullptr, h->L, stp);
-        CK(scan_inplace<i64, false>(h, (i64 *)off.p, n + 1, ws, &l));
-        HIPCK(h, hipGetLastError());
-        i64 npairs = 0;
-        CK(read_i64(h, (const i64 *)off.p + n, &npairs));
-        if (npairs > 0) {
-            ScratchFlush sf(h, "esp_precon_lu");
-            CK(sf.open(n, n, npairs));
-            hipLaunchKernelGGL(lu_pair_k<true>, dim3(g), dim3(LT), 0, s, gr, (const u32 *)o.level.p, (const u32 *const *)o.ancptr.p,
-                               (const u32 *)o.newpos.p, n, (i64 *)nullptr, (const i64 *)off.p, sf.keys(), sf.vals(), sf.L(), stp);
-            HIPCK(h, hipGetLastError());
-            HIPCK(h, hipMemcpyAsync(h->pin_scalar, stp, sizeof(u64), hipMemcpyDeviceToHost, s));
-            HIPCK(h, hipStreamSynchronize(s));
-            if (h->pin_scalar[0] != 0) FAIL(h, ESP_ERR_HIP, "esp_precon_lu: the record pass of struct disagrees with its count pass");
-            CK(sf.flush(-1));
-            const i64 nnzS = sf.nnz();
-            sf.take(scp, srv, snz);
-            hs.v.assign(2, nullptr);
-            for (esp_handle *&q : hs.v) CK(amg_make_handle(h, n, n, &q));
-            install(hs.v[0], scp, srv, snz, nnzS);
-            const int32_t ts = esp_transpose(hs.v[0], hs.v[1], nullptr);
-            if (ts != ESP_OK) FAIL(h, ts, "esp_precon_lu: transpose of the struct lists: %s", hs.v[1]->err.c_str());
-            x = Struct{(const i64 *)hs.v[0]->colptr.p, (const i64 *)hs.v[0]->rowval.p, (const i64 *)hs.v[1]->colptr.p,
-                       (const i64 *)hs.v[1]->rowval.p};
-        }
+        CK(lu_structs(h, o, "esp_precon_lu", hs, x));
         hipLaunchKernelGGL(lu_bcount_k, dim3(g), dim3(LT), 0, s, x, (const u32 *)o.nstart.p, (const u32 *)o.nsize.p, n, (i64 *)cp.p, stp);
         CK(scan_inplace<i64, false>(h, (i64 *)cp.p, n + 1, ws, &l));
     }
@@ -607,6 +611,8 @@ int32_t lu_current(esp_precon *p, const char *what) {
     return ESP_OK;
 }
 
+}  // namespace
+
 int32_t lu_check_args(esp_handle *h, const char *what, int32_t leaf_size, int32_t max_depth) {
     if (leaf_size < 1) FAIL(h, ESP_ERR_INVALID, "%s: leaf_size = %d < 1", what, leaf_size);
     if (max_depth < 0 || max_depth > 64) FAIL(h, ESP_ERR_INVALID, "%s: max_depth = %d is outside 0..64", what, max_depth);
@@ -614,8 +620,6 @@ int32_t lu_check_args(esp_handle *h, const char *what, int32_t leaf_size, int32_
     if (windowed(h) || h->shard_user) FAIL(h, ESP_ERR_UNSUPPORTED, "%s: a column window / column shard", what);
     return ESP_OK;
 }
-
-}  // namespace
 
 int32_t lu_update(esp_precon *p) { return derived_update(p, "esp_precon_lu", build_b, ""); }
 

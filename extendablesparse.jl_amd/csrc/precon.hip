@@ -313,6 +313,7 @@ int32_t ldiv_launch(esp_precon *p, const double *v, double *u) {
     if (p->kind == ESP_PRECON_ILUK || p->kind == ESP_PRECON_ILUT) return ldiv_launch(p->der.inner, v, u);  // ILUAM of B / over F on the caller's vectors
     if (p->kind == ESP_PRECON_ILUAM) return iluam_solve(p, v, u, false);
     if (p->kind == ESP_PRECON_AMG) return amg_solve(p, v, u, false);
+    if (p->kind == ESP_PRECON_CHOLESKY) return chol_solve(p, v, u, false);
     if (p->kind == ESP_PRECON_SPAI && p->spai_order != 0) return spai_apply(p, v, u, false);  // u = M*v
     const unsigned g = grid_for(n, PT);
     if (diag_applied(p)) {  // Jacobi's invdiag / SPAI-0's diagonal M
@@ -375,6 +376,7 @@ extern "C" int32_t esp_precon_update(esp_precon *p) {
     if (p->kind == ESP_PRECON_COLORED) return color_update(p);  // the colouring, A[c,c] and the inner preconditioner (color.hip)
     if (p->kind == ESP_PRECON_SPAI) return spai_update(p);      // the approximate inverse M (spai.hip)
     if (p->kind == ESP_PRECON_LU) return lu_update(p);          // the ordering, the filled matrix and the inner ILUAM (lu.hip)
+    if (p->kind == ESP_PRECON_CHOLESKY) return chol_update(p);  // the ordering, the panels and the numeric factorization (cholesky.hip)
     esp_handle *h = p->h;
     CK(check_handle(h, "esp_precon_update"));
     p->n = h->n;
@@ -428,6 +430,7 @@ extern "C" int32_t esp_precon_destroy(esp_precon *p) {
     color_release(p);
     spai_release(p);
     lu_release(p);
+    chol_release(p);
     for (DevBuf *b : {&p->diag, &p->lptr, &p->uptr, &p->lcol, &p->ucol, &p->lpos, &p->upos, &p->dpos, &p->lval, &p->uval, &p->u1, &p->res,
                       &p->partial, &p->scanws, &p->hv, &p->hu})
         release(*b);
@@ -491,6 +494,8 @@ extern "C" int32_t esp_simple(esp_handle *h, esp_precon *p, const double *b, dou
                 CK(iluam_solve(p, res, du, true));
             } else if (p->kind == ESP_PRECON_AMG) {
                 CK(amg_solve(p, res, du, true));
+            } else if (p->kind == ESP_PRECON_CHOLESKY) {
+                CK(chol_solve(p, res, du, true));
             } else if (p->kind == ESP_PRECON_SPAI) {
                 CK(spai_apply(p, res, du, true));
             } else {

@@ -40,7 +40,7 @@ import math
 
 import numpy as np
 
-from ._lib import ESP_ORTH_CGS, ESP_ORTH_DGKS, ESP_ORTH_MGS, ESP_PRECON_AMG, ESP_PRECON_BLOCK, ESP_PRECON_COLORED, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_ILUK, ESP_PRECON_ILUT, ESP_PRECON_JACOBI, ESP_PRECON_LU, ESP_PRECON_SPAI
+from ._lib import ESP_ORTH_CGS, ESP_ORTH_DGKS, ESP_ORTH_MGS, ESP_PRECON_AMG, ESP_PRECON_BLOCK, ESP_PRECON_COLORED, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_ILUK, ESP_PRECON_ILUT, ESP_PRECON_JACOBI, ESP_PRECON_LU, ESP_PRECON_SPAI, ESP_CHOL_STATS, ESP_PRECON_CHOLESKY
 from .matrix import ExtendableSparseMatrix, _vp
 
 
@@ -592,28 +592,103 @@ class LUFactorization(_ILUAMFactors, _PointPreconditioner):
 SparspakLU = LUFactorization
 
 
+class CholeskyFactorization(_PointPreconditioner):
+    """CholeskyFactorization(A, leaf_size=32, max_depth=48) (src/factorizations/cholmod_cholesky.jl): A[c,c] = L L' on the device
+    (include/esparse_hip.h, esp_precon_cholesky_create).  As Symmetric(A.cscmatrix) does, only A's stored upper triangle is read.
+    The ordering and the tree are LUFactorization's; every tree node owns a dense column-major panel, and the numeric factorization
+    and the solves walk the tree depth by depth.  solve(b) = ldiv is u[c] = L' \\ (L \\ v[c]).  The panels hold copies: a value
+    change of A reaches solve only through update(), which keeps the ordering, the tables and the panels' layout when only values
+    changed.  A matrix that is not positive definite raises PosDefError (it names the position in c and A's column); after such an
+    update() the object refuses ldiv until an update succeeds.  DEVIATIONS from CHOLMOD: the ordering is nested dissection, not AMD;
+    no LDL' fallback."""
+    KIND = ESP_PRECON_CHOLESKY
+
+    def __init__(self, A, leaf_size=32, max_depth=48):
+        if not isinstance(A, ExtendableSparseMatrix):
+            raise TypeError("CholeskyFactorization(A, ...): A must be an ExtendableSparseMatrix")
+        if int(leaf_size) != leaf_size or not 1 <= leaf_size < 2 ** 31:
+            raise ValueError("CholeskyFactorization: leaf_size = %r (an integer >= 1)" % (leaf_size,))
+        if int(max_depth) != max_depth or not 0 <= max_depth <= 64:
+            raise ValueError("CholeskyFactorization: max_depth = %r (an integer in 0..64)" % (max_depth,))
+        self.leaf_size, self.max_depth = int(leaf_size), int(max_depth)
+        self._bind(A, "esp_precon_cholesky_create", self.leaf_size, self.max_depth)
+
+    def permutation(self):
+        """c, the unknowns sorted by (level descending, node, index), in the index base of A[i, j] (1-based)"""
+        out = np.empty(self.A.n, np.int64)
+        if self.A.n:
+            self._ck(self.A._d.lib.esp_precon_cholesky_perm(self._live(), _vp(out), 0))
+        return out + 1
+
+    def tree(self):
+        """(level, node_root) per unknown, as LUFactorization.tree()"""
+        level, root = np.empty(self.A.n, np.int32), np.empty(self.A.n, np.int64)
+        if self.A.n:
+            self._ck(self.A._d.lib.esp_precon_cholesky_tree(self._live(), _vp(level), _vp(root), 0))
+        return level, root + 1
+
+    def factor(self):
+        """L as host CSC arrays (colptr, rowval, nzval) in positions of c, Julia layout -- for tests and inspection"""
+        lib, n = self.A._d.lib, self.A.n
+        cp = np.empty(n + 1, np.int64)
+        self._ck(lib.esp_precon_cholesky_factor(self._live(), _vp(cp), None, None, 0))
+        nnz = int(cp[n]) - 1
+        rv, nz = np.empty(nnz, np.int64), np.empty(nnz, np.float64)
+        if nnz:
+            self._ck(lib.esp_precon_cholesky_factor(self._live(), None, _vp(rv), _vp(nz), 0))
+        return cp, rv, nz
+
+    def stats(self):
+        """dict: nnz (of L), rounds, deepest (level), nodes, largest_node, panel_doubles, ordering_launches (since the create: an
+        update() with the pattern kept adds none), factor_launches (of the last numeric factorization), ldiv_launches (of one ldiv),
+        small_nodes / wide_nodes (taken by either form), wide_block_columns (the block-column steps of the wide form)"""
+        out = (C.c_int64 * ESP_CHOL_STATS)()
+        self._ck(self.A._d.lib.esp_precon_cholesky_stats(self._live(), out))
+        names = ("nnz", "rounds", "deepest", "nodes", "largest_node", "panel_doubles", "ordering_launches", "factor_launches",
+                 "ldiv_launches", "small_nodes", "wide_nodes", "wide_block_columns")
+        return dict(zip(names, (int(x) for x in out)))
+
+    def solve(self, b, out=None):
+        """cholfact \\ b: an alias of ldiv"""
+        return self.ldiv(b, out)
+
+
+def cholesky(A, **kw):
+    """cholesky(A): CholeskyFactorization(A, **kw)"""
+    return CholeskyFactorization(A, **kw)
+
+
+def cholesky_(fact, A):
+    """cholesky!(fact, A): the factorization of A in fact -- bound anew when A is another matrix, else update()"""
+    if not isinstance(fact, CholeskyFactorization):
+        raise TypeError("cholesky_(fact, A): fact must be a CholeskyFactorization")
+    return lu_(fact, A)
+
+
 def lu(A, **kw):
     """lu(A) (docs/src/linearsolve.md): LUFactorization(A, **kw)"""
     return LUFactorization(A, **kw)
 
 
 def lu_(fact, A):
-    """lu!(fact, A): the factorization of A in fact -- bound anew when A is another matrix, else update()"""
-    if not isinstance(fact, LUFactorization):
-        raise TypeError("lu_(fact, A): fact must be an LUFactorization")
+    """lu!(fact, A): the factorization of A in fact -- bound anew when A is another matrix, else update().  A CholeskyFactorization
+    is taken too (the reference's tests call lu!(CholeskyFactorization(), A))"""
+    if not isinstance(fact, (LUFactorization, CholeskyFactorization)):
+        raise TypeError("lu_(fact, A): fact must be an LUFactorization or a CholeskyFactorization")
     if not isinstance(A, ExtendableSparseMatrix):
         raise TypeError("lu_(fact, A): A must be an ExtendableSparseMatrix")
     if A is fact.A and fact._p is not None:
         return fact.update()
     fact.close()
-    fact._bind(A, "esp_precon_lu_create", fact.leaf_size, fact.max_depth)
+    create = "esp_precon_cholesky_create" if isinstance(fact, CholeskyFactorization) else "esp_precon_lu_create"
+    fact._bind(A, create, fact.leaf_size, fact.max_depth)
     return fact
 
 
 def factorize_(fact, A):
     """factorize!(fact, A) (src/factorizations/factorizations.jl): lu_ for an LUFactorization; a preconditioner is bound to its
     matrix and takes update()"""
-    if isinstance(fact, LUFactorization):
+    if isinstance(fact, (LUFactorization, CholeskyFactorization)):
         return lu_(fact, A)
     if not isinstance(fact, _PointPreconditioner):
         raise TypeError("factorize_(fact, A): fact must be a factorization or a preconditioner")
@@ -623,9 +698,10 @@ def factorize_(fact, A):
 
 
 def issolver(f):
-    """issolver(f) (factorizations.jl): True for the direct solver LUFactorization (an instance or the class), False for every
-    preconditioner"""
-    return isinstance(f, LUFactorization) or (isinstance(f, type) and issubclass(f, LUFactorization))
+    """issolver(f) (factorizations.jl): True for the direct solvers LUFactorization and CholeskyFactorization (an instance or the
+    class), False for every preconditioner"""
+    direct = (LUFactorization, CholeskyFactorization)
+    return isinstance(f, direct) or (isinstance(f, type) and issubclass(f, direct))
 
 
 def nested_dissection(A, leaf_size=32, max_depth=48):

@@ -50,7 +50,8 @@ typedef enum {
     ESP_ERR_NOMEM = -4,       /* device or pinned allocation failed                */
     ESP_ERR_UNSUPPORTED = -5, /* dimension / count outside the supported range     */
     ESP_ERR_STATE = -6,       /* call not valid in the handle's current state      */
-    ESP_ERR_NODEVICE = -7     /* no usable GPU (the product never falls back)      */
+    ESP_ERR_NODEVICE = -7,    /* no usable GPU (the product never falls back)      */
+    ESP_ERR_NOTPOSDEF = -8    /* CholeskyFactorization: a pivot is not positive    -> Julia PosDefException */
 } esp_status;
 
 /* How an appended entry combines with what is already stored at (i,j).
@@ -710,6 +711,58 @@ int32_t esp_precon_lu_matrix(esp_precon *p, esp_handle **b);
 int32_t esp_precon_lu_stats(esp_precon *p, int64_t out[6]);
 int32_t esp_nested_dissection(esp_handle *h, int32_t leaf_size, int32_t max_depth, int64_t *c, int32_t *level, int32_t on_device);
 int32_t esp_debug_lu_fill_cap(esp_handle *h, int64_t cap);
+/* CholeskyFactorization (src/factorizations/cholmod_cholesky.jl; test/test_default_cholesky.jl): A[c,c] = L*transpose(L) on the
+ * device, on dense column-major panels per node of LUFactorization's dissection tree.  The reference wraps CHOLMOD, which is not part
+ * of its tree: the rule is stated in full here and in DESIGN.md 5r; tests/cholesky_model.c restates it as plain loops and is normative;
+ * the device equals it bit for bit.  Indices 0-based.
+ *   input     as Symmetric(A.cscmatrix) does, only stored entries A[r,s] with r <= s are read; the strict lower triangle of A is never
+ *             read.  Its pattern still takes part in the graph (above), which gives a superset.
+ *   ordering  c, level, the nodes and struct(K) are LUFactorization's for the same leaf_size / max_depth.
+ *   pattern   in positions of c, column j of L has the rows pat(j) = the positions of node(j) from j on, then struct(node(j)),
+ *             ascending: the lower half of B.
+ *   values    a_ij for i >= j in pat(j) is the bits of the stored A[min(c[i],c[j]), max(c[i],c[j])]; an entry that is not stored is
+ *             +0.0 (a missing diagonal therefore fails the pivot test and is no error of its own).
+ *   factor    every entry is one chain, each product rounded, then each difference rounded (no contraction): t = a_ij; for every
+ *             k < j ascending with i in pat(k) and j in pat(k): t = t - l_ik*l_jk; i == j: the column fails when !(t > 0), else
+ *             l_jj = sqrt(t) correctly rounded; i > j: l_ij = t / l_jj, a true division.
+ *   failure   the factorization reports the smallest position j whose pivot fails and A's column c[j]: ESP_ERR_NOTPOSDEF (the chain
+ *             is fixed, so j does not depend on the schedule).
+ *   solve     y = v[c].  Forward, j ascending: t = y_j; for k < j ascending with j in pat(k): t = t - l_jk*y_k; y_j = t / l_jj.
+ *             Backward, j descending: t = y_j; first for i in struct(node(j)) ascending: t = t - l_ij*x_i; then for the positions
+ *             i > j of node(j) DESCENDING: t = t - l_ij*x_i; x_j = t / l_jj (a node's triangle can then run right-looking, one lane
+ *             per row).  u[c] = x; u may alias v.
+ * Any schedule that respects these chains gives the same bits.  The device walks the tree depth by depth, from the deepest nodes to
+ * depth 0 (nodes of equal depth are independent: a chain only reaches into a node's own descendants): a load kernel scatters A's
+ * upper triangle into the zeroed panels; per depth, the nodes narrower than the wide-form width (default 33) are finished by one
+ * workgroup each in one launch (the small form), the others block column by block column (32 columns) for all of them at once, two
+ * launches per block column with the tiles spread over the grid (the wide form); plain FP64 multiplies and subtractions, no matrix
+ * instructions.  A failing pivot goes to one device word by atomicMin, read back once after the last depth.
+ * esp_precon_cholesky_create(h, leaf_size, max_depth): the result is an esp_precon bound to h; esp_precon_update / _ldiv / _destroy,
+ *   esp_simple, esp_cg, esp_bicgstabl and esp_gmres take it unchanged; esp_precon_get_factor -> ESP_ERR_INVALID, esp_precon_levels /
+ *   _launches give zeros (as for AMG).  esp_precon_ldiv only enqueues launches: a gather, at most 4 per depth, a scatter.
+ * esp_precon_update: with A's pattern kept the load kernel and the numeric factorization alone (the ordering, the tree, the tables and
+ *   the panels' layout are kept; bitwise what a fresh create gives); after a pattern change everything anew.  The panels hold copies: a
+ *   value change of A reaches ldiv! only through the update, a pattern change of A without it is ESP_ERR_STATE.  After an update that
+ *   fails (ESP_ERR_NOTPOSDEF included) the object refuses ldiv! with ESP_ERR_STATE until an update succeeds.
+ * Inspection: esp_precon_cholesky_perm / _tree: as esp_precon_lu_perm / _tree.  esp_precon_cholesky_factor: L as a CSC in positions of c
+ *   (colptr[n + 1] and rowval[nnz(L)] int64, 1-based; nzval[nnz(L)]), host, or device when on_device != 0; any pointer may be NULL.
+ *   esp_precon_cholesky_stats: out = nnz(L), the rounds, the deepest level, the nodes, the largest node, the panel doubles allocated,
+ *   the ordering launches since the create (an update! with the pattern kept adds none), the launches of the last numeric
+ *   factorization, the launches of one ldiv!, the nodes taken by the small and by the wide form, the block-column steps of the wide
+ *   form (per depth the block columns of its widest wide node, summed).
+ *   esp_debug_cholesky_wide_from(h, w): a test hook; the factorizations created on h afterwards use the wide form from width w on
+ *   (0 restores the default).
+ * ESP_ERR_INVALID: a rectangular matrix; leaf_size < 1; max_depth outside 0..64.  ESP_ERR_STATE: pending entries.
+ *   ESP_ERR_UNSUPPORTED: a column window / column shard on h; n >= 2^32 - 16.  n == 0 is valid.  Cholesky is no inner kind of
+ *   esp_precon_block_create or esp_precon_colored_create.  A live factorization makes h refuse esp_destroy. */
+#define ESP_PRECON_CHOLESKY 10
+#define ESP_CHOL_STATS 12
+int32_t esp_precon_cholesky_create(esp_handle *h, int32_t leaf_size, int32_t max_depth, esp_precon **out);
+int32_t esp_precon_cholesky_perm(esp_precon *p, int64_t *c, int32_t on_device);
+int32_t esp_precon_cholesky_tree(esp_precon *p, int32_t *level, int64_t *node_root, int32_t on_device);
+int32_t esp_precon_cholesky_factor(esp_precon *p, int64_t *colptr, int64_t *rowval, double *nzval, int32_t on_device);
+int32_t esp_precon_cholesky_stats(esp_precon *p, int64_t out[ESP_CHOL_STATS]);
+int32_t esp_debug_cholesky_wide_from(esp_handle *h, int64_t w);
 /* simple!(u, A, b; abstol, reltol, maxiter, Pl = p) (src/factorizations/simple_iteration.jl:21-45) statement by
  * statement: res = A*u - b; then per step ldiv!(upd, Pl, res), u .-= upd, mul!(res, A, u), res .-= b, r = norm(res),
  * stop when (r / r0) < reltol || r < abstol (literally: r0 = 0 gives NaN or Inf there).  u (in/out) is bit-identical to

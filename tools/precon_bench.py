@@ -105,6 +105,11 @@ through esp_nested_dissection, ILUAM's analysis + factorization of a copy of B, 
 ldiv!, nnz(B)/nnz(A), the rounds and launches of the ordering, ILUAM's level counts, and one solve of A x = 1 to 1e-8: A.solve(b)
 (create + solve) against cg with ILU0 and with ILUAM (create + cg) in the same run.  Medians over --rounds.
     python tools/precon_bench.py --kind lu [--n 32] [--leaf-size 32] [--iters 5] [--rounds 5]
+--kind cholesky [--leaf-size L] [--lu-rounds R] times CholeskyFactorization (esp_precon_cholesky_create) on fdrand(n,n,n) beside
+LUFactorization, the yardstick, in the same process and the same alternating rounds (LU in the first R of them): the ordering alone,
+the create, a values-only update! and ldiv! on device vectors; every round's value, medians, spreads (max - min), the ratios, the launch
+counts, nnz(L), the panel bytes, the residual for b = ones, and cg with ILU0 to 1e-8 from the same run.
+    python tools/precon_bench.py --kind cholesky [--n 24] [--lu-rounds 5] [--iters 5] [--rounds 5]
 """
 import argparse
 import ctypes as C
@@ -958,6 +963,91 @@ def bench_lu(a, torch, esp):
     print(json.dumps(rnd(out)))
 
 
+def bench_cholesky(a, torch, esp):
+    """CholeskyFactorization on fdrand n^3 beside LUFactorization, the yardstick, in the same process and the same alternating rounds
+    (--lu-rounds R: LU takes part in the first R rounds only; 0: not at all): per round the ordering alone, the create, a values-only
+    update! (the load and the numeric factorization) and ldiv! on device vectors of each.  Reported: every round's value, the median
+    and the spread (max - min); symbolic_ms = create - ordering - update (the tables and the panels); the launch counts, nnz(L), the
+    panel bytes, |A x - b| / |b| for b = ones; and one solve of A x = 1 to 1e-8 by cg with ILU0 (create + cg) from the same run."""
+    import numpy as np
+    A = esp.fdrand(a.n, a.n, a.n)
+    d = A._d
+    stream = torch.cuda.current_stream()
+    d.ck(d.lib.esp_set_stream(d.h, C.c_void_p(stream.cuda_stream)))
+    N, Z = A.n, A.nnz()
+    v = torch.randn(N, dtype=torch.float64, device="cuda")
+    u = torch.empty_like(v)
+    b = torch.ones_like(v)
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()                                   # (create, update!, ldiv! and the solvers return synchronised)
+        return (time.perf_counter() - t0) * 1e3, r
+
+    out = {"workload": "cholesky_fdrand", "n": a.n, "N": N, "nnz": Z, "leaf_size": a.leaf_size, "rounds": a.rounds, "lu_rounds": a.lu_rounds}
+    Pw = esp.ILU0Preconditioner(A)     # builds the row-wise index the ordering shares, so that the creates below are their own
+    Pw.close()
+    P = esp.CholeskyFactorization(A, a.leaf_size)       # (a warm-up create: code objects, allocations)
+    st = P.stats()
+    P.close()
+    kinds = [("cholesky", esp.CholeskyFactorization)]
+    if a.lu_rounds > 0:
+        kinds.append(("lu", esp.LUFactorization))
+    rec = {name: {"create_ms": [], "update_values_ms": [], "ldiv_ms": []} for name, _ in kinds}
+    ordering = []
+    resid = {}
+    for r in range(a.rounds):
+        ordering.append(wall(lambda: esp.nested_dissection(A, a.leaf_size))[0])
+        for name, cls in kinds:
+            if name == "lu" and r >= a.lu_rounds:
+                continue
+            t, Q = wall(lambda: cls(A, a.leaf_size))
+            rec[name]["create_ms"].append(t)
+            rec[name]["update_values_ms"].append(wall(Q.update)[0])
+            Q.ldiv(v, out=u)
+            rec[name]["ldiv_ms"].append(wall(lambda: [Q.ldiv(v, out=u) for _ in range(a.iters)])[0] / a.iters)
+            if name not in resid:
+                x = Q.solve(b)
+                resid[name] = float(torch.linalg.norm(A.mul(x) - b) / torch.linalg.norm(b))
+            Q.close()
+            print("cholesky n=%d round %d %s: %s" % (a.n, r, name, json.dumps({k: x[-1] for k, x in rec[name].items()})), file=sys.stderr, flush=True)
+    out["ordering_ms"] = {"rounds": ordering, "median": float(np.median(ordering))}
+    for name, _ in kinds:
+        out[name] = {k: {"rounds": x, "median": float(np.median(x)), "spread": float(max(x) - min(x))} for k, x in rec[name].items()}
+        out[name]["solve_residual"] = resid[name]
+    c = out["cholesky"]
+    c["symbolic_ms"] = c["create_ms"]["median"] - out["ordering_ms"]["median"] - c["update_values_ms"]["median"]
+    c["stats"] = st
+    c["panel_bytes"] = 8 * st["panel_doubles"]
+    if "lu" in out:
+        out["lu_over_cholesky"] = {k: out["lu"][k]["median"] / c[k]["median"] for k in ("create_ms", "update_values_ms", "ldiv_ms")}
+
+    def run():
+        Q = esp.ILU0Preconditioner(A)
+        try:
+            return esp.cg(A, b, Pl=Q, reltol=1e-8, maxiter=a.tol_maxiter, log=True)
+        finally:
+            Q.close()
+    run()
+    ts, log = [], None
+    for _ in range(a.rounds):
+        t, (_, log) = wall(run)
+        ts.append(t)
+    out["solve_1e-8"] = {"cg+ilu0": {"ms": float(np.median(ts)), "iterations": log["iters"], "converged": log["isconverged"]},
+                         "cholesky create + solve": {"ms": c["create_ms"]["median"] + c["ldiv_ms"]["median"], "residual": resid["cholesky"]}}
+
+    def rnd(x):
+        if isinstance(x, float):
+            return round(x, 4) if abs(x) >= 1e-3 else float("%.3e" % x)
+        if isinstance(x, dict):
+            return {k: rnd(y) for k, y in x.items()}
+        if isinstance(x, list):
+            return [rnd(y) for y in x]
+        return x
+    print(json.dumps(rnd(out)))
+
+
 def bench_ilut(a, torch, esp):
     import numpy as np
     A = esp.fdrand(a.n, a.n, a.n)
@@ -1186,8 +1276,9 @@ def main():
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "gmres", "gmres-trace", "block", "block-trace", "block-trace-diff", "amg", "iluk", "colored", "spai0", "spai1", "spai1sym", "ilut", "lu"], default="point")
+    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "gmres", "gmres-trace", "block", "block-trace", "block-trace-diff", "amg", "iluk", "colored", "spai0", "spai1", "spai1sym", "ilut", "lu", "cholesky"], default="point")
     ap.add_argument("--leaf-size", type=int, default=32)
+    ap.add_argument("--lu-rounds", type=int, default=0, help="--kind cholesky: the rounds LUFactorization, the yardstick, takes part in")
     ap.add_argument("--droptol", type=float, default=1e-3)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--sweeps", type=int, default=3)
@@ -1233,6 +1324,8 @@ def main():
         return bench_ilut(a, torch, esp)
     if a.kind == "lu":
         return bench_lu(a, torch, esp)
+    if a.kind == "cholesky":
+        return bench_cholesky(a, torch, esp)
     if a.kind == "amg":
         return bench_amg(a, torch, esp)
     if a.kind == "colored":
