@@ -668,3 +668,296 @@ def test_clique_components_node_sizes(tmp_path_factory):
     got, st = nodes(*fp.CLIQUE_TAILS_AT_THE_EDGE)
     assert [g for g in got if g[0] > 59] == [(63, 1), (64, 1), (65, 1)] and st["rounds"] == 2
     assert sorted(g for g in got if g[0] <= 59) == [(1, 0)] * 3 + [(7, 1)] * 3   # the separators and the far ends of the paths
+
+
+# =================================================================================================================================
+# the approximate-inverse and threshold side: tests/approx_patterns.py
+# =================================================================================================================================
+import os  # noqa: E402
+
+import approx_patterns as xp  # noqa: E402
+import ilut_modellib  # noqa: E402
+import spai_modellib  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def spai(tmp_path_factory):
+    return spai_modellib.Model(tmp_path_factory.mktemp("edge_spai_model"))
+
+
+@pytest.fixture(scope="module")
+def ilut(tmp_path_factory):
+    return ilut_modellib.Model(tmp_path_factory.mktemp("edge_ilut_model"))
+
+
+def spai_limits(esp):
+    return esp._lib.ESP_SPAI_WAVE_DOUBLES, esp._lib.ESP_SPAI_DENSE_MAX
+
+
+def named_tier(esp, csc, k=0):
+    p, q, tc, maxlen = xp.column_sizes(csc, k)
+    return (p, q, tc), xp.spai_tier(p, q, tc, maxlen, *spai_limits(esp))
+
+
+def lstsq_error(csc, m, columns):
+    """the largest |m - m_ref|_inf / max(1, |m_ref|_inf) over `columns`, m_ref by numpy.linalg.lstsq on the same I and J, and the
+    largest condition number of a B"""
+    cp, rv, nz = csc
+    n = len(cp) - 1
+    A = sp.csc_matrix((nz, rv - 1, cp - 1), shape=(n, n))
+    worst, cond = 0.0, 0.0
+    for k in columns:
+        J = rv[cp[k] - 1:cp[k + 1] - 1] - 1
+        I = np.unique(np.concatenate([rv[cp[j] - 1:cp[j + 1] - 1] - 1 for j in J]))
+        B = A[I][:, J].toarray()
+        ref = np.linalg.lstsq(B, (I == k).astype(np.float64), rcond=None)[0]
+        got = m[cp[k] - 1:cp[k + 1] - 1]
+        worst = max(worst, float(np.max(np.abs(got - ref)) / max(1.0, np.max(np.abs(ref)))))
+        cond = max(cond, float(np.linalg.cond(B)))
+    return worst, cond
+
+
+def test_approx_constants(esp):
+    W, D = spai_limits(esp)
+    assert (W, D, xp.SORT_MAX, xp.SIZE_WAVE, xp.GRID_MAX, xp.RGRID) == (512, 12288, 16384, 512, 1 << 20, 1024)
+    assert 22 * 22 <= W < 23 * 23 and 110 * 110 <= D < 111 * 111 and 128 * 128 == xp.SORT_MAX < 129 * 129
+    # (the three are not exported: tied to the source, whatever its spacing)
+    import re
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "extendablesparse.jl_amd", "csrc", "spai.hip")).read()
+    for pattern in (r"SORT_MAX\s*=\s*16384\s*;", r"GRID_MAX\s*=\s*1u\s*<<\s*20\s*;",
+                    r"min<i64>\(\s*stats\[3\]\s*,\s*1024\s*\)\s*,\s*\(\s*\(i64\)\s*1\s*<<\s*27\s*\)\s*/\s*rslot"):
+        assert re.search(pattern, text), pattern
+    assert xp.R_DOUBLES == 1 << 27
+
+
+@pytest.mark.parametrize("m,tier", [(22, xp.TIER_WAVE), (23, xp.TIER_WIDE), (110, xp.TIER_WIDE)])
+def test_dense_block_accepted(esp, spai, m, tier):
+    """p = q = m and tc = m * m in every column; 22: the wave form's sort full (484 of 512 words, no wide column), 23: q q > 512 and
+    tc > 512; 110: 12100 <= 12288 doubles, 16384 padded words of sort.  Every column against lstsq"""
+    csc = xp.dense_block(m)
+    for k in (0, m // 2, m - 1):
+        assert named_tier(esp, csc, k) == ((m, m, m * m), (tier, m))
+    assert xp.size_form(m * m) == ("wave" if m == 22 else "group")
+    assert 1 << (m * m - 1).bit_length() == {22: 512, 23: 1024, 110: 16384}[m]
+    vals, pcol, stats = spai.spai1(csc)
+    assert np.all(pcol == m) and stats == (m, m, m * m)
+    err, cond = lstsq_error(csc, vals, range(m))
+    print("dense_block(%d): model against lstsq %.3e, cond(B) %.3f" % (m, err, cond))
+    assert err <= 1e-10, (err, cond)
+
+
+@pytest.mark.parametrize("m,tier,p", [(111, xp.TIER_REFUSED, 111), (128, xp.TIER_REFUSED, 128), (129, xp.TIER_REFUSED_BOUND, 129)])
+def test_dense_block_refused(esp, m, tier, p):
+    """tc = 12321 and 16384 are sorted and refused with p; 16641 > SORT_MAX is refused unsorted with the bound
+    max(maxlen, ceil(tc / q)) = 129"""
+    csc = xp.dense_block(m)
+    assert named_tier(esp, csc, 0) == ((m, m, m * m), (tier, p))
+    assert (m * m > xp.SORT_MAX) == (tier == xp.TIER_REFUSED_BOUND) and m * m > spai_limits(esp)[1]
+
+
+@pytest.mark.parametrize("p,q,tier,form", [(64, 8, xp.TIER_WAVE, "wave"), (57, 9, xp.TIER_WIDE, "group")])
+def test_full_lists(esp, spai, p, q, tier, form):
+    """test_tier_boundary's (p, q) with tc = p q: 512 is the wave form's last size, 513 the workgroup form's first"""
+    csc = xp.full_lists(p, q)
+    assert named_tier(esp, csc, 0) == ((p, q, p * q), (tier, p)) and xp.size_form(p * q) == form
+    assert xp.diagonal_position(csc, 0) == -1 and 1 in csc[1][csc[0][1] - 1:csc[0][2] - 1]        # row 0 is in I
+    for k in range(1, q + 1):                                  # the q columns: p unknowns over p rows, the workgroup tier's
+        assert named_tier(esp, csc, k) == ((p, p, q + q * p + (p - q - 1)), (xp.TIER_WIDE, p))
+    vals, pcol, stats = spai.spai1(csc)
+    assert pcol[0] == p and stats == (p, p, p * p)
+    err, cond = lstsq_error(csc, vals, [0])
+    print("full_lists(%d, %d): model against lstsq %.3e, cond(B) %.3f" % (p, q, err, cond))
+    assert err <= 1e-10 and np.abs(vals[:q]).max() > 0.0, (err, cond)
+
+
+@pytest.mark.parametrize("p,q", [(768, 16), (128, 96)])
+def test_sized_at_the_cap(esp, spai, p, q):
+    """p q = ESP_SPAI_DENSE_MAX exactly, tc = p + q - 1; every column against lstsq"""
+    csc = xp.sized(p, q)
+    assert p * q == spai_limits(esp)[1]
+    assert named_tier(esp, csc, 0) == ((p, q, p + q - 1), (xp.TIER_WIDE, p))
+    ps, qs, tcs = xp.all_sizes(csc)
+    assert (ps * qs).max() == p * q and int((ps * qs).argmax()) == 0 and ps[0] == p and tcs[0] == p + q - 1
+    vals, pcol, stats = spai.spai1(csc)
+    assert np.array_equal(pcol, ps) and stats == (p, max(q, int(qs.max())), p * q)
+    err, cond = lstsq_error(csc, vals, range(p))
+    print("sized(%d, %d): model against lstsq %.3e, cond(B) %.3f" % (p, q, err, cond))
+    assert err <= 1e-10, (err, cond)
+
+
+def fan_tiers(esp, p, q, shared=False):
+    """the sizes and tiers of fan(p, q): column 0, and the q columns of its unknowns"""
+    csc = xp.fan(p, q, shared)
+    assert p * q == spai_limits(esp)[1]
+    assert named_tier(esp, csc, 0) == ((p, q, p * q if shared else p), (xp.TIER_WIDE, p))
+    for k in range(1, q + 1):
+        own = p if shared else k * p // q - (k - 1) * p // q                    # the column's unknowns
+        seen = q if shared or k == 1 else 0                                   # column 0 is the only one of them that stores rows
+        assert named_tier(esp, csc, k) == ((seen, own, seen), (xp.TIER_WIDE, seen))
+    return csc
+
+
+@pytest.mark.parametrize("p,q,shared", [(1536, 8, False), (1536, 8, True), (4096, 3, False), (6144, 2, False)])
+def test_fan_at_the_cap(esp, spai, p, q, shared):
+    """p q = ESP_SPAI_DENSE_MAX with p / q = 192, 1365 and 3072 (24, 64 and 96 lane strides): only columns without a diagonal over
+    empty columns allow it (a column of len rows that stores its diagonal has a problem of len * len doubles at least).  (1536, 8)
+    with all eight lists full: tc = 12288 = ESP_SPAI_DENSE_MAX exactly, what spai1_k's `fits` compares, every row eight times in
+    a sort of 16384 padded words.  Column 0 against lstsq"""
+    csc = fan_tiers(esp, p, q, shared)
+    with np.errstate(all="ignore"):
+        vals, pcol, stats = spai.spai1(csc)
+    assert pcol[0] == p and stats == (p, p if shared else -(-p // q), p * q)
+    err, cond = lstsq_error(csc, vals, [0])
+    print("fan(%d, %d%s): model against lstsq %.3e, cond(B) %.3f" % (p, q, ", shared" if shared else "", err, cond))
+    assert err <= 1e-10 and np.all(np.isfinite(vals[:q])) and np.abs(vals[:q]).max() > 0.0
+
+
+def test_one_unknown_at_the_cap(esp, spai):
+    """(p, q) = (12288, 1): I full, tc = p = ESP_SPAI_DENSE_MAX, 192 lane strides, no column d > c; the model against the closed form
+    m = b_0 / (b . b).  The column that the unknown names holds 12288 rows, so its own problem has 12288 unknowns over one row
+    (accepted: 12288 doubles): 75 million ordered sums, most of this test's eight seconds"""
+    p = 12288
+    csc = fan_tiers(esp, p, 1)
+    with np.errstate(all="ignore"):
+        vals, pcol, stats = spai.spai1(csc)
+    assert (pcol[0], pcol[1]) == (p, 1) and stats == (p, p, p)
+    b = csc[2][csc[0][1] - 1:csc[0][2] - 1]
+    ref = b[0] / np.dot(b, b)
+    err = abs(vals[0] - ref) / max(1.0, abs(ref))
+    print("fan(12288, 1): model against the closed form %.3e" % err)
+    assert err <= 1e-10 and vals[0] != 0.0
+
+
+def test_r_slots():
+    """the second term of the launch's grid: 1 GiB of R slots"""
+    assert xp.r_slots(1030, 40) == 1024 and xp.r_slots(110, 110) == 110
+    assert xp.r_slots(9, 192) == 9 and xp.r_slots(9, 1536) == 9 and xp.r_slots(4, 1366) == 4 and xp.r_slots(3, 3072) == 3
+    assert xp.r_slots(57, 1536) == 56 and xp.r_slots(2, 12288) == 1
+
+
+@pytest.mark.parametrize("h,wide", [(22, 0), (23, 1)])
+def test_hubs_on_the_qq_rule(esp, h, wide):
+    """p q = 3 h <= 69: the q q rule alone decides"""
+    csc = xp.hub(h)
+    want = xp.TIER_WIDE if wide else xp.TIER_WAVE
+    assert named_tier(esp, csc, 0) == ((3, h, h + 2), (want, 3)) and 3 * h <= spai_limits(esp)[0]
+    assert (h * h > spai_limits(esp)[0]) == bool(wide)
+    for k in range(1, h + 1):
+        assert named_tier(esp, csc, k)[1][0] == xp.TIER_WAVE
+
+
+def test_many_wide(esp):
+    csc = xp.many_wide(1030)
+    n = len(csc[0]) - 1
+    assert n == 515 * 24 + 515 * 41 == 33475
+    ps, qs, tcs = xp.all_sizes(csc)
+    W, D = spai_limits(esp)
+    wide = (ps * qs > W) | (qs * qs > W)
+    assert int(wide.sum()) == 1030 > xp.RGRID and (ps * qs).max() <= D and tcs.max() <= xp.SIZE_WAVE
+    assert sorted(set(qs[wide])) == [23, 40] and np.all(ps[wide] == 3)
+    listed = np.flatnonzero(wide)
+    assert qs[listed[0]] == 23 and qs[listed[1]] == 40 and qs[listed[1024]] == 23 and qs[listed[1025]] == 40
+    assert (int(ps.max()), int(qs.max()), int((ps * qs).max())) == (41, 40, 123)
+
+
+def test_tridiagonal_past_the_grid(spai):
+    n = xp.GRID_MAX + 1
+    csc = xp.tridiagonal(n)
+    cp, rv, nz = csc
+    assert len(rv) == 3 * n - 2 and np.array_equal(np.diff(cp)[[0, 1, n - 1]], [2, 3, 2])
+    assert np.array_equal(rv[:5], [1, 2, 1, 2, 3]) and np.array_equal(rv[-2:], [n - 1, n])
+    assert xp.column_sizes(csc, n - 1) == (3, 2, 5, 3) and xp.column_sizes(csc, 5) == (5, 3, 9, 3)
+    small = xp.tridiagonal(40)
+    vals, pcol, stats = spai.spai1(small)
+    assert stats == (5, 3, 15)
+    assert lstsq_error(small, vals, range(40))[0] <= 1e-10
+
+
+def test_spai0_columns(spai):
+    csc = xp.spai0_matrix()
+    cp, rv, nz = csc
+    n = len(cp) - 1
+    assert n == xp.SPAI0_N and n % 4 == 3
+    lens = np.diff(cp)
+    assert [int(lens[j]) for j in sorted(xp.SPAI0_COLUMNS)] == [63, 64, 65, 130, 200, 200, 130, 0]
+    pos = {j: xp.diagonal_position(csc, j) for j in xp.SPAI0_COLUMNS}
+    assert pos == {5: 5, 70: 63, 100: 64, 150: 129, 160: 160, 180: -1, 190: 109, 200: -1}
+    assert pos[150] == lens[150] - 1 and pos[150] // xp.WAVE == 2 and pos[100] // xp.WAVE == 1 and pos[190] // xp.WAVE == 1
+    with np.errstate(all="ignore"):
+        d = spai.spai0(csc)
+        s = spai.spai0(xp.spai0_matrix(special=True))
+    A = sp.csc_matrix((nz, rv - 1, cp - 1), shape=(n, n)).toarray()
+    keep = np.ones(n, bool)
+    keep[[180, 200]] = False
+    assert np.allclose(d[keep], np.diag(A)[keep] / (A * A).sum(0)[keep], rtol=1e-14, atol=0.0)
+    assert bits(d[180:181])[0] == 0 and np.isnan(d[200])
+    assert np.isnan(s[160]) and s[150] == 0.0 and np.array_equal(np.isfinite(s), np.isfinite(d) & (np.arange(n) != 160))
+
+
+COMBS = [(200, 12), (300, 12), (4200, 12)]
+
+
+@pytest.mark.parametrize("up,L", COMBS)
+def test_comb_reaches_every_end_of_the_lookup(esp, ilut, up, L):
+    csc, j = xp.comb(up, L)
+    cp, rv, nz = csc
+    n = len(cp) - 1
+    ups = xp.upper_counts(csc)
+    assert ups[j] == up and 8 * L < up and np.delete(ups, j).max() == 1
+    Wv, G = esp._lib.ESP_ILUT_WAVE_UPPER, esp._lib.ESP_ILUT_GROUP_UPPER
+    assert (up <= Wv, Wv < up <= G, up > G) == {200: (True, False, False), 300: (False, True, False), 4200: (False, False, True)}[up]
+    rows = rv[cp[j] - 1:cp[j + 1] - 1] - 1
+    K = rows[:up]
+    assert j - K.max() - 1 >= 40 and np.all(np.diff(K) == 2)
+    perrow = np.bincount(rv - 1, minlength=n)
+    assert np.all(perrow[rows[rows != j]] == L)
+    S = sp.csc_matrix((nz, rv - 1, cp - 1), shape=(n, n))
+    d = S.diagonal()
+    assert np.all(d > np.asarray(abs(S).sum(axis=0)).ravel() - d) and np.all(d > np.asarray(abs(S).sum(axis=1)).ravel() - d)
+    out = xp.sweep_outcomes(csc)
+    print("comb(%d, %d): n = %d, nnz = %d, %s" % (up, L, n, len(rv), out))
+    assert min(out["hit"], out["miss"], out["exhausted"], out["bound"], out["carried"]) >= 16 and out["merge"] > 0
+    assert out["lookup"] == len(rows) and out["merge"] == len(rv) - len(rows)
+    for par in ((0.0, 0, 1), (1e-3, 1, 2)):
+        P = ilut.precon(csc, *par)
+        assert np.isfinite(P.F).all()
+        got = xp.upper_counts((P.S[0], P.S[1]))
+        assert got[j] == up if par[0] == 0.0 else up - 8 <= got[j] <= up      # (the drop rule takes an entry or two of the long column)
+        tier = lambda u: int(u > Wv) + int(u > G)      # noqa: E731
+        assert tier(got[j]) == tier(up) and np.delete(got, j).max() <= Wv
+
+
+@pytest.mark.parametrize("L", [5, 31])
+def test_switch_pair_sits_on_the_switch(esp, L):
+    (a, ja), (b, jb) = xp.switch_pair(L)
+    for (csc, j), up, look in ((a, ja), 8 * L, False), ((b, jb), 8 * L + 1, True):
+        cp, rv, _ = csc
+        n = len(cp) - 1
+        assert xp.upper_counts(csc)[j] == up <= esp._lib.ESP_ILUT_WAVE_UPPER
+        rows = rv[cp[j] - 1:cp[j + 1] - 1] - 1
+        perrow = np.bincount(rv - 1, minlength=n)
+        assert np.all(perrow[rows[rows != j]] == L) and perrow[j] == 2
+        assert np.all((perrow[rows[rows != j]] * 8 < up) == look)
+        out = xp.sweep_outcomes(csc)
+        assert out["lookup"] == (len(rows) if look else 1)        # (row j itself holds two entries: always the look-up, ended at once)
+        if look:
+            assert min(out["hit"], out["miss"], out["exhausted"], out["bound"]) >= 16
+
+
+@pytest.mark.parametrize("name", ["comb200", "comb300", "pair5a", "pair5b", "pair31a", "pair31b"])
+def test_ilut_model_against_the_dense_restatement_on_the_combs(ilut, name):
+    """test_ilut_model.py's comparison and bound (the patterns equal, the values to 1e-12 of the largest entry) on the look-up
+    patterns: no sum holds more than L - 3 products here"""
+    csc = {"comb200": lambda: xp.comb(200, 12), "comb300": lambda: xp.comb(300, 12), "pair5a": lambda: xp.switch_pair(5)[0],
+           "pair5b": lambda: xp.switch_pair(5)[1], "pair31a": lambda: xp.switch_pair(31)[0], "pair31b": lambda: xp.switch_pair(31)[1]}[name]()[0]
+    n = len(csc[0]) - 1
+    worst = 0.0
+    for tau, steps, sweeps in ((0.0, 0, 3), (1e-3, 1, 2)):
+        P = ilut.precon(csc, tau, steps, sweeps, max_fill=1e6)
+        Pd, Fd = ilut_modellib.dense_ilut(csc, tau, steps, sweeps)
+        Pm, Fm = ilut_modellib.dense_from(P.S, P.F, n)
+        assert np.array_equal(Pm, Pd), (name, tau, steps)
+        err = np.abs(Fm - Fd).max() / np.abs(Fd).max()
+        worst = max(worst, err)
+        assert err <= 1e-12, (name, tau, steps, err)
+    print("%s: model against the dense restatement %.3e" % (name, worst))
