@@ -17,9 +17,10 @@ __device__ __forceinline__ PairPlace pair_place(u32 ec, u32 *lw, int lane, int w
     if (lane == 63) lw[w] = einc;
     __syncthreads();
     PairPlace pl{einc - ec, 0u};
+    const int wu = __builtin_amdgcn_readfirstlane(w);  // (the wave's number: the same in its lanes, so `i < wu` is a scalar compare)
 #pragma unroll
     for (int i = 0; i < WAVES; i++) {
-        pl.at0 += i < w ? lw[i] : 0u;
+        pl.at0 += i < wu ? lw[i] : 0u;
         pl.total += lw[i];
     }
     return pl;
@@ -33,13 +34,45 @@ __device__ __forceinline__ bool pair_table_hit(u64 dst, u64 dst_next, u32 total,
 }
 
 // store: coalesced rowval / nzval stores of the dense records; the lane of a column writes its colptr (the columns' range is
-// clamped: [c_lo, c_hi)), the last pair the closing one.  row_add makes the records' rows 1-based.  KEEP: the values alone
+// clamped: [c_lo, c_hi)), the last pair the closing one.  row_add makes the records' rows 1-based.  KEEP: the values alone.
+// A lane stores two consecutive records per round, 16 bytes to each array: where out_val + dst is no multiple of 16 bytes one
+// record goes first by itself, and one follows where a record is left over -- the parity is the address's own, so every 16-byte
+// store is aligned and the stores cover [dst, dst + total) exactly, as one record per lane did.  (rowval and nzval are both arrays
+// of 8-byte elements: where their bases differ in parity -- no allocation of the handle's does -- a lane stores one record.)
 template <bool KEEP>
 __device__ __forceinline__ void pair_store(const Args &a, const u32 *rows, const double *vals, i64 row_add, u64 dst, PairPlace pl, u64 hi,
                                            int ncl, int s, int t) {
-    for (int p = t; p < (int)pl.total; p += THREADS) {
-        if constexpr (!KEEP) a.out_row[dst + p] = (i64)rows[p] + row_add;
-        a.out_val[dst + p] = vals[p];
+    typedef double dbl2 __attribute__((ext_vector_type(2)));
+    typedef long long ll2 __attribute__((ext_vector_type(2)));
+    const int total = (int)pl.total;
+    double *const ov = a.out_val + dst;
+    i64 *orow = nullptr;  // (the values-only form never forms an address in rowval)
+    bool wide = true;
+    if constexpr (!KEEP) {
+        orow = a.out_row + dst;
+        wide = (((uintptr_t)ov ^ (uintptr_t)orow) & 8) == 0;
+    }
+    if (wide) {
+        const int head = (int)(((uintptr_t)ov >> 3) & 1);  // (the first record does not start a 16-byte unit)
+        if (t == 0 && head && total > 0) {
+            if constexpr (!KEEP) orow[0] = (i64)rows[0] + row_add;
+            ov[0] = vals[0];
+        }
+        const int npair = (total - head) >> 1;  // (total = 0, head = 1: -1, no round)
+        for (int q = t; q < npair; q += THREADS) {
+            const int p = head + 2 * q;  // p + 1 < total
+            if constexpr (!KEEP) *reinterpret_cast<ll2 *>(orow + p) = ll2{(i64)rows[p] + row_add, (i64)rows[p + 1] + row_add};
+            *reinterpret_cast<dbl2 *>(ov + p) = dbl2{vals[p], vals[p + 1]};
+        }
+        if (t == ESP_WAVE && total > head && ((total - head) & 1)) {  // (another wave than the head's)
+            if constexpr (!KEEP) orow[total - 1] = (i64)rows[total - 1] + row_add;
+            ov[total - 1] = vals[total - 1];
+        }
+    } else {
+        for (int p = t; p < total; p += THREADS) {
+            if constexpr (!KEEP) orow[p] = (i64)rows[p] + row_add;
+            ov[p] = vals[p];
+        }
     }
     if constexpr (!KEEP) {
         const i64 c_lo = (i64)(hi >> a.rb);
