@@ -153,6 +153,9 @@ SIGNATURES = {
     "esp_precon_ilut_stats": (i32, [vp, P(i64)]),
     "esp_precon_ilut_limits": (i32, [P(i64)]),
     "esp_precon_lu_create": (i32, [vp, i32, i32, P(vp)]),
+    "esp_precon_lu_create_form": (i32, [vp, i32, i32, i32, P(vp)]),
+    "esp_precon_lu_panel_stats": (i32, [vp, P(i64)]),
+    "esp_debug_lu_wide_from": (i32, [vp, i64]),
     "esp_precon_lu_perm": (i32, [vp, vp, i32]),
     "esp_precon_lu_tree": (i32, [vp, vp, vp, i32]),
     "esp_precon_lu_matrix": (i32, [vp, P(vp)]),

@@ -228,6 +228,7 @@ int32_t block_ldiv_launch(esp_precon *p, const double *v, double *u, bool sub) {
     const i64 n = p->n;
     if (n == 0) return ESP_OK;
     CK(derived_follow_stream(p));
+    if (p->lup) return lup_solve(p, v, u, sub);  // LUFactorization's panel form: its own gather, depth launches and scatter
     if (p->blk_path == 0) {  // (simple! fuses its `u .-= upd` into the inner kind's own kernels there)
         if (sub) FAIL(h, ESP_ERR_STATE, "esp_precon_block: the identity path has no subtracting ldiv!");
         return precon_ldiv_launch(p->der.inner, v, u);

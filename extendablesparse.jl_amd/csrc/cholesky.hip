@@ -8,7 +8,8 @@
 // that order gives the same bits; this one walks the tree depth by depth.
 //
 //   panels     node K (width w, h = |struct(K)|) owns a dense (w + h) x w column-major panel, all panels in one allocation (64-bit
-//              offsets).  CholNode holds offset, w, h, start, depth, where struct(K) lies in S's rowval, and K's update list: the
+//              offsets).  The tables, their builder, struct_find and the gather / scatter of v[c] live in panels.hpp, shared with
+//              lu_panels.hip.  CholNode holds offset, w, h, start, depth, where struct(K) lies in S's rowval, and K's update list: the
 //              descendants J with struct(J) meeting K, ascending by position (from the transpose of S; built on the host at set-up).
 //              A position is found in J's panel by bisection in the sorted struct(J).
 //   load       chol_load_k: the panels are zeroed, then one lane per column s of A scatters the stored A[r, s], r <= s.  It is the
@@ -27,44 +28,19 @@
 //              from the update list with k ascending, then the triangle right-looking, t in LDS up to TRI_LDS rows, else in a
 //              second vector); backward per depth from 0 down (chol_bwd_k: struct first, then the triangle from the last position
 //              up); scatter u[c] = x.  Launches on the handle's stream and nothing else.
-#include "lu.hpp"
+#include "panels.hpp"
 
 using namespace espamg;
 using namespace esplu;
+using namespace esppanel;
 
-struct CholNode {
-    i64 off;      // the panel's first double
-    i64 sbase;    // struct(K) = srv[sbase .. sbase + h) (1-based positions, ascending)
-    u32 w, h, start, depth;
-    u32 ub, ue;   // the update list: ulist[ub .. ue)
-};
-
-struct CholLaunch {  // one block column of the wide nodes of a depth: dlist[first .. first + count), tiles per node
-    u32 first, count, bc, tiles_u, tiles_f;
-};
-struct CholDepth {
-    u32 all_first = 0, all_count = 0;      // dlist: every node of the depth (the solves)
-    u32 small_first = 0, small_count = 0;  // flist: the small nodes, then the wide ones by block columns descending
-    std::vector<CholLaunch> wide;
-};
-
-struct CholData {
-    esp_handle *S = nullptr;  // the struct lists (column start(K) = struct(K)); nullptr when no node has one
-    DevBuf nodes, ulist, dlist, flist, nodeof, panels, fail, y, y2, lcp;
-    std::vector<CholDepth> depth;
-    i64 nnodes = 0, panel_doubles = 0, nnzL = 0;
+struct CholData : PanelTree {
+    DevBuf panels, fail, y, y2, lcp;
     bool failed = false;
     i64 stats[ESP_CHOL_STATS] = {0};
 };
 
 namespace {
-
-constexpr int CT = 256;       // threads of every kernel here
-constexpr int NB = 32;        // columns of a block column = of the update tile = the factor block width = W_small
-constexpr int TR = 64;        // rows of the update tile
-constexpr int KB = 16;        // columns of a descendant staged at once
-constexpr int FR = 128;       // rows below the diagonal block a workgroup divides at once (one per lane of its first two waves)
-constexpr int TRI_LDS = 1024; // rows of a node's triangle the solves keep in LDS
 
 struct Dev {
     const CholNode *nodes;
@@ -73,20 +49,7 @@ struct Dev {
     double *panels;
 };
 
-// the index of position pos (0-based) in struct(J), or -1
-__device__ __forceinline__ int struct_find(const Dev &d, const CholNode &J, u32 pos) {
-    const i64 *s = d.srv + J.sbase;
-    int lo = 0, hi = (int)J.h - 1;
-    const i64 want = (i64)pos + 1;
-    while (lo <= hi) {
-        const int mid = (lo + hi) >> 1;
-        const i64 v = s[mid];
-        if (v == want) return mid;
-        if (v < want) lo = mid + 1;
-        else hi = mid - 1;
-    }
-    return -1;
-}
+__device__ __forceinline__ int struct_find(const Dev &d, const CholNode &J, u32 pos) { return esppanel::struct_find(d.srv, J, pos); }
 
 // ---- load ----------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(CT) void chol_load_k(Dev d, espfold::Csc A, const u32 *__restrict__ newpos, const u32 *__restrict__ nodeof, i64 n) {
@@ -321,18 +284,6 @@ __global__ __launch_bounds__(CT) void chol_factor_k(Dev d, const u32 *__restrict
 }
 
 // ---- solve ---------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(CT) void chol_gather_k(const u32 *__restrict__ perm, const double *__restrict__ v, double *__restrict__ y, i64 n) {
-    const i64 k = (i64)blockIdx.x * CT + threadIdx.x;
-    if (k < n) y[k] = v[perm[k]];
-}
-// u[c[k]] = x[k], or simple!'s step u[c[k]] = u[c[k]] - x[k]
-__global__ __launch_bounds__(CT) void chol_scatter_k(const u32 *__restrict__ perm, const double *__restrict__ x, double *__restrict__ u, i64 n, bool sub) {
-    const i64 k = (i64)blockIdx.x * CT + threadIdx.x;
-    if (k >= n) return;
-    const u32 i = perm[k];
-    u[i] = sub ? u[i] - x[k] : x[k];
-}
-
 // forward: a workgroup per node of list.  t lives in LDS (w <= TRI_LDS) or in y2
 __global__ __launch_bounds__(CT) void chol_fwd_k(Dev d, const u32 *__restrict__ list, double *__restrict__ y, double *__restrict__ y2) {
     __shared__ double sh[TRI_LDS];
@@ -415,25 +366,10 @@ Dev dev_of(const CholData *c) {
     return Dev{(const CholNode *)c->nodes.p, (const u32 *)c->ulist.p, c->S ? (const i64 *)c->S->rowval.p : nullptr, (double *)c->panels.p};
 }
 
-template <typename T>
-int32_t download(esp_handle *h, std::vector<T> &out, const void *src, size_t count) {
-    out.resize(count);
-    if (count) HIPCK(h, hipMemcpyAsync(out.data(), src, sizeof(T) * count, hipMemcpyDeviceToHost, h->stream));
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    return ESP_OK;
-}
-template <typename T>
-int32_t upload(esp_handle *h, DevBuf &b, const std::vector<T> &v) {
-    CK(ensure(h, b, sizeof(T) * std::max<size_t>(v.size(), 1)));
-    if (!v.empty()) HIPCK(h, hipMemcpyAsync(b.p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCK(h, hipStreamSynchronize(h->stream));  // (v is free from here)
-    return ESP_OK;
-}
-
 void chol_drop(CholData *c) {
     if (!c) return;
-    if (c->S) (void)esp_destroy(c->S);
-    for (DevBuf *b : {&c->nodes, &c->ulist, &c->dlist, &c->flist, &c->nodeof, &c->panels, &c->fail, &c->y, &c->y2, &c->lcp}) release(*b);
+    tree_drop(*c);
+    for (DevBuf *b : {&c->panels, &c->fail, &c->y, &c->y2, &c->lcp}) release(*b);
     delete c;
 }
 
@@ -446,133 +382,35 @@ int32_t chol_symbolic(esp_precon *p, CholData **out, Order &o) {
     Handles hs;
     Struct x{nullptr, nullptr, nullptr, nullptr};
     CK(lu_structs(h, o, "esp_precon_cholesky", hs, x));
-    std::vector<u32> nstart, nsize, level, perm;
-    std::vector<i64> scp, tcp, trv;
-    if (n > 0) {
-        CK(download(h, nstart, o.nstart.p, (size_t)n));
-        CK(download(h, nsize, o.nsize.p, (size_t)n));
-        CK(download(h, level, o.level.p, (size_t)n));
-        CK(download(h, perm, o.perm.p, (size_t)n));
-        if (x.scp) {
-            CK(download(h, scp, x.scp, (size_t)n + 1));
-            CK(download(h, tcp, x.tcp, (size_t)n + 1));
-            CK(download(h, trv, x.trv, (size_t)hs.v[1]->nnz));
-        }
-    }
     CholData *c = new CholData();
     struct Guard {
         CholData *c;
         ~Guard() { chol_drop(c); }
     } guard{c};
     const u32 wide_from = h->debug_chol_wide > 0 ? (u32)std::min<i64>(h->debug_chol_wide, 0xFFFFFFFFll) : (u32)NB + 1;
-    std::vector<CholNode> nodes;
-    std::vector<u32> nodeof((size_t)n), ulist;
-    i64 off = 0, nnzL = 0, largest = 0;
-    for (i64 k = 0; k < n;) {
-        CholNode K{};
-        K.start = (u32)k;
-        K.w = nsize[(size_t)k];
-        if (K.w == 0 || nstart[(size_t)k] != (u32)k || k + K.w > n) FAIL(h, ESP_ERR_HIP, "esp_precon_cholesky: the nodes of the ordering do not tile the positions");
-        K.depth = level[perm[(size_t)k]];
-        K.h = scp.empty() ? 0u : (u32)(scp[(size_t)k + 1] - scp[(size_t)k]);
-        K.sbase = scp.empty() ? 0 : scp[(size_t)k] - 1;
-        K.off = off;
-        off += ((i64)K.w + K.h) * K.w;
-        nnzL += (i64)K.w * (K.w + 1) / 2 + (i64)K.w * K.h;
-        largest = std::max<i64>(largest, K.w);
-        for (u32 t = 0; t < K.w; t++) nodeof[(size_t)k + t] = (u32)nodes.size();
-        nodes.push_back(K);
-        k += K.w;
-    }
-    if ((i64)nodes.size() != o.nodes) FAIL(h, ESP_ERR_HIP, "esp_precon_cholesky: %lld nodes counted, %lld listed", (long long)o.nodes, (long long)nodes.size());
-    // the update lists: the nodes whose struct holds a position of K, ascending (T's column k lists them by start)
-    std::vector<u32> tmp;
-    for (CholNode &K : nodes) {
-        tmp.clear();
-        if (!tcp.empty())
-            for (u32 t = 0; t < K.w; t++)
-                for (i64 q = tcp[(size_t)K.start + t] - 1; q < tcp[(size_t)K.start + t + 1] - 1; q++) tmp.push_back(nodeof[(size_t)(trv[(size_t)q] - 1)]);
-        std::sort(tmp.begin(), tmp.end());
-        tmp.erase(std::unique(tmp.begin(), tmp.end()), tmp.end());
-        K.ub = (u32)ulist.size();
-        ulist.insert(ulist.end(), tmp.begin(), tmp.end());
-        K.ue = (u32)ulist.size();
-        if (ulist.size() >= 0xFFFFFFF0ull) FAIL(h, ESP_ERR_UNSUPPORTED, "esp_precon_cholesky: the update lists hold 2^32 entries");
-    }
-    // the schedule: the nodes are sorted by depth descending already
-    c->depth.assign((size_t)(n > 0 ? o.deepest + 1 : 0), CholDepth());
-    std::vector<u32> dlist, flist;
-    i64 nsmall = 0, nwide = 0, nbcols = 0;
-    for (size_t a = 0; a < nodes.size();) {
-        size_t b = a;
-        while (b < nodes.size() && nodes[b].depth == nodes[a].depth) b++;
-        if (nodes[a].depth >= c->depth.size()) FAIL(h, ESP_ERR_HIP, "esp_precon_cholesky: a node lies deeper than the deepest level");
-        CholDepth &D = c->depth[nodes[a].depth];
-        if (D.all_count) FAIL(h, ESP_ERR_HIP, "esp_precon_cholesky: the nodes are not sorted by depth");
-        D.all_first = (u32)dlist.size();
-        D.all_count = (u32)(b - a);
-        for (size_t q = a; q < b; q++) dlist.push_back((u32)q);
-        D.small_first = (u32)flist.size();
-        std::vector<u32> wide;
-        for (size_t q = a; q < b; q++) {
-            if (nodes[q].w < wide_from) flist.push_back((u32)q);
-            else wide.push_back((u32)q);
-        }
-        D.small_count = (u32)flist.size() - D.small_first;
-        nsmall += D.small_count;
-        nwide += (i64)wide.size();
-        std::stable_sort(wide.begin(), wide.end(), [&](u32 l, u32 r) { return nodes[l].w > nodes[r].w; });
-        const u32 wfirst = (u32)flist.size();
-        flist.insert(flist.end(), wide.begin(), wide.end());
-        const u32 maxbc = wide.empty() ? 0u : (nodes[wide[0]].w + NB - 1) / NB;
-        for (u32 bc = 0; bc < maxbc; bc++) {
-            CholLaunch Lc{wfirst, 0, bc, 1, 1};
-            i64 rows = 0;
-            for (u32 q : wide) {
-                if ((nodes[q].w + NB - 1) / NB <= bc) break;
-                Lc.count++;
-                rows = std::max<i64>(rows, (i64)nodes[q].w + nodes[q].h - (i64)bc * NB);
-            }
-            Lc.tiles_u = (u32)std::max<i64>(1, (rows + TR - 1) / TR);
-            Lc.tiles_f = (u32)std::max<i64>(1, (rows + FR - 1) / FR);  // (the rows below a short last block column: a bound)
-            if ((i64)Lc.count * std::max(Lc.tiles_u, Lc.tiles_f) > 0x7FFFFFFFll) FAIL(h, ESP_ERR_UNSUPPORTED, "esp_precon_cholesky: a depth's grid exceeds 2^31 workgroups");
-            D.wide.push_back(Lc);
-        }
-        nbcols += maxbc;
-        a = b;
-    }
+    CK(tree_build(h, o, hs, x, "esp_precon_cholesky", wide_from, *c));
     // L's column starts
     std::vector<i64> lcp((size_t)n + 1);
     lcp[0] = 1;
-    for (const CholNode &K : nodes)
+    for (const CholNode &K : c->host_nodes)
         for (u32 t = 0; t < K.w; t++) lcp[(size_t)K.start + t + 1] = lcp[(size_t)K.start + t] + (K.w - t) + K.h;
-    CK(upload(h, c->nodes, nodes));
-    CK(upload(h, c->ulist, ulist));
-    CK(upload(h, c->dlist, dlist));
-    CK(upload(h, c->flist, flist));
-    CK(upload(h, c->nodeof, nodeof));
+    c->host_nodes.clear();
+    const i64 off = c->panel_doubles;
     CK(upload(h, c->lcp, lcp));
     CK(ensure(h, c->panels, sizeof(double) * (size_t)std::max<i64>(off, 1)));
     CK(ensure(h, c->fail, sizeof(u64)));
     CK(ensure(h, c->y, sizeof(double) * (size_t)std::max<i64>(n, 1)));
     CK(ensure(h, c->y2, sizeof(double) * (size_t)std::max<i64>(n, 1)));
-    if (!hs.v.empty()) {
-        c->S = hs.v[0];
-        hs.v[0] = nullptr;
-    }
-    c->nnodes = (i64)nodes.size();
-    c->panel_doubles = off;
-    c->nnzL = nnzL;
     i64 *st = c->stats;
-    st[0] = nnzL;
+    st[0] = c->nnzL;
     st[1] = o.rounds;
     st[2] = n > 0 ? o.deepest : 0;
-    st[3] = (i64)nodes.size();
-    st[4] = largest;
+    st[3] = c->nnodes;
+    st[4] = c->largest;
     st[5] = off;
-    st[9] = nsmall;
-    st[10] = nwide;
-    st[11] = nbcols;
+    st[9] = c->nsmall;
+    st[10] = c->nwide;
+    st[11] = c->nbcols;
     i64 solve = n > 0 ? 2 : 0;
     for (const CholDepth &D : c->depth) solve += D.all_count ? 2 : 0;
     st[8] = solve;
@@ -671,7 +509,7 @@ int32_t chol_solve(esp_precon *p, const double *v, double *u, bool sub) {
     const u32 *perm = (const u32 *)p->lu_perm.p, *dlist = (const u32 *)c->dlist.p;
     double *y = (double *)c->y.p, *y2 = (double *)c->y2.p;
     const unsigned g = grid_for(n, CT);
-    hipLaunchKernelGGL(chol_gather_k, dim3(g), dim3(CT), 0, s, perm, v, y, n);
+    hipLaunchKernelGGL(panel_gather_k, dim3(g), dim3(CT), 0, s, perm, v, y, n);
     for (size_t dep = c->depth.size(); dep-- > 0;) {
         const CholDepth &D = c->depth[dep];
         if (D.all_count) hipLaunchKernelGGL(chol_fwd_k, dim3(D.all_count), dim3(CT), 0, s, d, dlist + D.all_first, y, y2);
@@ -680,7 +518,7 @@ int32_t chol_solve(esp_precon *p, const double *v, double *u, bool sub) {
         const CholDepth &D = c->depth[dep];
         if (D.all_count) hipLaunchKernelGGL(chol_bwd_k, dim3(D.all_count), dim3(CT), 0, s, d, dlist + D.all_first, y, y2);
     }
-    hipLaunchKernelGGL(chol_scatter_k, dim3(g), dim3(CT), 0, s, perm, (const double *)y, u, n, sub);
+    hipLaunchKernelGGL(panel_scatter_k, dim3(g), dim3(CT), 0, s, perm, (const double *)y, u, n, sub);
     return ESP_OK;
 }
 

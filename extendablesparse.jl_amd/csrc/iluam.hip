@@ -452,6 +452,7 @@ extern "C" int32_t esp_precon_get_factor(esp_precon *p, double *nzval, int32_t o
         if (h->pattern_version != p->pattern_version || h->nnz != p->nnz)
             FAIL(h, ESP_ERR_STATE, "esp_precon_get_factor: the matrix pattern changed since the preconditioner's last update!");
         CK(derived_follow_stream(p));
+        if (p->lup) return lup_factor(p, nzval, on_device);  // LUFactorization's panel form: exported from the panels
         const int32_t st = esp_precon_get_factor(p->der.inner, nzval, on_device);
         if (st != ESP_OK) FAIL(h, st, "%s", p->der.bh->err.c_str());
         return ESP_OK;

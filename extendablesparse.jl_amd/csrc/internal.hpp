@@ -22,6 +22,8 @@
 //                  matrix B in an internal handle, ILUAM on it
 //   lu.hip         LUFactorization: the nested-dissection ordering by level-synchronous component and search launches, the supernodal
 //                  symbolic fill from the dissection tree, the filled reordered matrix B with ILUAM as the inner kind
+//   lu_panels.hip  LUFactorization's panel form: ILUAM's chains over B on two dense panels per tree node (panels.hpp: the tables it
+//                  shares with cholesky.hip), the solves in ILUAM's orders
 //   cholesky.hip   CholeskyFactorization: lu.hip's ordering and tree (lu.hpp), dense column-major panels per node, the numeric
 //                  factorization and the solves depth by depth (small form: a workgroup per node; wide form: tiles over the grid)
 //   ilut.hip       ILUTPreconditioner: the threshold ILU by synchronous sweeps (wave / workgroup / stride tiers of the sweep kernel),
@@ -100,6 +102,7 @@ struct esp_handle {
     bool g3_wide = false;                 // ... for its rows alone (spread over more than 2^18): the kernel's wide form serves this handle
     bool debug_fail_bucket = false;       // esp_debug_fail_next_bucket_stage (test hook, one shot)
     i64 debug_chol_wide = 0;              // esp_debug_cholesky_wide_from: the width from which CholeskyFactorization uses its wide form (test hook; 0: the default)
+    i64 debug_lu_wide = 0;                // esp_debug_lu_wide_from: the same for LUFactorization's panel form
     i64 debug_lu_cap = 0;                 // esp_debug_lu_fill_cap: LUFactorization refuses nnz(B) >= this (test hook; 0: the 32-bit limit)
     double debug_plan_cap = 0.0;          // esp_debug_plan_cap: plan as if the bucket kernel took segments of this many entries (test hook)
     int last_group3 = 0;                  // the last flush's bucket kernel was group3_k (esp_debug_last_local_small reports 2)
@@ -678,6 +681,10 @@ struct esp_precon {
     int lu_leaf = 32, lu_depth = 48;
     DevBuf lu_perm, lu_level, lu_root;  // u32 n each: c, the depth every vertex was placed at, the root vertex naming its tree node
     i64 lu_stats[6] = {0, 0, 0, 0, 0, 0};  // esp_precon_lu_stats' layout
+    // ... its panel form (lu_form == ESP_LU_PANELS, lu_panels.hip): B, src and the maps as above, NO inner preconditioner; the node
+    // table, the update lists, the schedule and the two panels per node in lup; ldiv! is lup_solve through blk_t and blk_s
+    int lu_form = 0;
+    struct LuPanelData *lup = nullptr;
     // CholeskyFactorization (kind ESP_PRECON_CHOLESKY, cholesky.hip): lu_leaf / lu_depth, lu_perm / lu_level / lu_root and blk_new (the
     // inverse of c) as above; the node table, the update lists, the schedule and the panels in chol
     struct CholData *chol = nullptr;
@@ -753,6 +760,11 @@ void color_release(esp_precon *p);
 // preconditioner, src and the inverse permutation are block_release's)
 int32_t lu_update(esp_precon *p);
 void lu_release(esp_precon *p);
+// lu_panels.hip: ldiv! of LUFactorization's panel form on device vectors (u may be v; sub: u[i] = u[i] - x[i], simple!'s step;
+// launches on the handle's stream only); esp_precon_get_factor's answer, nnz(B) doubles in B's position order exported from the
+// panels; the rest of its interface is lu.hpp's
+int32_t lup_solve(esp_precon *p, const double *v, double *u, bool sub);
+int32_t lup_factor(esp_precon *p, double *nzval, int32_t on_device);
 // cholesky.hip: update! (after a pattern change the ordering, the tables and the panels anew; else the load and the numeric
 // factorization), ldiv! on device vectors (u may be v; sub: u[i] = u[i] - x[i], simple!'s step; launches on the handle's stream only),
 // release of everything

@@ -31,6 +31,9 @@
 //                src[q], the position in A's nzval of A[c[row], c[k]] by bisection or ILUK_FILL.
 //   the kind     update!, the value gather and the inner ILUAM are derived.hip's; ldiv! is block.hip's gather / inner ldiv! /
 //                scatter over blk_new = the inverse of c (block_built holds for this kind).
+//   panel form   esp_precon_lu_create_form(.., ESP_LU_PANELS, ..): build_b as above (B, src, the maps), then the tables and the two panels
+//                per node of lu_panels.hip in the inner ILUAM's place; panels_update is derived_update's order of statements with
+//                lup_numeric where the inner update! stood; ldiv! and esp_precon_get_factor branch on p->lup (block.hip, iluam.hip).
 #include "lu.hpp"
 
 using namespace espamg;
@@ -588,6 +591,10 @@ int32_t build_b(esp_precon *p) {
         HIPCK(h, hipGetLastError());
         HIPCK(h, hipStreamSynchronize(s));
     }
+    LuPanelData *lp = nullptr;
+    if (p->lu_form == ESP_LU_PANELS) CK(lup_symbolic(p, o, hs, x, &lp));  // (the last thing that can fail)
+    lup_drop(p->lup);
+    p->lup = lp;
     install(p->der.bh, cp, rv, nz, nnzB);
     std::swap(p->der.src, src);
     std::swap(p->blk_new, o.newpos);
@@ -621,9 +628,37 @@ int32_t lu_check_args(esp_handle *h, const char *what, int32_t leaf_size, int32_
     return ESP_OK;
 }
 
-int32_t lu_update(esp_precon *p) { return derived_update(p, "esp_precon_lu", build_b, ""); }
+// the panel form's update!: derived_update's order of statements with the numeric factorization on the panels in the inner
+// preconditioner's place (no inner object, no level analysis, no schedules)
+static int32_t panels_update(esp_precon *p) {
+    esp_handle *h = p->h, *bh = p->der.bh;
+    CK(precon_check_handle(h, "esp_precon_update"));
+    if (windowed(h) || h->shard_user) FAIL(h, ESP_ERR_UNSUPPORTED, "esp_precon_lu: a column window / column shard");
+    CK(derived_follow_stream(p));
+    if (derived_stale(p)) {
+        CK(build_b(p));
+        p->pattern_version = 0;
+        p->der.rebuild = false;
+    } else {
+        p->pattern_version = 0;
+        if (bh->nnz > 0)
+            derived_gather_launch(h->stream, nullptr, (u32 *)p->der.src.p, nullptr, (const u64 *)h->nzval.p, (u64 *)bh->nzval.p, bh->nnz, nullptr);
+        HIPCK(h, hipGetLastError());
+        bh->values_version++;
+    }
+    CK(lup_numeric(p));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    p->nnz = h->nnz;
+    p->pattern_version = h->pattern_version;
+    p->values_version = h->values_version;
+    return ESP_OK;
+}
+
+int32_t lu_update(esp_precon *p) { return p->lu_form == ESP_LU_PANELS ? panels_update(p) : derived_update(p, "esp_precon_lu", build_b, ""); }
 
 void lu_release(esp_precon *p) {
+    lup_drop(p->lup);
+    p->lup = nullptr;
     for (DevBuf *b : {&p->lu_perm, &p->lu_level, &p->lu_root}) release(*b);
 }
 
@@ -640,11 +675,17 @@ extern "C" int32_t esp_nested_dissection(esp_handle *h, int32_t leaf_size, int32
 }
 
 extern "C" int32_t esp_precon_lu_create(esp_handle *h, int32_t leaf_size, int32_t max_depth, esp_precon **out) {
+    return esp_precon_lu_create_form(h, leaf_size, max_depth, ESP_LU_COLUMNS, out);
+}
+
+extern "C" int32_t esp_precon_lu_create_form(esp_handle *h, int32_t leaf_size, int32_t max_depth, int32_t form, esp_precon **out) {
     if (!h || !out) return ESP_ERR_INVALID;
     *out = nullptr;
+    if (form != ESP_LU_COLUMNS && form != ESP_LU_PANELS) return ESP_ERR_INVALID;
     CK(lu_check_args(h, "esp_precon_lu_create", leaf_size, max_depth));
     esp_precon *p = precon_new(h, ESP_PRECON_LU);
     p->der.inner_kind = ESP_PRECON_ILUAM;
+    p->lu_form = form;
     p->lu_leaf = leaf_size;
     p->lu_depth = max_depth;
     p->der.rebuild = true;

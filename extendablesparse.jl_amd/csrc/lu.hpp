@@ -1,5 +1,5 @@
 // lu.hpp -- what lu.hip (the nested-dissection ordering, the tree, the struct lists, LUFactorization) shares with cholesky.hip
-// (CholeskyFactorization: the same ordering and tree, dense panels per node)
+// (CholeskyFactorization: the same ordering and tree, dense panels per node) and lu_panels.hip (LUFactorization's panel form)
 #pragma once
 #include "amg.hpp"
 
@@ -37,4 +37,10 @@ int32_t lu_structs(esp_handle *h, esplu::Order &o, const char *what, espamg::Han
 // array, as int64 (wide) or as they are
 int32_t lu_check_args(esp_handle *h, const char *what, int32_t leaf_size, int32_t max_depth);
 int32_t lu_export(esp_handle *h, const DevBuf &src, void *out, bool wide, int32_t on_device);
+// lu_panels.hip, LUFactorization's panel form (p->lu_form == ESP_LU_PANELS): the tables and the panels' layout of the ordered tree (a
+// new LuPanelData, p untouched: build_b calls it behind its last refusal); the load from B's values and the numeric factorization;
+// release (ldiv! and the factor in B's position order: internal.hpp)
+int32_t lup_symbolic(esp_precon *p, esplu::Order &o, espamg::Handles &hs, const esplu::Struct &x, struct LuPanelData **out);
+int32_t lup_numeric(esp_precon *p);
+void lup_drop(struct LuPanelData *c);
 #pragma GCC visibility pop

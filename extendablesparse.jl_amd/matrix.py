@@ -620,12 +620,12 @@ class ExtendableSparseMatrix:
         d.ck(d.lib.esp_mul(d.h, _vp(x), _vp(r), 0))
         return r
 
-    def solve(self, b):
+    def solve(self, b, form="columns"):
         """A \\ b (abstractextendablesparsematrixcsc.jl: `\\` of a square matrix; test/test_backslash.jl): a one-shot
-        LUFactorization(A).solve(b) on the device, closed afterwards.  b: a NumPy array or a CUDA torch tensor; the result lives
-        where b does."""
+        LUFactorization(A, form=form).solve(b) on the device, closed afterwards.  b: a NumPy array or a CUDA torch tensor; the
+        result lives where b does.  form: "columns" or "panels" (LUFactorization: the same bits either way)."""
         from .precon import LUFactorization   # (precon.py imports this module)
-        f = LUFactorization(self)
+        f = LUFactorization(self, form=form)
         try:
             return f.solve(b)
         finally:

@@ -540,18 +540,41 @@ class LUFactorization(_ILUAMFactors, _PointPreconditioner):
     max_depth caps the rounds (what is left becomes dense leaves).  B holds copies: a value change of A reaches solve only through
     update(), which keeps the ordering, the tree, B's pattern and the schedules when only values changed and orders anew after a
     pattern change.  DEVIATIONS from UMFPACK / Sparspak: no pivoting -- a zero or NaN pivot propagates as in ILUAM --, and the
-    ordering is the one above, not AMD / MMD."""
+    ordering is the one above, not AMD / MMD.
+    form="columns" (the default) runs ILUAM's column kernel over B; form="panels" walks the same chains on two dense panels per tree
+    node (esp_precon_lu_create_form): the permutation, the tree, B, factor() and every bit of ldiv are the same, the
+    numeric factorization and the solves take a launch or two per depth of the tree instead of one per level of B's dependency
+    graph.  In the panel form levels() and launches() give zeros, debug_factor_form() / last_factor_form() raise (there is no inner
+    ILUAM), and panel_stats() tells what ran."""
     KIND = ESP_PRECON_LU
+    FORMS = {"columns": 0, "panels": 1}
 
-    def __init__(self, A, leaf_size=32, max_depth=48):
+    def __init__(self, A, leaf_size=32, max_depth=48, form="columns"):
         if not isinstance(A, ExtendableSparseMatrix):
             raise TypeError("LUFactorization(A, ...): A must be an ExtendableSparseMatrix")
         if int(leaf_size) != leaf_size or not 1 <= leaf_size < 2 ** 31:
             raise ValueError("LUFactorization: leaf_size = %r (an integer >= 1)" % (leaf_size,))
         if int(max_depth) != max_depth or not 0 <= max_depth <= 64:
             raise ValueError("LUFactorization: max_depth = %r (an integer in 0..64)" % (max_depth,))
-        self.leaf_size, self.max_depth = int(leaf_size), int(max_depth)
-        self._bind(A, "esp_precon_lu_create", self.leaf_size, self.max_depth)
+        if form not in self.FORMS:
+            raise ValueError("LUFactorization: form = %r (\"columns\" or \"panels\")" % (form,))
+        self.leaf_size, self.max_depth, self.form = int(leaf_size), int(max_depth), form
+        self._bind_form(A)
+
+    def _bind_form(self, A):
+        if self.form == "columns":
+            self._bind(A, "esp_precon_lu_create", self.leaf_size, self.max_depth)
+        else:
+            self._bind(A, "esp_precon_lu_create_form", self.leaf_size, self.max_depth, self.FORMS[self.form])
+
+    def panel_stats(self):
+        """the panel form's dict (esp_precon_lu_panel_stats): panel_doubles (allocated), factor_launches (of the last numeric
+        factorization), ldiv_launches (of one ldiv), small_nodes / wide_nodes (taken by either form), wide_block_columns (the
+        block-column steps of the wide form); an error on a column-form object"""
+        out = (C.c_int64 * 6)()
+        self._ck(self.A._d.lib.esp_precon_lu_panel_stats(self._live(), out))
+        names = ("panel_doubles", "factor_launches", "ldiv_launches", "small_nodes", "wide_nodes", "wide_block_columns")
+        return dict(zip(names, (int(x) for x in out)))
 
     def _factored(self):
         b = C.c_void_p()
@@ -680,8 +703,10 @@ def lu_(fact, A):
     if A is fact.A and fact._p is not None:
         return fact.update()
     fact.close()
-    create = "esp_precon_cholesky_create" if isinstance(fact, CholeskyFactorization) else "esp_precon_lu_create"
-    fact._bind(A, create, fact.leaf_size, fact.max_depth)
+    if isinstance(fact, CholeskyFactorization):
+        fact._bind(A, "esp_precon_cholesky_create", fact.leaf_size, fact.max_depth)
+    else:
+        fact._bind_form(A)   # (the object keeps its form)
     return fact
 
 
@@ -716,11 +741,11 @@ def nested_dissection(A, leaf_size=32, max_depth=48):
     return c + 1, level
 
 
-def solve(A, b):
-    """A \\ b: A.solve(b)"""
+def solve(A, b, form="columns"):
+    """A \\ b: A.solve(b, form=form)"""
     if not isinstance(A, ExtendableSparseMatrix):
         raise TypeError("solve(A, b): A must be an ExtendableSparseMatrix")
-    return A.solve(b)
+    return A.solve(b, form=form)
 
 
 def AMGCL_RLXPreconditioner(A, type="spai0"):

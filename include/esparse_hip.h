@@ -702,9 +702,39 @@ int32_t esp_precon_ilut_limits(int64_t out[4]);
  *   before B is allocated, esp_last_error gives nnz(B) (esp_debug_lu_fill_cap(h, cap) lowers that limit for the factorizations created
  *   on h afterwards, a test hook; 0 restores it).  n == 0 is valid.  LU is no inner kind of esp_precon_block_create or
  *   esp_precon_colored_create.  A live factorization makes h refuse esp_destroy; esp_precon_destroy releases B, the inner
- *   preconditioner and every buffer. */
+ *   preconditioner and every buffer.
+ * esp_precon_lu_create_form(h, leaf_size, max_depth, form): form ESP_LU_COLUMNS is esp_precon_lu_create, unchanged.  ESP_LU_PANELS is a
+ *   second schedule of the SAME numerics on dense panels per tree node; any other form is ESP_ERR_INVALID.  The rule: the
+ *   ordering, the tree, B (built as above: the missing-diagonal refusal, the fill guard, esp_precon_lu_matrix and the values-only
+ *   gather are the column form's) and every bit of the factor and of ldiv! are those of the column form, because ILUAM's factorization
+ *   of B is one fixed chain per entry (k, j) of B's pattern: t = b_kj; for every i < min(k, j) ascending with (i, j) and (k, i) in B's
+ *   pattern: t = t - u_ij*l_ki (the product rounded, then the difference); k > j: l_kj = t / u_jj, a true division.  (i, j) and (k, i)
+ *   lie in the pattern exactly when i belongs to a descendant J with j and k in node(J) + struct(J), or to the entry's own node: the
+ *   panel form walks these chains node by node from the deepest depth up.  Node K (width w, h = |struct(K)|) owns two column-major
+ *   (w + h) x w panels, PL[r, j] = B[row r, K_j] for r >= j and PU[r, j] = B[K_j, row r] for r > j: twice CholeskyFactorization's memory.
+ *   A load kernel scatters B's values into the zeroed panels; per depth the nodes narrower than the wide-form width (default 33) are
+ *   finished by one workgroup each in one launch, the others block column by block column (32 columns), two launches per block column;
+ *   plain FP64 multiplies and subtractions, no matrix instructions, no pivot test (a zero or NaN pivot propagates as in ILUAM).  The
+ *   solves are ILUAM's orders on the panels: forward acc = 0, the stored k < j ascending, the right-hand side added last; backward
+ *   acc = y_j, the stored i > j DESCENDING, the division last.  esp_precon_ldiv only enqueues launches: a gather, at most 4 per depth,
+ *   a scatter.  The object is an ESP_PRECON_LU one: esp_precon_update / _ldiv / _destroy, esp_simple, esp_cg, esp_bicgstabl, esp_gmres,
+ *   esp_precon_lu_perm / _tree / _matrix / _stats take it unchanged.  esp_precon_get_factor gives nnz(B) doubles in B's position order
+ *   exported from the panels (bitwise the column form's); esp_precon_levels / _launches give zeros (there is no inner ILUAM, no level
+ *   analysis and no schedule), esp_debug_iluam_form / esp_debug_last_iluam_form -> ESP_ERR_INVALID.  esp_precon_update with A's pattern
+ *   kept: the values gather of B, the load kernel and the numeric factorization (no ordering launch; bitwise a fresh create).
+ * esp_precon_lu_panel_stats: out = the panel doubles allocated, the launches of the last numeric factorization, the launches of one
+ *   ldiv!, the nodes taken by the small and by the wide form, the block-column steps of the wide form (per depth the block columns of
+ *   its widest wide node, summed).  ESP_ERR_INVALID on a column-form object.
+ * esp_debug_lu_wide_from(h, w): a test hook; the panel-form factorizations created on h afterwards use the wide form from width w on
+ *   (0 restores the default). */
 #define ESP_PRECON_LU 9
+#define ESP_LU_COLUMNS 0
+#define ESP_LU_PANELS 1
+#define ESP_LU_PANEL_STATS 6
 int32_t esp_precon_lu_create(esp_handle *h, int32_t leaf_size, int32_t max_depth, esp_precon **out);
+int32_t esp_precon_lu_create_form(esp_handle *h, int32_t leaf_size, int32_t max_depth, int32_t form, esp_precon **out);
+int32_t esp_precon_lu_panel_stats(esp_precon *p, int64_t out[ESP_LU_PANEL_STATS]);
+int32_t esp_debug_lu_wide_from(esp_handle *h, int64_t w);
 int32_t esp_precon_lu_perm(esp_precon *p, int64_t *c, int32_t on_device);
 int32_t esp_precon_lu_tree(esp_precon *p, int32_t *level, int64_t *node_root, int32_t on_device);
 int32_t esp_precon_lu_matrix(esp_precon *p, esp_handle **b);

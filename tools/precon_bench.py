@@ -105,6 +105,9 @@ through esp_nested_dissection, ILUAM's analysis + factorization of a copy of B, 
 ldiv!, nnz(B)/nnz(A), the rounds and launches of the ordering, ILUAM's level counts, and one solve of A x = 1 to 1e-8: A.solve(b)
 (create + solve) against cg with ILU0 and with ILUAM (create + cg) in the same run.  Medians over --rounds.
     python tools/precon_bench.py --kind lu [--n 32] [--leaf-size 32] [--iters 5] [--rounds 5]
+--kind lu --form both | panels times the forms of LUFactorization side by side in alternating rounds in one process (both: the column
+form, the yardstick, and the panel form; panels: the panel form alone), CholeskyFactorization and cg with ILU0 beside them:
+    python tools/precon_bench.py --kind lu --form both [--n 24] [--leaf-size 32] [--iters 5] [--rounds 5]
 --kind cholesky [--leaf-size L] [--lu-rounds R] times CholeskyFactorization (esp_precon_cholesky_create) on fdrand(n,n,n) beside
 LUFactorization, the yardstick, in the same process and the same alternating rounds (LU in the first R of them): the ordering alone,
 the create, a values-only update! and ldiv! on device vectors; every round's value, medians, spreads (max - min), the ratios, the launch
@@ -963,6 +966,86 @@ def bench_lu(a, torch, esp):
     print(json.dumps(rnd(out)))
 
 
+def bench_lu_forms(a, torch, esp):
+    """--kind lu --form panels | both: the forms of LUFactorization on fdrand n^3 side by side in alternating rounds in one process
+    (both: the column form, the yardstick, takes part; panels: the panel form alone), CholeskyFactorization beside them: per round the
+    create, a values-only update! and ldiv! on device vectors (--iters of them) of each.  Reported: every round's value, the median and
+    the spread (max - min); whether each panel-form median lies below the column form's by more than the column form's spread; the
+    ratio to Cholesky; the panel form's stats; |A x - b| / |b| for b = ones; and cg with ILU0 to 1e-8 (create + cg) from the same run."""
+    import numpy as np
+    A = esp.fdrand(a.n, a.n, a.n)
+    d = A._d
+    stream = torch.cuda.current_stream()
+    d.ck(d.lib.esp_set_stream(d.h, C.c_void_p(stream.cuda_stream)))
+    N, Z = A.n, A.nnz()
+    v = torch.randn(N, dtype=torch.float64, device="cuda")
+    u = torch.empty_like(v)
+    b = torch.ones_like(v)
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        r = fn()                                   # (create, update!, ldiv! and the solvers return synchronised)
+        return (time.perf_counter() - t0) * 1e3, r
+
+    out = {"workload": "lu_forms_fdrand", "n": a.n, "N": N, "nnz": Z, "leaf_size": a.leaf_size, "rounds": a.rounds, "iters": a.iters,
+           "form": a.form}
+    Pw = esp.ILU0Preconditioner(A)     # builds the row-wise index the ordering shares, so that the creates below are their own
+    Pw.close()
+    P = esp.LUFactorization(A, a.leaf_size, form="panels")       # (a warm-up create: code objects, allocations)
+    out["stats"], out["panel_stats"] = P.stats(), P.panel_stats()
+    P.close()
+    kinds = [("panels", lambda: esp.LUFactorization(A, a.leaf_size, form="panels")),
+             ("cholesky", lambda: esp.CholeskyFactorization(A, a.leaf_size))]
+    if a.form == "both":
+        kinds.insert(0, ("columns", lambda: esp.LUFactorization(A, a.leaf_size)))
+    rec = {name: {"create_ms": [], "update_values_ms": [], "ldiv_ms": []} for name, _ in kinds}
+    resid = {}
+    for r in range(a.rounds):
+        for name, make in kinds:
+            t, Q = wall(make)
+            rec[name]["create_ms"].append(t)
+            rec[name]["update_values_ms"].append(wall(Q.update)[0])
+            Q.ldiv(v, out=u)
+            rec[name]["ldiv_ms"].append(wall(lambda: [Q.ldiv(v, out=u) for _ in range(a.iters)])[0] / a.iters)
+            if name not in resid:
+                x = Q.solve(b)
+                resid[name] = float(torch.linalg.norm(A.mul(x) - b) / torch.linalg.norm(b))
+            Q.close()
+            print("lu forms n=%d round %d %s: %s" % (a.n, r, name, json.dumps({k: x[-1] for k, x in rec[name].items()})), file=sys.stderr, flush=True)
+    for name, _ in kinds:
+        out[name] = {k: {"rounds": x, "median": float(np.median(x)), "spread": float(max(x) - min(x))} for k, x in rec[name].items()}
+        out[name]["solve_residual"] = resid[name]
+    keys = ("create_ms", "update_values_ms", "ldiv_ms")
+    out["panels_over_cholesky"] = {k: out["panels"][k]["median"] / out["cholesky"][k]["median"] for k in keys}
+    if a.form == "both":
+        out["columns_over_panels"] = {k: out["columns"][k]["median"] / out["panels"][k]["median"] for k in keys}
+        out["below_by_more_than_the_spread"] = {k: out["panels"][k]["median"] < out["columns"][k]["median"] - out["columns"][k]["spread"] for k in keys}
+
+    def run():
+        Q = esp.ILU0Preconditioner(A)
+        try:
+            return esp.cg(A, b, Pl=Q, reltol=1e-8, maxiter=a.tol_maxiter, log=True)
+        finally:
+            Q.close()
+    run()
+    ts, log = [], None
+    for _ in range(a.rounds):
+        t, (_, log) = wall(run)
+        ts.append(t)
+    out["solve_1e-8"] = {"cg+ilu0": {"ms": float(np.median(ts)), "rounds": ts, "iterations": log["iters"], "converged": log["isconverged"]}}
+
+    def rnd(x):
+        if isinstance(x, float):
+            return round(x, 4) if abs(x) >= 1e-3 else float("%.3e" % x)
+        if isinstance(x, dict):
+            return {k: rnd(y) for k, y in x.items()}
+        if isinstance(x, list):
+            return [rnd(y) for y in x]
+        return x
+    print(json.dumps(rnd(out)))
+
+
 def bench_cholesky(a, torch, esp):
     """CholeskyFactorization on fdrand n^3 beside LUFactorization, the yardstick, in the same process and the same alternating rounds
     (--lu-rounds R: LU takes part in the first R rounds only; 0: not at all): per round the ordering alone, the create, a values-only
@@ -1278,6 +1361,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "gmres", "gmres-trace", "block", "block-trace", "block-trace-diff", "amg", "iluk", "colored", "spai0", "spai1", "spai1sym", "ilut", "lu", "cholesky"], default="point")
     ap.add_argument("--leaf-size", type=int, default=32)
+    ap.add_argument("--form", choices=["columns", "panels", "both"], default="columns",
+                    help="--kind lu: columns: the column form's breakdown; panels / both: the forms side by side in alternating rounds")
     ap.add_argument("--lu-rounds", type=int, default=0, help="--kind cholesky: the rounds LUFactorization, the yardstick, takes part in")
     ap.add_argument("--droptol", type=float, default=1e-3)
     ap.add_argument("--steps", type=int, default=3)
@@ -1323,7 +1408,7 @@ def main():
     if a.kind == "ilut":
         return bench_ilut(a, torch, esp)
     if a.kind == "lu":
-        return bench_lu(a, torch, esp)
+        return bench_lu(a, torch, esp) if a.form == "columns" else bench_lu_forms(a, torch, esp)
     if a.kind == "cholesky":
         return bench_cholesky(a, torch, esp)
     if a.kind == "amg":
