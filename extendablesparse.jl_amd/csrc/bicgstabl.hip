@@ -134,6 +134,10 @@ __global__ __launch_bounds__(KT) void bicg_upd_k(const double *__restrict__ rho_
     const double sigma = level2(sig_p1, nb1, sred);
     const double alpha = rho / sigma;
     const i64 n2 = n >> 1;
+    // rs and us are the handle's (16-byte aligned: ns is even, the base comes from ensure); x is the CALLER's when the vectors are
+    // resident, and a view into a larger array is only 8-byte aligned: plain double accesses then (the same bits, every element
+    // is computed by itself; the branch is uniform over the grid)
+    const bool xvec = (reinterpret_cast<uintptr_t>(x) & 15) == 0;
     for (i64 e = (i64)blockIdx.x * KT + threadIdx.x; e < n2; e += (i64)gridDim.x * KT) {
         for (int k = 0; k <= j; k++) {
             const double2 uv = ((const double2 *)(us + (k + 1) * ns))[e];
@@ -143,10 +147,15 @@ __global__ __launch_bounds__(KT) void bicg_upd_k(const double *__restrict__ rho_
             ((double2 *)(rs + k * ns))[e] = rv;
         }
         const double2 u0 = ((const double2 *)us)[e];
-        double2 xv = ((double2 *)x)[e];
-        xv.x = xv.x + alpha * u0.x;
-        xv.y = xv.y + alpha * u0.y;
-        ((double2 *)x)[e] = xv;
+        if (xvec) {
+            double2 xv = ((double2 *)x)[e];
+            xv.x = xv.x + alpha * u0.x;
+            xv.y = xv.y + alpha * u0.y;
+            ((double2 *)x)[e] = xv;
+        } else {
+            x[2 * e] = x[2 * e] + alpha * u0.x;
+            x[2 * e + 1] = x[2 * e + 1] + alpha * u0.y;
+        }
     }
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
         for (int k = 0; k <= j; k++) rs[k * ns + n - 1] = rs[k * ns + n - 1] - alpha * us[(k + 1) * ns + n - 1];

@@ -82,6 +82,7 @@ int32_t elements_by_items(esp_handle *h, espelem::Args a, i64 E, bool *took) {
             else
                 hipLaunchKernelGGL(espelem::elem_items_k, dim3(grid_for(NI, espelem::THREADS)), dim3(espelem::THREADS), 0, h->stream, a);
             sp.add(1);
+            h->last_append_route = cellrec ? 7 : 6;
         }
         // the flush's partition over the items: a temporary view of the handle (sort_msd reads count, keys, keys2 and the
         // key window -- here the records' virtual one)
@@ -417,6 +418,7 @@ extern "C" int32_t esp_append_elements(esp_handle *h, int32_t nloc, int64_t ncel
                 hipLaunchKernelGGL(espelem::elem_stream_k, dim3(grid_for(cnt, espelem::THREADS)), dim3(espelem::THREADS), 0, h->stream, b, cnt);
                 sp.add(1);
             }
+            h->last_append_route = 8;
         }
         HIPCK(h, hipMemcpyAsync(h->pin_scalar, d_err, 8, hipMemcpyDeviceToHost, h->stream));
         HIPCK(h, hipStreamSynchronize(h->stream));

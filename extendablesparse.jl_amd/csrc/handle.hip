@@ -464,6 +464,12 @@ int32_t reserve_append(esp_handle *h, i64 add) {
     return ESP_OK;
 }
 
+// esp_debug_last_append_route: which kernels read the caller's triplets
+static int32_t note_route(esp_handle *h, int route) {
+    h->last_append_route = route;
+    return ESP_OK;
+}
+
 // pack count triples that already sit in device memory; checks bounds before committing
 int32_t pack_device(esp_handle *h, const i64 *d_rows, const i64 *d_cols, const double *d_vals,
                            const uint8_t *d_kinds, int kind_all, int op, i64 count) {
@@ -473,12 +479,13 @@ int32_t pack_device(esp_handle *h, const i64 *d_rows, const i64 *d_cols, const d
     if (!d_kinds) {  // an empty buffer and one kind: the append is the partition (no packed stream is written)
         bool took = false;
         CK(append_partitioned(h, d_rows, d_cols, d_vals, kind_all, op, count, &took));
-        if (took) return ESP_OK;
+        if (took) return note_route(h, 2 + h->last_plan_reused);
         CK(append_tail_partitioned(h, d_rows, d_cols, d_vals, kind_all, op, count, &took));  // (behind a batch over a stored pattern)
-        if (took) return ESP_OK;
+        if (took) return note_route(h, 4);
         CK(append_first_pass(h, d_rows, d_cols, d_vals, kind_all, op, count, &took));  // (a shuffled stream: the first radix pass of its flush, from the caller's arrays)
-        if (took) return ESP_OK;
+        if (took) return note_route(h, 5);
     }
+    h->last_append_route = 1;
     CK(reserve_append(h, count));
     h->pin_scalar[0] = ~0ull;
     CK(ensure(h, h->misc, 256));
@@ -1378,6 +1385,11 @@ extern "C" int32_t esp_debug_last_colptr_direct(const esp_handle *h, int32_t *di
 extern "C" int32_t esp_debug_last_plan_reused(const esp_handle *h, int32_t *reused) {
     if (!h || !reused) return ESP_ERR_INVALID;
     *reused = h->last_plan_reused;
+    return ESP_OK;
+}
+extern "C" int32_t esp_debug_last_append_route(const esp_handle *h, int32_t *route) {
+    if (!h || !route) return ESP_ERR_INVALID;
+    *route = h->last_append_route;
     return ESP_OK;
 }
 extern "C" int32_t esp_debug_last_partition(const esp_handle *h, int32_t *kind) {

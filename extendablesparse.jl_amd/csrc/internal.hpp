@@ -365,6 +365,7 @@ struct esp_handle {
     int last_run_order = 0;      // esp_debug_last_run_order
     int last_plan_reused = 0;    // the last append-is-the-partition of caller triplets used the previous assembly's run lists
     int last_colptr_direct = 0;  // the bucket kernel of the last flush wrote colptr itself
+    int last_append_route = 0;   // esp_debug_last_append_route: which kernels read the caller's arrays of the last device append
     hipStream_t aux = nullptr;   // second stream + event: small device-to-host reads beside a running kernel
     hipEvent_t aux_ev = nullptr;  // (created on first use, aux_ready)
     // shard cache

@@ -966,6 +966,14 @@ class ExtendableSparseMatrix:
         self._d.ck(self._d.lib.esp_debug_last_plan_reused(self._d.h, C.byref(k)))
         return k.value
 
+    def debug_last_append_route(self):
+        """Which kernels read the caller's arrays in the last device-side append (esp_debug_last_append_route): 1 stream-order pack,
+        2 the append was the partition, 3 the same over kept run lists, 4 a partitioned tail, 5 the flush's first radix pass,
+        6 / 7 esp_append_elements' item partition per item / per cell, 8 its stream-order form"""
+        p = C.c_int32()
+        self._d.ck(self._d.lib.esp_debug_last_append_route(self._d.h, C.byref(p)))
+        return p.value
+
     def debug_last_run_order(self):
         """1 = ranking kernel, 2 = radix-ordered run list, 3 = ranking given up, radix-ordered list used"""
         p = C.c_int32()

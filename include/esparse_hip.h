@@ -274,7 +274,17 @@ int32_t esp_pattern_hash(esp_handle *h, uint64_t *hash);
  * separately -- bit-identical to the reference's column loop (no atomics; a row-wise index of the CSC is
  * built on first use after a pattern change).  x has n, r has m elements; on_device != 0: both are
  * device pointers (a consumer that never leaves the GPU); x may be NULL when n == 0 and r when m == 0 (a vector
- * without elements need not have an address).  Pending entries -> ESP_ERR_STATE: flush first. */
+ * without elements need not have an address).  Pending entries -> ESP_ERR_STATE: flush first.
+ *
+ * THE HAND-OVER OF DEVICE ARRAYS, here and in every call of this header that takes a device pointer (`on_device != 0`, and
+ * the arrays of esp_append_device, esp_append_elements[_again], esp_generate_fem_mesh, esp_shard_export):
+ *   - an array needs the NATURAL ALIGNMENT OF ITS ELEMENT TYPE and nothing more (8 bytes for double and int64_t, 4 for int32_t,
+ *     1 for uint8_t): a view into the middle of a larger allocation is as good as an allocation of its own.  Where a kernel
+ *     uses wider accesses it looks at the pointer first and takes a scalar form otherwise; the results are the same bits;
+ *   - an INPUT (a `const` pointer) is never written;
+ *   - of an array of n elements only [0, n) is read or written: nothing in front of it, nothing behind it, whatever the
+ *     kernels' chunk sizes are.
+ * tests/test_device_handover_gpu.py holds every such call to this with arrays at odd offsets between guard bands. */
 int32_t esp_mul(esp_handle *h, const double *x, double *r, int32_t on_device);
 
 /* mark_dirichlet(A; penalty) / eliminate_dirichlet!(A, marker) (sparsematrixcsc.jl:97-140) on the device CSC
@@ -1287,6 +1297,15 @@ int32_t esp_debug_last_plan_reused(const esp_handle *h, int32_t *reused);
  * 8 = as 6, and the tail had been partitioned as it was appended (one kind, a pre-sorted stream): both flushes start at the
  *     bucket kernel */
 int32_t esp_debug_last_partition(const esp_handle *h, int32_t *kind);
+/* which kernels read the CALLER's arrays in the handle's last device-side append (read-only; 0: none yet):
+ * esp_append_device / esp_commit -- 1 = packed in stream order (pack_k), 2 = the append was the partition (the run-based pass
+ *     counted the columns and scattered rows, columns and values), 3 = the same over the previous assembly's run lists
+ *     (esp_debug_last_plan_reused 1), 4 = partitioned as a tail behind a batch over a stored pattern, 5 = the first radix pass of
+ *     the flush ran from the caller's arrays (a shuffled stream of 2^18 entries or more);
+ * esp_append_elements -- 6 = the item partition, one thread per item (elem_items_k), 7 = the item partition, one thread per cell,
+ *     which leaves cell records (elem_cells_k: cells of 3 or 4 nodes), 8 = the updates written in stream order (elem_stream_k: 4096
+ *     updates or fewer, a non-empty buffer, a cell that names a node twice) */
+int32_t esp_debug_last_append_route(const esp_handle *h, int32_t *route);
 
 #ifdef __cplusplus
 }
