@@ -200,6 +200,9 @@ SIGNATURES = {
     "esp_debug_last_lazy_items": (i32, [vp, P(i32)]),
     "esp_debug_last_lazy_stencil": (i32, [vp, P(i32)]),
     "esp_debug_last_kept_structure": (i32, [vp, P(i32)]),
+    "esp_debug_last_march": (i32, [vp, P(i32)]),
+    "esp_debug_force_march": (i32, [vp, i32]),
+    "esp_debug_march_rule": (i32, [i64, i64, i64, i32, i32, P(i32)]),
     "esp_debug_last_sum_join": (i32, [vp, P(i32)]),
     "esp_debug_last_sum_ms": (i32, [vp, P(C.c_double), P(C.c_double)]),
     "esp_debug_last_sum_batched": (i32, [vp, P(C.c_int32)]),

@@ -371,15 +371,21 @@ static int32_t launch_attempt(esp_handle *h, const Sorted &st, const LocalChoice
         // (what the output arrays hold: a stale table must not send a pair's stores outside them)
         const u64 out_cap = (u64)std::min(h->keys2.bytes / sizeof(i64), h->vals2.bytes / sizeof(double));
         const u64 *pred = (const u64 *)h->pred.tab.p;
-        for (i64 first = 0; first < Sp; first += max_grid) {
+        // (the fused kernel marches: the unit of a slice is then its workgroup, several planes of pairs -- pair_gen_set_march)
+        i64 units = Sp;
+        if (t.use_pred && st.stencil) {
+            units = esplocal::pair_gen_set_march(ap, st.stencil->a, h->compute_units, h->force_march);
+        }
+        for (i64 first = 0; first < units; first += max_grid) {
             ap.first = first;
-            const unsigned grid = (unsigned)std::min<i64>(max_grid, Sp - first);
+            const unsigned grid = (unsigned)std::min<i64>(max_grid, units - first);
             if (t.use_pred && st.stencil) {
                 if (!esplocal::launch_pair_gen_predicted(var, grid, h->stream, ap, st.stencil->a, pred, out_cap, c.keep))
                     return ESP_RETRY_EXPANDED;  // (a cut the fused kernel does not take: nothing has happened)
             } else if (!(t.use_pred ? esplocal::launch_pair_predicted(var, grid, h->stream, ap, pred, out_cap) : esplocal::launch(var, grid, h->stream, ap)))
                 FAIL(h, ESP_ERR_STATE, "esp_flush: internal error (no pair kernel for this flush)");
         }
+        if (t.use_pred && st.stencil) h->last_march = ap.march;  // (every slice was launched: a refused launch leaves 0)
         t.used_pair = true;
         sp.add(1);
         return ESP_OK;
@@ -534,6 +540,7 @@ int32_t flush_local(esp_handle *h, const Sorted &st, int mode, i64 *Zn_out) {
         // (the KEEP form stored values into the scratch array at most: colptr and rowval are as they were, and the retry writes all
         // of them -- the stamp is gone since esp_flush's entry)
         if (c.keep) h->last_kept = 2;
+        h->last_march = 0;  // (the retry is not the fused kernel's)
         drop_kept(h);
         CK(retry_attempt(h, st, c, lay, a, t));
     } else if (pred_tried) {
@@ -1015,6 +1022,7 @@ extern "C" int32_t esp_flush(esp_handle *h, int32_t mode, int64_t *new_nnz, int3
     h->kept.candidate = h->kept.valid;
     h->kept.valid = false;
     h->last_kept = 0;
+    h->last_march = 0;
     bool use_local = h->force_path != ESP_PATH_GENERAL;
     if (h->ones_pending && windowed(h)) CK(fix_tail(h));  // (cannot happen: a window is declared through fix_tail)
     if (h->pre.valid) {  // the producer's partition serves this flush if nothing changed since (appends BEHIND it may have)

@@ -256,6 +256,7 @@ extern "C" int32_t esp_create(int64_t m, int64_t n, int32_t device, int64_t capa
         FAIL((esp_handle *)nullptr, ESP_ERR_HIP, "esp_create: cannot create a stream on device %d", device);
     }
     h->own_stream = true;
+    if (hipDeviceGetAttribute(&h->compute_units, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) h->compute_units = 0;
     // (8 slots for the small copies, then the 8 of pin_words: the default flags give mapped, coherent host memory)
     if (hipHostMalloc((void **)&h->pin_scalar, 128, hipHostMallocDefault) != hipSuccess) {
         (void)hipStreamDestroy(h->stream);

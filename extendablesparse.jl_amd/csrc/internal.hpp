@@ -201,6 +201,9 @@ struct esp_handle {
         unsigned long long pattern_version = 0;
     } kept;
     int last_kept = 0;           // esp_debug_last_kept_structure: 0 stored everything, 1 kept, 2 the kept form missed and the retry rewrote everything
+    int last_march = 0;          // esp_debug_last_march: planes per workgroup of the last flush's fused launch (0: not fused)
+    int force_march = 0;         // esp_debug_force_march: 0 automatic, else the march of every grid that conforms (clamped to nz)
+    int compute_units = 0;       // of the handle's device (esp_create): what the march rule sizes its workgroup count by
     int last_rebuild = 0;        // the last flush's tail rebuilt the matrix (flush_rebuild: the stored CSC as the first piece of a fresh flush)
     int last_lazy_items = 0;     // the last flush's bucket kernel formed its updates from item records (esp_debug_last_lazy_items)
     int last_sum_join = 0;     // esp_debug_last_sum_join

@@ -89,6 +89,10 @@ struct Args {
     // launch and read by it after the stream's synchronise -- [0] the grand total, [1] error bits (PRED_MISS), [2] spare.  The
     // kernel writes no status granule and no err word: nothing is cleared before it and nothing copied after it
     u64 *host_words;
+    // ... and its march (pair_gen_set_march): a workgroup handles `march` consecutive planes of the same 512 (i, j) columns, the
+    // pairs s, s + march_step, ... with march_step the pairs of a plane; S still counts pairs, `first` and the grid count marching
+    // workgroups.  0 or 1: a workgroup is a pair
+    int march, march_step;
 };
 constexpr int MAX_PIECES = 64;
 
@@ -143,6 +147,10 @@ bool launch_pair_predicted(const Variant &v, unsigned grid, hipStream_t stream, 
 // generator's over the full node range and was never written (esp_handle::LazyStencil) -- keys_in / vals_in / seg_start are not read
 bool launch_pair_gen_predicted(const Variant &v, unsigned grid, hipStream_t stream, const Args &a, const espgen::FdArgs &fd, const u64 *pred,
                                u64 out_cap, bool keep);  // local_x.hip (keep: colptr and rowval stay as they are, values only)
+// ... its march: the planes a workgroup handles (1: the grid does not conform; force > 0: that many wherever it conforms, clamped
+// to nz), written into a.march / a.march_step; returns the workgroups of the flush.  a.S counts pairs
+i64 pair_gen_set_march(Args &a, const espgen::FdArgs &fd, int compute_units, int force);
+int pair_gen_march_rule(i64 nx, i64 ny, i64 nz, int cl_bits, int compute_units);  // the automatic rule alone
 // pred[s] = colptr[first column of pair s] - 1 for s < Sp, pred[Sp] = colptr[col_end] - 1: the table a look-back flush leaves
 void launch_pair_record(hipStream_t stream, const i64 *colptr, i64 col_end, int ncl_bits, int Sp, u64 *pred);
 

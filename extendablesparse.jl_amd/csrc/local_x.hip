@@ -31,8 +31,17 @@
 // source (no select per draw) and the plain division is gone (the launcher refuses spacings outside [2^-100, 2^100] before it
 // launches anything), the FLAGS fold above, pair_store's 16-byte stores and pair_place's scalar wave number (pair.hpp, shared
 // with pair_k and pair_pred_k): 0.2231 -> 0.2037 ms a step, 212 -> 192 us.  Measured and dropped: unpredicated record writes
-// for a wave whose lanes all hold seven rows (its range overlapped its parent's).  Not built: the three reciprocals once per
-// plan -- Consts still forms them in every thread; a timing probe puts them at another 2 % of the step.
+// for a wave whose lanes all hold seven rows (its range overlapped its parent's).
+// Round 22 (NOTES/round22.md): the march.  Where a plane of the grid is a whole number of pairs (nx ny % ncl == 0, the flush from
+// column 0 over the whole grid) a workgroup handles the same 512 (i, j) columns in a.march consecutive z planes: the pairs s,
+// s + P, ... with P the pairs of a plane.  Once per march it forms what does not depend on the plane -- the reciprocals (round
+// 21's open part: closed by this), the node's (i, j, k), the counter of its draw 0, the strides; the compares on i and j stay lane
+// masks across the planes --, per plane k advances by 1 and the counter by 6 nx ny GOLDEN, and the z pair towards l - nx ny is
+// the vhi[2] the same lane formed one plane below: a draw in the workgroup's first plane only.  Every other grid runs one plane
+// per workgroup through the same body without the loop (the template parameter MARCH).  The march length is the host's
+// (pair_gen_march_rule below): 3 planes at 256^3 on 256 compute units, 0.2016 -> 0.1954 ms a step, 188.8 -> 182.6 us in one
+// session; longer marches lost to the partly filled last round of workgroups.  The table words must be scalar loads (`pred` is restrict, s a scalar): as a vector load their wait counts the
+// stores of the plane below.
 //
 // Where the values come from is the template parameter SRC (FdSource: the built-in generator's draws, the expressions and the
 // operation order of espgen::fdrand_part_k -- compiled without FMA contraction like every unit); a source that reads edge
@@ -53,9 +62,11 @@ constexpr int G_CAP = THREADS * G_ROWS;    // records of a pair
 // strides nx ny, nx, 1); v: the pair's value -- the off-diagonal update is -v, the diagonal one +v; b(q) / vb: the node's boundary
 // terms in x, y, z.  The flags are compares on the node's (i, j, k), taken where they are used: a compare leaves a lane mask in
 // scalar registers, a flag kept from upper() to the fold is a byte in a vector register that every use has to test again.
+// (i, j, k) and the extents in 32 bits: the launcher takes grids whose rows fit 32 bits only (a.rb < 32), so every one of them is
+// below 2^32 -- and the registers a marching thread carries from plane to plane are half as many.
 struct StencilColumn {
     i64 stride[3];
-    i64 i, j, k, nx, ny, nz;
+    u32 i, j, k, nx, ny, nz;
     double vlo[3], vhi[3], vb[3];
     __device__ __forceinline__ bool lo(int q) const { return q == 0 ? k > 1 : q == 1 ? j > 1 : i > 1; }
     __device__ __forceinline__ bool hi(int q) const { return q == 0 ? i < nx : q == 1 ? j < ny : k < nz; }
@@ -104,7 +115,13 @@ struct FdSource {
     // what a thread forms once, whatever its column: the three denominators' reciprocals
     struct Consts {
         espgen::SharedDiv x, y, z;
-        __device__ __forceinline__ explicit Consts(const FdSource &s) : x(s.hx), y(s.hy), z(s.hz) {}
+        // (the same in every lane: the refined reciprocals go to scalar registers, where a march keeps them for nothing)
+        __device__ __forceinline__ explicit Consts(const FdSource &s) : x(s.hx), y(s.hy), z(s.hz) {
+            x.r = uniform(x.r), y.r = uniform(y.r), z.r = uniform(z.r);
+        }
+        __device__ __forceinline__ static double uniform(double v) {
+            return __longlong_as_double((long long)esp_uniform_u64((u64)__double_as_longlong(v)));
+        }
     };
     __device__ __forceinline__ double over(double n, const espgen::SharedDiv &by) const {
         return by.quot_mid(n);
@@ -112,13 +129,24 @@ struct FdSource {
     // draw q of node gg: counter 6 gg + q (espgen::fd_rand_z); z0(g - d) = z0(g) - 6 d GOLDEN exactly (the arithmetic wraps)
     __device__ __forceinline__ u64 z0(i64 g) const { return seed + (6ull * (u64)g + 1ull) * ESP_GOLDEN; }
 
-    // the column's flags and the three pairs its node starts (vhi[0], vhi[1]: what the lanes above take from LDS)
-    __device__ __forceinline__ void upper(const Consts &k, i64 g, StencilColumn &c) const {
-        espgen::fd_node(*this, g, &c.i, &c.j, &c.k);
-        constexpr int md = MODE;
-        const u64 zg = z0(g);
+    // what a thread forms once per march: the node's (i, j, k), the strides and extents, and the counter of the node's draw 0
+    __device__ __forceinline__ u64 begin(i64 g, StencilColumn &c) const {
+        i64 i, j, k;
+        espgen::fd_node(*this, g, &i, &j, &k);
+        c.i = (u32)i, c.j = (u32)j, c.k = (u32)k;
         c.stride[0] = nx * ny, c.stride[1] = nx, c.stride[2] = 1;
-        c.nx = nx, c.ny = ny, c.nz = nz;
+        c.nx = (u32)nx, c.ny = (u32)ny, c.nz = (u32)nz;
+        return z0(g);
+    }
+    // one plane up, node g + nx ny: the same (i, j), k + 1, and z0(g + nx ny) = z0(g) + 6 nx ny GOLDEN exactly (the arithmetic wraps)
+    __device__ __forceinline__ u64 next_plane(u64 zg, StencilColumn &c) const {
+        c.k += 1;
+        return zg + zsub[0];
+    }
+    // the three pairs the column's node starts (vhi[0], vhi[1]: what the lanes above take from LDS; vhi[2]: what the same lane
+    // takes one plane up)
+    __device__ __forceinline__ void upper(const Consts &k, u64 zg, StencilColumn &c) const {
+        constexpr int md = MODE;
         c.vhi[0] = over(espgen::fd_rand_z(md, zg, 0) * hy * hz, k.x);
         c.vhi[1] = over(espgen::fd_rand_z(md, zg, 2) * hx * hz, k.y);
         c.vhi[2] = over(espgen::fd_rand_z(md, zg, 4) * hx * hy, k.z);
@@ -126,13 +154,18 @@ struct FdSource {
     // the lower neighbours' pairs and the boundary terms; sx / sy: vhi[0] / vhi[1] of the workgroup's lanes, slot = lane.
     // A draw is formed only where some lane of the wave uses it (the kernel's step() does not look at a value whose flag is off:
     // 0.0 stands there).  At 256^3 the y and z boundary draws are skipped in more than 99 % of the waves, the x boundary draw in
-    // half of them, the x draw in all but a pair's first wave and the y draw in its upper four.
-    __device__ __forceinline__ void lower(const Consts &k, i64 g, int t, const double *sx, const double *sy, StencilColumn &c) const {
+    // half of them, the x draw in all but a pair's first wave and the y draw in its upper four.  The z pair towards l - nx ny is
+    // drawn in the first plane of a march only (`first`: the node below belongs to another workgroup); one plane up it is z_below,
+    // the vhi[2] this lane formed for that node -- the same expression on the same counter, the same bits.
+    __device__ __forceinline__ void lower(const Consts &k, u64 zg, int t, const double *sx, const double *sy, bool first, double z_below,
+                                          StencilColumn &c) const {
         constexpr int md = MODE;
-        const u64 zg = z0(g);
         const bool x_in = c.lo(2) && t >= 1, y_in = c.lo(1) && (i64)t >= nx;
         const double x_lds = sx[x_in ? t - 1 : 0], y_lds = sy[y_in ? t - (int)nx : 0];  // (slots 0 .. t - 1)
-        c.vlo[0] = draw_if(c.lo(0), [&] { return over(espgen::fd_rand_z(md, zg - zsub[0], 4) * hx * hy, k.z); });
+        if (first)
+            c.vlo[0] = draw_if(c.lo(0), [&] { return over(espgen::fd_rand_z(md, zg - zsub[0], 4) * hx * hy, k.z); });
+        else
+            c.vlo[0] = z_below;
         const double y_drawn = draw_if(c.lo(1) && !y_in, [&] { return over(espgen::fd_rand_z(md, zg - zsub[1], 2) * hx * hz, k.y); });
         const double x_drawn = draw_if(c.lo(2) && !x_in, [&] { return over(espgen::fd_rand_z(md, zg - zsub[2], 0) * hy * hz, k.x); });
         c.vlo[1] = y_in ? y_lds : y_drawn;
@@ -147,8 +180,13 @@ struct FdSource {
 // the grid's whole structural pattern (esp_handle::KeptStructure) -- a step that hits the table in every pair then has that very
 // pattern, so the kernel stores the values alone: no srow (the LDS holds the values only), no out_row, no colptr.  Everything that
 // decides is the writing form's: the fold, pair_place, pair_table_hit, PRED_MISS and the grand total.
-template <int KEYS, class SRC, bool KEEP>
-__global__ __launch_bounds__(THREADS, 6) void pair_gen_pred_k(Args a, SRC src, const u64 *pred, u64 out_cap) {
+//
+// MARCH: the workgroup handles a.march > 1 planes.  Without it (a grid that does not conform, or one the rule gives no march) the
+// loop below runs once and is none: the kernel is the one-plane kernel of round 21, with its registers and its launch bound --
+// the march's prologue, the scalars it keeps across planes and the 8-waves bound of its KEEP form cost a one-plane launch more
+// than they give it (NOTES/round22.md).
+template <int KEYS, class SRC, bool KEEP, bool MARCH>
+__global__ __launch_bounds__(THREADS, KEEP && MARCH ? 8 : 6) void pair_gen_pred_k(Args a, SRC src, const u64 *__restrict__ pred, u64 out_cap) {
     static_assert(KEYS == 1 || KEYS == 2, "one kind: 2 = every update is an UPDATE");
     constexpr bool UPD = KEYS == 2;
     constexpr bool FLAGS = UPD && SRC::positive;  // no value is zero: a row is present exactly when its flag is on
@@ -158,102 +196,185 @@ __global__ __launch_bounds__(THREADS, 6) void pair_gen_pred_k(Args a, SRC src, c
     __shared__ u32 lw[WAVES];
 
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int s = (int)(a.first + (i64)blockIdx.x);
-    if (s >= a.S) return;
-    const u64 dst = esp_uniform_u64(pred[s]);
-    const u64 dst_next = esp_uniform_u64(pred[s + 1]);
+    // ---- the workgroup's march: pairs s, s + s_step, ... -- the same 512 (i, j) in a.march consecutive planes (pair_gen_march)
     const int ncl = 2 << a.cl_bits;
-    const u64 hi = ((u64)s << (a.rem_bits + 1)) + a.base;  // the pair's prefix: that of its first bucket
-    const i64 c_lo = (i64)(hi >> a.rb);
-    const i64 c_hi = min(c_lo + (i64)ncl, a.col_end);
-    const bool has = c_lo + t < c_hi;  // lane t owns column c_lo + t
-    // ---- the column's run, folded as it is formed: row q of the seven (rows strictly increasing where they exist)
-    bool present[G_ROWS];
-    double acc[G_ROWS];
-    u32 row[G_ROWS];
-#pragma unroll
-    for (int q = 0; q < G_ROWS; q++) present[q] = false, acc[q] = 0.0, row[q] = 0u;
-    // the node's own pairs first; the x and y ones go through LDS to the lanes whose columns they end in.  The barrier stands
-    // outside `has`: every lane of a workgroup that got past the uniform return above reaches it.
+    int s = (int)(a.first + (i64)blockIdx.x), s_step = 0;
+    if constexpr (MARCH) {
+        const u32 wg = (u32)s, P = (u32)a.march_step, chunk = wg / P;  // (workgroup = (pair in plane, chunk), the pair fastest)
+        // (the quotient comes out of vector registers; s must be a scalar: the table words are then scalar loads, which wait for no
+        // store of the plane below -- a vector load's wait counts the stores too and would hold every plane behind the last one's)
+        s = esp_uniform_i32((int)(chunk * (u32)a.march * P + (wg - chunk * P)));
+        s_step = (int)P;
+    }
+    if (s >= a.S) return;
+    // what does not depend on the plane, formed once: the reciprocals, the node's (i, j, k) and the counter of its first plane, the
+    // strides.  `has` too: a marching grid has full pairs only (every lane owns a column in every plane), a grid that does not
+    // conform runs one plane.
     const typename SRC::Consts k(src);
     StencilColumn c;
-    if (has) {
-        src.upper(k, c_lo + t, c);
-        shx[t] = c.vhi[0];
-        shy[t] = c.vhi[1];
-    }
-    __syncthreads();
-    if (has) {
-        src.lower(k, c_lo + t, t, shx, shy, c);
-        const i64 l = c_lo + t + 1;
+    const i64 g = (i64)((((u64)s << (a.rem_bits + 1)) + a.base) >> a.rb) + t;  // lane t owns column g (0-based) of the first plane
+    const bool has = g < min(g - t + (i64)ncl, a.col_end);
+    u64 zg = 0ull;
+    if (has) zg = src.begin(g, c);
+    c.vhi[2] = 0.0;
+    u32 l = (u32)g + 1u;  // the column, 1-based (the records' rows are 32 bits wide: a.rb < 32)
+    // Barriers.  A plane has three: (1) behind the writes of shx / shy, (2) pair_place's behind lw, (3) behind the records in
+    // sval / srow.  They are enough from one plane to the next: plane m + 1 writes shx / shy behind barrier 3 of plane m, so behind
+    // every lane's reads of them (lower(), in front of barrier 2); it writes lw behind its own barrier 1, so behind every lane's
+    // reads of lw (pair_place, in front of barrier 3 of plane m); it writes sval / srow behind its own barrier 2, so behind every
+    // lane's pair_store of plane m (in front of barrier 1 of plane m + 1).  The returns are the workgroup's: s, the table words and
+    // pl.total are the same in every lane.
+#pragma nounroll
+    for (int m = 0;;) {
+        const u64 dst = esp_uniform_u64(pred[s]);
+        const u64 dst_next = esp_uniform_u64(pred[s + 1]);
+        const u64 hi = ((u64)s << (a.rem_bits + 1)) + a.base;  // the pair's prefix: that of its first bucket
+        // ---- the column's run, folded as it is formed: row q of the seven (rows strictly increasing where they exist)
+        bool present[G_ROWS];
+        double acc[G_ROWS];
+        u32 row[G_ROWS];
 #pragma unroll
-        for (int q = 0; q < 3; q++) row[q] = (u32)(l - c.stride[q]), row[4 + q] = (u32)(l + c.stride[2 - q]);
-        row[3] = (u32)l;
-        if constexpr (FLAGS) {
-            // an off-diagonal record is -v, the bits of 0.0 + (-v) for v != 0; the diagonal takes its terms in call order, 0.0 for
-            // a term that is off (x + 0.0 is x: no sum here is -0.0)
-#pragma unroll
-            for (int q = 0; q < 3; q++) {
-                present[q] = c.lo(q), acc[q] = -c.vlo[q];
-                present[4 + q] = c.hi(q), acc[4 + q] = -c.vhi[q];
-            }
-            bool any = false;
-            double d = 0.0;
-#pragma unroll
-            for (int q = 0; q < 3; q++) any = any || c.lo(q), d = d + (c.lo(q) ? c.vlo[q] : 0.0);
-#pragma unroll
-            for (int q = 0; q < 3; q++) {
-                any = any || c.hi(q) || c.b(q);
-                d = d + (c.hi(q) ? c.vhi[q] : 0.0);
-                d = d + (c.b(q) ? c.vb[q] : 0.0);
-            }
-            present[3] = any, acc[3] = d;
-        } else {
-            // (MODE 2 can draw 0, RAWUPDATE creates a row whatever the value: the fold's own state machine)
-            auto step = [&](int q, bool on, double v) {
-                if (!on) return;
-                if constexpr (UPD)
-                    espfold::fold_step_update(present[q], acc[q], v);
-                else
-                    espfold::fold_step_sel(present[q], acc[q], a.kind32, v);
-            };
-#pragma unroll
-            for (int q = 0; q < 3; q++) step(q, c.lo(q), -c.vlo[q]);
-#pragma unroll
-            for (int q = 0; q < 3; q++) step(3, c.lo(q), c.vlo[q]);
-#pragma unroll
-            for (int q = 0; q < 3; q++) {
-                step(3, c.hi(q), c.vhi[q]);
-                step(3, c.b(q), c.vb[q]);
-            }
-#pragma unroll
-            for (int q = 0; q < 3; q++) step(4 + q, c.hi(q), -c.vhi[q]);
+        for (int q = 0; q < G_ROWS; q++) present[q] = false, acc[q] = 0.0, row[q] = 0u;
+        // the node's own pairs first; the x and y ones go through LDS to the lanes whose columns they end in.  The barrier stands
+        // outside `has`: every lane of a workgroup that got past the uniform returns reaches it.
+        const double z_below = c.vhi[2];  // (the plane below's z pair, in front of upper() forming this plane's)
+        if (has) {
+            src.upper(k, zg, c);
+            shx[t] = c.vhi[0];
+            shy[t] = c.vhi[1];
         }
-    }
-    // entries the run emits: one per row that one of its updates creates
-    u32 ec = 0;
+        __syncthreads();
+        if (has) {
+            src.lower(k, zg, t, shx, shy, m == 0, z_below, c);
 #pragma unroll
-    for (int q = 0; q < G_ROWS; q++) ec += present[q] ? 1u : 0u;
-    const PairPlace pl = pair_place(ec, lw, lane, w);
-    // ---- place: the table's, or nothing is stored
-    if (!pair_table_hit(dst, dst_next, pl.total, out_cap, s)) {
-        if (t == 0) a.host_words[1] = (u64)PRED_MISS;  // (the same constant from every missing pair: a plain store)
-        return;
-    }
-    {
-        u32 at = pl.at0;
+            for (int q = 0; q < 3; q++) row[q] = l - (u32)c.stride[q], row[4 + q] = l + (u32)c.stride[2 - q];
+            row[3] = l;
+            if constexpr (FLAGS) {
+                // an off-diagonal record is -v, the bits of 0.0 + (-v) for v != 0; the diagonal takes its terms in call order, 0.0 for
+                // a term that is off (x + 0.0 is x: no sum here is -0.0)
 #pragma unroll
-        for (int q = 0; q < G_ROWS; q++) {
-            if (present[q]) {
-                if constexpr (!KEEP) srow[at] = row[q];
-                sval[at] = acc[q];
-                at++;
+                for (int q = 0; q < 3; q++) {
+                    present[q] = c.lo(q), acc[q] = -c.vlo[q];
+                    present[4 + q] = c.hi(q), acc[4 + q] = -c.vhi[q];
+                }
+                bool any = false;
+                double d = 0.0;
+#pragma unroll
+                for (int q = 0; q < 3; q++) any = any || c.lo(q), d = d + (c.lo(q) ? c.vlo[q] : 0.0);
+#pragma unroll
+                for (int q = 0; q < 3; q++) {
+                    any = any || c.hi(q) || c.b(q);
+                    d = d + (c.hi(q) ? c.vhi[q] : 0.0);
+                    d = d + (c.b(q) ? c.vb[q] : 0.0);
+                }
+                present[3] = any, acc[3] = d;
+            } else {
+                // (MODE 2 can draw 0, RAWUPDATE creates a row whatever the value: the fold's own state machine)
+                auto step = [&](int q, bool on, double v) {
+                    if (!on) return;
+                    if constexpr (UPD)
+                        espfold::fold_step_update(present[q], acc[q], v);
+                    else
+                        espfold::fold_step_sel(present[q], acc[q], a.kind32, v);
+                };
+#pragma unroll
+                for (int q = 0; q < 3; q++) step(q, c.lo(q), -c.vlo[q]);
+#pragma unroll
+                for (int q = 0; q < 3; q++) step(3, c.lo(q), c.vlo[q]);
+#pragma unroll
+                for (int q = 0; q < 3; q++) {
+                    step(3, c.hi(q), c.vhi[q]);
+                    step(3, c.b(q), c.vb[q]);
+                }
+#pragma unroll
+                for (int q = 0; q < 3; q++) step(4 + q, c.hi(q), -c.vhi[q]);
             }
         }
+        // entries the run emits: one per row that one of its updates creates
+        u32 ec = 0;
+#pragma unroll
+        for (int q = 0; q < G_ROWS; q++) ec += present[q] ? 1u : 0u;
+        const PairPlace pl = pair_place(ec, lw, lane, w);
+        // ---- place: the table's, or nothing is stored
+        if (!pair_table_hit(dst, dst_next, pl.total, out_cap, s)) {
+            if (t == 0) a.host_words[1] = (u64)PRED_MISS;  // (the same constant from every missing pair: a plain store)
+            return;
+        }
+        {
+            u32 at = pl.at0;
+#pragma unroll
+            for (int q = 0; q < G_ROWS; q++) {
+                if (present[q]) {
+                    if constexpr (!KEEP) srow[at] = row[q];
+                    sval[at] = acc[q];
+                    at++;
+                }
+            }
+        }
+        __syncthreads();
+        pair_store<KEEP>(a, srow, sval, 0, dst, pl, hi, ncl, s, t);  // (srow holds 1-based rows)
+        if (s == a.S - 1 && t == 0) a.host_words[0] = pair_grand_total(dst, pl.total);
+        // ---- one plane up: the pair s_step further, k + 1, the counter a constant further
+        if (!MARCH || ++m >= a.march) return;
+        s += s_step;
+        if (s >= a.S) return;  // (the last chunk of an nz that is no multiple of the march)
+        if (has) l += (u32)c.stride[0], zg = src.next_plane(zg, c);
     }
-    __syncthreads();
-    pair_store<KEEP>(a, srow, sval, 0, dst, pl, hi, ncl, s, t);  // (srow holds 1-based rows)
-    if (s == a.S - 1 && t == 0) a.host_words[0] = pair_grand_total(dst, pl.total);
+}
+
+// ---- the march length: the one place that decides it
+// The automatic rule as a pure function of the grid, the cut and the device.  A grid conforms when a plane is a whole number of
+// pairs (nx ny % ncl == 0); P = nx ny / ncl pairs then make a plane, pair s + P holds lane for lane the (i, j) of pair s one
+// plane up, and every pair is full.  A longer march saves more of what a thread forms once and more z draws ((L - 1) / L of
+// them), but it leaves fewer and longer workgroups, and a launch ends with a round of workgroups that fills the device only in
+// part.  Measured at 256^3 on 256 compute units (NOTES/round22.md; R = 1024 workgroups at once, four per compute unit: the LDS
+// bounds them): 3 planes (10.75 rounds of R) beat the parent by 3 %; 2 planes (16 rounds) lost 1 to 4 %, 5, 6 and 8 planes (6.5,
+// 5.4 and 4 rounds) lost 10 %, 4 planes (8 rounds) went either way from run to run -- a round count just above a whole number
+// pays for a whole round more.  So the rule marches only what a run backs: MARCH_PLANES planes, where that leaves at least the
+// measured 10.75 rounds and where the planes a slot of the device works through, L ceil(W / R + 1/4) with W = P ceil(nz / L)
+// workgroups (the quarter: workgroups drift apart, an exact fit does not stay one), are at most 33 / 32 of what one plane per
+// workgroup has -- 33 against 32 was the measured gain.  Everything else runs one plane per workgroup.
+namespace {
+constexpr int MARCH_PLANES = 3;
+constexpr i64 MARCH_RESIDENT_PER_CU = 4;
+constexpr i64 MARCH_ROUNDS_X4 = 43;  // 10.75 rounds
+i64 march_pairs_per_plane(i64 nx, i64 ny, int cl_bits) {  // P, or 0 for a grid that does not conform
+    if (nx < 1 || ny < 1 || cl_bits < 0 || (2 << cl_bits) > THREADS) return 0;
+    const i64 ncl = (i64)2 << cl_bits, nxny = nx * ny;
+    return nxny % ncl == 0 ? nxny / ncl : 0;
+}
+}  // namespace
+
+int pair_gen_march_rule(i64 nx, i64 ny, i64 nz, int cl_bits, int compute_units) {
+    const i64 P = march_pairs_per_plane(nx, ny, cl_bits);
+    if (P == 0 || nz < MARCH_PLANES) return 1;
+    const i64 R = MARCH_RESIDENT_PER_CU * (i64)std::max(compute_units, 1);
+    auto workgroups = [&](i64 L) { return P * ((nz + L - 1) / L); };
+    auto planes_per_slot = [&](i64 L) { return L * ((4 * workgroups(L) + R + 4 * R - 1) / (4 * R)); };  // L ceil(W / R + 1/4)
+    const i64 L = MARCH_PLANES;
+    return 4 * workgroups(L) >= MARCH_ROUNDS_X4 * R && planes_per_slot(L) * 32 <= planes_per_slot(1) * 33 ? (int)L : 1;
+}
+
+// The march of one fused flush: 1 unless the grid conforms, the flush starts at column 0, covers the whole grid and its pairs are
+// exactly the grid's (a.S = P nz, so a marching workgroup's pairs are all in the table and all full); then `force` (clamped to
+// nz) or the rule.  a.S is the number of pairs.
+static int pair_gen_march(const Args &a, const espgen::FdArgs &fd, int compute_units, int force) {
+    const i64 P = march_pairs_per_plane(fd.nx, fd.ny, a.cl_bits);
+    if (P == 0 || fd.nz < 1 || a.rb >= 32 || (a.base >> a.rb) != 0 || a.col_end != fd.nx * fd.ny * fd.nz || (i64)a.S != P * fd.nz || P > 0x7fffffff)
+        return 1;
+    if (force > 0) return (int)std::min<i64>(force, fd.nz);
+    return pair_gen_march_rule(fd.nx, fd.ny, fd.nz, a.cl_bits, compute_units);
+}
+
+// ... written into the argument block (a.march, a.march_step); returns the workgroups of the flush: the pairs, or (pairs of a
+// plane) x (chunks of `march` planes) -- the unit of a.first and of a launch's grid
+i64 pair_gen_set_march(Args &a, const espgen::FdArgs &fd, int compute_units, int force) {
+    a.march = pair_gen_march(a, fd, compute_units, force);
+    a.march_step = 0;
+    if (a.march <= 1) return (i64)a.S;
+    const i64 P = march_pairs_per_plane(fd.nx, fd.ny, a.cl_bits);
+    a.march_step = (int)P;
+    return P * ((fd.nz + a.march - 1) / a.march);
 }
 
 bool launch_pair_gen_predicted(const Variant &v, unsigned grid, hipStream_t stream, const Args &a, const espgen::FdArgs &fd, const u64 *pred,
@@ -263,16 +384,24 @@ bool launch_pair_gen_predicted(const Variant &v, unsigned grid, hipStream_t stre
     // (FdSource: the division.  Other spacings are not the fused kernel's: the caller serves the flush unfused)
     auto mid = [](double h) { return h >= 0x1.0p-100 && h <= 0x1.0p100; };
     if (!(mid(fd.hx) && mid(fd.hy) && mid(fd.hz))) return false;
+    // (a march is pair_gen_set_march's or none: the kernel's mapping holds for a grid that conforms only)
+    if (a.march > 1 && (a.march != pair_gen_march(a, fd, 0, a.march) || (i64)a.march_step != march_pairs_per_plane(fd.nx, fd.ny, a.cl_bits)))
+        return false;
     auto go = [&](auto M) {
         using Src = FdSource<decltype(M)::value>;
         const Src src{fd.nx, fd.ny, fd.nz, fd.hx, fd.hy, fd.hz, fd.seed, fd.fast, fd.magic_nx, fd.magic_nxny,
                       {6ull * (u64)(fd.nx * fd.ny) * ESP_GOLDEN, 6ull * (u64)fd.nx * ESP_GOLDEN, 6ull * ESP_GOLDEN}};
         return pair_for_keys(v.keys, [&](auto K) {
             constexpr int KEYS = decltype(K)::value;
-            if (keep)
-                hipLaunchKernelGGL((pair_gen_pred_k<KEYS, Src, true>), dim3(grid), dim3(THREADS), 0, stream, a, src, pred, out_cap);
-            else
-                hipLaunchKernelGGL((pair_gen_pred_k<KEYS, Src, false>), dim3(grid), dim3(THREADS), 0, stream, a, src, pred, out_cap);
+            auto run = [&](auto KP, auto MA) {
+                hipLaunchKernelGGL((pair_gen_pred_k<KEYS, Src, decltype(KP)::value, decltype(MA)::value>), dim3(grid), dim3(THREADS), 0, stream, a,
+                                   src, pred, out_cap);
+            };
+            const bool march = a.march > 1;
+            if (keep && march) run(std::true_type{}, std::true_type{});
+            else if (keep) run(std::true_type{}, std::false_type{});
+            else if (march) run(std::false_type{}, std::true_type{});
+            else run(std::false_type{}, std::false_type{});
         });
     };
     // (the mode as the generator reads it: 0, 1, anything else)

@@ -410,6 +410,21 @@ extern "C" int32_t esp_debug_last_kept_structure(const esp_handle *h, int32_t *s
     *state = h->last_kept;
     return ESP_OK;
 }
+extern "C" int32_t esp_debug_last_march(const esp_handle *h, int32_t *planes) {
+    if (!h || !planes) return ESP_ERR_INVALID;
+    *planes = h->last_march;
+    return ESP_OK;
+}
+extern "C" int32_t esp_debug_force_march(esp_handle *h, int32_t planes) {
+    if (!h || planes < 0) return ESP_ERR_INVALID;
+    h->force_march = planes;
+    return ESP_OK;
+}
+extern "C" int32_t esp_debug_march_rule(int64_t nx, int64_t ny, int64_t nz, int32_t cl_bits, int32_t compute_units, int32_t *planes) {
+    if (!planes || nx < 1 || ny < 1 || nz < 1) return ESP_ERR_INVALID;
+    *planes = esplocal::pair_gen_march_rule(nx, ny, nz, cl_bits, compute_units);
+    return ESP_OK;
+}
 extern "C" int32_t esp_debug_last_sum_join(const esp_handle *h, int32_t *segments) {
     if (!h || !segments) return ESP_ERR_INVALID;
     *segments = h->last_sum_join;

@@ -944,6 +944,26 @@ class ExtendableSparseMatrix:
         self._d.ck(self._d.lib.esp_debug_last_kept_structure(self._d.h, C.byref(p)))
         return p.value
 
+    def debug_last_march(self):
+        """Planes per workgroup of the last flush's fused stencil launch (esp_debug_last_march); 0: the last flush was not fused"""
+        p = C.c_int32()
+        self._d.ck(self._d.lib.esp_debug_last_march(self._d.h, C.byref(p)))
+        return p.value
+
+    def debug_force_march(self, planes):
+        """Test hook (esp_debug_force_march): 0 the automatic rule, else the march of every grid that conforms, clamped to nz"""
+        self._d.ck(self._d.lib.esp_debug_force_march(self._d.h, int(planes)))
+
+    @staticmethod
+    def debug_march_rule(nx, ny, nz, cl_bits, compute_units):
+        """The automatic march of the fused stencil kernel as a pure function of the grid, the bucket cut and the device's compute
+        units (esp_debug_march_rule)"""
+        p = C.c_int32()
+        rc = L.load().esp_debug_march_rule(int(nx), int(ny), int(nz), int(cl_bits), int(compute_units), C.byref(p))
+        if rc != 0:
+            raise ValueError("esp_debug_march_rule: invalid arguments")
+        return p.value
+
     def debug_last_rebuild(self):
         """1: the last flush rebuilt the matrix for the entries behind a re-assembly's batch (stored entries as a first piece)"""
         p = C.c_int32()

@@ -1262,6 +1262,19 @@ int32_t esp_debug_last_lazy_stencil(const esp_handle *h, int32_t *state);
  * result installed into the handle, esp_clone, a shard call, esp_release_buffers -- makes the next flush store everything), 2 the
  * KEEP form missed (some pair's count differs from the table's) and the retry rewrote everything.  esp_debug_force_path(45): never 1 */
 int32_t esp_debug_last_kept_structure(const esp_handle *h, int32_t *state);
+/* the march of the fused stencil kernel: a workgroup handles `planes` consecutive z planes of the same 512 (i, j) columns, forms
+ * what does not depend on the plane once and takes each z pair value from the register that formed it one plane below.  A grid
+ * conforms when nx ny is a multiple of the columns of a pair (2 << cl_bits, esp_debug_last_bucket_cut); every other grid runs one
+ * plane per workgroup.  last_march: planes per workgroup of the last flush's fused launch, 0 when the last flush was not fused (or
+ * the fused kernel missed and the flush was served again without it) */
+int32_t esp_debug_last_march(const esp_handle *h, int32_t *planes);
+/* test hook: 0 the automatic rule; planes > 0: that march wherever the grid conforms, clamped to nz (a grid that does not conform
+ * still runs one plane per workgroup) */
+int32_t esp_debug_force_march(esp_handle *h, int32_t planes);
+/* the automatic rule as a pure function (no handle, no device): 3 planes where the grid conforms, nz >= 3, that leaves at least
+ * 10.75 rounds of the workgroups the device holds at once (four per compute unit) and the last, partly filled round costs no more
+ * than 1 / 32 of the launch -- the one march a measurement backs, see pair_gen_march_rule (csrc/local_x.hip); else 1 */
+int32_t esp_debug_march_rule(int64_t nx, int64_t ny, int64_t nz, int32_t cl_bits, int32_t compute_units, int32_t *planes);
 /* how many neighbouring segments of the folds' plan the combine flush of the last esp_flush_sum of that kind (last_lazy_items 2)
  * joined into one (1, 2, 4 or 8: as many as keep the longest joined segment within the bucket kernel's capacity); 0 otherwise */
 int32_t esp_debug_last_sum_join(const esp_handle *h, int32_t *segments);
