@@ -8,7 +8,7 @@ from . import _lib
 from ._lib import (ESP_AMG_COARSEN_RS, ESP_AMG_COARSEN_SA, ESP_COO, ESP_FLUSH_PLUS, ESP_FLUSH_ROUTED, ESP_OP_ADD, ESP_OP_SUB, ESP_ORTH_CGS, ESP_ORTH_DGKS, ESP_ORTH_MGS, ESP_PATH_NO_KEPT_STRUCTURE, ESP_PRECON_AMG, ESP_PRECON_BLOCK, ESP_PRECON_CHOLESKY, ESP_PRECON_COLORED, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_ILUK, ESP_PRECON_ILUT, ESP_PRECON_JACOBI, ESP_PRECON_LU, ESP_PRECON_SPAI,
                    ESP_RAWUPDATE, ESP_SET, ESP_UPDATE, BoundsError, EspError, NoDeviceError, PosDefError)
 from .matrix import (Diagonal, ExtendableSparseMatrix, GenericExtendableSparseMatrixCSC,
-                     GenericMTExtendableSparseMatrixCSC, SparseMatrixCSC, SparseMatrixHIPCOO)
+                     GenericMTExtendableSparseMatrixCSC, SparseMatrixCSC, SparseMatrixHIPCOO, many_layout)
 from . import fdrand as fdrand_module
 from .fdrand import fdrand, fdrand_, fdrand_coo, fdrand_device_
 from .sharded import GroupShardedMatrix, owner_ranges

@@ -26,6 +26,7 @@ ESP_PRECON_ILUT = 8
 ESP_PRECON_LU = 9
 ESP_PRECON_CHOLESKY = 10
 ESP_CHOL_STATS = 12
+ESP_MANY_CHUNK = 8  # columns of a chunk of esp_mul_many / esp_precon_ldiv_many
 ESP_ILUT_WAVE_UPPER, ESP_ILUT_GROUP_UPPER, ESP_ILUT_STEPS_MAX, ESP_ILUT_STATS = 256, 4096, 16, 40
 ESP_ILUK_WAVE_VISITS, ESP_ILUK_VISIT_MAX = 512, 8192
 ESP_SPAI_WAVE_DOUBLES, ESP_SPAI_DENSE_MAX = 512, 12288
@@ -111,6 +112,7 @@ SIGNATURES = {
     "esp_pending_getindex": (i32, [vp, i64, i64, P(f64), P(i32)]),
     "esp_release_buffers": (i32, [vp]),
     "esp_mul": (i32, [vp, vp, vp, i32]),
+    "esp_mul_many": (i32, [vp, vp, i64, vp, i64, i64, i32]),
     "esp_mark_dirichlet": (i32, [vp, f64, vp, i32]),
     "esp_eliminate_dirichlet": (i32, [vp, vp, i32]),
     "esp_jacobi_setup": (i32, [vp, vp, i32]),
@@ -118,6 +120,7 @@ SIGNATURES = {
     "esp_precon_create": (i32, [vp, i32, P(vp)]),
     "esp_precon_update": (i32, [vp]),
     "esp_precon_ldiv": (i32, [vp, vp, vp, i32]),
+    "esp_precon_ldiv_many": (i32, [vp, vp, i64, vp, i64, i64, i32]),
     "esp_precon_destroy": (i32, [vp]),
     "esp_precon_get_factor": (i32, [vp, vp, i32]),
     "esp_precon_levels": (i32, [vp, P(i64)]),

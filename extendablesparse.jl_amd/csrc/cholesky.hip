@@ -27,7 +27,9 @@
 //   solve      gather y = v[c]; forward per depth from the deepest up (chol_fwd_k, a workgroup per node: one lane per row gathers
 //              from the update list with k ascending, then the triangle right-looking, t in LDS up to TRI_LDS rows, else in a
 //              second vector); backward per depth from 0 down (chol_bwd_k: struct first, then the triangle from the last position
-//              up); scatter u[c] = x.  Launches on the handle's stream and nothing else.
+//              up); scatter u[c] = x.  Launches on the handle's stream and nothing else.  Several right-hand sides
+//              (esp_precon_ldiv_many): chol_fwd_many_k / chol_bwd_many_k carry RC = 8 columns per pass over the panels,
+//              a lane per (row of the node, right-hand side) pair, the work vectors stored right-hand-side-fastest.
 #include "panels.hpp"
 
 using namespace espamg;
@@ -36,6 +38,7 @@ using namespace esppanel;
 
 struct CholData : PanelTree {
     DevBuf panels, fail, y, y2, lcp;
+    DevBuf ym, y2m;  // the work vectors of the chunked solves, n * RC doubles each, from the first esp_precon_ldiv_many on
     bool failed = false;
     i64 stats[ESP_CHOL_STATS] = {0};
 };
@@ -347,6 +350,80 @@ __global__ __launch_bounds__(CT) void chol_bwd_k(Dev d, const u32 *__restrict__ 
     }
 }
 
+// ---- solve, several right-hand sides -----------------------------------------------------------------------------------
+// chol_fwd_k over nr <= RC right-hand sides at once: y and y2 hold RC doubles per position (y[pos * RC + r]); a lane owns right-hand
+// side r = tid % RC of the rows slot, slot + RR, ... of the node and walks chol_fwd_k's chain for that pair.  The RC lanes of a row
+// read the same panel entry (one fetch) and RC neighbouring doubles of y.  t: w x RC doubles, in LDS up to TRI_LDS_MANY rows
+__global__ __launch_bounds__(CT) void chol_fwd_many_k(Dev d, const u32 *__restrict__ list, double *__restrict__ y, double *__restrict__ y2, int nr) {
+    __shared__ double sh[TRI_LDS_MANY * RC];
+    const ManyLane m = many_lane(nr);
+    const CholNode K = d.nodes[list[blockIdx.x]];
+    const i64 ld = (i64)K.w + K.h;
+    const double *P = d.panels + K.off;
+    double *t = K.w <= (u32)TRI_LDS_MANY ? sh : y2 + (i64)K.start * RC;
+    for (u32 j0 = 0; j0 < K.w; j0 += RR) {  // (uniform over the workgroup: the shuffle of many_found needs every lane)
+        const u32 j = j0 + (u32)m.slot;
+        const bool valid = j < K.w;
+        double a = (valid && m.on) ? y[(i64)(K.start + j) * RC + m.r] : 0.0;
+        for (u32 u0 = K.ub; u0 < K.ue; u0 += RC) {
+            const int mine = struct_find_spread(d.nodes, d.ulist, d.srv, u0, K.ue, K.start + j, valid, m);
+            for (int q = 0; q < RC && u0 + q < K.ue; q++) {  // the update list ascending, as chol_fwd_k walks it
+                const int f = many_found(mine, q, m);
+                if (f < 0 || !m.on) continue;
+                const CholNode J = d.nodes[d.ulist[u0 + q]];
+                const i64 ldj = (i64)J.w + J.h;
+                const double *R = d.panels + J.off + J.w + f;
+                const double *yj = y + (i64)J.start * RC + m.r;
+                for (u32 k = 0; k < J.w; k++) {
+                    const double pr = R[(i64)k * ldj] * yj[(i64)k * RC];
+                    a = a - pr;
+                }
+            }
+        }
+        if (valid && m.on) t[(i64)j * RC + m.r] = a;
+    }
+    for (u32 k = 0; k < K.w; k++) {
+        __syncthreads();
+        if (!m.on) continue;
+        const double yk = t[(i64)k * RC + m.r] / P[(i64)k * ld + k];
+        if (m.slot == 0) y[(i64)(K.start + k) * RC + m.r] = yk;
+        for (u32 i = k + 1 + (u32)m.slot; i < K.w; i += RR) {
+            const double pr = P[(i64)k * ld + i] * yk;
+            t[(i64)i * RC + m.r] = t[(i64)i * RC + m.r] - pr;
+        }
+    }
+}
+// chol_bwd_k in the same way
+__global__ __launch_bounds__(CT) void chol_bwd_many_k(Dev d, const u32 *__restrict__ list, double *__restrict__ y, double *__restrict__ y2, int nr) {
+    __shared__ double sh[TRI_LDS_MANY * RC];
+    const ManyLane m = many_lane(nr);
+    const CholNode K = d.nodes[list[blockIdx.x]];
+    const i64 ld = (i64)K.w + K.h;
+    const double *P = d.panels + K.off;
+    const i64 *st = d.srv + K.sbase;
+    double *t = K.w <= (u32)TRI_LDS_MANY ? sh : y2 + (i64)K.start * RC;
+    if (m.on)
+        for (u32 j = (u32)m.slot; j < K.w; j += RR) {
+            double a = y[(i64)(K.start + j) * RC + m.r];
+            const double *C = P + (i64)j * ld + K.w;
+            for (u32 i = 0; i < K.h; i++) {
+                const double pr = C[i] * y[(st[i] - 1) * RC + m.r];
+                a = a - pr;
+            }
+            t[(i64)j * RC + m.r] = a;
+        }
+    for (u32 k = K.w; k-- > 0;) {
+        __syncthreads();
+        if (!m.on) continue;
+        const double xk = t[(i64)k * RC + m.r] / P[(i64)k * ld + k];
+        if (m.slot == 0) y[(i64)(K.start + k) * RC + m.r] = xk;
+        for (u32 j = (u32)m.slot; j < k; j += RR) {
+            const double pr = P[(i64)j * ld + k] * xk;
+            t[(i64)j * RC + m.r] = t[(i64)j * RC + m.r] - pr;
+        }
+    }
+}
+
 // ---- L as a CSC ----------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(CT) void chol_export_k(Dev d, const u32 *__restrict__ nodeof, const i64 *__restrict__ lcp, i64 n, i64 *__restrict__ rv,
                                                     double *__restrict__ nz) {
@@ -369,7 +446,7 @@ Dev dev_of(const CholData *c) {
 void chol_drop(CholData *c) {
     if (!c) return;
     tree_drop(*c);
-    for (DevBuf *b : {&c->panels, &c->fail, &c->y, &c->y2, &c->lcp}) release(*b);
+    for (DevBuf *b : {&c->panels, &c->fail, &c->y, &c->y2, &c->lcp, &c->ym, &c->y2m}) release(*b);
     delete c;
 }
 
@@ -519,6 +596,36 @@ int32_t chol_solve(esp_precon *p, const double *v, double *u, bool sub) {
         if (D.all_count) hipLaunchKernelGGL(chol_bwd_k, dim3(D.all_count), dim3(CT), 0, s, d, dlist + D.all_first, y, y2);
     }
     hipLaunchKernelGGL(panel_scatter_k, dim3(g), dim3(CT), 0, s, perm, (const double *)y, u, n, sub);
+    return ESP_OK;
+}
+
+// U[:, r] = A \ V[:, r] for k columns on device arrays (U may be V where ldu == ldv), RC columns per pass over the panels
+int32_t chol_solve_many(esp_precon *p, const double *v, i64 ldv, double *u, i64 ldu, i64 k) {
+    esp_handle *h = p->h;
+    hipStream_t s = h->stream;
+    const i64 n = p->n;
+    CholData *c = p->chol;
+    if (!c || c->failed) FAIL(h, ESP_ERR_STATE, "esp_precon_ldiv: the last update! of the factorization failed");
+    if (n == 0 || k == 0) return ESP_OK;
+    CK(ensure(h, c->ym, sizeof(double) * (size_t)n * RC));
+    CK(ensure(h, c->y2m, sizeof(double) * (size_t)n * RC));
+    const Dev d = dev_of(c);
+    const u32 *perm = (const u32 *)p->lu_perm.p, *dlist = (const u32 *)c->dlist.p;
+    double *y = (double *)c->ym.p, *y2 = (double *)c->y2m.p;
+    const unsigned g = grid_for(n * RC, CT);
+    for (i64 r0 = 0; r0 < k; r0 += RC) {
+        const int nr = (int)std::min<i64>(RC, k - r0);
+        hipLaunchKernelGGL(panel_gather_many_k, dim3(g), dim3(CT), 0, s, perm, v + r0 * ldv, ldv, y, n, nr);
+        for (size_t dep = c->depth.size(); dep-- > 0;) {
+            const CholDepth &D = c->depth[dep];
+            if (D.all_count) hipLaunchKernelGGL(chol_fwd_many_k, dim3(D.all_count), dim3(CT), 0, s, d, dlist + D.all_first, y, y2, nr);
+        }
+        for (size_t dep = 0; dep < c->depth.size(); dep++) {
+            const CholDepth &D = c->depth[dep];
+            if (D.all_count) hipLaunchKernelGGL(chol_bwd_many_k, dim3(D.all_count), dim3(CT), 0, s, d, dlist + D.all_first, y, y2, nr);
+        }
+        hipLaunchKernelGGL(panel_scatter_many_k, dim3(g), dim3(CT), 0, s, perm, (const double *)y, u + r0 * ldu, ldu, n, nr);
+    }
     return ESP_OK;
 }
 

@@ -273,6 +273,73 @@ extern "C" int32_t esp_mul(esp_handle *h, const double *x, double *r, int32_t on
     return ESP_OK;
 }
 
+// ---- R = A*X for several columns (include/esparse_hip.h, SEVERAL RIGHT-HAND SIDES) ---------------------------------------------------
+// spmv_rows_k over nr <= MB columns of X at once: a lane owns row i and MB accumulators, reads rval[k] and tcol[k] once and runs
+// spmv_rows_k's statement for every column, k ascending.  MB = 8: 34 VGPRs, no scratch (NOTES/multi_rhs.md)
+constexpr int MB = ESP_MANY_CHUNK;
+__global__ __launch_bounds__(256) void spmm_rows_k(const u64 *__restrict__ rowptr0, const double *__restrict__ rval, const u32 *__restrict__ tcol,
+                                                   const double *__restrict__ x, i64 ldx, i64 m, double *__restrict__ r, i64 ldr, int nr) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    double acc[MB];
+#pragma unroll
+    for (int c = 0; c < MB; c++) acc[c] = 0.0;
+    const u64 b = rowptr0[i + 1], e = rowptr0[i + 2];
+    for (u64 k = b; k < e; k++) {
+        const double a = rval[k];
+        const double *xc = x + tcol[k];
+#pragma unroll
+        for (int c = 0; c < MB; c++)
+            if (c < nr) acc[c] = acc[c] + a * xc[(i64)c * ldx];
+    }
+#pragma unroll
+    for (int c = 0; c < MB; c++)
+        if (c < nr) r[(i64)c * ldr + i] = acc[c];
+}
+
+extern "C" int32_t esp_mul_many(esp_handle *h, const double *X, int64_t ldx, double *R, int64_t ldr, int64_t k, int32_t on_device) {
+    if (!h) return ESP_ERR_INVALID;
+    const i64 n = h->n, m = h->m;
+    if (k < 0 || ldx < std::max<i64>(n, 1) || ldr < std::max<i64>(m, 1))
+        FAIL(h, ESP_ERR_INVALID, "esp_mul_many: k = %lld, ldx = %lld, ldr = %lld for a %lld x %lld matrix", (long long)k, (long long)ldx, (long long)ldr, (long long)m, (long long)n);
+    if ((!X && k * n > 0) || (!R && k * m > 0)) return ESP_ERR_INVALID;
+    if (k * n > 0 && k * m > 0 && X < R + (k - 1) * ldr + m && R < X + (k - 1) * ldx + n) FAIL(h, ESP_ERR_INVALID, "esp_mul_many: X and R overlap");
+    if (k == 1) return esp_mul(h, X, R, on_device);  // the single-vector path itself
+    if (h->count != 0) FAIL(h, ESP_ERR_STATE, "esp_mul: pending entries (flush first, like mul!(r, ext, x) does)");
+    (void)hipSetDevice(h->device);
+    if (!h->csc_valid) CK(init_empty_csc(h));
+    CK(fix_tail(h));
+    CK(csr_current(h));
+    if (k == 0 || m == 0) return ESP_OK;
+    if (!on_device) {
+        CK(ensure(h, h->mul_x, sizeof(double) * (size_t)std::max<i64>(n, 1) * MB));
+        CK(ensure(h, h->mul_r, sizeof(double) * (size_t)m * MB));
+    }
+    for (i64 r0 = 0; r0 < k; r0 += MB) {
+        const int nr = (int)std::min<i64>(MB, k - r0);
+        const double *dx = X + r0 * ldx;
+        double *dr = R + r0 * ldr;
+        i64 dldx = ldx, dldr = ldr;
+        if (!on_device) {
+            if (n > 0)
+                HIPCK(h, hipMemcpy2DAsync(h->mul_x.p, sizeof(double) * (size_t)n, dx, sizeof(double) * (size_t)ldx, sizeof(double) * (size_t)n, (size_t)nr,
+                                          hipMemcpyHostToDevice, h->stream));
+            dx = (const double *)h->mul_x.p;
+            dr = (double *)h->mul_r.p;
+            dldx = std::max<i64>(n, 1);
+            dldr = m;
+        }
+        hipLaunchKernelGGL(spmm_rows_k, dim3(grid_for(m, 256)), dim3(256), 0, h->stream, (const u64 *)h->csr_rowptr.p, (const double *)h->csr_val.p,
+                           (const u32 *)h->csr_col.p, dx, dldx, m, dr, dldr, nr);
+        HIPCK(h, hipGetLastError());
+        if (!on_device)
+            HIPCK(h, hipMemcpy2DAsync(R + r0 * ldr, sizeof(double) * (size_t)ldr, dr, sizeof(double) * (size_t)m, sizeof(double) * (size_t)m, (size_t)nr,
+                                      hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    return ESP_OK;
+}
+
 // ---- Dirichlet edits of the assembled CSC (sparsematrixcsc.jl:97-140) --------------------------------
 // one thread per column, the same statements as the reference loops (order inside a column kept)
 __global__ void mark_dirichlet_k(const i64 *__restrict__ colptr, const i64 *__restrict__ rowval, const double *__restrict__ nzval,

@@ -768,12 +768,16 @@ void lu_release(esp_precon *p);
 // launches on the handle's stream only); esp_precon_get_factor's answer, nnz(B) doubles in B's position order exported from the
 // panels; the rest of its interface is lu.hpp's
 int32_t lup_solve(esp_precon *p, const double *v, double *u, bool sub);
+// ... and of k columns in chunks of ESP_MANY_CHUNK (v: n x k column-major with leading dimension ldv, u with ldu; u may be v where
+// ldu == ldv): per chunk a gather, two launches per depth and a scatter, nothing else
+int32_t lup_solve_many(esp_precon *p, const double *v, i64 ldv, double *u, i64 ldu, i64 k);
 int32_t lup_factor(esp_precon *p, double *nzval, int32_t on_device);
 // cholesky.hip: update! (after a pattern change the ordering, the tables and the panels anew; else the load and the numeric
 // factorization), ldiv! on device vectors (u may be v; sub: u[i] = u[i] - x[i], simple!'s step; launches on the handle's stream only),
 // release of everything
 int32_t chol_update(esp_precon *p);
 int32_t chol_solve(esp_precon *p, const double *v, double *u, bool sub);
+int32_t chol_solve_many(esp_precon *p, const double *v, i64 ldv, double *u, i64 ldu, i64 k);  // (as lup_solve_many)
 void chol_release(esp_precon *p);
 // spai.hip: update! (after a pattern change the size pass, the tiers and M anew; else the numeric kernels alone), M's handles moved
 // to the stream A runs on, ldiv! of order 1 on device vectors (u may be v; sub: u[i] = u[i] - x[i], simple!'s step; launches and at

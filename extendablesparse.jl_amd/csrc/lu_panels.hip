@@ -36,6 +36,7 @@ using namespace esppanel;
 
 struct LuPanelData : PanelTree {
     DevBuf panels, y2;  // PL of every node, then PU of every node (2 * panel_doubles); the triangles wider than TRI_LDS
+    DevBuf bm, ym, y2m;  // the work vectors of the chunked solves, n * RC doubles each, from the first esp_precon_ldiv_many on
     i64 stats[ESP_LU_PANEL_STATS] = {0};
 };
 
@@ -374,6 +375,80 @@ __global__ __launch_bounds__(CT) void lup_bwd_k(Dev d, const u32 *__restrict__ l
     }
 }
 
+// ---- solve, several right-hand sides -----------------------------------------------------------------------------------
+// lup_fwd_k over nr <= RC right-hand sides at once: b, y and y2 hold RC doubles per position (y[pos * RC + r]); a lane owns right-hand
+// side r = tid % RC of the rows slot, slot + RR, ... of the node and walks lup_fwd_k's chain for that pair (cholesky.hip's
+// chol_fwd_many_k states the layout)
+__global__ __launch_bounds__(CT) void lup_fwd_many_k(Dev d, const u32 *__restrict__ list, const double *__restrict__ b, double *y, double *y2, int nr) {
+    __shared__ double sh[TRI_LDS_MANY * RC];
+    const ManyLane m = many_lane(nr);
+    const CholNode K = d.nodes[list[blockIdx.x]];
+    const i64 ld = (i64)K.w + K.h;
+    const double *P = d.pl + K.off;
+    double *t = K.w <= (u32)TRI_LDS_MANY ? sh : y2 + (i64)K.start * RC;
+    for (u32 j0 = 0; j0 < K.w; j0 += RR) {  // (uniform over the workgroup: the shuffle of many_found needs every lane)
+        const u32 j = j0 + (u32)m.slot;
+        const bool valid = j < K.w;
+        double a = 0.0;
+        for (u32 u0 = K.ub; u0 < K.ue; u0 += RC) {
+            const int mine = struct_find_spread(d.nodes, d.ulist, d.srv, u0, K.ue, K.start + j, valid, m);
+            for (int q = 0; q < RC && u0 + q < K.ue; q++) {  // the update list ascending, as lup_fwd_k walks it
+                const int f = many_found(mine, q, m);
+                if (f < 0 || !m.on) continue;
+                const CholNode J = d.nodes[d.ulist[u0 + q]];
+                const i64 ldj = (i64)J.w + J.h;
+                const double *R = d.pl + J.off + J.w + f;
+                const double *yj = y + (i64)J.start * RC + m.r;
+                for (u32 k = 0; k < J.w; k++) {
+                    const double pr = R[(i64)k * ldj] * yj[(i64)k * RC];
+                    a = a - pr;
+                }
+            }
+        }
+        if (valid && m.on) t[(i64)j * RC + m.r] = a;
+    }
+    for (u32 k = 0; k < K.w; k++) {
+        __syncthreads();
+        if (!m.on) continue;
+        const double yk = t[(i64)k * RC + m.r] + b[(i64)(K.start + k) * RC + m.r];  // (the right-hand side comes last)
+        if (m.slot == 0) y[(i64)(K.start + k) * RC + m.r] = yk;
+        for (u32 i = k + 1 + (u32)m.slot; i < K.w; i += RR) {
+            const double pr = P[(i64)k * ld + i] * yk;
+            t[(i64)i * RC + m.r] = t[(i64)i * RC + m.r] - pr;
+        }
+    }
+}
+// lup_bwd_k in the same way
+__global__ __launch_bounds__(CT) void lup_bwd_many_k(Dev d, const u32 *__restrict__ list, double *y, double *y2, int nr) {
+    __shared__ double sh[TRI_LDS_MANY * RC];
+    const ManyLane m = many_lane(nr);
+    const CholNode K = d.nodes[list[blockIdx.x]];
+    const i64 ld = (i64)K.w + K.h;
+    const double *PL = d.pl + K.off, *PU = d.pu + K.off;
+    const i64 *st = d.srv + K.sbase;
+    double *t = K.w <= (u32)TRI_LDS_MANY ? sh : y2 + (i64)K.start * RC;
+    if (m.on)
+        for (u32 j = (u32)m.slot; j < K.w; j += RR) {
+            double a = y[(i64)(K.start + j) * RC + m.r];
+            const double *C = PU + (i64)j * ld + K.w;
+            for (u32 i = K.h; i-- > 0;) {
+                const double pr = C[i] * y[(st[i] - 1) * RC + m.r];
+                a = a - pr;
+            }
+            t[(i64)j * RC + m.r] = a;
+        }
+    for (u32 k = K.w; k-- > 0;) {
+        __syncthreads();
+        if (!m.on) continue;
+        const double xk = t[(i64)k * RC + m.r] / PL[(i64)k * ld + k];
+        if (m.slot == 0) y[(i64)(K.start + k) * RC + m.r] = xk;
+        for (u32 j = (u32)m.slot; j < k; j += RR) {
+            const double pr = PU[(i64)j * ld + k] * xk;
+            t[(i64)j * RC + m.r] = t[(i64)j * RC + m.r] - pr;
+        }
+    }
+}
+
 Dev dev_of(const LuPanelData *c) {
     double *pl = (double *)c->panels.p;
     return Dev{(const CholNode *)c->nodes.p, (const u32 *)c->ulist.p, c->S ? (const i64 *)c->S->rowval.p : nullptr, pl, pl + c->panel_doubles};
@@ -385,7 +460,7 @@ void lup_drop(LuPanelData *c) {
     if (!c) return;
     tree_drop(*c);
     release(c->panels);
-    release(c->y2);
+    for (DevBuf *b : {&c->y2, &c->bm, &c->ym, &c->y2m}) release(*b);
     delete c;
 }
 
@@ -473,6 +548,34 @@ int32_t lup_solve(esp_precon *p, const double *v, double *u, bool sub) {
         if (D.all_count) hipLaunchKernelGGL(lup_bwd_k, dim3(D.all_count), dim3(CT), 0, s, d, dlist + D.all_first, y, y2);
     }
     hipLaunchKernelGGL(panel_scatter_k, dim3(g), dim3(CT), 0, s, perm, (const double *)y, u, n, sub);
+    return ESP_OK;
+}
+
+// U[:, r] = B's LU \ V[:, r] for k columns on device arrays (U may be V where ldu == ldv), RC columns per pass over the panels
+int32_t lup_solve_many(esp_precon *p, const double *v, i64 ldv, double *u, i64 ldu, i64 k) {
+    esp_handle *h = p->h;
+    hipStream_t s = h->stream;
+    const i64 n = p->n;
+    LuPanelData *c = p->lup;
+    if (n == 0 || k == 0) return ESP_OK;
+    for (DevBuf *w : {&c->bm, &c->ym, &c->y2m}) CK(ensure(h, *w, sizeof(double) * (size_t)n * RC));
+    const Dev d = dev_of(c);
+    const u32 *perm = (const u32 *)p->lu_perm.p, *dlist = (const u32 *)c->dlist.p;
+    double *b = (double *)c->bm.p, *y = (double *)c->ym.p, *y2 = (double *)c->y2m.p;
+    const unsigned g = grid_for(n * RC, CT);
+    for (i64 r0 = 0; r0 < k; r0 += RC) {
+        const int nr = (int)std::min<i64>(RC, k - r0);
+        hipLaunchKernelGGL(panel_gather_many_k, dim3(g), dim3(CT), 0, s, perm, v + r0 * ldv, ldv, b, n, nr);
+        for (size_t dep = c->depth.size(); dep-- > 0;) {
+            const CholDepth &D = c->depth[dep];
+            if (D.all_count) hipLaunchKernelGGL(lup_fwd_many_k, dim3(D.all_count), dim3(CT), 0, s, d, dlist + D.all_first, (const double *)b, y, y2, nr);
+        }
+        for (size_t dep = 0; dep < c->depth.size(); dep++) {
+            const CholDepth &D = c->depth[dep];
+            if (D.all_count) hipLaunchKernelGGL(lup_bwd_many_k, dim3(D.all_count), dim3(CT), 0, s, d, dlist + D.all_first, y, y2, nr);
+        }
+        hipLaunchKernelGGL(panel_scatter_many_k, dim3(g), dim3(CT), 0, s, perm, (const double *)y, u + r0 * ldu, ldu, n, nr);
+    }
     return ESP_OK;
 }
 

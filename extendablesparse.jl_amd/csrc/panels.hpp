@@ -40,6 +40,13 @@ constexpr int TR = 64;        // rows of the update tile
 constexpr int KB = 16;        // columns of a descendant staged at once
 constexpr int FR = 128;       // rows below the diagonal block a workgroup divides at once (one per lane of its first two waves)
 constexpr int TRI_LDS = 1024; // rows of a node's triangle the solves keep in LDS
+// the solves of several right-hand sides: RC columns share one pass over the panels.  8 = ESP_MANY_CHUNK fills a
+// workgroup with 32 rows x 8 columns, which is exactly a leaf of leaf_size 32 (the default), and the 8 lanes of a row read one
+// 64-byte line of the work vector
+constexpr int RC = ESP_MANY_CHUNK;
+constexpr int RR = CT / RC;        // rows of a node a workgroup walks at once
+constexpr int TRI_LDS_MANY = 512;  // rows of a node's triangle the chunked solves keep in LDS: 512 x RC doubles = 32 KiB, four workgroups per CU
+static_assert(CT % RC == 0 && 64 % RC == 0 && TRI_LDS_MANY * RC * 8 <= 64 * 1024, "a row's lanes lie in one wave; static LDS <= 64 KiB");
 
 // the index of position pos (0-based) in struct(J), or -1
 __device__ __forceinline__ int struct_find(const i64 *__restrict__ srv, const CholNode &J, u32 pos) {
@@ -68,6 +75,40 @@ static __global__ __launch_bounds__(CT) void panel_scatter_k(const u32 *__restri
     const u32 i = perm[k];
     u[i] = sub ? u[i] - x[k] : x[k];
 }
+
+// the chunked forms over nr <= RC columns: y[k * RC + r] = V[c[k], r] (v: column-major, leading dimension ldv) ...
+static __global__ __launch_bounds__(CT) void panel_gather_many_k(const u32 *__restrict__ perm, const double *__restrict__ v, i64 ldv, double *__restrict__ y,
+                                                                 i64 n, int nr) {
+    const i64 e = (i64)blockIdx.x * CT + threadIdx.x, k = e / RC;
+    const int r = (int)(e % RC);
+    if (k < n && r < nr) y[e] = v[(i64)r * ldv + perm[k]];
+}
+// ... and U[c[k], r] = x[k * RC + r]
+static __global__ __launch_bounds__(CT) void panel_scatter_many_k(const u32 *__restrict__ perm, const double *__restrict__ x, double *__restrict__ u, i64 ldu,
+                                                                  i64 n, int nr) {
+    const i64 e = (i64)blockIdx.x * CT + threadIdx.x, k = e / RC;
+    const int r = (int)(e % RC);
+    if (k < n && r < nr) u[(i64)r * ldu + perm[k]] = x[e];
+}
+// what a lane of the chunked solves owns: right-hand side r of the row slot `slot` (the RC lanes of a row are neighbours in one wave)
+struct ManyLane {
+    int r, slot, head;  // head: the wave lane of the row's first right-hand side
+    bool on;            // r < nr: a narrower last chunk is masked
+};
+__device__ __forceinline__ ManyLane many_lane(int nr) {
+    const int tid = threadIdx.x;
+    return ManyLane{tid % RC, tid / RC, (tid & 63) & ~(RC - 1), tid % RC < nr};
+}
+// struct_find once per (row, descendant), the RC lanes of a row sharing the work: lane r bisects position pos in the r-th node of
+// ulist[u0 .. min(u0 + RC, ue)) (a masked lane too) and every lane of the row reads answer q by many_found.  (With the bisection
+// on the row's first lane alone seven lanes of eight wait on its chain of loads: NOTES/multi_rhs.md has that form's times)
+__device__ __forceinline__ int struct_find_spread(const CholNode *__restrict__ nodes, const u32 *__restrict__ ulist, const i64 *__restrict__ srv, u32 u0,
+                                                  u32 ue, u32 pos, bool valid, const ManyLane &m) {
+    const u32 u = u0 + (u32)m.r;
+    return (valid && u < ue) ? struct_find(srv, nodes[ulist[u]], pos) : -1;
+}
+// the answer of the row's lane q.  Every lane of the wave calls it
+__device__ __forceinline__ int many_found(int mine, int q, const ManyLane &m) { return __shfl(mine, m.head + q); }
 
 template <typename T>
 inline int32_t download(esp_handle *h, std::vector<T> &out, const void *src, size_t count) {

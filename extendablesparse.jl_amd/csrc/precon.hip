@@ -419,6 +419,49 @@ extern "C" int32_t esp_precon_ldiv(esp_precon *p, const double *v, double *u, in
     return ESP_OK;
 }
 
+// ldiv! of k columns (include/esparse_hip.h, SEVERAL RIGHT-HAND SIDES).  The two panel kinds run their chunked solves; every other
+// kind runs ldiv_launch column by column.  Host arrays pass through p->hv, ESP_MANY_CHUNK columns at a time
+extern "C" int32_t esp_precon_ldiv_many(esp_precon *p, const double *V, int64_t ldv, double *U, int64_t ldu, int64_t k, int32_t on_device) {
+    if (!p) return ESP_ERR_INVALID;
+    esp_handle *h = p->h;
+    const i64 n = p->n, ldmin = std::max<i64>(n, 1);
+    if (k < 0 || ldv < ldmin || ldu < ldmin) FAIL(h, ESP_ERR_INVALID, "esp_precon_ldiv_many: k = %lld, ldv = %lld, ldu = %lld for n = %lld", (long long)k, (long long)ldv, (long long)ldu, (long long)n);
+    if (k > 0 && n > 0) {
+        if (!V || !U) return ESP_ERR_INVALID;
+        const double *ve = V + (k - 1) * ldv + n, *ue = U + (k - 1) * ldu + n;
+        if (V < ue && U < ve && !(U == V && ldu == ldv))
+            FAIL(h, ESP_ERR_INVALID, "esp_precon_ldiv_many: U and V overlap (only U == V with ldu == ldv is an in-place solve)");
+    }
+    if (k == 1 && n > 0) return esp_precon_ldiv(p, V, U, on_device);  // the single-vector path itself
+    CK(precon_ready(p, "esp_precon_ldiv"));
+    const bool chol = p->kind == ESP_PRECON_CHOLESKY, lup = block_built(p) && p->lup;
+    if (k == 0 || n == 0) return ESP_OK;
+    if (!on_device) CK(ensure(h, p->hv, sizeof(double) * (size_t)n * ESP_MANY_CHUNK));
+    const i64 step = on_device ? k : ESP_MANY_CHUNK;  // (device arrays: one pass; the panel kinds chunk them themselves)
+    for (i64 r0 = 0; r0 < k; r0 += step) {
+        const i64 nr = std::min<i64>(step, k - r0);
+        const double *dv = V + r0 * ldv;
+        double *du = U + r0 * ldu;
+        i64 dldv = ldv, dldu = ldu;
+        if (!on_device) {
+            HIPCK(h, hipMemcpy2DAsync(p->hv.p, sizeof(double) * (size_t)n, dv, sizeof(double) * (size_t)ldv, sizeof(double) * (size_t)n, (size_t)nr,
+                                      hipMemcpyHostToDevice, h->stream));
+            dv = du = (double *)p->hv.p;
+            dldv = dldu = n;
+        }
+        if (chol) CK(chol_solve_many(p, dv, dldv, du, dldu, nr));
+        else if (lup) CK(lup_solve_many(p, dv, dldv, du, dldu, nr));
+        else
+            for (i64 r = 0; r < nr; r++) CK(ldiv_launch(p, dv + r * dldv, du + r * dldu));
+        HIPCK(h, hipGetLastError());
+        if (!on_device)
+            HIPCK(h, hipMemcpy2DAsync(U + r0 * ldu, sizeof(double) * (size_t)ldu, du, sizeof(double) * (size_t)n, sizeof(double) * (size_t)n, (size_t)nr,
+                                      hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    return ESP_OK;
+}
+
 extern "C" int32_t esp_precon_destroy(esp_precon *p) {
     if (!p) return ESP_OK;
     esp_handle *h = p->h;

@@ -42,6 +42,64 @@ def _vp(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _is_cuda(x):
+    return hasattr(x, "is_cuda") and x.is_cuda
+
+
+def many_layout(n, X):
+    """The layout decision of every call that takes several right-hand sides (esp_mul_many, esp_precon_ldiv_many): X is a 2-D
+    (n, k) float64 NumPy array or CUDA torch tensor.  Returns (holder, ld, k): an array whose memory is column-major with leading
+    dimension ld >= max(n, 1) -- X itself where its columns are contiguous (F-order, or a row slice of an F-ordered array: ld is the
+    column stride), else, for a NumPy array of any other order, one F-ordered copy.  A tensor is never copied: it must have
+    stride(0) == 1 and stride(1) >= n (X.t().contiguous().t()).  Anything else raises ValueError("DimensionMismatch").  Pure: it
+    touches no device."""
+    if _is_cuda(X):
+        import torch
+        if X.dim() != 2 or X.dtype != torch.float64 or X.shape[0] != n:
+            raise ValueError("DimensionMismatch")
+        k = int(X.shape[1])
+        s0, s1 = (int(s) for s in X.stride())
+        if n * k == 0:
+            return X, max(n, 1), k
+        if not ((n == 1 or s0 == 1) and (k == 1 or s1 >= n)):
+            raise ValueError("DimensionMismatch")
+        return X, (s1 if k > 1 else n), k
+    if not isinstance(X, np.ndarray) or X.ndim != 2 or X.dtype != np.float64 or X.shape[0] != n:
+        raise ValueError("DimensionMismatch")
+    k = X.shape[1]
+    s0, s1 = X.strides
+    if n * k > 0 and (n == 1 or s0 == 8) and (k == 1 or (s1 % 8 == 0 and s1 >= 8 * n)):
+        return X, (s1 // 8 if k > 1 else n), k
+    return np.asfortranarray(X), max(n, 1), k
+
+
+def _many_result(m, k, like, out, what):
+    """the (m, k) result of a several-right-hand-sides call living where `like` does: `out` checked, or a new column-major array.
+    Returns (holder, ld)."""
+    if _is_cuda(like):
+        import torch
+        if out is None:
+            out = torch.empty((k, m), dtype=torch.float64, device=like.device).t()
+        elif not _is_cuda(out):
+            raise ValueError("%s must live where the argument does" % what)
+        holder, ld, ko = many_layout(m, out)
+    else:
+        if out is None:
+            out = np.empty((m, k), np.float64, order="F")
+        elif not isinstance(out, np.ndarray):
+            raise ValueError("%s must live where the argument does" % what)
+        holder, ld, ko = many_layout(m, out)
+        if holder is not out:
+            raise ValueError("%s must be a float64 array with contiguous columns" % what)
+    if ko != k:
+        raise ValueError("DimensionMismatch")
+    return holder, ld
+
+
+def _many_ptr(holder):
+    return C.c_void_p(holder.data_ptr()) if _is_cuda(holder) else _vp(holder)
+
+
 class SparseMatrixCSC:
     """Host CSC container with Julia's layout: Int64 1-based colptr (n+1) / rowval, Float64 nzval."""
 
@@ -602,9 +660,19 @@ class ExtendableSparseMatrix:
     def mul(self, x, out=None):
         """LinearAlgebra.mul!(r, ext, x) (abstractextendablesparsematrixcsc.jl:179-181): flush!, then r = A*x on
         the device CSC, every r[i] summed in increasing column order like the reference's column loop.
-        x, out: NumPy arrays (copied through the device) or CUDA torch tensors (used in place)."""
+        x, out: NumPy arrays (copied through the device) or CUDA torch tensors (used in place).
+        A 2-D (n, k) x gives the (m, k) product column by column (esp_mul_many: every column is mul's bits): a NumPy array of any
+        order, brought to column-major once, gives an F-ordered array; a tensor needs stride(0) == 1 and stride(1) >= n."""
         self.flush()
         d = self._d
+        if getattr(x, "ndim", 1) != 1:
+            X, ldx, k = many_layout(self.n, x)
+            R, ldr = _many_result(self.m, k, X, out, "out")
+            if _is_cuda(X):
+                import torch
+                torch.cuda.current_stream(X.device).synchronize()   # the library runs on its own stream
+            d.ck(d.lib.esp_mul_many(d.h, _many_ptr(X), ldx, _many_ptr(R), ldr, k, 1 if _is_cuda(X) else 0))
+            return R
         if hasattr(x, "is_cuda") and x.is_cuda:
             import torch
             assert x.dtype == torch.float64 and x.numel() == self.n and x.is_contiguous()
@@ -623,7 +691,8 @@ class ExtendableSparseMatrix:
     def solve(self, b, form="columns"):
         """A \\ b (abstractextendablesparsematrixcsc.jl: `\\` of a square matrix; test/test_backslash.jl): a one-shot
         LUFactorization(A, form=form).solve(b) on the device, closed afterwards.  b: a NumPy array or a CUDA torch tensor; the
-        result lives where b does.  form: "columns" or "panels" (LUFactorization: the same bits either way)."""
+        result lives where b does.  form: "columns" or "panels" (LUFactorization: the same bits either way).  A 2-D (n, k) b is
+        `A \\ B`: k right-hand sides behind the one factorization (LUFactorization.ldiv)."""
         from .precon import LUFactorization   # (precon.py imports this module)
         f = LUFactorization(self, form=form)
         try:

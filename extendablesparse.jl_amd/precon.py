@@ -41,11 +41,7 @@ import math
 import numpy as np
 
 from ._lib import ESP_ORTH_CGS, ESP_ORTH_DGKS, ESP_ORTH_MGS, ESP_PRECON_AMG, ESP_PRECON_BLOCK, ESP_PRECON_COLORED, ESP_PRECON_ILU0, ESP_PRECON_ILUAM, ESP_PRECON_ILUK, ESP_PRECON_ILUT, ESP_PRECON_JACOBI, ESP_PRECON_LU, ESP_PRECON_SPAI, ESP_CHOL_STATS, ESP_PRECON_CHOLESKY
-from .matrix import ExtendableSparseMatrix, _vp
-
-
-def _is_cuda(x):
-    return hasattr(x, "is_cuda") and x.is_cuda
+from .matrix import ExtendableSparseMatrix, _is_cuda, _many_ptr, _many_result, _vp, many_layout
 
 
 def _check_cuda(t, n):
@@ -129,10 +125,21 @@ class _PointPreconditioner:
         return self
 
     def ldiv(self, v, out=None):
-        """ldiv!(out, p, v); out may be v.  NumPy arrays or CUDA torch tensors (float64, contiguous, n elements)."""
+        """ldiv!(out, p, v); out may be v.  NumPy arrays or CUDA torch tensors (float64, contiguous, n elements).
+        A 2-D (n, k) v solves k right-hand sides in one call (esp_precon_ldiv_many: every column is ldiv's bits): a NumPy array of
+        any order, brought to column-major once, gives an F-ordered (n, k) array; a tensor needs stride(0) == 1 and
+        stride(1) >= n and is used in place.  out=v is the in-place solve."""
         p = self._live()
         A = self.A
         A._push_edits()   # (a device consumer: host edits of a handed-out copy go up first, as for mul)
+        if getattr(v, "ndim", 1) != 1:
+            V, ldv, k = many_layout(A.n, v)
+            U, ldu = _many_result(A.n, k, V, out, "out")
+            if _is_cuda(V):
+                import torch
+                torch.cuda.current_stream(V.device).synchronize()   # the library runs on its own stream
+            self._ck(A._d.lib.esp_precon_ldiv_many(p, _many_ptr(V), ldv, _many_ptr(U), ldu, k, 1 if _is_cuda(V) else 0))
+            return U
         pv, pu, _, dev, u = _handover(A.n, v, out, "out", zeros=False)
         self._ck(A._d.lib.esp_precon_ldiv(p, pv, pu, dev))
         return u

@@ -1320,6 +1320,33 @@ int32_t esp_debug_last_partition(const esp_handle *h, int32_t *kind);
  *     updates or fewer, a non-empty buffer, a cell that names a node twice) */
 int32_t esp_debug_last_append_route(const esp_handle *h, int32_t *route);
 
+/* SEVERAL RIGHT-HAND SIDES: mul!(R, ext, X) and ldiv!(U, fact, V) with matrices (the reference forwards both to SparseArrays
+ * and to the factorization, which take them).  esp_mul_many: R[:, r] = A * X[:, r], r = 0 .. k-1; X is n x k column-major with
+ * leading dimension ldx, R is m x k with ldr.  esp_precon_ldiv_many: U[:, r] = ldiv!(p, V[:, r]); n x k column-major, leading
+ * dimensions ldv and ldu.  on_device != 0: device pointers (the hand-over rules of esp_mul), else host arrays.
+ * CONTRACT: column r of the result is bit for bit what esp_mul / esp_precon_ldiv gives for column r alone -- for every kind of
+ *   esp_precon and every stored value (+-0.0, NaN, Inf).  A NaN or Inf of one column never reaches another column.  Rows
+ *   n .. ld-1 between the columns of X and V are never read, those of R and U never written.
+ * ALIASING: U == V with ldu == ldv is the in-place solve.  Any other overlap of the two ranges ([V, V + (k-1)*ldv + n) and U's),
+ *   and any overlap of X and R, is refused with ESP_ERR_INVALID before anything is launched.
+ * ARGUMENTS: k == 0 returns ESP_OK after the state checks.  ESP_ERR_INVALID: k < 0; a leading dimension below max(n, 1) (max(m, 1)
+ *   for ldr); a NULL array that would hold an element.  Every state check and message of the single-vector call applies unchanged:
+ *   pending entries, a pattern changed since the last update!, a failed last update! (ESP_ERR_STATE).
+ * HOW: k == 1 IS the single-vector call: the same launches of the same kernels.  Otherwise the columns go in chunks of
+ *   ESP_MANY_CHUNK, a narrower last chunk masked; everything is enqueued on the handle's stream, which is synchronised ONCE at the
+ *   end.  The library's scratch grows with ESP_MANY_CHUNK, never with k: host arrays are staged ESP_MANY_CHUNK columns at a time.
+ *   - esp_mul_many: one launch per chunk over the row-wise index of esp_mul; a lane owns a row and ESP_MANY_CHUNK accumulators,
+ *     reads every stored value and column once and runs esp_mul's statement acc_r = acc_r + a_ij * x_r[j] per column, j ascending.
+ *   - CholeskyFactorization and LUFactorization's panel form: per chunk a gather into work vectors stored right-hand-side-fastest
+ *     (y[pos * ESP_MANY_CHUNK + r]), ONE launch per depth of the tree per direction, a scatter; a lane owns one (row of the node,
+ *     right-hand side) pair and walks exactly the single call's chain for it, so one read of a panel entry serves the whole chunk.
+ *     No allocation, copy or synchronisation in between; esp_precon_cholesky_stats / esp_precon_lu_panel_stats do not change.
+ *   - every other kind (Jacobi, ILU0, ILUAM, Block, ILU(k), ILUT, Colored, SPAI, AMG, RS-AMG, LU's column form): the single call's
+ *     launches column after column inside the one call. */
+#define ESP_MANY_CHUNK 8
+int32_t esp_mul_many(esp_handle *h, const double *X, int64_t ldx, double *R, int64_t ldr, int64_t k, int32_t on_device);
+int32_t esp_precon_ldiv_many(esp_precon *p, const double *V, int64_t ldv, double *U, int64_t ldu, int64_t k, int32_t on_device);
+
 #ifdef __cplusplus
 }
 #endif

@@ -113,6 +113,13 @@ LUFactorization, the yardstick, in the same process and the same alternating rou
 the create, a values-only update! and ldiv! on device vectors; every round's value, medians, spreads (max - min), the ratios, the launch
 counts, nnz(L), the panel bytes, the residual for b = ones, and cg with ILU0 to 1e-8 from the same run.
     python tools/precon_bench.py --kind cholesky [--n 24] [--lu-rounds 5] [--iters 5] [--rounds 5]
+--nrhs K[,K...] with --kind cholesky, --kind lu --form columns|panels or --kind mul times several right-hand sides in one call
+(esp_precon_ldiv_many / esp_mul_many) against K single-vector calls of the same build in the same process, on device
+arrays: alternating rounds of --iters repetitions each; every round's value, medians, spreads (max - min), the time per column and
+the ratio K singles / one call.  It first asserts that the columns of the two agree bit for bit.
+    python tools/precon_bench.py --kind cholesky --nrhs 1,8,32 [--n 32] [--iters 3] [--rounds 5]
+    python tools/precon_bench.py --kind lu --form panels --nrhs 1,8,32 [--n 32]
+    python tools/precon_bench.py --kind mul --nrhs 1,8,32 [--n 128] [--iters 10]
 """
 import argparse
 import ctypes as C
@@ -1354,12 +1361,68 @@ def bench_spai(a, torch, esp):
     print(json.dumps(rnd(out)))
 
 
+def bench_many(a, torch, esp):
+    """--nrhs K[,K...] with --kind cholesky | lu [--form columns|panels] | mul: several right-hand sides in one call
+    (esp_precon_ldiv_many / esp_mul_many) against K single-vector calls of the same build in the same process, on fdrand n^3 and device
+    arrays.  --rounds alternating rounds; a round times --iters repetitions of the one call, then of the K calls, and reports the mean
+    of each.  Per K: every round's value, the medians, the spread (max - min), the time per column and the ratio K singles / one call."""
+    import numpy as np
+    A = esp.fdrand(a.n, a.n, a.n)
+    d = A._d
+    d.ck(d.lib.esp_set_stream(d.h, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    N = A.n
+    ks = [int(x) for x in str(a.nrhs).split(",")]
+    out = {"workload": "many_rhs_fdrand", "kind": a.kind, "form": a.form if a.kind == "lu" else None, "n": a.n, "N": N, "nnz": A.nnz(),
+           "leaf_size": a.leaf_size, "rounds": a.rounds, "iters": a.iters, "nrhs": {}}
+    if a.kind == "mul":
+        P, rows = None, A.m
+        one, many = (lambda x, r: A.mul(x, r)), (lambda X, R: A.mul(X, R))
+    else:
+        t0 = time.perf_counter()
+        P = esp.CholeskyFactorization(A, a.leaf_size) if a.kind == "cholesky" else esp.LUFactorization(A, a.leaf_size, form=a.form)
+        out["create_ms"] = (time.perf_counter() - t0) * 1e3
+        out["stats"] = P.stats()
+        rows = N
+        one, many = (lambda x, r: P.ldiv(x, r)), (lambda X, R: P.ldiv(X, R))
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.iters):
+            fn()                                   # (every call returns synchronised)
+        return (time.perf_counter() - t0) * 1e3 / a.iters
+
+    for k in ks:
+        X = torch.randn((k, N), dtype=torch.float64, device="cuda").t()
+        R = torch.empty((k, rows), dtype=torch.float64, device="cuda").t()
+        cols = [(X[:, r], torch.empty(rows, dtype=torch.float64, device="cuda")) for r in range(k)]
+        singles = lambda: [one(x, r) for x, r in cols]
+        for _ in range(max(a.warmup, 1)):
+            many(X, R), singles()
+        assert all(bool((R[:, r].view(torch.int64) == cols[r][1].view(torch.int64)).all()) for r in range(k)), "the columns differ"
+        rec = {"many_ms": [], "singles_ms": []}
+        for _ in range(a.rounds):
+            rec["many_ms"].append(wall(lambda: many(X, R)))
+            rec["singles_ms"].append(wall(singles))
+        res = {}
+        for name, v in rec.items():
+            res[name] = {"rounds": [round(x, 4) for x in v], "median": round(float(np.median(v)), 4), "spread": round(max(v) - min(v), 4)}
+        res["many_ms_per_column"] = round(res["many_ms"]["median"] / k, 4)
+        res["singles_ms_per_column"] = round(res["singles_ms"]["median"] / k, 4)
+        res["ratio_singles_over_many"] = round(res["singles_ms"]["median"] / res["many_ms"]["median"], 3)
+        out["nrhs"][str(k)] = res
+    if P is not None:
+        P.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "gmres", "gmres-trace", "block", "block-trace", "block-trace-diff", "amg", "iluk", "colored", "spai0", "spai1", "spai1sym", "ilut", "lu", "cholesky"], default="point")
+    ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "gmres", "gmres-trace", "block", "block-trace", "block-trace-diff", "amg", "iluk", "colored", "spai0", "spai1", "spai1sym", "ilut", "lu", "cholesky", "mul"], default="point")
+    ap.add_argument("--nrhs", default="", help="--kind cholesky | lu | mul: K or K,K,...: K right-hand sides in one call against K single calls")
     ap.add_argument("--leaf-size", type=int, default=32)
     ap.add_argument("--form", choices=["columns", "panels", "both"], default="columns",
                     help="--kind lu: columns: the column form's breakdown; panels / both: the forms side by side in alternating rounds")
@@ -1389,6 +1452,10 @@ def main():
     torch.cuda.init()
     from esparse_loader import load
     esp = load()
+    if a.nrhs or a.kind == "mul":
+        if a.kind not in ("cholesky", "lu", "mul") or not a.nrhs or (a.kind == "lu" and a.form == "both"):
+            ap.error("--nrhs K goes with --kind cholesky, --kind lu --form columns|panels or --kind mul")
+        return bench_many(a, torch, esp)
     if a.kind == "iluam":
         return bench_iluam(a, torch, esp)
     if a.kind == "cg":
