@@ -32,6 +32,8 @@
 //                  calls on internal handles, the fused V-cycle kernels); amg.hpp holds what it shares with rsamg.hip
 //   rsamg.hip      RS_AMGPreconditioner's coarsening: row-wise strength, the PMIS splitting, direct interpolation (the rest is amg.hip's)
 //   krylov.hip     preconditioned conjugate gradients (esp_cg): fused vector kernels, ordered dot products, scalars on the device
+//   krylov_many.hip  conjugate gradients for several right-hand sides (esp_cg_many): k independent recurrences in lockstep, 8
+//                  columns a launch behind a live mask; the many-column forms of Jacobi's and ILU0's ldiv!
 //   bicgstabl.hip  BiCGStab(l) for non-symmetric systems (esp_bicgstabl): the same design with l+1 residuals and search vectors;
 //                  krylov.hpp holds what the solvers share: the summation shape's kernels, the preconditioned product
 //                  (PreconProduct) and the hand-over of host b / x
@@ -405,6 +407,8 @@ struct esp_handle {
     // esp_gmres (gmres.hip) uses the same buffers: bv holds its restart+1 basis vectors, sc its H, nullvec, rhs, h, c and scalars.
     // krylov.hpp holds what the three share on the host side too: stage_vectors / return_x fill hb and hx and copy x back, and
     // PreconProduct issues every A*v, Pl \ v and Pl \ (A*v) of a solve (t is its scratch between the two).
+    // esp_cg_many (krylov_many.hip) holds ESP_MANY_CHUNK columns in each of r, u, c, hb and hx (leading dimension n rounded up to
+    // even) and the chunk's partial sums side by side in part; t is ILU0's pass-1 scratch there.
     struct Krylov {
         DevBuf r, u, c, part, hb, hx, bv, t, sc;
     } kry;
@@ -725,6 +729,9 @@ void iluam_release(esp_precon *p);
 // ldiv! into the scratch p->u1 (pass 2 is krylov.hpp's own, in PreconProduct::ldiv: it carries the dot product)
 int32_t solver_ready(esp_handle *h, esp_precon *p, const char *what);
 void ilu0_lower_launch(esp_precon *p, const double *v);
+// krylov_many.hip, for esp_precon_ldiv_many: ldiv! of Jacobi (SPAI-0) and ILU0 for k columns on device arrays (v: n x k column-major
+// with leading dimension ldv, u with ldu; u may be v where ldu == ldv), ESP_MANY_CHUNK columns a launch; launches only
+int32_t precon_ldiv_many_launch(esp_precon *p, const double *v, i64 ldv, double *u, i64 ldu, i64 k);
 // precon.hip, for block.hip: the checks of every preconditioner call on the handle; ldiv! on device vectors (u may be v)
 int32_t precon_check_handle(esp_handle *h, const char *what);
 int32_t precon_ldiv_launch(esp_precon *p, const double *v, double *u);

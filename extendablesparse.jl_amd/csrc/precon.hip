@@ -419,8 +419,9 @@ extern "C" int32_t esp_precon_ldiv(esp_precon *p, const double *v, double *u, in
     return ESP_OK;
 }
 
-// ldiv! of k columns (include/esparse_hip.h, SEVERAL RIGHT-HAND SIDES).  The two panel kinds run their chunked solves; every other
-// kind runs ldiv_launch column by column.  Host arrays pass through p->hv, ESP_MANY_CHUNK columns at a time
+// ldiv! of k columns (include/esparse_hip.h, SEVERAL RIGHT-HAND SIDES).  The two panel kinds run their chunked solves, Jacobi
+// (SPAI-0) and ILU0 the many-column kernels of krylov_many.hip; every other kind runs ldiv_launch column by column.  Host arrays
+// pass through p->hv, ESP_MANY_CHUNK columns at a time
 extern "C" int32_t esp_precon_ldiv_many(esp_precon *p, const double *V, int64_t ldv, double *U, int64_t ldu, int64_t k, int32_t on_device) {
     if (!p) return ESP_ERR_INVALID;
     esp_handle *h = p->h;
@@ -435,6 +436,7 @@ extern "C" int32_t esp_precon_ldiv_many(esp_precon *p, const double *V, int64_t 
     if (k == 1 && n > 0) return esp_precon_ldiv(p, V, U, on_device);  // the single-vector path itself
     CK(precon_ready(p, "esp_precon_ldiv"));
     const bool chol = p->kind == ESP_PRECON_CHOLESKY, lup = block_built(p) && p->lup;
+    const bool fused = !block_built(p) && (diag_applied(p) || p->kind == ESP_PRECON_ILU0);
     if (k == 0 || n == 0) return ESP_OK;
     if (!on_device) CK(ensure(h, p->hv, sizeof(double) * (size_t)n * ESP_MANY_CHUNK));
     const i64 step = on_device ? k : ESP_MANY_CHUNK;  // (device arrays: one pass; the panel kinds chunk them themselves)
@@ -451,6 +453,7 @@ extern "C" int32_t esp_precon_ldiv_many(esp_precon *p, const double *V, int64_t 
         }
         if (chol) CK(chol_solve_many(p, dv, dldv, du, dldu, nr));
         else if (lup) CK(lup_solve_many(p, dv, dldv, du, dldu, nr));
+        else if (fused) CK(precon_ldiv_many_launch(p, dv, dldv, du, dldu, nr));
         else
             for (i64 r = 0; r < nr; r++) CK(ldiv_launch(p, dv + r * dldv, du + r * dldu));
         HIPCK(h, hipGetLastError());

@@ -887,7 +887,11 @@ def cg(A, b, Pl=None, x=None, abstol=0.0, reltol=math.sqrt(np.finfo(np.float64).
     """cg / cg!(x, A, b; Pl, abstol, reltol, maxiter, log) of IterativeSolvers.jl (include/esparse_hip.h, esp_cg): preconditioned
     conjugate gradients until norm(r) <= max(reltol*norm(r0), abstol) or maxiter (None: n) iterations.  x = None starts from zeros
     (cg); a given x is updated in place (cg!).  Pl: a preconditioner of A, or None (Identity).
-    log=True returns (x, {"resnorm": the norm after every iteration, "r0": the initial one, "iters": k, "isconverged": bool})."""
+    log=True returns (x, {"resnorm": the norm after every iteration, "r0": the initial one, "iters": k, "isconverged": bool}).
+    A 2-D (n, k) b solves k right-hand sides in one call (esp_cg_many: k independent recurrences in lockstep, every column the
+    single call's bits).  The layout rules are many_layout's; the result is an F-ordered (n, k) array, or a tensor with
+    stride(0) == 1, living where b lives.  A given x is an (n, k) array of that layout living where b lives, updated in place.
+    log=True then returns (X, logs): a list of k dicts with the single call's keys and values."""
     _check_solver("cg", A, Pl)
     p = Pl._live() if Pl is not None else None
     A.flush()
@@ -896,6 +900,8 @@ def cg(A, b, Pl=None, x=None, abstol=0.0, reltol=math.sqrt(np.finfo(np.float64).
     maxiter = n if maxiter is None else int(maxiter)
     if maxiter < 0:
         raise ValueError("maxiter < 0")
+    if getattr(b, "ndim", 1) != 1:
+        return _cg_many(d, p, n, b, x, float(abstol), float(reltol), maxiter, log)
     hist = np.empty(maxiter + 1, np.float64)
     its = C.c_int64()
     conv = C.c_int32()
@@ -906,6 +912,31 @@ def cg(A, b, Pl=None, x=None, abstol=0.0, reltol=math.sqrt(np.finfo(np.float64).
         k = its.value
         return x, {"resnorm": hist[1:k + 1].copy(), "r0": float(hist[0]), "iters": k, "isconverged": bool(conv.value)}
     return x
+
+
+def _cg_many(d, p, n, b, x, abstol, reltol, maxiter, log):
+    """cg with a 2-D b: the hand-over of the (n, k) arrays, esp_cg_many, the k logs"""
+    B, ldb, k = many_layout(n, b)
+    zero = 1 if x is None else 0
+    if x is None:
+        if _is_cuda(B):
+            import torch
+            x = torch.zeros((k, n), dtype=torch.float64, device=B.device).t()
+        else:
+            x = np.zeros((n, k), np.float64, order="F")
+    X, ldx = _many_result(n, k, B, x, "x")
+    if _is_cuda(B):
+        import torch
+        torch.cuda.current_stream(B.device).synchronize()   # the library runs on its own stream
+    hist = np.empty((maxiter + 1, k), np.float64, order="F")
+    its = np.zeros(k, np.int64)
+    conv = np.zeros(k, np.int32)
+    d.ck(d.lib.esp_cg_many(d.h, p, _many_ptr(B), ldb, _many_ptr(X), ldx, k, 1 if _is_cuda(B) else 0, zero, maxiter, abstol, reltol,
+                           _vp(hist), _vp(its), _vp(conv)))
+    if log:
+        return X, [{"resnorm": hist[1:int(its[r]) + 1, r].copy(), "r0": float(hist[0, r]), "iters": int(its[r]),
+                    "isconverged": bool(conv[r])} for r in range(k)]
+    return X
 
 
 def bicgstabl(A, b, l=2, Pl=None, x=None, abstol=0.0, reltol=math.sqrt(np.finfo(np.float64).eps), max_mv_products=None,

@@ -1341,11 +1341,34 @@ int32_t esp_debug_last_append_route(const esp_handle *h, int32_t *route);
  *     (y[pos * ESP_MANY_CHUNK + r]), ONE launch per depth of the tree per direction, a scatter; a lane owns one (row of the node,
  *     right-hand side) pair and walks exactly the single call's chain for it, so one read of a panel entry serves the whole chunk.
  *     No allocation, copy or synchronisation in between; esp_precon_cholesky_stats / esp_precon_lu_panel_stats do not change.
- *   - every other kind (Jacobi, ILU0, ILUAM, Block, ILU(k), ILUT, Colored, SPAI, AMG, RS-AMG, LU's column form): the single call's
- *     launches column after column inside the one call. */
+ *   - Jacobi (SPAI-0) and ILU0: the many-column kernels of esp_cg_many, one or two launches per chunk.
+ *   - every other kind (ILUAM, Block, ILU(k), ILUT, Colored, SPAI-1, AMG, RS-AMG, LU's column form): the single call's launches
+ *     column after column inside the one call. */
 #define ESP_MANY_CHUNK 8
 int32_t esp_mul_many(esp_handle *h, const double *X, int64_t ldx, double *R, int64_t ldr, int64_t k, int32_t on_device);
 int32_t esp_precon_ldiv_many(esp_precon *p, const double *V, int64_t ldv, double *U, int64_t ldu, int64_t k, int32_t on_device);
+/* CONJUGATE GRADIENTS FOR SEVERAL RIGHT-HAND SIDES: esp_cg for the k columns of B (n x k column-major, leading dimension ldb) into
+ * the k columns of X (ldx), as k INDEPENDENT recurrences run in lockstep, ESP_MANY_CHUNK columns at a time.  This is not block CG.
+ * CONTRACT: for every column r, X[:, r], the whole residual history of r, iterations[r] and converged[r] are bit for bit what
+ *   esp_cg gives for B[:, r] alone with the same arguments, whatever the other columns hold and whenever they stop.  Every column
+ *   has its own rho, beta, alpha, residual, tolerance and stopping test; the summation shape of every dot product, the true
+ *   divisions and the absence of contraction are esp_cg's, per column.
+ * ARGUMENTS: history is (maxiter+1) x k column-major host doubles or NULL (column r holds iterations[r]+1 norms); iterations and
+ *   converged hold k entries or are NULL.  ESP_ERR_INVALID: k < 0, a leading dimension below max(n, 1), any overlap of the ranges
+ *   of B and X, a NULL array that would hold an element, maxiter < 0, p bound to another handle.  Every state check of esp_cg
+ *   applies unchanged.  k == 1 IS esp_cg.  k == 0 returns after the state checks; for n == 0 every column has 0 iterations, is
+ *   converged and has residual 0.  Rows n .. ld-1 between the columns are never read or written; B is never written.
+ * HOW: all columns of a chunk share the iteration counter.  After each iteration ONE copy of 8 bytes per column brings the chunk's
+ *   residual sums of squares to the host, which takes the square roots and runs every column's stop test.  A column that has
+ *   stopped is frozen: the live columns go to every kernel of the next iteration as a bit mask in an argument, a frozen column's
+ *   x, r and history are never written again, and the chunk ends when no column is live or at maxiter (a NaN residual keeps its
+ *   column live to maxiter, as in esp_cg).  A's index and values are read once per chunk and product, and the launches of an
+ *   iteration do not depend on the number of columns for Identity, Jacobi and ILU0 (many-column kernels, csrc/krylov_many.hip);
+ *   CholeskyFactorization and LUFactorization's panel form run their chunked solves, every other kind its single ldiv! per live
+ *   column.  Host arrays are staged a chunk at a time; the work vectors (4 x ESP_MANY_CHUNK x n doubles) belong to the handle. */
+int32_t esp_cg_many(esp_handle *h, esp_precon *p, const double *B, int64_t ldb, double *X, int64_t ldx, int64_t k, int32_t on_device,
+                    int32_t initially_zero, int64_t maxiter, double abstol, double reltol, double *history, int64_t *iterations,
+                    int32_t *converged);
 
 #ifdef __cplusplus
 }

@@ -120,6 +120,12 @@ the ratio K singles / one call.  It first asserts that the columns of the two ag
     python tools/precon_bench.py --kind cholesky --nrhs 1,8,32 [--n 32] [--iters 3] [--rounds 5]
     python tools/precon_bench.py --kind lu --form panels --nrhs 1,8,32 [--n 32]
     python tools/precon_bench.py --kind mul --nrhs 1,8,32 [--n 128] [--iters 10]
+--nrhs K[,K...] with --kind cg [--cg-only identity|jacobi|ilu0|iluam] times cg(A, B) with K columns in one call (esp_cg_many, DESIGN.md
+5u) against K single cg calls of the same build in the same process, on fdrand(n,n,n) and device arrays, random right-hand sides, the
+default tolerance and at most --iters iterations a solve: one solve of each per alternating round; every round's value, medians,
+spreads (max - min), the time per column, the ratio K singles / one call and the iteration counts.  It first asserts that x, the
+history, the iteration count and the flag of every column agree bit for bit.
+    python tools/precon_bench.py --kind cg --cg-only ilu0 --nrhs 1,8,32 [--n 128] [--iters 50] [--rounds 5]
 """
 import argparse
 import ctypes as C
@@ -1416,13 +1422,77 @@ def bench_many(a, torch, esp):
     print(json.dumps(out))
 
 
+def bench_cg_many(a, torch, esp):
+    """--nrhs K[,K...] with --kind cg: cg(A, B) with K columns in one call (esp_cg_many) against K single cg calls of the same build in
+    the same process, in the shape of bench_many: --rounds alternating rounds of one solve each (default tolerance, at most --iters
+    iterations), after an assertion that the columns of the two agree bit for bit"""
+    import numpy as np
+    A = esp.fdrand(a.n, a.n, a.n)
+    d = A._d
+    d.ck(d.lib.esp_set_stream(d.h, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    N = A.n
+    name = a.cg_only or "ilu0"
+    P = {"identity": lambda A: None, "jacobi": esp.JacobiPreconditioner, "ilu0": esp.ILU0Preconditioner,
+         "iluam": esp.ILUAMPreconditioner}[name](A)
+    ks = [int(x) for x in str(a.nrhs).split(",")]
+    out = {"workload": "cg_many_fdrand", "kind": name, "n": a.n, "N": N, "nnz": A.nnz(), "rounds": a.rounds, "maxiter": a.iters, "nrhs": {}}
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()                                       # (every call returns synchronised)
+        return (time.perf_counter() - t0) * 1e3
+
+    torch.manual_seed(1)
+    for k in ks:
+        B = torch.randn((k, N), dtype=torch.float64, device="cuda").t()
+        X = torch.empty((k, N), dtype=torch.float64, device="cuda").t()
+        xs = [torch.empty(N, dtype=torch.float64, device="cuda") for _ in range(k)]
+        bs = [B[:, r].contiguous() for r in range(k)]
+
+        def many(log=False):
+            X.zero_()
+            return esp.cg(A, B, Pl=P, x=X, maxiter=a.iters, log=log)
+
+        def singles(log=False):
+            for x in xs:
+                x.zero_()
+            return [esp.cg(A, b, Pl=P, x=x, maxiter=a.iters, log=log) for b, x in zip(bs, xs)]
+
+        for _ in range(max(min(a.warmup, 2), 1)):
+            many(), singles()
+        got = many(log=True)
+        want = singles(log=True)
+        logs = got[1]                              # (a 2-D B of one column takes the many-column entry as well: a list of one dict)
+        for r in range(k):
+            col = X[:, r]
+            assert bool((col.contiguous().view(torch.int64) == want[r][0].view(torch.int64)).all()), "x differs in column %d" % r
+            assert logs[r]["iters"] == want[r][1]["iters"] and logs[r]["isconverged"] == want[r][1]["isconverged"], "column %d" % r
+            assert np.array_equal(np.concatenate([[logs[r]["r0"]], logs[r]["resnorm"]]).view(np.uint64),
+                                  np.concatenate([[want[r][1]["r0"]], want[r][1]["resnorm"]]).view(np.uint64)), "history of column %d" % r
+        rec = {"many_ms": [], "singles_ms": []}
+        for _ in range(a.rounds):
+            rec["many_ms"].append(wall(many))
+            rec["singles_ms"].append(wall(singles))
+        res = {"iterations": [int(l["iters"]) for l in logs]}
+        for what, v in rec.items():
+            res[what] = {"rounds": [round(x, 3) for x in v], "median": round(float(np.median(v)), 3), "spread": round(max(v) - min(v), 3)}
+        res["many_ms_per_column"] = round(res["many_ms"]["median"] / k, 3)
+        res["singles_ms_per_column"] = round(res["singles_ms"]["median"] / k, 3)
+        res["ratio_singles_over_many"] = round(res["singles_ms"]["median"] / res["many_ms"]["median"], 3)
+        out["nrhs"][str(k)] = res
+    if P is not None:
+        P.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=256)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--kind", choices=["point", "iluam", "cg", "bicgstabl", "gmres", "gmres-trace", "block", "block-trace", "block-trace-diff", "amg", "iluk", "colored", "spai0", "spai1", "spai1sym", "ilut", "lu", "cholesky", "mul"], default="point")
-    ap.add_argument("--nrhs", default="", help="--kind cholesky | lu | mul: K or K,K,...: K right-hand sides in one call against K single calls")
+    ap.add_argument("--nrhs", default="", help="--kind cholesky | lu | mul | cg: K or K,K,...: K right-hand sides in one call against K single calls")
     ap.add_argument("--leaf-size", type=int, default=32)
     ap.add_argument("--form", choices=["columns", "panels", "both"], default="columns",
                     help="--kind lu: columns: the column form's breakdown; panels / both: the forms side by side in alternating rounds")
@@ -1452,9 +1522,11 @@ def main():
     torch.cuda.init()
     from esparse_loader import load
     esp = load()
+    if a.nrhs and a.kind == "cg":
+        return bench_cg_many(a, torch, esp)
     if a.nrhs or a.kind == "mul":
         if a.kind not in ("cholesky", "lu", "mul") or not a.nrhs or (a.kind == "lu" and a.form == "both"):
-            ap.error("--nrhs K goes with --kind cholesky, --kind lu --form columns|panels or --kind mul")
+            ap.error("--nrhs K goes with --kind cholesky, --kind lu --form columns|panels, --kind mul or --kind cg")
         return bench_many(a, torch, esp)
     if a.kind == "iluam":
         return bench_iluam(a, torch, esp)
