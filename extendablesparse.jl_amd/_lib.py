@@ -26,7 +26,7 @@ ESP_PRECON_ILUT = 8
 ESP_PRECON_LU = 9
 ESP_PRECON_CHOLESKY = 10
 ESP_CHOL_STATS = 12
-ESP_MANY_CHUNK = 8  # columns of a chunk of esp_mul_many / esp_precon_ldiv_many / esp_cg_many
+ESP_MANY_CHUNK = 8  # columns of a chunk of esp_mul_many / esp_precon_ldiv_many / esp_cg_many / esp_gmres_many
 ESP_ILUT_WAVE_UPPER, ESP_ILUT_GROUP_UPPER, ESP_ILUT_STEPS_MAX, ESP_ILUT_STATS = 256, 4096, 16, 40
 ESP_ILUK_WAVE_VISITS, ESP_ILUK_VISIT_MAX = 512, 8192
 ESP_SPAI_WAVE_DOUBLES, ESP_SPAI_DENSE_MAX = 512, 12288
@@ -176,6 +176,7 @@ SIGNATURES = {
     "esp_cg_many": (i32, [vp, vp, vp, i64, vp, i64, i64, i32, i32, i64, f64, f64, vp, vp, vp]),
     "esp_bicgstabl": (i32, [vp, vp, i32, vp, vp, vp, i32, i32, i64, f64, f64, vp, P(i64), P(i64), P(i32)]),
     "esp_gmres": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i64, f64, f64, vp, P(i64), P(i64), P(i64), P(i32)]),
+    "esp_gmres_many": (i32, [vp, vp, vp, i64, vp, i64, i64, i32, i32, i32, i32, i64, f64, f64, vp, vp, vp, vp, vp]),
     "esp_matmul": (i32, [vp, vp, vp, P(i64)]),
     "esp_add": (i32, [vp, vp, i32, vp, P(i64)]),
     "esp_diag_scale": (i32, [vp, vp, i32, i32, vp]),

@@ -257,14 +257,16 @@ extern "C" int32_t esp_create(int64_t m, int64_t n, int32_t device, int64_t capa
     }
     h->own_stream = true;
     if (hipDeviceGetAttribute(&h->compute_units, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) h->compute_units = 0;
-    // (8 slots for the small copies, then the 8 of pin_words: the default flags give mapped, coherent host memory)
-    if (hipHostMalloc((void **)&h->pin_scalar, 128, hipHostMallocDefault) != hipSuccess) {
+    // (8 slots for the small copies, then the 8 of pin_words, then the 16 of pin_many: the default flags give mapped, coherent host
+    // memory)
+    if (hipHostMalloc((void **)&h->pin_scalar, 256, hipHostMallocDefault) != hipSuccess) {
         (void)hipStreamDestroy(h->stream);
         delete h;
         FAIL((esp_handle *)nullptr, ESP_ERR_NOMEM, "esp_create: pinned scalar allocation failed");
     }
-    memset(h->pin_scalar, 0, 128);
+    memset(h->pin_scalar, 0, 256);
     h->pin_words = h->pin_scalar + 8;
+    h->pin_many = (double *)(h->pin_scalar + 16);
     if (hipHostGetDevicePointer((void **)&h->pin_words_dev, h->pin_words, 0) != hipSuccess || !h->pin_words_dev) {
         (void)hipHostFree(h->pin_scalar);
         (void)hipStreamDestroy(h->stream);

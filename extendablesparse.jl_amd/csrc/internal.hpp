@@ -38,7 +38,10 @@
 //                  krylov.hpp holds what the solvers share: the summation shape's kernels, the preconditioned product
 //                  (PreconProduct) and the hand-over of host b / x
 //   gmres.hip      restarted GMRES (esp_gmres): fused modified Gram-Schmidt steps, batched classical / DGKS passes behind a device
-//                  predicate, H, the residual recurrence, the rotations and y in a scalar block on the device
+//                  predicate, H, the residual recurrence, the rotations and y in a scalar block on the device; gmres.hpp holds the
+//                  bodies of its kernels
+//   gmres_many.hip   restarted GMRES for several right-hand sides (esp_gmres_many): gmres.hpp's bodies per column, the columns on
+//                  gridDim.y behind a live mask; krylov_many.hpp holds what it shares with krylov_many.hip
 //   matops.hip     the algebra of assembled matrices on the device: A*B (esp_matmul), A+B / A-B (esp_add), Diagonal scaling
 //   linalg.hip     transpose (esp_transpose), transpose(A)*x (esp_mul_transpose), issymmetric, opnorm, norm on the device CSC
 //   local_*.hip    the instantiations of the bucket kernel (local.hpp; local_h.hip: group3.hpp, the group tier with three workgroups per CU;
@@ -351,6 +354,9 @@ struct esp_handle {
     // address the device uses for them
     unsigned long long *pin_words = nullptr;
     unsigned long long *pin_words_dev = nullptr;
+    // ... and behind those, 16 doubles of their own: the target of esp_gmres_many's read-back of a chunk (current and the pass count of
+    // up to ESP_MANY_CHUNK columns), which would not fit the 8 slots of pin_scalar
+    double *pin_many = nullptr;
     u64 *pin_mw = nullptr;  // pinned source of prepart_begin's asynchronous upload of the window bases (<= MW_MAX)
     hipEvent_t pin_mw_done = nullptr;
     // kind bookkeeping of the pending batch: when every pending entry was appended with ONE known kind the run-based
@@ -409,6 +415,8 @@ struct esp_handle {
     // PreconProduct issues every A*v, Pl \ v and Pl \ (A*v) of a solve (t is its scratch between the two).
     // esp_cg_many (krylov_many.hip) holds ESP_MANY_CHUNK columns in each of r, u, c, hb and hx (leading dimension n rounded up to
     // even) and the chunk's partial sums side by side in part; t is ILU0's pass-1 scratch there.
+    // esp_gmres_many (gmres_many.hip): bv holds (restart+1) x ESP_MANY_CHUNK basis vectors, t one or two n x ESP_MANY_CHUNK blocks of
+    // product scratch, sc ESP_MANY_CHUNK scalar blocks, part the chunk's partial sums and what the host reads back.
     struct Krylov {
         DevBuf r, u, c, part, hb, hx, bv, t, sc;
     } kry;

@@ -983,7 +983,11 @@ def gmres(A, b, Pl=None, x=None, restart=None, maxiter=None, abstol=0.0, reltol=
     (classical with up to three correction passes).  x = None starts from zeros; a given x is updated in place.  Pl: a
     preconditioner of A, or None (Identity).
     log=True returns (x, {"resnorm": the norm after every iteration, "r0": the initial one, "iters": iterations, "mvps":
-    matrix-vector products, "reorth": DGKS correction passes, "isconverged": bool})."""
+    matrix-vector products, "reorth": DGKS correction passes, "isconverged": bool}).
+    A 2-D (n, k) b solves k right-hand sides in one call (esp_gmres_many: k independent recurrences in lockstep, every column the
+    single call's bits; not block GMRES).  The layout rules are many_layout's; the result is an F-ordered (n, k) array, or a tensor
+    with stride(0) == 1, living where b lives.  A given x is an (n, k) array of that layout living where b lives, updated in place.
+    log=True then returns (X, logs): a list of k dicts with the single call's keys and values."""
     _check_solver("gmres", A, Pl)
     if orth_meth not in _ORTH:
         raise ValueError("gmres: orth_meth = %r (one of 'mgs', 'cgs', 'dgks')" % (orth_meth,))
@@ -995,6 +999,8 @@ def gmres(A, b, Pl=None, x=None, restart=None, maxiter=None, abstol=0.0, reltol=
     maxiter = n if maxiter is None else int(maxiter)
     if maxiter < 0:
         raise ValueError("maxiter < 0")
+    if getattr(b, "ndim", 1) != 1:
+        return _gmres_many(d, p, n, b, x, restart, _ORTH[orth_meth], maxiter, float(abstol), float(reltol), log)
     hist = np.empty(maxiter + 1, np.float64)
     its, mvs, reorth = C.c_int64(), C.c_int64(), C.c_int64()
     conv = C.c_int32()
@@ -1007,3 +1013,28 @@ def gmres(A, b, Pl=None, x=None, restart=None, maxiter=None, abstol=0.0, reltol=
         return x, {"resnorm": hist[1:k + 1].copy(), "r0": float(hist[0]), "iters": k, "mvps": mvs.value, "reorth": reorth.value,
                    "isconverged": bool(conv.value)}
     return x
+
+
+def _gmres_many(d, p, n, b, x, restart, orth, maxiter, abstol, reltol, log):
+    """gmres with a 2-D b: the hand-over of the (n, k) arrays, esp_gmres_many, the k logs"""
+    B, ldb, k = many_layout(n, b)
+    zero = 1 if x is None else 0
+    if x is None:
+        if _is_cuda(B):
+            import torch
+            x = torch.zeros((k, n), dtype=torch.float64, device=B.device).t()
+        else:
+            x = np.zeros((n, k), np.float64, order="F")
+    X, ldx = _many_result(n, k, B, x, "x")
+    if _is_cuda(B):
+        import torch
+        torch.cuda.current_stream(B.device).synchronize()   # the library runs on its own stream
+    hist = np.empty((maxiter + 1, k), np.float64, order="F")
+    its, mvs, reorth = np.zeros(k, np.int64), np.zeros(k, np.int64), np.zeros(k, np.int64)
+    conv = np.zeros(k, np.int32)
+    d.ck(d.lib.esp_gmres_many(d.h, p, _many_ptr(B), ldb, _many_ptr(X), ldx, k, 1 if _is_cuda(B) else 0, zero, restart, orth, maxiter,
+                              abstol, reltol, _vp(hist), _vp(its), _vp(mvs), _vp(reorth), _vp(conv)))
+    if log:
+        return X, [{"resnorm": hist[1:int(its[r]) + 1, r].copy(), "r0": float(hist[0, r]), "iters": int(its[r]), "mvps": int(mvs[r]),
+                    "reorth": int(reorth[r]), "isconverged": bool(conv[r])} for r in range(k)]
+    return X

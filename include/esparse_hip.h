@@ -1369,6 +1369,42 @@ int32_t esp_precon_ldiv_many(esp_precon *p, const double *V, int64_t ldv, double
 int32_t esp_cg_many(esp_handle *h, esp_precon *p, const double *B, int64_t ldb, double *X, int64_t ldx, int64_t k, int32_t on_device,
                     int32_t initially_zero, int64_t maxiter, double abstol, double reltol, double *history, int64_t *iterations,
                     int32_t *converged);
+/* RESTARTED GMRES FOR SEVERAL RIGHT-HAND SIDES: esp_gmres for the k columns of B (n x k column-major, leading dimension ldb) into
+ * the k columns of X (ldx), as k INDEPENDENT recurrences run in lockstep, ESP_MANY_CHUNK columns at a time.  This is not block
+ * GMRES: every column has its own Krylov basis, H, nullvec, rhs / y, beta, acc, current, tolerance, DGKS predicate and pass counter.
+ * CONTRACT: for every column r, X[:, r], the whole residual history of r, iterations[r], mv_products[r], reorth_passes[r] and
+ *   converged[r] are bit for bit what esp_gmres gives for B[:, r] alone with the same arguments, whatever the other columns hold and
+ *   whenever they stop.  The summation shape of every dot product, the true divisions and square roots and the absence of
+ *   contraction are esp_gmres's, per column; tests/gmres_model.c stays the normative statement of the order of every operation.
+ * ARGUMENTS: history is (maxiter+1) x k column-major host doubles or NULL (column r at history + r*(maxiter+1) holds
+ *   iterations[r]+1 norms); iterations, mv_products, reorth_passes and converged hold k entries or are NULL.  ESP_ERR_INVALID: k < 0,
+ *   a leading dimension below max(n, 1), any overlap of the ranges of B and X, a NULL array that would hold an element, p bound to
+ *   another handle, and what esp_gmres refuses: restart outside 1..ESP_GMRES_RESTART_MAX, an unknown orth_meth, maxiter < 0.  Every
+ *   state check of esp_gmres applies unchanged.  k == 1 with n > 0 IS esp_gmres.  k == 0 returns after the state checks; for n == 0
+ *   every column has 0 iterations and products, is converged and has residual 0.  Rows n .. ld-1 between the columns are never read
+ *   or written; B is never written.  Stream use and "returns synchronised" as esp_cg_many; ESP_ERR_NOMEM leaves the handle usable.
+ * LOCKSTEP: the columns of a chunk share the iteration counter and the position in the cycle: they start together, so they
+ *   restart together.  After each iteration ONE copy of 16 bytes per column (current, the pass count) reaches the host, which
+ *   keeps every column's history and counters and runs its stop test.  The live columns go to every kernel as a bit mask in an
+ *   argument (no device flag, no fence); a kernel skips a column that is not live or, in a DGKS correction pass, whose device
+ *   predicate is false.  The columns that END after an iteration are all live ones when the cycle is full or at maxiter, else
+ *   those with current <= tol; for them alone y is solved and x updated, with the shared m = position - 1.  Converged columns are
+ *   frozen: their basis, scalars, x, history and counters are never touched again.  The others keep their position: a neighbour's
+ *   convergence does not restart them.  Only a full cycle sets the position back and runs the init sequence for the columns still
+ *   live.  A NaN residual keeps its column live to maxiter.  A column with current <= tol at the start (b = 0 from x = 0, a tiny b
+ *   under abstol) never enters the loop: history = [r0], 0 iterations, x untouched.  maxiter == 0 touches no x.
+ * HOW: the launches of an iteration equal one column's (csrc/gmres_many.hip).  Every column has its own basis, so the
+ *   orthogonalisation shares no reads across columns; only Pl \ (A*v) reads A's and ILU0's index and values once per chunk
+ *   (Identity, Jacobi, ILU0: many-column row kernels; CholeskyFactorization and LUFactorization's panel form: their chunked solves,
+ *   a frozen column solved into scratch; every other kind its single ldiv! per live column).
+ * WORK SPACE (the handle's, sized on first use, released with it): the basis block of (restart+1) x ESP_MANY_CHUNK vectors of n
+ *   doubles rounded up to 32 -- 8.6 GB at n = 2e6 with restart 64, 2.8 GB with restart 20 --, n x ESP_MANY_CHUNK doubles of product
+ *   scratch behind a preconditioner (twice that for ILU0, Cholesky and the LU panels), the partial sums (ESP_MANY_CHUNK times the
+ *   single call's), ESP_MANY_CHUNK scalar blocks, and 2 n x ESP_MANY_CHUNK for host arrays, which are staged a chunk at a time. */
+int32_t esp_gmres_many(esp_handle *h, esp_precon *p, const double *B, int64_t ldb, double *X, int64_t ldx, int64_t k,
+                       int32_t on_device, int32_t initially_zero, int32_t restart, int32_t orth_meth, int64_t maxiter,
+                       double abstol, double reltol, double *history, int64_t *iterations, int64_t *mv_products,
+                       int64_t *reorth_passes, int32_t *converged);
 
 #ifdef __cplusplus
 }

@@ -126,6 +126,11 @@ default tolerance and at most --iters iterations a solve: one solve of each per 
 spreads (max - min), the time per column, the ratio K singles / one call and the iteration counts.  It first asserts that x, the
 history, the iteration count and the flag of every column agree bit for bit.
     python tools/precon_bench.py --kind cg --cg-only ilu0 --nrhs 1,8,32 [--n 128] [--iters 50] [--rounds 5]
+--nrhs K[,K...] with --kind gmres [--cg-only identity|jacobi|ilu0|iluam] [--restart 20] [--orth mgs|cgs|dgks] times gmres(A, B) with
+K columns in one call (esp_gmres_many) against K single gmres calls in the same way; reltol = 0 and --iters iterations
+a solve, so every column takes all of them.  It first asserts that x, the history, the three counters and the flag of every column
+agree bit for bit.
+    python tools/precon_bench.py --kind gmres --cg-only ilu0 --nrhs 1,8,32 --iters 40 [--n 128] [--restart 20] [--orth mgs]
 """
 import argparse
 import ctypes as C
@@ -1486,6 +1491,72 @@ def bench_cg_many(a, torch, esp):
     print(json.dumps(out))
 
 
+def bench_gmres_many(a, torch, esp):
+    """--nrhs K[,K...] with --kind gmres: gmres(A, B) with K columns in one call (esp_gmres_many) against K single gmres calls of the
+    same build in the same process, in the shape of bench_cg_many: --rounds alternating rounds of one solve each (reltol = 0 and
+    --iters iterations, so every column takes all of them), after an assertion that the columns of the two agree bit for bit"""
+    import numpy as np
+    A = esp.fdrand(a.n, a.n, a.n)
+    d = A._d
+    d.ck(d.lib.esp_set_stream(d.h, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    N = A.n
+    name = a.cg_only or "ilu0"
+    P = {"identity": lambda A: None, "jacobi": esp.JacobiPreconditioner, "ilu0": esp.ILU0Preconditioner,
+         "iluam": esp.ILUAMPreconditioner}[name](A)
+    ks = [int(x) for x in str(a.nrhs).split(",")]
+    kw = dict(restart=a.restart, orth_meth=a.orth, maxiter=a.iters, reltol=0.0)
+    out = {"workload": "gmres_many_fdrand", "kind": name, "n": a.n, "N": N, "nnz": A.nnz(), "rounds": a.rounds, "maxiter": a.iters,
+           "restart": a.restart, "orth": a.orth, "nrhs": {}}
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()                                       # (every call returns synchronised)
+        return (time.perf_counter() - t0) * 1e3
+
+    def history(log):
+        return np.concatenate([[log["r0"]], log["resnorm"]]).view(np.uint64)
+
+    torch.manual_seed(1)
+    for k in ks:
+        B = torch.randn((k, N), dtype=torch.float64, device="cuda").t()
+        X = torch.empty((k, N), dtype=torch.float64, device="cuda").t()
+        xs = [torch.empty(N, dtype=torch.float64, device="cuda") for _ in range(k)]
+        bs = [B[:, r].contiguous() for r in range(k)]
+
+        def many(log=False):
+            X.zero_()
+            return esp.gmres(A, B, Pl=P, x=X, log=log, **kw)
+
+        def singles(log=False):
+            for x in xs:
+                x.zero_()
+            return [esp.gmres(A, b, Pl=P, x=x, log=log, **kw) for b, x in zip(bs, xs)]
+
+        for _ in range(max(min(a.warmup, 2), 1)):
+            many(), singles()
+        logs = many(log=True)[1]                   # (a 2-D B of one column takes the many-column entry as well: a list of one dict)
+        want = singles(log=True)
+        for r in range(k):
+            assert bool((X[:, r].contiguous().view(torch.int64) == want[r][0].view(torch.int64)).all()), "x differs in column %d" % r
+            assert all(logs[r][key] == want[r][1][key] for key in ("iters", "mvps", "reorth", "isconverged")), "column %d" % r
+            assert np.array_equal(history(logs[r]), history(want[r][1])), "history of column %d" % r
+        rec = {"many_ms": [], "singles_ms": []}
+        for _ in range(a.rounds):
+            rec["many_ms"].append(wall(many))
+            rec["singles_ms"].append(wall(singles))
+        res = {"iterations": [int(l["iters"]) for l in logs], "reorth": [int(l["reorth"]) for l in logs]}
+        for what, v in rec.items():
+            res[what] = {"rounds": [round(x, 3) for x in v], "median": round(float(np.median(v)), 3), "spread": round(max(v) - min(v), 3)}
+        res["many_ms_per_column"] = round(res["many_ms"]["median"] / k, 3)
+        res["singles_ms_per_column"] = round(res["singles_ms"]["median"] / k, 3)
+        res["ratio_singles_over_many"] = round(res["singles_ms"]["median"] / res["many_ms"]["median"], 3)
+        out["nrhs"][str(k)] = res
+    if P is not None:
+        P.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=256)
@@ -1511,6 +1582,8 @@ def main():
     ap.add_argument("--cpu-model", action="store_true")
     ap.add_argument("--ls", default="1,2,4")
     ap.add_argument("--orths", default="mgs,dgks")
+    ap.add_argument("--restart", type=int, default=20, help="--kind gmres --nrhs: the length of a cycle")
+    ap.add_argument("--orth", choices=["mgs", "cgs", "dgks"], default="mgs", help="--kind gmres --nrhs: the orthogonalisation")
     ap.add_argument("--no-composed", action="store_true")
     ap.add_argument("--coarsen", choices=["sa", "rs"], default="sa")
     ap.add_argument("--cd-n", type=int, default=64)
@@ -1524,9 +1597,11 @@ def main():
     esp = load()
     if a.nrhs and a.kind == "cg":
         return bench_cg_many(a, torch, esp)
+    if a.nrhs and a.kind == "gmres":
+        return bench_gmres_many(a, torch, esp)
     if a.nrhs or a.kind == "mul":
         if a.kind not in ("cholesky", "lu", "mul") or not a.nrhs or (a.kind == "lu" and a.form == "both"):
-            ap.error("--nrhs K goes with --kind cholesky, --kind lu --form columns|panels, --kind mul or --kind cg")
+            ap.error("--nrhs K goes with --kind cholesky, --kind lu --form columns|panels, --kind mul, --kind cg or --kind gmres")
         return bench_many(a, torch, esp)
     if a.kind == "iluam":
         return bench_iluam(a, torch, esp)
