@@ -125,6 +125,7 @@ SIGNATURES = {
     "esp_precon_get_factor": (i32, [vp, vp, i32]),
     "esp_precon_levels": (i32, [vp, P(i64)]),
     "esp_precon_launches": (i32, [vp, P(i64)]),
+    "esp_precon_many_stats": (i32, [vp, P(i64)]),
     "esp_debug_iluam_form": (i32, [vp, i32]),
     "esp_debug_last_iluam_form": (i32, [vp, P(i32)]),
     "esp_precon_block_create": (i32, [vp, i32, i64, vp, vp, i32, P(vp)]),

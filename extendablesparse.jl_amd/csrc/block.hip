@@ -156,6 +156,26 @@ __global__ void blk_vec_scatter_k(const u32 *__restrict__ newpos, const double *
     u[i] = sub ? u[i] - x : x;
 }
 
+// the two for the live columns of a chunk: t[new(i) + d*ldt] = v[i + d*ldv]; u[i + d*ldu] = s[new(i) + d*lds] (new(i) read once)
+__global__ void blk_vec_gather_many_k(const u32 *__restrict__ newpos, const double *__restrict__ v, i64 ldv, double *__restrict__ t, i64 ldt,
+                                      i64 n, u32 live) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const i64 q = newpos[i];
+#pragma unroll
+    for (int d = 0; d < ESP_MANY_CHUNK; d++)
+        if (is_live(live, d)) t[(i64)d * ldt + q] = v[(i64)d * ldv + i];
+}
+__global__ void blk_vec_scatter_many_k(const u32 *__restrict__ newpos, const double *__restrict__ s, i64 lds, double *__restrict__ u, i64 ldu,
+                                       i64 n, u32 live) {
+    const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const i64 q = newpos[i];
+#pragma unroll
+    for (int d = 0; d < ESP_MANY_CHUNK; d++)
+        if (is_live(live, d)) u[(i64)d * ldu + i] = s[(i64)d * lds + q];
+}
+
 // derived_update's builder: B from A's current CSC, installed in p->der.bh, src in p->der.src.  Everything that can fail comes in
 // front of the two, the vectors of the permuted path included: nothing of p changes when it fails
 int32_t build_b(esp_precon *p) {
@@ -239,6 +259,34 @@ int32_t block_ldiv_launch(esp_precon *p, const double *v, double *u, bool sub) {
     hipLaunchKernelGGL(blk_vec_gather_k, dim3(g), dim3(BT), 0, h->stream, newpos, v, t, n);
     CK(precon_ldiv_launch(p->der.inner, t, sv));
     hipLaunchKernelGGL(blk_vec_scatter_k, dim3(g), dim3(BT), 0, h->stream, newpos, (const double *)sv, u, n, sub);
+    return ESP_OK;
+}
+
+// ldiv! of the live columns of one chunk (nr <= ESP_MANY_CHUNK; u may be v where ldu == ldv).  The inner solve is iluam_solve_many
+// or, for an inner Jacobi / ILU0, the many-column kernels of krylov_many.hip.  The identity path adds no launch; the permuted path
+// has one gather and one scatter for the whole chunk
+int32_t block_ldiv_many_launch(esp_precon *p, const double *v, i64 ldv, double *u, i64 ldu, int nr, u32 live) {
+    esp_handle *h = p->h;
+    const i64 n = p->n;
+    live &= all_live(nr);
+    if (n == 0 || nr <= 0) return ESP_OK;
+    CK(derived_follow_stream(p));
+    if (p->lup) FAIL(h, ESP_ERR_STATE, "esp_precon_block: LUFactorization's panel form has its own many-column solve");
+    esp_precon *inner = p->der.inner;
+    auto inner_solve = [&](const double *src, i64 lds, double *dst, i64 ldd) -> int32_t {
+        if (inner->kind == ESP_PRECON_ILUAM) return iluam_solve_many(inner, src, lds, dst, ldd, nr, live);
+        return precon_ldiv_chunk_launch(inner, src, lds, dst, ldd, nr, live);
+    };
+    if (p->blk_path == 0) return inner_solve(v, ldv, u, ldu);
+    CK(ensure(h, p->blk_t, sizeof(double) * (size_t)n * ESP_MANY_CHUNK));
+    CK(ensure(h, p->blk_s, sizeof(double) * (size_t)n * ESP_MANY_CHUNK));
+    const u32 *newpos = (const u32 *)p->blk_new.p;
+    double *t = (double *)p->blk_t.p, *sv = (double *)p->blk_s.p;
+    const unsigned g = grid_for(n, BT);
+    hipLaunchKernelGGL(blk_vec_gather_many_k, dim3(g), dim3(BT), 0, h->stream, newpos, v, ldv, t, n, n, live);
+    CK(inner_solve(t, n, sv, n));
+    hipLaunchKernelGGL(blk_vec_scatter_many_k, dim3(g), dim3(BT), 0, h->stream, newpos, (const double *)sv, n, u, ldu, n, live);
+    HIPCK(h, hipGetLastError());
     return ESP_OK;
 }
 

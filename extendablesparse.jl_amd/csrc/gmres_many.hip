@@ -30,7 +30,8 @@
 //   1. W = Pl \ (A*V[kpos-1]) into V[kpos], with (MGS) level 0 of dot(V[0], w): Identity row_dot_many_k<MUL_DOT>; Jacobi
 //      row_jac_dot_many_k; ILU0 the product into the scratch, then row_chain_many_k and row_dot_many_k<UPPER_DOT>; Cholesky and the
 //      LU panels chol_solve_many / lup_solve_many over the chunk's first nr columns (a frozen column is solved into scratch nobody
-//      reads); every other kind PreconProduct::ldiv per live column; the last two followed by one dot_many_k when MGS wants its dot
+//      reads); ILUAM and the kinds that end in it precon_levels_many_launch, one pass over the level schedules for the live columns;
+//      AMG and SPAI-1 PreconProduct::ldiv per live column; the last three followed by one dot_many_k when MGS wants its dot
 //   2. MGS: fold_batch_k, then kpos times mgs_step_many_k + fold_batch_k.  CGS / DGKS: bdot_many_k, gm_fold_many_k, coef_many_k,
 //      comb_many_k<true>, gm_fold_many_k; DGKS then pred_many_k and the same five kernels three times, unconditionally
 //   3. norm_many_k: H column, nullvec, acc, current; current and the pass count of column d to out[2d], out[2d + 1]
@@ -158,6 +159,7 @@ extern "C" int32_t esp_gmres_many(esp_handle *h, esp_precon *p, const double *B,
         if (!B || !X) return ESP_ERR_INVALID;
         if (B < X + (k - 1) * ldx + n && X < B + (k - 1) * ldb + n) FAIL(h, ESP_ERR_INVALID, "esp_gmres_many: B and X overlap");
     }
+    if (k == 1 && n > 0 && p) many_note(p, 0, 0, 0);
     if (k == 1 && n > 0)  // the single-vector path itself
         return esp_gmres(h, p, B, X, on_device, initially_zero, restart, orth_meth, maxiter, abstol, reltol, history, iterations, mv_products,
                          reorth_passes, converged);
@@ -184,6 +186,7 @@ extern "C" int32_t esp_gmres_many(esp_handle *h, esp_precon *p, const double *B,
     const bool lup = p && block_built(p) && p->lup;
     const bool jac = !lup && fp && !blk && diag_applied(fp), ilu0 = !lup && fp && !blk && !jac && fp->kind == ESP_PRECON_ILU0;
     const bool chol = !lup && fp && !blk && fp->kind == ESP_PRECON_CHOLESKY;
+    esp_precon *const lev = lup ? nullptr : blk ? blk : fp && fp->kind == ESP_PRECON_ILUAM ? fp : nullptr;  // (levels_many's kinds)
     const bool mgs = orth_meth == ESP_ORTH_MGS;
     CK(ensure(h, w.bv, sizeof(double) * (size_t)vs * (size_t)(restart + 1)));
     // A*v and the unpreconditioned residual; behind it ILU0's pass 1, or where Cholesky and the LU panels solve the whole chunk
@@ -227,6 +230,7 @@ extern "C" int32_t esp_gmres_many(esp_handle *h, esp_precon *p, const double *B,
         };
         // dst = Pl \ src (blocks with leading dimension ns), with level 0 of dot(dst, V[0]) when dot
         auto solve = [&](const double *src, double *dst, bool dot, u32 live) -> int32_t {
+            many_note(p, lup || chol || lev || jac || ilu0 ? 2 : 1, nr, r0 / MC + 1);
             if (jac) {
                 jacobi_many(fp, src, ns, dst, ns, nilw, live);
             } else if (ilu0) {
@@ -236,6 +240,8 @@ extern "C" int32_t esp_gmres_many(esp_handle *h, esp_precon *p, const double *B,
                 if (lup) CK(lup_solve_many(p, src, ns, U1, ns, nr));
                 else CK(chol_solve_many(fp, src, ns, U1, ns, nr));
                 hipLaunchKernelGGL(start_many_k, dim3(gv), dim3(KT), 0, st, (const double *)U1, ns, nil, dst, ns, n, nb0, p0, live);
+            } else if (lev) {  // one pass over the level schedules
+                CK(precon_levels_many_launch(lev, src, ns, dst, ns, nr, live));
             } else {
                 for (int d = 0; d < nr; d++)
                     if (is_live(live, d)) CK(pp.ldiv(src + d * ns, dst + d * ns, src + d * ns, false));

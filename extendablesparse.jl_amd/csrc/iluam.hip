@@ -26,6 +26,9 @@
 // already.  The diagonal positions, the row parts and the two solve schedules are built as above; the factor schedule is not, and
 // FactorOp does not run: fval is a copy of the handle's values, and a values-only update! is that copy and the gather.
 //
+// Several right-hand sides (iluam_solve_many): a chunk of up to ESP_MANY_CHUNK columns goes through the two solve
+// schedules in ONE pass -- the launch lists as they are, ESP_MANY_CHUNK adjacent lanes per row, the scratch interleaved.
+//
 // esp_debug_iluam_form (a test hook) forces FactorOp or FactorWaveOp at the next update!, and esp_debug_last_iluam_form tells which ran.
 #include "internal.hpp"
 
@@ -172,16 +175,28 @@ struct FactorWaveOp {
 };
 // forward row: y[i] = ((0 - l*y[j1]) - l*y[j2] - ...) + b[i].  The row parts lie in SLOT order (permute_part): the lanes
 // of a level read one contiguous slice of pointers, columns and values.
+// The statements of both rows are written ONCE, for the single-vector Ops and the many-column ones below: element j of the scratch
+// is y[j * S] -- S = 1: the vector itself; S = MC: column d of the interleaved scratch, y = Y + d --, b is the right-hand side's
+// own column.
+template <int S>
+__device__ __forceinline__ void forward_row(const u32 *lptr, const u32 *lcol, const double *lval, u32 slot, u32 i, const double *b, double *y) {
+    double acc = 0.0;
+    for (u32 k = lptr[slot], e = lptr[slot + 1]; k < e; k++) acc = acc - lval[k] * y[(u64)lcol[k] * S];
+    y[(u64)i * S] = acc + b[i];
+}
+// ... the backward row's x[i], which the caller stores (xs: where the finished x[j] are read)
+template <int S>
+__device__ __forceinline__ double backward_row(const u32 *uptr, const u32 *ucol, const double *uval, const double *diag, u32 slot, u32 i,
+                                               const double *y, const double *xs) {
+    double acc = y[(u64)i * S];
+    for (u32 k = uptr[slot], e = uptr[slot + 1]; k < e; k++) acc = acc - uval[k] * xs[(u64)ucol[k] * S];
+    return acc / diag[slot];
+}
 struct ForwardOp {
     const u32 *order, *lptr, *lcol;
     const double *lval, *b;
     double *y;
-    __device__ __forceinline__ void operator()(u32 slot) const {
-        const u32 i = order[slot];
-        double acc = 0.0;
-        for (u32 k = lptr[slot], e = lptr[slot + 1]; k < e; k++) acc = acc - lval[k] * y[lcol[k]];
-        y[i] = acc + b[i];
-    }
+    __device__ __forceinline__ void operator()(u32 slot) const { forward_row<1>(lptr, lcol, lval, slot, order[slot], b, y); }
 };
 // backward row: x[i] = ((y[i] - u*x[j1]) - ...)/u_ii.  ldiv!: xs == dst.  simple!'s `u .-= upd` fused: x replaces y in the
 // scratch (nobody but row i reads y[i]), dst[i] = dst[i] - x[i] with x[i] rounded first.
@@ -192,15 +207,39 @@ struct BackwardOp {
     bool sub;
     __device__ __forceinline__ void operator()(u32 slot) const {
         const u32 i = order[slot];
-        double acc = y[i];
-        for (u32 k = uptr[slot], e = uptr[slot + 1]; k < e; k++) acc = acc - uval[k] * xs[ucol[k]];
-        const double x = acc / diag[slot];
+        const double x = backward_row<1>(uptr, ucol, uval, diag, slot, i, y, xs);
         if (sub) {
             xs[i] = x;
             dst[i] = dst[i] - x;
         } else {
             dst[i] = x;
         }
+    }
+};
+// The many-column forms (iluam_solve_many): a lane owns one (slot, column d) pair.  The scratch is interleaved, Y[i * MC + d]: the MC
+// lanes of a row are adjacent, gather one 64-byte line per stored entry and read lval[k] / lcol[k] at one address (the layout
+// panels.hpp argues for).  V and U are the caller's column-major arrays.  Backward: x replaces y in the scratch, as sub does above
+constexpr int MC = ESP_MANY_CHUNK;
+static_assert(LT % MC == 0, "the MC lanes of a slot share a workgroup");
+struct ForwardManyOp {
+    const u32 *order, *lptr, *lcol;
+    const double *lval, *V;
+    i64 ldv;
+    double *Y;
+    __device__ __forceinline__ void operator()(u32 slot, int d) const {
+        forward_row<MC>(lptr, lcol, lval, slot, order[slot], V + (i64)d * ldv, Y + d);
+    }
+};
+struct BackwardManyOp {
+    const u32 *order, *uptr, *ucol;
+    const double *uval, *diag;
+    double *Y, *U;
+    i64 ldu;
+    __device__ __forceinline__ void operator()(u32 slot, int d) const {
+        const u32 i = order[slot];
+        const double x = backward_row<MC>(uptr, ucol, uval, diag, slot, i, Y + d, Y + d);
+        Y[(u64)i * MC + d] = x;
+        U[(i64)d * ldu + i] = x;
     }
 };
 
@@ -217,6 +256,42 @@ __global__ __launch_bounds__(LT) void level_thin_k(Op op, const u32 *__restrict_
         if (b + threadIdx.x < e) op(b + threadIdx.x);
         __syncthreads();
     }
+}
+// The many-column launches: the same launch list, MC lanes per member (d = t % MC, member = t / MC).  A lane whose column is not
+// live, or whose member lies past the level's end, skips its loads and stores
+template <class Op>
+__global__ __launch_bounds__(LT) void level_wide_many_k(Op op, u32 first, u32 count, u32 live) {
+    const u64 t = (u64)blockIdx.x * LT + threadIdx.x;
+    const int d = (int)(t % MC);
+    const u64 member = t / MC;
+    if (member < count && is_live(live, d)) op(first + (u32)member, d);
+}
+// ... one workgroup takes the members of a level LT / MC at a time (a level of a thin launch holds up to LT members: up to MC passes,
+// independent of each other).  Every lane reaches every barrier: the loop bounds are the workgroup's, there is no early return
+template <class Op>
+__global__ __launch_bounds__(LT) void level_thin_many_k(Op op, const u32 *__restrict__ loff, u32 l0, u32 l1, u32 live) {
+    const int d = threadIdx.x % MC;
+    const u32 member = threadIdx.x / MC;
+    const bool on = is_live(live, d);
+    for (u32 l = l0; l < l1; l++) {
+        const u32 e = loff[l + 1];
+        for (u32 b = loff[l]; b < e; b += LT / MC)
+            if (on && b + member < e) op(b + member, d);
+        __syncthreads();
+    }
+}
+// (returns the launches it issued)
+template <class Op>
+i64 run_schedule_many(const esp_precon *p, const IluamSched &s, const Op &op, u32 live) {
+    i64 issued = 0;
+    for (const IluamLaunch &L : s.launches) {
+        if (L.thin)
+            hipLaunchKernelGGL(level_thin_many_k<Op>, dim3(1), dim3(LT), 0, p->h->stream, op, (const u32 *)s.loff.p, L.l0, L.l1, live);
+        else
+            hipLaunchKernelGGL(level_wide_many_k<Op>, dim3(grid_for((i64)L.count * MC, LT)), dim3(LT), 0, p->h->stream, op, L.first, L.count, live);
+        issued++;
+    }
+    return issued;
 }
 // the wave form: a wave per member (a wide level: LT / 64 members per workgroup; a thin launch: the waves of the one workgroup take
 // the members of a level in turn)
@@ -437,6 +512,24 @@ int32_t iluam_solve(esp_precon *p, const double *v, double *dst, bool sub) {
     return ESP_OK;
 }
 
+// ldiv! of the live columns of one chunk: the two launch lists walked once each, whatever nr is (live: bits below nr).  A frozen
+// column's u is never written.  The scratch grows to MC * n doubles here: a preconditioner that never sees a many-column call keeps
+// the n doubles of update!
+int32_t iluam_solve_many(esp_precon *p, const double *v, i64 ldv, double *u, i64 ldu, int nr, u32 live) {
+    esp_handle *h = p->h;
+    const i64 n = p->n;
+    live &= all_live(nr);
+    if (n == 0 || nr <= 0) return ESP_OK;
+    CK(ensure(h, p->u1, sizeof(double) * (size_t)n * MC));
+    double *Y = (double *)p->u1.p;
+    i64 issued = run_schedule_many(p, p->sched[S_FWD], ForwardManyOp{(const u32 *)p->sched[S_FWD].order.p, (const u32 *)p->lptr.p, (const u32 *)p->lcol.p, (const double *)p->lval.p, v, ldv, Y}, live);
+    issued += run_schedule_many(p, p->sched[S_BWD], BackwardManyOp{(const u32 *)p->sched[S_BWD].order.p, (const u32 *)p->uptr.p, (const u32 *)p->ucol.p, (const double *)p->uval.p,
+                                                                   (const double *)p->diag.p, Y, u, ldu}, live);
+    p->many_stats[2] = issued;
+    HIPCK(h, hipGetLastError());
+    return ESP_OK;
+}
+
 void iluam_release(esp_precon *p) {
     release(p->fval);
     for (IluamSched &s : p->sched) {
@@ -492,6 +585,13 @@ extern "C" int32_t esp_debug_last_iluam_form(esp_precon *p, int32_t *form) {
     esp_precon *q = iluam_of(p);
     if (!q || !form) return ESP_ERR_INVALID;
     *form = q->iluam_form;
+    return ESP_OK;
+}
+
+extern "C" int32_t esp_precon_many_stats(esp_precon *p, int64_t out[4]) {
+    if (!p || !out) return ESP_ERR_INVALID;
+    if (holds_derived(p) && p->der.inner) p = p->der.inner;
+    for (int k = 0; k < 4; k++) out[k] = p->many_stats[k];
     return ESP_OK;
 }
 

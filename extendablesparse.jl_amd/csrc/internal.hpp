@@ -632,6 +632,9 @@ struct esp_precon {
     DevBuf fval;
     IluamSched sched[3];  // 0: columns of the factorization, 1: rows of the forward solve, 2: rows of the backward solve
     int iluam_force = 0, iluam_form = 0;  // esp_debug_iluam_form's choice; the form of the last numeric factorization (0 none, 1 lane, 2 wave)
+    // esp_precon_many_stats' layout: the most recent many-column solve (form, columns of the last chunk, the level launches
+    // iluam_solve_many issued for it, chunks of the call).  A kind that holds a derived matrix keeps them on its inner preconditioner
+    i64 many_stats[4] = {0, 0, 0, 0};
     // The kinds that hold a derived matrix (holds_derived: Block, Colored, ILU(k)): h is A; a matrix B made from A's stored CSC --
     // Block: the stored A[i,j] with part(i) == part(j); Colored: A[c,c]; ILU(k): every position of level <= iluk_k -- lives in the
     // internal handle bh (A's device and stream), and inner is an ordinary preconditioner of inner_kind bound to bh.  src[q] is the
@@ -721,6 +724,24 @@ static inline bool block_permuted(const esp_precon *p) { return p && block_built
 // the kinds whose ldiv! is u = diag .* v: Jacobi (invdiag) and SPAI-0 (its diagonal M) -- one branch in precon.hip and krylov.hpp
 static inline bool diag_applied(const esp_precon *p) { return p->kind == ESP_PRECON_JACOBI || (p->kind == ESP_PRECON_SPAI && p->spai_order == 0); }
 static inline esp_handle *spai_applied(const esp_precon *p) { return p->spai_sym ? p->spai_sh : p->spai_rh; }
+// the live columns of a chunk of ESP_MANY_CHUNK right-hand sides: a plain bit mask that goes to every kernel as an argument
+__host__ __device__ __forceinline__ bool is_live(u32 live, int d) { return (live >> d) & 1u; }
+static inline u32 all_live(i64 nr) { return (1u << nr) - 1u; }
+// the kinds whose ldiv! ends in ILUAM's level schedules or in block.hip's gather / inner solve / scatter: precon_levels_many_launch
+// carries a chunk through them in one pass (LUFactorization's panel form has lup_solve_many)
+static inline bool levels_many(const esp_precon *p) {
+    if (block_built(p)) return !p->lup;
+    return p->kind == ESP_PRECON_ILUAM || p->kind == ESP_PRECON_ILUK || p->kind == ESP_PRECON_ILUT;
+}
+// esp_precon_many_stats: the record of the most recent many-column solve, kept where the call reads it (the inner preconditioner of
+// a kind that holds a derived matrix).  form 2 over ILUAM keeps the launch count iluam_solve_many left there
+static inline void many_note(esp_precon *p, i64 form, i64 cols, i64 chunks) {
+    esp_precon *q = holds_derived(p) && p->der.inner ? p->der.inner : p;
+    q->many_stats[0] = form;
+    q->many_stats[1] = cols;
+    if (form != 2 || q->kind != ESP_PRECON_ILUAM || q->n == 0) q->many_stats[2] = 0;
+    q->many_stats[3] = chunks;
+}
 constexpr u32 ILUK_FILL = 0xFFFFFFFFu;  // src of a fill entry of ILU(k): no position (every update! refuses nnz(A) >= 2^32 - 16)
 
 #pragma GCC visibility push(hidden)
@@ -732,6 +753,9 @@ int32_t split_build(esp_precon *p, bool reversed);
 // step); release of the buffers above
 int32_t iluam_update(esp_precon *p, bool rebuild);
 int32_t iluam_solve(esp_precon *p, const double *v, double *dst, bool sub);
+// ... and of the live columns of one chunk (nr <= ESP_MANY_CHUNK columns; v: n x nr column-major with leading dimension ldv, u with
+// ldu; u may be v where ldu == ldv): ONE pass over the two launch lists, the scratch p->u1 grown to ESP_MANY_CHUNK * n; launches only
+int32_t iluam_solve_many(esp_precon *p, const double *v, i64 ldv, double *u, i64 ldu, int nr, u32 live);
 void iluam_release(esp_precon *p);
 // precon.hip, for the Krylov solvers: the checks in front of a solve (p == nullptr: those of the handle alone); pass 1 of ILU0's
 // ldiv! into the scratch p->u1 (pass 2 is krylov.hpp's own, in PreconProduct::ldiv: it carries the dot product)
@@ -740,6 +764,11 @@ void ilu0_lower_launch(esp_precon *p, const double *v);
 // krylov_many.hip, for esp_precon_ldiv_many: ldiv! of Jacobi (SPAI-0) and ILU0 for k columns on device arrays (v: n x k column-major
 // with leading dimension ldv, u with ldu; u may be v where ldu == ldv), ESP_MANY_CHUNK columns a launch; launches only
 int32_t precon_ldiv_many_launch(esp_precon *p, const double *v, i64 ldv, double *u, i64 ldu, i64 k);
+// ... and the live columns of ONE chunk of nr <= ESP_MANY_CHUNK columns (block.hip's inner Jacobi / ILU0 under a live mask)
+int32_t precon_ldiv_chunk_launch(esp_precon *p, const double *v, i64 ldv, double *u, i64 ldu, int nr, u32 live);
+// precon.hip: the live columns of one chunk through a kind that levels_many names -- ILUAM itself, the inner ILUAM of ILU(k) and ILUT,
+// block_ldiv_many_launch for the kinds block.hip serves; launches only
+int32_t precon_levels_many_launch(esp_precon *p, const double *v, i64 ldv, double *u, i64 ldu, int nr, u32 live);
 // precon.hip, for block.hip: the checks of every preconditioner call on the handle; ldiv! on device vectors (u may be v)
 int32_t precon_check_handle(esp_handle *h, const char *what);
 int32_t precon_ldiv_launch(esp_precon *p, const double *v, double *u);
@@ -761,6 +790,9 @@ void derived_gather_launch(hipStream_t s, const u64 *pay, u32 *src, int32_t *lev
 // step), release of B, the inner preconditioner and every buffer
 int32_t block_update(esp_precon *p);
 int32_t block_ldiv_launch(esp_precon *p, const double *v, double *u, bool sub);
+// ... and of the live columns of one chunk (as iluam_solve_many): the identity path is the inner many-column solve on the caller's
+// arrays; the permuted path gathers the chunk into blk_t, solves into blk_s and scatters (both grown to ESP_MANY_CHUNK * n here)
+int32_t block_ldiv_many_launch(esp_precon *p, const double *v, i64 ldv, double *u, i64 ldu, int nr, u32 live);
 void block_release(esp_precon *p);
 // iluk.hip: update! (derived_update over the pattern search), release of the transpose and the level array (B, the inner
 // preconditioner and src are block_release's)

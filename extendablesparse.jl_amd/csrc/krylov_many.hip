@@ -25,7 +25,8 @@
 //
 // Kernels of one iteration (ILU0; Jacobi and Identity have dot_many_k in place of the first two; Cholesky and LU's panel form run
 // chol_solve_many / lup_solve_many over the chunk -- its first nr columns, so a frozen column is solved as well, into the scratch c
-// that nobody reads --, every other kind PreconProduct::ldiv per live column, followed by one dot_many_k):
+// that nobody reads --, ILUAM and the kinds that end in it precon_levels_many_launch: one pass over the level schedules for the live
+// columns --, AMG and SPAI-1 PreconProduct::ldiv per live column, each followed by one dot_many_k):
 //   row_chain_many_k          pass 1 of ldiv! for the live columns
 //   row_dot_many_k<UPPER_DOT> pass 2, c stored, level 0 of dot(c, r)
 //   fold_batch_k              level 1 (gridDim.y = the chunk's columns)
@@ -115,16 +116,24 @@ __global__ __launch_bounds__(KT) void finish_many_k(const double *__restrict__ p
 // esp_precon_ldiv_many's branch of these kinds.  Every column is precon.hip's ldiv_launch bit for bit (ILU0's pass-1 scratch p->u1
 // grows to a chunk's width)
 int32_t precon_ldiv_many_launch(esp_precon *p, const double *v, i64 ldv, double *u, i64 ldu, i64 k) {
+    for (i64 r0 = 0; r0 < k; r0 += MC) {
+        const int nr = (int)std::min<i64>(MC, k - r0);
+        CK(precon_ldiv_chunk_launch(p, v + r0 * ldv, ldv, u + r0 * ldu, ldu, nr, all_live(nr)));
+    }
+    return ESP_OK;
+}
+// ... one chunk's live columns (block.hip's inner Jacobi / ILU0 under a solver's live mask: a frozen column's u is never written)
+int32_t precon_ldiv_chunk_launch(esp_precon *p, const double *v, i64 ldv, double *u, i64 ldu, int nr, u32 live) {
     esp_handle *h = p->h;
     const i64 n = p->n;
-    if (n == 0 || k == 0) return ESP_OK;
-    const bool jac = diag_applied(p);
+    live &= all_live(nr);
+    if (n == 0 || nr <= 0) return ESP_OK;
     const i64 ld1 = even_ld(n);
-    if (!jac) CK(ensure(h, p->u1, sizeof(double) * (size_t)ld1 * MC));
-    for (i64 r0 = 0; r0 < k; r0 += MC) {
-        const i64 nr = std::min<i64>(MC, k - r0);
-        if (jac) jacobi_many(p, v + r0 * ldv, ldv, u + r0 * ldu, ldu, nullptr, all_live(nr));
-        else ilu0_many(p, v + r0 * ldv, ldv, (double *)p->u1.p, ld1, nullptr, 0, u + r0 * ldu, ldu, nullptr, all_live(nr));
+    if (diag_applied(p)) {
+        jacobi_many(p, v, ldv, u, ldu, nullptr, live);
+    } else {
+        CK(ensure(h, p->u1, sizeof(double) * (size_t)ld1 * MC));
+        ilu0_many(p, v, ldv, (double *)p->u1.p, ld1, nullptr, 0, u, ldu, nullptr, live);
     }
     HIPCK(h, hipGetLastError());
     return ESP_OK;
@@ -143,8 +152,10 @@ extern "C" int32_t esp_cg_many(esp_handle *h, esp_precon *p, const double *B, in
         if (!B || !X) return ESP_ERR_INVALID;
         if (B < X + (k - 1) * ldx + n && X < B + (k - 1) * ldb + n) FAIL(h, ESP_ERR_INVALID, "esp_cg_many: B and X overlap");
     }
-    if (k == 1 && n > 0)  // the single-vector path itself
+    if (k == 1 && n > 0) {  // the single-vector path itself
+        if (p) many_note(p, 0, 0, 0);
         return esp_cg(h, p, B, X, on_device, initially_zero, maxiter, abstol, reltol, history, iterations, converged);
+    }
     CK(solver_ready(h, p, "esp_cg"));
     CK(csr_current(h));
     if (k == 0) return ESP_OK;
@@ -165,6 +176,7 @@ extern "C" int32_t esp_cg_many(esp_handle *h, esp_precon *p, const double *B, in
     const bool lup = p && block_built(p) && p->lup;
     const bool jac = !lup && fp && !blk && diag_applied(fp), ilu0 = !lup && fp && !blk && !jac && fp->kind == ESP_PRECON_ILU0;
     const bool chol = !lup && fp && !blk && fp->kind == ESP_PRECON_CHOLESKY;
+    esp_precon *const lev = lup ? nullptr : blk ? blk : fp && fp->kind == ESP_PRECON_ILUAM ? fp : nullptr;  // (levels_many's kinds)
     CK(ensure(h, w.r, wbytes));
     CK(ensure(h, w.u, wbytes));
     CK(ensure(h, w.c, wbytes));
@@ -230,6 +242,7 @@ extern "C" int32_t esp_cg_many(esp_handle *h, esp_precon *p, const double *B, in
             if (lup || chol || (fp && !jac && !ilu0)) {
                 if (lup) CK(lup_solve_many(p, R, ldw, Cw, ldw, nr));
                 else if (chol) CK(chol_solve_many(fp, R, ldw, Cw, ldw, nr));
+                else if (lev) CK(precon_levels_many_launch(lev, R, ldw, Cw, ldw, nr, live));  // one pass over the level schedules
                 else
                     for (int d = 0; d < nr; d++)
                         if (is_live(live, d)) CK(pp.ldiv(R + d * ldw, Cw + d * ldw, R + d * ldw, false));
@@ -243,6 +256,7 @@ extern "C" int32_t esp_cg_many(esp_handle *h, esp_precon *p, const double *B, in
             } else {
                 ilu0_many(fp, R, ldw, U1, ldw, R, ldw, Cw, ldw, p0, live);
             }
+            if (p) many_note(p, lup || chol || lev || jac || ilu0 ? 2 : 1, nr, r0 / MC + 1);
             fold(rho);
             // rho_prev = rho; rho = dot(c, r); beta = rho/rho_prev; u = c + beta*u
             hipLaunchKernelGGL(direction_many_k, dim3(gv), dim3(KT), 0, st, (const double *)rho,

@@ -13,7 +13,7 @@ namespace {
 constexpr int MC = ESP_MANY_CHUNK;
 static_assert(MC == 8, "the live mask, the trees and the read-back slots are laid out for 8 columns");
 
-__host__ __device__ __forceinline__ bool is_live(u32 live, int d) { return (live >> d) & 1u; }
+// (is_live and all_live, the mask's two readers, are internal.hpp's: iluam.hip and block.hip take the mask as well)
 
 // level 2 of the live columns at once: column d has its partial1 at p1 + d*nb1; the results in sres[0 .. 7], visible to every
 // thread on return (sred is free again).  Lane t adds p1[t], p1[t + 256], ... to 0.0 as level2 does, then the same tree
@@ -200,6 +200,5 @@ void ilu0_many(esp_precon *p, const double *src, i64 lds, double *u1, i64 ld1, c
 }
 
 inline i64 even_ld(i64 n) { return std::max<i64>((n + 1) & ~(i64)1, 2); }
-inline u32 all_live(i64 nr) { return (1u << nr) - 1u; }
 
 }  // namespace

@@ -334,6 +334,12 @@ int32_t ldiv_launch(esp_precon *p, const double *v, double *u) {
 int32_t solver_ready(esp_handle *h, esp_precon *p, const char *what) { return p ? precon_ready(p, what) : check_handle(h, what); }
 int32_t precon_check_handle(esp_handle *h, const char *what) { return check_handle(h, what); }
 int32_t precon_ldiv_launch(esp_precon *p, const double *v, double *u) { return ldiv_launch(p, v, u); }
+// the many-column twin of ldiv_launch's first three branches (levels_many's kinds): one pass over the schedules for the chunk
+int32_t precon_levels_many_launch(esp_precon *p, const double *v, i64 ldv, double *u, i64 ldu, int nr, u32 live) {
+    if (block_built(p)) return block_ldiv_many_launch(p, v, ldv, u, ldu, nr, live);
+    if (p->kind == ESP_PRECON_ILUK || p->kind == ESP_PRECON_ILUT) p = p->der.inner;  // ILUAM of B / over F on the caller's arrays
+    return iluam_solve_many(p, v, ldv, u, ldu, nr, live);
+}
 
 void ilu0_lower_launch(esp_precon *p, const double *v) {
     hipLaunchKernelGGL((row_chain_k<ILU_LOWER, u32>), dim3(grid_for(p->n, PT)), dim3(PT), 0, p->h->stream, (const u32 *)p->lptr.p,
@@ -420,8 +426,10 @@ extern "C" int32_t esp_precon_ldiv(esp_precon *p, const double *v, double *u, in
 }
 
 // ldiv! of k columns (include/esparse_hip.h, SEVERAL RIGHT-HAND SIDES).  The two panel kinds run their chunked solves, Jacobi
-// (SPAI-0) and ILU0 the many-column kernels of krylov_many.hip; every other kind runs ldiv_launch column by column.  Host arrays
-// pass through p->hv, ESP_MANY_CHUNK columns at a time
+// (SPAI-0) and ILU0 the many-column kernels of krylov_many.hip, every kind that ends in ILUAM's level schedules or in block.hip's
+// gather / inner solve / scatter (levels_many) ONE pass over them per chunk of ESP_MANY_CHUNK columns, a narrower last chunk masked
+// (precon_levels_many_launch); AMG and SPAI-1 alone run ldiv_launch column by column.  Host arrays pass through p->hv,
+// ESP_MANY_CHUNK columns at a time.  esp_precon_many_stats tells afterwards which form ran
 extern "C" int32_t esp_precon_ldiv_many(esp_precon *p, const double *V, int64_t ldv, double *U, int64_t ldu, int64_t k, int32_t on_device) {
     if (!p) return ESP_ERR_INVALID;
     esp_handle *h = p->h;
@@ -433,11 +441,18 @@ extern "C" int32_t esp_precon_ldiv_many(esp_precon *p, const double *V, int64_t 
         if (V < ue && U < ve && !(U == V && ldu == ldv))
             FAIL(h, ESP_ERR_INVALID, "esp_precon_ldiv_many: U and V overlap (only U == V with ldu == ldv is an in-place solve)");
     }
-    if (k == 1 && n > 0) return esp_precon_ldiv(p, V, U, on_device);  // the single-vector path itself
+    if (k == 1 && n > 0) {  // the single-vector path itself
+        many_note(p, 0, 0, 0);
+        return esp_precon_ldiv(p, V, U, on_device);
+    }
     CK(precon_ready(p, "esp_precon_ldiv"));
     const bool chol = p->kind == ESP_PRECON_CHOLESKY, lup = block_built(p) && p->lup;
     const bool fused = !block_built(p) && (diag_applied(p) || p->kind == ESP_PRECON_ILU0);
-    if (k == 0 || n == 0) return ESP_OK;
+    const bool lev = !lup && levels_many(p);
+    if (k == 0) return ESP_OK;
+    const i64 chunks = ceil_div<i64>(k, ESP_MANY_CHUNK);
+    many_note(p, k == 1 ? 0 : chol || lup || fused || lev ? 2 : 1, k == 1 ? 0 : k - (chunks - 1) * ESP_MANY_CHUNK, k == 1 ? 0 : chunks);
+    if (n == 0) return ESP_OK;
     if (!on_device) CK(ensure(h, p->hv, sizeof(double) * (size_t)n * ESP_MANY_CHUNK));
     const i64 step = on_device ? k : ESP_MANY_CHUNK;  // (device arrays: one pass; the panel kinds chunk them themselves)
     for (i64 r0 = 0; r0 < k; r0 += step) {
@@ -454,6 +469,11 @@ extern "C" int32_t esp_precon_ldiv_many(esp_precon *p, const double *V, int64_t 
         if (chol) CK(chol_solve_many(p, dv, dldv, du, dldu, nr));
         else if (lup) CK(lup_solve_many(p, dv, dldv, du, dldu, nr));
         else if (fused) CK(precon_ldiv_many_launch(p, dv, dldv, du, dldu, nr));
+        else if (lev)
+            for (i64 c0 = 0; c0 < nr; c0 += ESP_MANY_CHUNK) {
+                const int nc = (int)std::min<i64>(ESP_MANY_CHUNK, nr - c0);
+                CK(precon_levels_many_launch(p, dv + c0 * dldv, dldv, du + c0 * dldu, dldu, nc, all_live(nc)));
+            }
         else
             for (i64 r = 0; r < nr; r++) CK(ldiv_launch(p, dv + r * dldv, du + r * dldu));
         HIPCK(h, hipGetLastError());

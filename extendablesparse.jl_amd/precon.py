@@ -209,6 +209,15 @@ class _ILUAMFactors:
         self._ck(self.A._d.lib.esp_precon_launches(self._live(), out))
         return tuple((int(out[2 * k]), int(out[2 * k + 1])) for k in range(3))
 
+    def many_stats(self):
+        """(form, columns of the last chunk, level launches of that chunk, chunks of the call) of the most recent solve with
+        several right-hand sides (esp_precon_many_stats) -- ldiv with a 2-D v, or the last preconditioner application inside
+        cg / gmres with a 2-D b.  form: 0 none yet or one column, 1 column by column, 2 one pass over the level schedules for a
+        chunk of ESP_MANY_CHUNK columns; the level launches then equal launches()' forward plus backward entries"""
+        out = (C.c_int64 * 4)()
+        self._ck(self.A._d.lib.esp_precon_many_stats(self._live(), out))
+        return tuple(int(x) for x in out)
+
     def debug_factor_form(self, form):
         """test hook (esp_debug_iluam_form), takes effect at the next update(): 0 the automatic choice between the two forms of the
         column factorization, 1 always a lane per column, 2 always a wave per column -- the results never change"""

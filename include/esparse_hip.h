@@ -1342,11 +1342,23 @@ int32_t esp_debug_last_append_route(const esp_handle *h, int32_t *route);
  *     right-hand side) pair and walks exactly the single call's chain for it, so one read of a panel entry serves the whole chunk.
  *     No allocation, copy or synchronisation in between; esp_precon_cholesky_stats / esp_precon_lu_panel_stats do not change.
  *   - Jacobi (SPAI-0) and ILU0: the many-column kernels of esp_cg_many, one or two launches per chunk.
- *   - every other kind (ILUAM, Block, ILU(k), ILUT, Colored, SPAI-1, AMG, RS-AMG, LU's column form): the single call's launches
- *     column after column inside the one call. */
+ *   - ILUAM and every kind whose ldiv! ends in its two triangular solves (ILU(k), ILUT, Colored, Block, LU's column form): per chunk
+ *     ONE pass over the forward and the backward launch list -- as many level launches as a single ldiv!, whatever the chunk's
+ *     width.  A lane owns one (row, right-hand side) pair, the ESP_MANY_CHUNK lanes of a row are adjacent and the scratch is stored
+ *     right-hand-side-fastest (y[i * ESP_MANY_CHUNK + r]; it grows to ESP_MANY_CHUNK * n doubles at the first such call), so one
+ *     read of a factor entry serves the chunk.  Block, Colored and LU's column form add one gather and one scatter per chunk on
+ *     their permuted path and nothing on the identity path; an inner Jacobi / ILU0 runs the kernels of the line above.
+ *   - SPAI-1, AMG and RS-AMG: the single call's launches column after column inside the one call.
+ * esp_precon_many_stats: read-only; the most recent many-column solve this preconditioner ran, through esp_precon_ldiv_many or as
+ *   the last preconditioner application inside esp_cg_many / esp_gmres_many.  out[0] = its form: 0 none yet or k == 1 (the
+ *   single-vector path), 1 column by column, 2 one pass over the schedules or panels for the chunk; out[1] = the columns of the last
+ *   chunk; out[2] = the level launches that chunk issued, forward plus backward (0 for a kind without level schedules);
+ *   out[3] = the chunks of the last call.  A kind that holds a derived matrix answers with its inner preconditioner's record, as
+ *   esp_precon_launches does. */
 #define ESP_MANY_CHUNK 8
 int32_t esp_mul_many(esp_handle *h, const double *X, int64_t ldx, double *R, int64_t ldr, int64_t k, int32_t on_device);
 int32_t esp_precon_ldiv_many(esp_precon *p, const double *V, int64_t ldv, double *U, int64_t ldu, int64_t k, int32_t on_device);
+int32_t esp_precon_many_stats(esp_precon *p, int64_t out[4]);
 /* CONJUGATE GRADIENTS FOR SEVERAL RIGHT-HAND SIDES: esp_cg for the k columns of B (n x k column-major, leading dimension ldb) into
  * the k columns of X (ldx), as k INDEPENDENT recurrences run in lockstep, ESP_MANY_CHUNK columns at a time.  This is not block CG.
  * CONTRACT: for every column r, X[:, r], the whole residual history of r, iterations[r] and converged[r] are bit for bit what
@@ -1364,7 +1376,8 @@ int32_t esp_precon_ldiv_many(esp_precon *p, const double *V, int64_t ldv, double
  *   x, r and history are never written again, and the chunk ends when no column is live or at maxiter (a NaN residual keeps its
  *   column live to maxiter, as in esp_cg).  A's index and values are read once per chunk and product, and the launches of an
  *   iteration do not depend on the number of columns for Identity, Jacobi and ILU0 (many-column kernels, csrc/krylov_many.hip);
- *   CholeskyFactorization and LUFactorization's panel form run their chunked solves, every other kind its single ldiv! per live
+ *   CholeskyFactorization and LUFactorization's panel form run their chunked solves, ILUAM and the kinds that end in it one pass
+ *   over the level schedules for the live columns (see esp_precon_ldiv_many), SPAI-1 and the AMG kinds their single ldiv! per live
  *   column.  Host arrays are staged a chunk at a time; the work vectors (4 x ESP_MANY_CHUNK x n doubles) belong to the handle. */
 int32_t esp_cg_many(esp_handle *h, esp_precon *p, const double *B, int64_t ldb, double *X, int64_t ldx, int64_t k, int32_t on_device,
                     int32_t initially_zero, int64_t maxiter, double abstol, double reltol, double *history, int64_t *iterations,
@@ -1396,7 +1409,8 @@ int32_t esp_cg_many(esp_handle *h, esp_precon *p, const double *B, int64_t ldb, 
  * HOW: the launches of an iteration equal one column's (csrc/gmres_many.hip).  Every column has its own basis, so the
  *   orthogonalisation shares no reads across columns; only Pl \ (A*v) reads A's and ILU0's index and values once per chunk
  *   (Identity, Jacobi, ILU0: many-column row kernels; CholeskyFactorization and LUFactorization's panel form: their chunked solves,
- *   a frozen column solved into scratch; every other kind its single ldiv! per live column).
+ *   a frozen column solved into scratch; ILUAM and the kinds that end in it: one pass over the level schedules for the live
+ *   columns; SPAI-1 and the AMG kinds: the single ldiv! per live column).
  * WORK SPACE (the handle's, sized on first use, released with it): the basis block of (restart+1) x ESP_MANY_CHUNK vectors of n
  *   doubles rounded up to 32 -- 8.6 GB at n = 2e6 with restart 64, 2.8 GB with restart 20 --, n x ESP_MANY_CHUNK doubles of product
  *   scratch behind a preconditioner (twice that for ILU0, Cholesky and the LU panels), the partial sums (ESP_MANY_CHUNK times the

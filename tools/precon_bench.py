@@ -113,13 +113,15 @@ LUFactorization, the yardstick, in the same process and the same alternating rou
 the create, a values-only update! and ldiv! on device vectors; every round's value, medians, spreads (max - min), the ratios, the launch
 counts, nnz(L), the panel bytes, the residual for b = ones, and cg with ILU0 to 1e-8 from the same run.
     python tools/precon_bench.py --kind cholesky [--n 24] [--lu-rounds 5] [--iters 5] [--rounds 5]
---nrhs K[,K...] with --kind cholesky, --kind lu --form columns|panels or --kind mul times several right-hand sides in one call
+--nrhs K[,K...] with --kind cholesky, --kind lu --form columns|panels, --kind iluam, --kind colored or --kind mul times several right-hand sides in one call
 (esp_precon_ldiv_many / esp_mul_many) against K single-vector calls of the same build in the same process, on device
 arrays: alternating rounds of --iters repetitions each; every round's value, medians, spreads (max - min), the time per column and
 the ratio K singles / one call.  It first asserts that the columns of the two agree bit for bit.
     python tools/precon_bench.py --kind cholesky --nrhs 1,8,32 [--n 32] [--iters 3] [--rounds 5]
     python tools/precon_bench.py --kind lu --form panels --nrhs 1,8,32 [--n 32]
     python tools/precon_bench.py --kind mul --nrhs 1,8,32 [--n 128] [--iters 10]
+    python tools/precon_bench.py --kind iluam --nrhs 1,8,32 [--n 128]      (ILUAMPreconditioner: iluam_solve_many)
+    python tools/precon_bench.py --kind colored --nrhs 1,8,32 [--n 128]    (ColoredPreconditioner over ILUAM)
 --nrhs K[,K...] with --kind cg [--cg-only identity|jacobi|ilu0|iluam] times cg(A, B) with K columns in one call (esp_cg_many, DESIGN.md
 5u) against K single cg calls of the same build in the same process, on fdrand(n,n,n) and device arrays, random right-hand sides, the
 default tolerance and at most --iters iterations a solve: one solve of each per alternating round; every round's value, medians,
@@ -1390,9 +1392,14 @@ def bench_many(a, torch, esp):
         one, many = (lambda x, r: A.mul(x, r)), (lambda X, R: A.mul(X, R))
     else:
         t0 = time.perf_counter()
-        P = esp.CholeskyFactorization(A, a.leaf_size) if a.kind == "cholesky" else esp.LUFactorization(A, a.leaf_size, form=a.form)
+        if a.kind == "iluam":
+            P = esp.ILUAMPreconditioner(A)
+        elif a.kind == "colored":
+            P = esp.ColoredPreconditioner(A, esp.ILUAMPreconditioner)
+        else:
+            P = esp.CholeskyFactorization(A, a.leaf_size) if a.kind == "cholesky" else esp.LUFactorization(A, a.leaf_size, form=a.form)
         out["create_ms"] = (time.perf_counter() - t0) * 1e3
-        out["stats"] = P.stats()
+        out["stats"] = P.launches() if a.kind in ("iluam", "colored") else P.stats()
         rows = N
         one, many = (lambda x, r: P.ldiv(x, r)), (lambda X, R: P.ldiv(X, R))
 
@@ -1421,6 +1428,8 @@ def bench_many(a, torch, esp):
         res["many_ms_per_column"] = round(res["many_ms"]["median"] / k, 4)
         res["singles_ms_per_column"] = round(res["singles_ms"]["median"] / k, 4)
         res["ratio_singles_over_many"] = round(res["singles_ms"]["median"] / res["many_ms"]["median"], 3)
+        if hasattr(P, "many_stats"):               # (a build from before esp_precon_many_stats has none: the column loop)
+            res["many_stats"] = P.many_stats()
         out["nrhs"][str(k)] = res
     if P is not None:
         P.close()
@@ -1600,8 +1609,9 @@ def main():
     if a.nrhs and a.kind == "gmres":
         return bench_gmres_many(a, torch, esp)
     if a.nrhs or a.kind == "mul":
-        if a.kind not in ("cholesky", "lu", "mul") or not a.nrhs or (a.kind == "lu" and a.form == "both"):
-            ap.error("--nrhs K goes with --kind cholesky, --kind lu --form columns|panels, --kind mul, --kind cg or --kind gmres")
+        if a.kind not in ("cholesky", "lu", "mul", "iluam", "colored") or not a.nrhs or (a.kind == "lu" and a.form == "both"):
+            ap.error("--nrhs K goes with --kind cholesky, --kind lu --form columns|panels, --kind iluam, --kind colored, --kind mul, --kind cg "
+                     "or --kind gmres")
         return bench_many(a, torch, esp)
     if a.kind == "iluam":
         return bench_iluam(a, torch, esp)
